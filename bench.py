@@ -23,7 +23,15 @@ workload (every N): BASELINE config 3 as written -- Gaussian geospatial, n = Q =
          glmmr_mcml_dbg_emulate_world).  The time of the collectives themselves is NOT in it.
 Inputs are resident in HBM before the timed region starts.
 
-Launch: python bench.py --gpus 1 --steps K --warmup W      (single GPU)
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, roofline of the
+timed HMC products, the fit of the timed iterations, checked).  --full adds what takes work of its own after the
+timed region: the CPU baseline (cpu_baseline), BASELINE configs 2, 4 and 5 (other_configs) and the theta-step's
+objective re-evaluated at the fitted theta (config.fit.mvn_ll_at_theta).
+--dump-outputs DIR writes what the timed mcml_full call hands its caller after its last step (beta, theta, sigma,
+accept_rate, mean_e, leapfrog_total and the samples u, Q x columns) as DIR/<name>.npy, float64, at most 64 MB in
+all: if u does not fit, a fixed, seeded sample of its columns is written, with their indices in u_columns.npy.
+
+Launch: python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]     (single GPU)
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -174,12 +182,32 @@ def other_configs(api, synth, stream, iters=3):
     return out
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, res, u):
+    """--dump-outputs: the timed mcml_full call's results as path/<name>.npy (float64).  u keeps every column when the
+    whole dump fits in DUMP_BYTES, else a fixed, seeded sample of them (sorted; indices in u_columns.npy)."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.atleast_1d(np.asarray(res[k], dtype=np.float64))
+           for k in ("beta", "theta", "sigma", "accept_rate", "mean_e", "leapfrog_total")}
+    spare = DUMP_BYTES - sum(a.nbytes for a in out.values()) - (1 << 20)       # 1 MB for the .npy headers and indices
+    keep = max(1, spare // (8 * (u.shape[0] + 1)))
+    if u.shape[1] > keep:
+        cols = np.sort(np.random.default_rng(20240601).choice(u.shape[1], keep, replace=False))
+        out["u_columns"] = cols.astype(np.float64)
+        u = u[:, cols]
+    out["u"] = np.ascontiguousarray(u, dtype=np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--n", "--nobs", dest="n", type=int, default=CFG["n"], help="override n = Q (debug only; invalidates the metric)")
     ap.add_argument("--chains", type=int, default=0, help="chains per GPU (default: 1024 / gpus; with --weak 1024)")
     ap.add_argument("--weak", action="store_true", help="weak scaling: 1024 chains per GPU")
@@ -187,7 +215,12 @@ def main():
                     help="N > 1: the library's own RCCL communicator (default) or the torch.distributed hook")
     ap.add_argument("--dense-z", action="store_true", help="dense (non-identity) Z: ZL dense, no zero skipping")
     ap.add_argument("--as-rank-of", type=int, default=0, help="time one rank of an N-rank job on one GPU (peers emulated)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs 2, 4, 5 after the timed region")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip BASELINE configs 2, 4, 5 after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also the CPU baseline, BASELINE configs 2, 4, 5 and the objective at "
+                         "the fitted theta (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -302,9 +335,16 @@ def main():
         tdist.all_reduce(tt, op=tdist.ReduceOp.MAX)
         dt = float(tt.item())
     prof = ctx.profile(enable=False)
-    # what was computed (outside the timed region): the fit after `steps` iterations and the theta-step's objective there
+    if args.dump_outputs:
+        # the samples as mcml_full returns them (every rank's columns); every rank calls it, as the gather it may need is collective
+        u = ctx.get_u() if emu else ctx.get_u_all()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, res, u)
+        del u
+    # what was computed (outside the timed region): the fit after `steps` iterations and (--full) the theta-step's
+    # objective there
     fit = {"beta": [float(x) for x in res["beta"]], "theta": [float(x) for x in res["theta"]], "sigma": float(res["sigma"])}
-    if not emu:
+    if args.full and not emu:
         fit["mvn_ll_at_theta"] = float(ctx.mvn_ll(res["theta"]))
     th = np.asarray(res["theta"])
     fit_ok = bool(np.all(np.isfinite(res["beta"])) and np.all(np.isfinite(th)) and np.isfinite(res["sigma"]) and
@@ -385,14 +425,14 @@ def main():
                                       "value = this rank's chains / its step time; x%d = the job's rate if every rank takes this long"
                                       % (emu, C, 1 + shard["theta_rounds"] // max(1, args.steps), emu))
             line["config"]["projected_job_value"] = args.steps * C * emu / dt
-        if world == 1 and not args.no_cpu_baseline and not emu:
+        if args.full and world == 1 and not args.no_cpu_baseline and not emu:
             try:
                 cfg["chains_total_run"] = C * world; cfg["dense_z"] = bool(args.dense_z)
                 line["cpu_baseline"] = cpu_baseline(d, cfg)
             except Exception as e:           # the baseline never blocks the GPU number
                 line["cpu_baseline"] = {"value": None, "unit": "simlik evals/s", "cores": 0, "kind": "port",
                                         "sample": "failed: %r" % (e,)}
-        if world == 1 and not emu and not args.no_other_configs and args.n == CFG["n"] and args.chains <= 0 and not args.dense_z:
+        if args.full and world == 1 and not emu and not args.no_other_configs and args.n == CFG["n"] and args.chains <= 0 and not args.dense_z:
             ctx.close()
             line["other_configs"] = other_configs(api, synth, stream)
         print(json.dumps(line), flush=True)

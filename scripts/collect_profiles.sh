@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof_$TAG; mkdir -p $O
 PY=python3
 # 1. the bench line itself (no profiler) + kernel stats of the same command
-$PY bench.py --steps 5 --warmup 2 > $O/bench_line.json 2> $O/bench_line.err
+$PY bench.py --steps 5 --warmup 2 --full > $O/bench_line.json 2> $O/bench_line.err
 echo "bench line done" 
 rocprofv3 --kernel-trace -d $O/kt_bench -o b -- $PY bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs > $O/kt_bench.log 2>&1
 $PY scripts/rocpd_stats.py $O/kt_bench/b_results.db > $O/bench_kernel_stats.csv
