@@ -313,6 +313,17 @@ class Context:
         _lib.check(_lib.lib().glmmr_mcml_ctx_last_kernels(self._h, C.byref(f), C.byref(b)))
         return names[f.value], names[b.value]
 
+    def band_plan(self, chains, which="fwd"):
+        """the banded kernel's decomposition of the forward / backward product for `chains` columns (test hook,
+        include/glmmr_mcml_c.h glmmr_mcml_dbg_band_plan)"""
+        out = (C.c_int * 10)()
+        _lib.check(_lib.lib().glmmr_mcml_dbg_band_plan(self._h, {"fwd": 0, "bwd": 1}[which], int(chains), out))
+        keys = ("used", "nbands", "tiles", "gn", "nwg", "nred", "nslots", "paired", "nempty", "built")
+        d = dict(zip(keys, list(out)))
+        for k in ("used", "paired", "built"):
+            d[k] = bool(d[k])
+        return d
+
     def mcml_optim(self, start, trace=0, mcnr=False, maxfun=0, theta_batch=0):
         start = _f(start).ravel(); R = self.npar()
         b = np.zeros(self.P); t = np.zeros(R); sg = C.c_double()

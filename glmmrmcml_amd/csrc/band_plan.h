@@ -26,6 +26,7 @@ struct BandRed { int band, s0, s1, pad; };
 // ---- host: the decomposition ------------------------------------------------------------
 struct BandPlanDev {
     int gn = 0, nwg = 0, nred = 0, nslots = 0;
+    int paired = 0;                       // decompose() chose the paired form (else streamed)
     DevBuf items, wg_ptr, red, part;
 };
 
@@ -52,8 +53,8 @@ struct BandPlan {
         skinny.reset();
     }
 
-    // target_wg: workgroups the launch should have in all (one per CU)
-    static void decompose(const std::vector<int>& kr, int nbands, int gn, int target_wg, std::vector<BandItem>& items,
+    // target_wg: workgroups the launch should have in all (one per CU).  Returns true for the paired form.
+    static bool decompose(const std::vector<int>& kr, int nbands, int gn, int target_wg, std::vector<BandItem>& items,
                           std::vector<int>& wg_ptr, std::vector<BandRed>& red, int& nslots)
     {
         items.clear(); wg_ptr.clear(); red.clear(); nslots = 0;
@@ -66,7 +67,7 @@ struct BandPlan {
                 if (q > p) items.push_back({q, kr[2 * q], kr[2 * q + 1], -1});
             }
             wg_ptr.push_back((int)items.size());
-            return;
+            return true;
         }
         // Streamed: walk the bands in order and fill one workgroup after another up to a cost cap.  Cost in
         // half K tiles: 2 per K tile + OVH per item (ring fill, barrier, epilogue or partial store).  Per-workgroup
@@ -106,7 +107,7 @@ struct BandPlan {
             if (fill(mid, false) <= nwg) hi = mid; else lo = mid + 1;
         }
         fill(lo, true);
-        return;
+        return false;
     }
 
     int device_plan(int gn, hipStream_t s, BandPlanDev** out)
@@ -115,7 +116,7 @@ struct BandPlan {
         if (it != by_gn.end()) { *out = it->second.get(); return MCML_OK; }
         std::unique_ptr<BandPlanDev> d(new BandPlanDev());
         std::vector<BandItem> items; std::vector<int> wg_ptr; std::vector<BandRed> red; int nslots = 0;
-        decompose(kr, nbands, gn, 256, items, wg_ptr, red, nslots);
+        d->paired = decompose(kr, nbands, gn, 256, items, wg_ptr, red, nslots) ? 1 : 0;
         d->gn = gn; d->nwg = (int)wg_ptr.size() - 1; d->nred = (int)red.size(); d->nslots = nslots;
         MCML_TRY(d->items.ensure(sizeof(BandItem) * (items.size() + 1)));
         MCML_TRY(d->wg_ptr.ensure(sizeof(int) * wg_ptr.size()));

@@ -177,6 +177,32 @@ extern "C" int glmmr_mcml_ctx_last_kernels(glmmr_mcml_ctx* h, int* fwd, int* bwd
     return MCML_OK;
 }
 
+// read-only: the banded kernel's decomposition for `chains` columns of the forward (which = 0) or backward (1)
+// product -- the plan a product has built for that column-tile count, or the same decomposition computed on the host
+extern "C" int glmmr_mcml_dbg_band_plan(glmmr_mcml_ctx* h, int which, int chains, int* out10)
+{
+    MCML_REQUIRE(h && (which == 0 || which == 1) && chains >= 1 && out10, "dbg_band_plan: bad argument");
+    const Ctx& c = h->c;
+    const BandPlan& bp = which ? c.plan_bwd : c.plan_fwd;
+    const int gn = (chains + BD_BN - 1) / BD_BN;
+    int nempty = 0;
+    for (int b = 0; b < bp.nbands; ++b) nempty += bp.kr[2 * b] == bp.kr[2 * b + 1];
+    int nwg = 0, nred = 0, nslots = 0, paired = 0, built = 0;
+    auto it = bp.by_gn.find(gn);
+    if (it != bp.by_gn.end()) {
+        const BandPlanDev& d = *it->second;
+        nwg = d.nwg; nred = d.nred; nslots = d.nslots; paired = d.paired; built = 1;
+    } else if (bp.nbands > 0) {
+        std::vector<BandItem> items; std::vector<int> wg_ptr; std::vector<BandRed> red;
+        paired = BandPlan::decompose(bp.kr, bp.nbands, gn, 256, items, wg_ptr, red, nslots) ? 1 : 0;
+        nwg = (int)wg_ptr.size() - 1; nred = (int)red.size();
+    }
+    const int v[10] = {(which ? c.band_bwd : c.band_fwd) ? 1 : 0, bp.nbands, (int)bp.tiles, gn, nwg, nred, nslots,
+                       paired, nempty, built};
+    for (int i = 0; i < 10; ++i) out10[i] = v[i];
+    return MCML_OK;
+}
+
 extern "C" int glmmr_mcml_ctx_shard_stats(glmmr_mcml_ctx* h, long long* out6)
 {
     MCML_REQUIRE(h && out6, "shard_stats: null argument");

@@ -225,6 +225,12 @@ int glmmr_mcml_ctx_profile_launches(glmmr_mcml_ctx* ctx, long long* fwd, long lo
  * (dgemm_skinny.h), 1 banded FP64 MFMA kernel (dgemm_band.h), 2 dense direct-to-LDS MFMA kernel (dgemm_dlds.h),
  * 3 register-staged MFMA kernel (dgemm_mfma.h), 4 sparse chain-major operator (hmc_cm.h); -1 none yet */
 int glmmr_mcml_ctx_last_kernels(glmmr_mcml_ctx* ctx, int* fwd, int* bwd);
+/* The banded kernel's work decomposition (csrc/band_plan.h) for `chains` columns of the sampler's forward (which = 0) or
+ * backward (which = 1) product, read-only: out10 = [banded kernel selected for this operand, bands of 80 rows, K tiles
+ * multiplied, column tiles, workgroups per column tile, split bands (k_band_reduce blocks), partial slots,
+ * 1 paired / 0 streamed, bands with no nonzero K tile, 1 if a product has built this plan].  The plan a product has
+ * built is reported as it is; otherwise the same decomposition is computed on the host (nothing is cached). */
+int glmmr_mcml_dbg_band_plan(glmmr_mcml_ctx* ctx, int which, int chains, int* out10);
 /* Host wall-clock time per phase of the MCML iterations run by this process since the last reset (csrc/trace.h):
  * out8 (nullable) = [sample, beta-step, theta-step, refresh] ms, then the four phase counts.  enable / reset as above. */
 int glmmr_mcml_dbg_phase_ms(int enable, int reset, double* out8);
