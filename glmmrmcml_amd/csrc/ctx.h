@@ -8,7 +8,7 @@
 
 namespace mcml {
 
-constexpr int CHOL_NB = 128;     // leaf size of the recursive Cholesky / TRSM
+constexpr int CHOL_NB = 128;     // panel / leaf size of the blocked Cholesky / TRSM
 constexpr int SMALL_BLOCK = 32;  // blocks up to this size are factorised one wave each
 
 // cross-rank reduction hook (sum, f64, in place on a device buffer).  Single
@@ -142,7 +142,7 @@ struct CholGraph {
     float eager_ms = 0.f, best_ms = 0.f;
     hipGraphExec_t best = nullptr;      // fastest executable seen so far while `exec` is the one on trial
     int tries = 0, trial_launches = 0;  // an executable's first launch carries its upload: the second one is timed
-    bool timed = false, settled = false, branchy = false;
+    bool timed = false, settled = false;
     void release() {
         if (best && best != exec) (void)hipGraphExecDestroy(best);
         best = nullptr;
@@ -153,9 +153,11 @@ struct CholGraph {
     }
 };
 // a few graphs side by side: a model with two or more large covariance blocks of different size evaluates them in turn,
-// and a one-entry cache would re-capture (i.e. run eagerly) every time
+// and a one-entry cache would re-capture (i.e. run eagerly) every time.  Every graph is a two-chain one (a single
+// evaluation): at most two of those are kept alive (of three or more alive in a process every new instantiation measured
+// slow, whatever the number of tries)
 struct CholGraphCache {
-    static constexpr int CAP = 4;
+    static constexpr int CAP = 2;
     std::vector<CholGraph> g;
     long long tick = 0;
     void clear() { for (CholGraph& e : g) e.release(); g.clear(); }
@@ -165,23 +167,20 @@ struct CholGraphCache {
     CholGraphCache& operator=(const CholGraphCache&) = delete;
     CholGraphCache(CholGraphCache&& o) noexcept : g(std::move(o.g)), tick(o.tick) { o.g.clear(); }
     CholGraphCache& operator=(CholGraphCache&& o) noexcept { if (this != &o) { clear(); g = std::move(o.g); tick = o.tick; o.g.clear(); } return *this; }
-    // branchy: a two-chain graph (a single evaluation) -- at most two of those are kept alive (of three or more alive in
-    // a process every new instantiation measured slow, whatever the number of tries); one-chain graphs (batches): four
-    CholGraph& find(const double* A, const double* linv, int lda, int n, int extra, bool branchy) {
+    CholGraph& find(const double* A, const double* linv, int lda, int n, int extra) {
         ++tick;
         for (CholGraph& e : g)
             if (e.A == A && e.linv == linv && e.lda == lda && e.n == n && e.extra == extra) { e.used = tick; return e; }
-        const int cap = branchy ? 2 : CAP;
-        int have = 0; size_t old = g.size();
-        for (size_t i = 0; i < g.size(); ++i)
-            if (g[i].branchy == branchy) { ++have; if (old == g.size() || g[i].used < g[old].used) old = i; }
-        if (have >= cap) {
+        size_t old = 0;
+        for (size_t i = 1; i < g.size(); ++i)
+            if (g[i].used < g[old].used) old = i;
+        if ((int)g.size() >= CAP) {
             g[old].release();
             g[old] = CholGraph();
             std::swap(g[old], g.back());
         } else g.push_back(CholGraph());
         CholGraph& e = g.back();
-        e.A = A; e.linv = linv; e.lda = lda; e.n = n; e.extra = extra; e.seen = 0; e.used = tick; e.branchy = branchy;
+        e.A = A; e.linv = linv; e.lda = lda; e.n = n; e.extra = extra; e.seen = 0; e.used = tick;
         return e;
     }
 };
@@ -224,11 +223,10 @@ struct Ctx {
 
     // MVN workspaces
     DevMat Dwork;               // maxdim x maxdim
-    DevMat Uwork;               // maxdim x mcols
     DevBuf linv;                // (maxdim/128 + 1) x 128 x 128
     DevBuf partials;            // reduction partials
     DevBuf scalars;             // small device scalars: [0..15] results, [16] error flag (int)
-    int maxdim_large = 0;       // largest block that takes the recursive path
+    int maxdim_large = 0;       // largest block that takes the blocked (dense) path
     int n_small = 0, n_diag_rows = 0;
     DevBuf small_ids;                           // ids of the small dense blocks (mvn_setup), for k_small_ll
 

@@ -19,9 +19,8 @@ extern "C" int glmmr_mcml_dbg_dgemm(int M, int N, int K, const double* A, int ld
     hipStream_t s = nullptr;
     DevMat dA, dB, dC;
     if (force_tile == 40) {
-        // the sampler's dense direct-to-LDS kernel (dgemm_dlds.h: dgemm_dlds_asm_kernel unless GLMMR_MCML_DLDS picks a
-        // compiler-scheduled variant), with the operand contract the sampler meets: zero columns / rows up to the
-        // next multiple of 32 in K
+        // the sampler's dense direct-to-LDS kernel (dgemm_dlds.h: dgemm_dlds_asm_kernel), with the operand contract
+        // the sampler meets: zero columns / rows up to the next multiple of 32 in K
         MCML_REQUIRE(!b_nmajor && !lower_only, "dbg_dgemm: the direct-to-LDS kernel takes a K-major B and all tiles");
         const int kpad = round_up(K, 32);
         MCML_TRY(dA.alloc(M, K, 32));

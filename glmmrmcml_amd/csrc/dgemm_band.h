@@ -435,7 +435,7 @@ static inline int launch_gemm_band(hipStream_t s, BandPlan& plan, int N, const d
     BandP bp;
     bp.clocks = clocks;
     bp.mode = mode;
-    bp.g = GemmP{plan.M, N, plan.K, A, lda, B, ldb, 0, gn, 0, 0};
+    bp.g = GemmP{plan.M, N, plan.K, A, lda, B, ldb, 0, gn, 0};
     bp.items = d->items.as<BandItem>();
     bp.wg_ptr = d->wg_ptr.as<int>();
     bp.nwg = d->nwg;

@@ -1,6 +1,6 @@
 // dgemm_dl.h -- short-K GEMM for the Cholesky / triangular-solve updates.
 //
-// The panel updates of potrf_blocked / trsm_left_blocked (mvn.hip) are GEMMs with K = 128:
+// The panel updates of potrf_blocked / trsm_left_lower (mvn.hip) are GEMMs with K = 128:
 // eight K steps of 16.  With register staging (dgemm_mfma.h) every step waits for a global
 // load issued only one step earlier, so a launch costs ~8 memory latencies (20-40 us) for a
 // few microseconds of MFMA work.  This kernel stages global -> LDS with LDS-DMA
@@ -238,6 +238,10 @@ static inline int launch_gemm_dl_cfg(hipStream_t s, GemmP p, const Epi& epi, int
     return MCML_OK;
 }
 
+// The pick (tile 0): tile DL_TILE_BIG from DL_THR 128 x 128 tiles of C up, DL_TILE_SMALL below, the 64 x 64
+// tile 6 below DL_THR64 (not in place)
+constexpr int DL_TILE_BIG = 4, DL_TILE_SMALL = 5, DL_THR = 768, DL_THR64 = 128;
+
 // tile: 0 = pick;  1 = 128 x 128, 4-stage ring (one workgroup per CU);  2 = 64 x 128, 5 stages;
 // 3 = 128 x 32 (the 128 x m diagonal-block products of the blocked TRSM: m / 32 workgroups);
 // 4 = 128 x 128 with a 2-stage ring (64 KB) and 5 = 64 x 128 with 3 stages (72 KB): TWO workgroups per
@@ -253,16 +257,12 @@ static inline int launch_gemm_dl(hipStream_t s, int M, int N, int K, const doubl
 {
     MCML_REQUIRE(dl_applicable(M, N, K, A, lda, B, ldb, BNMAJOR), "dgemm_dl: shape/alignment contract violated "
                  "(M %d N %d K %d lda %d ldb %d)", M, N, K, lda, ldb);
-    GemmP p{M, N, K, A, lda, B, ldb, 0, 0, lower_only ? 1 : 0, 0, diag_shift, bsA, bsB};
+    GemmP p{M, N, K, A, lda, B, ldb, 0, 0, lower_only ? 1 : 0, diag_shift, bsA, bsB};
     if (tile == 0) {
         long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
         if (lower_only) t128 = t128 / 2 + (M + 127) / 128;
-        static const int big = getenv("GLMMR_MCML_DL_BIG") ? atoi(getenv("GLMMR_MCML_DL_BIG")) : 4;
-        static const int small = getenv("GLMMR_MCML_DL_SMALL") ? atoi(getenv("GLMMR_MCML_DL_SMALL")) : 5;
-        static const int thr = getenv("GLMMR_MCML_DL_THR") ? atoi(getenv("GLMMR_MCML_DL_THR")) : 768;
-        static const int thr64 = getenv("GLMMR_MCML_DL_THR64") ? atoi(getenv("GLMMR_MCML_DL_THR64")) : 128;
-        tile = t128 >= thr ? big : small;
-        if (inplace == 0 && t128 < thr64) tile = 6;
+        tile = t128 >= DL_THR ? DL_TILE_BIG : DL_TILE_SMALL;
+        if (inplace == 0 && t128 < DL_THR64) tile = 6;
         if (inplace == 2) tile = N >= 256 ? 3 : 1;
     }
     MCML_REQUIRE(!(inplace == 1 && (tile == 6 || tile == 8) && N > (tile == 6 ? 64 : 32)) &&

@@ -26,8 +26,7 @@
 namespace mcml {
 
 constexpr int DL_BM = 160, DL_BN = 128;
-// (K step, ring stages): (16, 3) keeps two tiles in flight in 108 KB; (32, 2) halves the
-// barriers with one tile in flight in 144 KB
+// (K step, ring stages): the kernel's (16, 3) keeps two tiles in flight in 108 KB
 template <int BK, int STAGES>
 struct DlCfg {
     static constexpr int A_BYTES = BK * DL_BM * 8;         // BK=16: 20 chunks of 1 KiB; 32: 40
@@ -64,135 +63,10 @@ static inline bool dma_offsets_fit(size_t elems_a, size_t elems_b)
     return elems_a * 8 < 0xffffffffull && elems_b * 8 < 0xffffffffull;
 }
 
-template <int BK, int STAGES, class Epi>
-__global__ __launch_bounds__(512) void dgemm_dlds_kernel(GemmP p, Epi epi)
-{
-    using Cfg = DlCfg<BK, STAGES>;
-    constexpr int DL_A_BYTES = Cfg::A_BYTES, DL_STAGE_BYTES = Cfg::STAGE_BYTES, DL_STAGES = STAGES;
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    char* lds = reinterpret_cast<char*>(smem);
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 2, wc = wave & 3;               // 2 x 4 waves, wave tile 80 x 32
-
-    const int nblk = p.gm * p.gn;
-    const int bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-    const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int bi = nid / p.gn, bj = nid - bi * p.gn;
-    const int m0 = bi * DL_BM, n0 = bj * DL_BN;
-
-    // ---- per-lane source pointers of this wave's LDS-DMA pieces (advance by a constant per K step)
-    // A: chunks c = wave, wave + 8, and wave + 16 for waves 0-3 (waves 4-7 repeat their second
-    // chunk: identical bytes to the same place, keeps the vmcnt bookkeeping uniform)
-    const double* pa[Cfg::NA]; int la[Cfg::NA];
-#pragma unroll
-    for (int s = 0; s < Cfg::NA; ++s) {
-        int c = wave + 8 * s;
-        if (c >= Cfg::A_CHUNKS) c = wave + 8;
-        const int o = c * 1024 + lane * 16;               // byte offset inside the A image
-        const int k = o / (DL_BM * 8), pos = (o - k * DL_BM * 8) >> 3;      // position (doubles) in row k
-        const int blk = pos >> 4, within = pos & 15;
-        const int m = (((blk ^ (k & 1)) << 4) | within);   // logical row of C this piece holds
-        int gm = m0 + m;
-        if (gm >= p.M) gm = 0;                             // clamped: feeds rows that are never stored
-        pa[s] = p.A + gm + (size_t)k * p.lda;
-        la[s] = c * 1024;
-    }
-    const double* pb[Cfg::NB]; int lb[Cfg::NB];
-#pragma unroll
-    for (int s = 0; s < Cfg::NB; ++s) {
-        const int c = wave + 8 * s;                        // 16 chunks: kp = c >> 1, half = c & 1
-        const int kp = c >> 1, n = ((c & 1) << 6) + lane;
-        int gn = n0 + n;
-        if (gn >= p.N) gn = 0;
-        pb[s] = p.B + 2 * kp + (size_t)gn * p.ldb;
-        lb[s] = DL_A_BYTES + c * 1024;
-    }
-    const size_t stepA = (size_t)BK * p.lda;
-
-    auto issue = [&](int stage) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        // (the host pass must not see the amdgcn builtin in this template-dependent context: clang
-        // would silently drop the whole kernel stub)
-        char* base = lds + stage * DL_STAGE_BYTES;
-#pragma unroll
-        for (int s = 0; s < Cfg::NA; ++s) {
-            __builtin_amdgcn_global_load_lds(pa[s], (lds_ptr_t)(base + la[s]), 16, 0, 0);
-            pa[s] += stepA;
-        }
-#pragma unroll
-        for (int s = 0; s < Cfg::NB; ++s) {
-            __builtin_amdgcn_global_load_lds(pb[s], (lds_ptr_t)(base + lb[s]), 16, 0, 0);
-            pb[s] += BK;
-        }
-#else
-        (void)stage; (void)stepA;
-#endif
-    };
-
-    d4 acc[5][2];
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-
-    const int l15 = lane & 15, lk = lane >> 4;
-    auto compute = [&](int stage) {
-        const double* as = reinterpret_cast<const double*>(lds + stage * DL_STAGE_BYTES);
-        const double* bs = reinterpret_cast<const double*>(lds + stage * DL_STAGE_BYTES + DL_A_BYTES);
-#pragma unroll
-        for (int ks = 0; ks < BK / 4; ++ks) {
-            const int kk = 4 * ks + lk;
-            double a[5], b[2];
-#pragma unroll
-            for (int i = 0; i < 5; ++i) a[i] = as[kk * DL_BM + (((wr * 5 + i) ^ (kk & 1)) << 4) + l15];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = bs[((kk >> 1) * DL_BN + wc * 32 + 16 * j + l15) * 2 + (kk & 1)];
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a[i], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    const int nk = (p.K + BK - 1) / BK;                    // operands are zero-padded to nk * BK
-    // each wave issues PER_TILE LDS-DMA pieces per tile; "leave t tiles in flight" = vmcnt(PER_TILE t)
-    auto wait_leave = [&](int tiles) {
-        static_assert(Cfg::PER_TILE == 5 || Cfg::PER_TILE == 9, "vmcnt immediates below");
-        if constexpr (Cfg::PER_TILE == 5) {
-            if (tiles >= 2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-            else if (tiles == 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-            if (tiles >= 2) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-            else if (tiles == 1) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    };
-    int issued = 0;
-    for (; issued < DL_STAGES - 1 && issued < nk; ++issued) issue(issued);
-    wait_leave(issued - 1);                                // tile 0 landed
-    __builtin_amdgcn_s_barrier();
-    int st = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        if (issued < nk) {                                 // its stage was last read in step kt-1
-            int sn = st + DL_STAGES - 1; if (sn >= DL_STAGES) sn -= DL_STAGES;
-            issue(sn);
-            ++issued;
-        }
-        compute(st);
-        wait_leave(issued - kt - 2);                       // tile kt+1 landed, later ones stay in flight
-        __builtin_amdgcn_s_barrier();
-        st = st + 1; if (st >= DL_STAGES) st = 0;
-    }
-
-    epi(acc, m0 + wr * 80, n0 + wc * 32, lane, p.M, p.N, bi * 2 + wr);
-}
-
-// ---- the same kernel (K step 16, 3 stages) with hand-scheduled operand reads ------------------
+// ---- the kernel (K step 16, 3 stages), with hand-scheduled operand reads ------------------------
 // As in dgemm_band.h: the compiler's `s_waitcnt lgkmcnt(0)` before every MFMA group also waits for
-// the reads just issued for the next group.  Here the ds_reads go through inline asm, double
+// the reads just issued for the next group (a compiler-scheduled version of this kernel, with
+// (16, 3) and (32, 2) rings, measured slower and was removed).  Here the ds_reads go through inline asm, double
 // buffered in registers with counted lgkmcnt(7) waits (5 A + 2 B reads per K substep), and the
 // end-of-tile vmcnt + barrier sits before the last MFMA group of a tile.
 // The XOR-1 block swizzle of the A image depends on the parity of the k row a lane reads (= lk & 1)
@@ -353,32 +227,16 @@ static inline bool dlds_applicable(int M, int N, int K, const double* A, int lda
            dma_offsets_fit((size_t)lda * 32 + M, (size_t)ldb * N + 32);
 }
 
-template <int BK, int STAGES, class Epi>
-static inline int launch_gemm_dlds_cfg(hipStream_t s, const GemmP& p, const Epi& epi)
-{
-    using Cfg = DlCfg<BK, STAGES>;
-    MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&dgemm_dlds_kernel<BK, STAGES, Epi>), (int)Cfg::LDS_BYTES));
-    hipLaunchKernelGGL((dgemm_dlds_kernel<BK, STAGES, Epi>), dim3(p.gm * p.gn), dim3(512), Cfg::LDS_BYTES, s, p, epi);
-    MCML_HIP(hipGetLastError());
-    return MCML_OK;
-}
-
 template <class Epi>
 static inline int launch_gemm_dlds(hipStream_t s, int M, int N, int K, const double* A, int lda,
                                    const double* B, int ldb, const Epi& epi)
 {
-    GemmP p{M, N, K, A, lda, B, ldb, (M + DL_BM - 1) / DL_BM, (N + DL_BN - 1) / DL_BN, 0, 0};
-    // GLMMR_MCML_DLDS: 0 = hand-scheduled reads (default), 1 = (32, 2) compiler-scheduled, 2 = (16, 3) compiler-scheduled
-    static const int variant = getenv("GLMMR_MCML_DLDS") ? atoi(getenv("GLMMR_MCML_DLDS")) : 0;
-    if (variant == 1) return launch_gemm_dlds_cfg<32, 2, Epi>(s, p, epi);
-    if (variant == 2) return launch_gemm_dlds_cfg<16, 3, Epi>(s, p, epi);
-    {
-        using Cfg = DlCfg<16, 3>;
-        MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&dgemm_dlds_asm_kernel<Epi>), (int)Cfg::LDS_BYTES));
-        hipLaunchKernelGGL((dgemm_dlds_asm_kernel<Epi>), dim3(p.gm * p.gn), dim3(512), Cfg::LDS_BYTES, s, p, epi);
-        MCML_HIP(hipGetLastError());
-        return MCML_OK;
-    }
+    GemmP p{M, N, K, A, lda, B, ldb, (M + DL_BM - 1) / DL_BM, (N + DL_BN - 1) / DL_BN, 0};
+    using Cfg = DlCfg<16, 3>;
+    MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&dgemm_dlds_asm_kernel<Epi>), (int)Cfg::LDS_BYTES));
+    hipLaunchKernelGGL((dgemm_dlds_asm_kernel<Epi>), dim3(p.gm * p.gn), dim3(512), Cfg::LDS_BYTES, s, p, epi);
+    MCML_HIP(hipGetLastError());
+    return MCML_OK;
 }
 
 }  // namespace mcml

@@ -40,7 +40,6 @@ struct GemmP {
     const double* B; int ldb;   // K-major: B[k + j*ldb];  N-major: B[j + k*ldb]
     int gm, gn;                 // tile grid
     int lower_only;             // skip tiles that lie strictly above the diagonal
-    int dbg_nostep;             // timing experiment only: do not advance the operand pointers
     int diag_shift = 0;         // dgemm_dl lower_only: row m of C is row m + diag_shift of the square matrix
     size_t bsA = 0, bsB = 0;    // dgemm_dl batches (blockIdx.y): element strides of A and B from one problem to the next
 };
@@ -159,8 +158,8 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
             pb[j] = p.B + 2 * kp + (size_t)(okn ? n : 0) * p.ldb;
         }
     }
-    const size_t stepA = (p.dbg_nostep & 1) ? 0 : (size_t)BK * p.lda;
-    const size_t stepB = (p.dbg_nostep & 1) ? 0 : (BNMAJOR ? (size_t)BK * p.ldb : (size_t)BK);
+    const size_t stepA = (size_t)BK * p.lda;
+    const size_t stepB = BNMAJOR ? (size_t)BK * p.ldb : (size_t)BK;
     unsigned kva = 0, kvb0 = 0, kvb1 = 0;   // bit i: load i of the tile in flight lies inside K
 
     // full = the whole tile lies inside K (every K step but possibly the last)
@@ -278,14 +277,14 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
     if constexpr (!STAGGER) {
         __syncthreads();
         for (int kt = 0; kt < nk; ++kt) {
-            const bool more = (kt + 1 < nk) && !(p.dbg_nostep & 2);   // bit 1: timing experiment, no staging
+            const bool more = kt + 1 < nk;
             if (more) load_tiles((kt + 1) * BK, (kt + 2) * BK <= p.K);
             __builtin_amdgcn_sched_barrier(0);   // loads are issued, not consumed, above here
             compute(cur);
             __builtin_amdgcn_sched_barrier(0);   // the loads' first use stays below the MFMAs
             if (more) store_tiles(cur ^ 1);
-            if (!(p.dbg_nostep & 4)) __syncthreads();               // bit 2: timing experiment, no barrier
-            if (!(p.dbg_nostep & 2)) cur ^= 1;
+            __syncthreads();
+            cur ^= 1;
         }
     } else {
         // The two waves of a SIMD (w and w + 4: a workgroup's waves are dealt to SIMDs cyclically)
@@ -393,8 +392,7 @@ static inline int launch_gemm(hipStream_t s, int M, int N, int K, const double* 
                               const double* B, int ldb, const Epi& epi, bool lower_only = false,
                               int force_tile = -1)
 {
-    static const int dbg_nostep = getenv("GLMMR_MCML_DBG_NOSTEP") ? atoi(getenv("GLMMR_MCML_DBG_NOSTEP")) : 0;
-    GemmP p{M, N, K, A, lda, B, ldb, 0, 0, lower_only ? 1 : 0, dbg_nostep};
+    GemmP p{M, N, K, A, lda, B, ldb, 0, 0, lower_only ? 1 : 0};
     MCML_TRY(check_gemm_args(p));
     MCML_REQUIRE(BNMAJOR ? ldb >= N : ldb >= K, "dgemm: ldb %d too small", ldb);
     int id = force_tile >= 0 ? force_tile : pick_tile(M, N, K).id;

@@ -10,16 +10,16 @@
 //     over u (HBM-bound: 8 B per element);
 //   * blocks of dim <= 32: one wave builds + factorises the block in LDS and
 //     forward-substitutes 64 sample columns at a time;
-//   * larger blocks: fused covariance build -> recursive blocked Cholesky whose
-//     trailing updates are FP64-MFMA GEMMs (dgemm_mfma.h), 128-wide leaves
-//     factorised and inverted in LDS -> recursive TRSM of all m sample columns
-//     (MFMA GEMMs against the inverted leaves) -> Frobenius norm + log-det.
+//   * larger blocks: fused covariance build -> right-looking blocked Cholesky whose
+//     panel and trailing updates are FP64-MFMA GEMMs (dgemm_dl.h), 128-wide leaves
+//     factorised and inverted in LDS; the m sample columns ride below the matrix
+//     as extra rows, so the same GEMMs forward-substitute them -> Frobenius norm
+//     + log-det.
 // Reductions are two-stage with a fixed order, so the result is run-to-run
 // bit-reproducible.
 #include "ctx.h"
 #include "dgemm_mfma.h"
 #include "dgemm_dl.h"
-#include "dgemm_dlds.h"
 #include "reduce.h"
 
 namespace mcml {
@@ -587,69 +587,19 @@ __global__ void k_zero_upper(double* A, int lda, int n)
 // LDS of k_potrf_leaf: the 128 x 129 block, the inverse's diagonal, 7 scratch tiles
 static constexpr size_t POTRF_LDS = sizeof(double) * (128 * 129 + 128 + 7 * 256 + 64);
 
-// ------------------------------------------------------------------ recursion (host)
-static inline int split128(int n)
-{
-    int h = (n / 2) / CHOL_NB * CHOL_NB;
-    return h < CHOL_NB ? CHOL_NB : h;
-}
-
-static int potrf_rec(Ctx& c, double* A0, int lda, int off, int n);
-static int trsm_right_rec(Ctx& c, const double* A0, int lda, int off, int n, double* X, int ldx, int M);
-
-// X (M x n) <- X * inv(L)^T, L = A0[off:off+n, off:off+n] lower
-static int trsm_right_rec(Ctx& c, const double* A0, int lda, int off, int n, double* X, int ldx, int M)
-{
-    if (n <= CHOL_NB) {
-        const double* Linv = c.linv.d() + (size_t)(off / CHOL_NB) * CHOL_NB * CHOL_NB;
-        EpiAxpby epi{X, ldx, 1.0, 0.0};
-        // in place: a workgroup reads its whole row band (K = n <= 128) before it writes
-        return launch_gemm<true>(c.stream, M, n, n, X, ldx, Linv, CHOL_NB, epi, false, 1);
-    }
-    const int n1 = split128(n), n2 = n - n1;
-    MCML_TRY(trsm_right_rec(c, A0, lda, off, n1, X, ldx, M));
-    const double* L21 = A0 + (off + n1) + (size_t)off * lda;
-    double* X2 = X + (size_t)n1 * ldx;
-    EpiAxpby epi{X2, ldx, -1.0, 1.0};
-    MCML_TRY(launch_gemm<true>(c.stream, M, n2, n1, X, ldx, L21, lda, epi));
-    return trsm_right_rec(c, A0, lda, off + n1, n2, X2, ldx, M);
-}
-
-static int potrf_rec(Ctx& c, double* A0, int lda, int off, int n)
-{
-    double* A = A0 + off + (size_t)off * lda;
-    if (n <= CHOL_NB) {
-        double* Linv = c.linv.d() + (size_t)(off / CHOL_NB) * CHOL_NB * CHOL_NB;
-        hipLaunchKernelGGL(k_potrf_leaf, dim3(1), dim3(LEAF_NT), POTRF_LDS, c.stream,
-                           A, lda, n, Linv, c.scalars.as<int>() + 32, nullptr);
-        MCML_HIP(hipGetLastError());
-        return MCML_OK;
-    }
-    const int n1 = split128(n), n2 = n - n1;
-    MCML_TRY(potrf_rec(c, A0, lda, off, n1));
-    double* A21 = A + n1;
-    MCML_TRY(trsm_right_rec(c, A0, lda, off, n1, A21, lda, n2));
-    double* A22 = A + n1 + (size_t)n1 * lda;
-    EpiAxpby epi{A22, lda, -1.0, 1.0};
-    MCML_TRY(launch_gemm<true>(c.stream, n2, n2, n1, A21, lda, A21, lda, epi, true));
-    return potrf_rec(c, A0, lda, off + n1, n2);
-}
-
-// The K = 128 panel GEMMs of the blocked factorisation / solve: deep-ring direct-to-LDS kernel
+// The K = 128 panel GEMMs of the blocked solve (trsm_left_lower): deep-ring direct-to-LDS kernel
 // (dgemm_dl.h) when its contract holds, the register-staged kernel otherwise.
 //   inplace: 0 none, 1 = C aliases A (N <= 128), 2 = C aliases B (M <= 128)
-//   GLMMR_MCML_CHOL_GEMM=reg : always the register-staged kernel
 template <bool BNMAJOR>
 static int chol_gemm(hipStream_t s, int M, int N, int K, const double* A, int lda, const double* B, int ldb,
                      const EpiAxpby& epi, bool lower_only, int inplace)
 {
-    static const bool use_dl = !(getenv("GLMMR_MCML_CHOL_GEMM") && !strcmp(getenv("GLMMR_MCML_CHOL_GEMM"), "reg"));
-    if (use_dl && dl_applicable(M, N, K, A, lda, B, ldb, BNMAJOR))
+    if (dl_applicable(M, N, K, A, lda, B, ldb, BNMAJOR))
         return launch_gemm_dl<BNMAJOR>(s, M, N, K, A, lda, B, ldb, epi, lower_only, 0, inplace);
     return launch_gemm<BNMAJOR>(s, M, N, K, A, lda, B, ldb, epi, lower_only, inplace ? inplace : -1);
 }
 
-// Right-looking variant: one 128-wide panel at a time -- leaf (factor + invert the diagonal
+// Right-looking blocked Cholesky: one 128-wide panel at a time -- leaf (factor + invert the diagonal
 // block in LDS), panel TRSM as a GEMM against the inverted block, SYRK of the trailing matrix.
 //
 // Look-ahead: the leaf is a single-workgroup, latency-bound kernel (~90 us) and the late
@@ -657,17 +607,6 @@ static int chol_gemm(hipStream_t s, int M, int N, int K, const double* A, int ld
 // time.  The trailing update is therefore split: the next panel's 128 columns are updated
 // first, the next leaf then runs on a high-priority side stream while the main stream updates
 // the rest of the trailing matrix (columns the leaf never touches).
-//   GLMMR_MCML_CHOL=rec    : the recursive variant;  =nola : this one without look-ahead
-static int chol_mode()
-{
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("GLMMR_MCML_CHOL");
-        v = (e && !strcmp(e, "rec")) ? 0 : (e && !strcmp(e, "nola")) ? 2 : 1;
-    }
-    return v;
-}
-static bool chol_blocked() { return chol_mode() != 0; }
 
 static int lookahead_setup(Ctx& c)
 {
@@ -697,17 +636,16 @@ static int lookahead_setup(Ctx& c)
 // it never waits for a CU to drain.  The main stream joins the leaf before step t+1.  Period: two small GEMMs
 // + max(bulk, leaf).  (A freer two-queue schedule measured ~10 % faster live but
 // hung intermittently; it exists as a captured graph only -- see "the hang" above potrf_la2_capture.)
-//   GLMMR_MCML_CHOL=rec : the recursive variant;  =nola : everything on one stream
 // Several matrices of the same shape factorised side by side (the candidate thetas of one theta-step round): every
 // launch of the schedule covers all of them (leaf: one workgroup per matrix; products: blockIdx.y), so the latency
 // chain of the late steps -- leaf, two single-block products, their gaps -- is paid once per round, not once per
 // candidate.  sA / sL: element strides from one matrix / one set of inverted diagonal blocks to the next.
 struct Bat { int n = 1; size_t sA = 0, sL = 0; int* err = nullptr; };   // err: one flag per matrix (null: the context's own)
 
-static int potrf_blocked(Ctx& c, double* A, int lda, int n, int extra, Bat bt = Bat(), bool one_stream = false)
+static int potrf_blocked(Ctx& c, double* A, int lda, int n, int extra, Bat bt = Bat())
 {
     int* errflag = bt.err ? bt.err : c.scalars.as<int>() + 32;
-    const bool two = chol_mode() == 1 && n > 2 * CHOL_NB && !one_stream;
+    const bool two = n > 2 * CHOL_NB;
     hipStream_t sM = c.stream, sL = c.stream;
     if (two) { MCML_TRY(lookahead_setup(c)); sL = c.aux; }
     auto leaf = [&](hipStream_t s, int k, int nb) -> int {
@@ -728,9 +666,8 @@ static int potrf_blocked(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
         return launch_gemm<true>(sM, M, N, K, Ap, lda, Bp, ldb, epi, lower, inplace ? inplace : -1);
     };
     const int nsteps = (n + CHOL_NB - 1) / CHOL_NB;
-    static const int SPW = CHOL_NB * (getenv("GLMMR_MCML_CHOL_SPW") ? atoi(getenv("GLMMR_MCML_CHOL_SPW")) : 8);   // super-panel width (panels)
-    static const bool tl_off = getenv("GLMMR_MCML_CHOL_TWOLEVEL") && !strcmp(getenv("GLMMR_MCML_CHOL_TWOLEVEL"), "0");
-    const bool twolevel = bt.n > 1 && n > SPW + CHOL_NB && !tl_off;
+    constexpr int SPW = CHOL_NB * 8;                              // super-panel width: 8 panels
+    const bool twolevel = bt.n > 1 && n > SPW + CHOL_NB;
     MCML_TRY(leaf(sM, 0, n < CHOL_NB ? n : CHOL_NB));
     bool forked = false;
     for (int t = 0; t < nsteps; ++t) {
@@ -901,28 +838,17 @@ static int potrf_la2_capture(Ctx& c, double* A, int lda, int n, int extra, Bat b
 // iteration and every evaluation is ~200 launches, ~80 event operations and the host calls behind them: the first
 // call with a given key runs eagerly (function attributes, allocations), the second is captured (fork / join of the
 // look-ahead included: the side stream joins the capture through its event waits), later ones are one hipGraphLaunch.
-// GLMMR_MCML_CHOL_GRAPH=0 keeps the eager launches.
-// GLMMR_MCML_CHOL_GRAPH: 0 eager launches; old = the graph of potrf_blocked's own fork-join; default = potrf_la2_capture
-static int chol_graph_kind()
+// The capture records potrf_la2_capture; GLMMR_MCML_CHOL_GRAPH=0 keeps the eager launches of potrf_blocked.
+// Single evaluations only (bt.n == 1): a batch runs potrf_blocked eagerly, see mvn_loglik_batch.
+static bool chol_graph_on()
 {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("GLMMR_MCML_CHOL_GRAPH");
-        v = (e && !strcmp(e, "0")) ? 0 : (e && !strcmp(e, "old")) ? 1 : 2;
-    }
-    return v;
+    static const bool on = !(getenv("GLMMR_MCML_CHOL_GRAPH") && !strcmp(getenv("GLMMR_MCML_CHOL_GRAPH"), "0"));
+    return on;
 }
-static bool chol_graph_on() { return chol_graph_kind() != 0; }
 static int potrf_graphed(Ctx& c, double* A, int lda, int n, int extra, Bat bt = Bat())
 {
-    if (!chol_graph_on() || !(chol_mode() == 1 && n > 2 * CHOL_NB)) return potrf_blocked(c, A, lda, n, extra, bt);
-    // A batch is launched EAGERLY with the two-stream fork-join of potrf_blocked (the leaf of step t+1 beside the bulk of
-    // step t): 13.4 ms per round of 8 at Q = 5000 and 1.95 ms at Q = 2000, against 14.4 / 2.21 ms for the one-chain graph
-    // (GLMMR_MCML_BATCH_GRAPH=1) -- a graph without a parallel branch cannot overlap the two, and one with a branch is
-    // subject to the executable lottery described at CholGraph.  The host keeps ahead easily (~250 launches per round).
-    static const bool batch_graph = getenv("GLMMR_MCML_BATCH_GRAPH") && !strcmp(getenv("GLMMR_MCML_BATCH_GRAPH"), "1");
-    if (bt.n > 1 && !batch_graph) return potrf_blocked(c, A, lda, n, extra, bt);
-    CholGraph& g = c.chol_graphs.find(A, c.linv.d(), lda, n, extra + (bt.n << 24), bt.n == 1);
+    if (!chol_graph_on() || n <= 2 * CHOL_NB) return potrf_blocked(c, A, lda, n, extra, bt);
+    CholGraph& g = c.chol_graphs.find(A, c.linv.d(), lda, n, extra);
     auto timed_begin = [&]() -> bool {
         if (!g.t0 && (hipEventCreate(&g.t0) != hipSuccess || hipEventCreate(&g.t1) != hipSuccess)) { (void)hipGetLastError(); return false; }
         return hipEventRecord(g.t0, c.stream) == hipSuccess;
@@ -936,7 +862,7 @@ static int potrf_graphed(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
             bool done = true;
             const hipError_t ee = hipEventElapsedTime(&ms, g.t0, g.t1);
             static const bool cal_trace = getenv("GLMMR_MCML_GRAPH_TRACE") != nullptr;
-            if (cal_trace) fprintf(stderr, "graph calibration: n=%d extra=%d trial %d: %.3f ms (eager %.3f, best %.3f) rc=%d\n", g.n, g.extra & 0xffffff, g.tries, ms, g.eager_ms, g.best_ms, (int)ee);
+            if (cal_trace) fprintf(stderr, "graph calibration: n=%d extra=%d trial %d: %.3f ms (eager %.3f, best %.3f) rc=%d\n", g.n, g.extra, g.tries, ms, g.eager_ms, g.best_ms, (int)ee);
             if (ee == hipSuccess && g.eager_ms > 0.f && g.tmpl) {
                 // keep the fastest executable seen; try another instantiation unless this one clearly beats the eager
                 // launches or four have been tried
@@ -962,7 +888,7 @@ static int potrf_graphed(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
         ++g.trial_launches;
         return MCML_OK;
     }
-    if (g.seen++ <= (bt.n == 1 ? 1 : 0)) {   // eager first (attributes, allocations); a single evaluation twice: the second run's time is the calibration's yardstick
+    if (g.seen++ <= 1) {   // eager twice first (attributes, allocations): the second run's time is the calibration's yardstick
         const bool tm = timed_begin();
         MCML_TRY(potrf_blocked(c, A, lda, n, extra, bt));
         if (tm && hipEventRecord(g.t1, c.stream) == hipSuccess && hipEventSynchronize(g.t1) == hipSuccess)
@@ -976,14 +902,7 @@ static int potrf_graphed(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
         g.seen = -(1 << 30);
         return potrf_blocked(c, A, lda, n, extra, bt);
     }
-    // A batch is captured as ONE chain (potrf_blocked on a single stream): with k matrices per launch the late steps'
-    // chain is amortised anyway (measured eagerly: 17.1 against 16.0 ms per round of 8 at Q = 5000), and a graph without
-    // a parallel branch does not depend on which hardware queue the runtime gives that branch -- see CholGraph: of
-    // several two-chain executables alive in a process only the first two reliably overlap their chains, and a theta-step
-    // uses a different batch width for its last, partial rounds.  The single evaluation keeps the two-chain graph.
-    const bool linear = bt.n > 1;
-    const int rc = linear ? potrf_blocked(c, A, lda, n, extra, bt, true)
-                          : chol_graph_kind() == 2 ? potrf_la2_capture(c, A, lda, n, extra, bt) : potrf_blocked(c, A, lda, n, extra, bt);
+    const int rc = potrf_la2_capture(c, A, lda, n, extra, bt);
     hipGraph_t graph = nullptr;
     const hipError_t e = hipStreamEndCapture(c.stream, &graph);
     if (rc != MCML_OK || e != hipSuccess || !graph) {
@@ -1000,14 +919,27 @@ static int potrf_graphed(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
         g.exec = nullptr; g.seen = -(1 << 30);
         return potrf_blocked(c, A, lda, n, extra, bt);
     }
-    g.tmpl = graph; g.tries = 0; g.settled = linear || !(g.eager_ms > 0.f); g.timed = false; g.best = nullptr; g.best_ms = 0.f;
+    g.tmpl = graph; g.tries = 0; g.settled = !(g.eager_ms > 0.f); g.timed = false; g.best = nullptr; g.best_ms = 0.f;
     if (g.settled) { (void)hipGraphDestroy(g.tmpl); g.tmpl = nullptr; }
     g.trial_launches = 1;                     // this first launch is not timed (it carries the executable's upload)
     MCML_HIP(hipGraphLaunch(g.exec, c.stream));
     return MCML_OK;
 }
 
-static int trsm_left_blocked(Ctx& c, const double* L, int ldl, int n, double* U, int ldu, int m)
+int potrf_lower(Ctx& c, double* A, int n, int lda)
+{
+    MCML_REQUIRE(n > 0 && lda >= n && (lda & 1) == 0, "potrf: bad shape n=%d lda=%d", n, lda);
+    MCML_TRY(c.linv.ensure(sizeof(double) * (size_t)(n / CHOL_NB + 1) * CHOL_NB * CHOL_NB));
+    // the leaves write the lower triangles of their inverses only (k_potrf_leaf)
+    MCML_HIP(hipMemsetAsync(c.linv.p, 0, sizeof(double) * (size_t)((n + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB, c.stream));
+    MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf), (int)POTRF_LDS));
+    return potrf_blocked(c, A, lda, n, 0);
+}
+
+// U (n x m) <- inv(L) U, L lower n x n; needs the leaf inverses potrf_lower left in c.linv.  Panel by panel: the
+// diagonal block against its inverse, then the rows below -= L21 U_k with K = 128 (a recursive variant with long-K
+// updates measured 3-15 % slower at Q = 5000, m = 1024, and was removed)
+int trsm_left_lower(Ctx& c, const double* L, int ldl, int n, double* U, int ldu, int m)
 {
     for (int k = 0; k < n; k += CHOL_NB) {
         const int nb = (n - k < CHOL_NB) ? n - k : CHOL_NB;
@@ -1024,50 +956,6 @@ static int trsm_left_blocked(Ctx& c, const double* L, int ldl, int n, double* U,
         MCML_TRY(chol_gemm<false>(c.stream, rem, m, nb, L21, ldl, Uk, ldu, epi, false, 0));
     }
     return MCML_OK;
-}
-
-int potrf_lower(Ctx& c, double* A, int n, int lda)
-{
-    MCML_REQUIRE(n > 0 && lda >= n && (lda & 1) == 0, "potrf: bad shape n=%d lda=%d", n, lda);
-    MCML_TRY(c.linv.ensure(sizeof(double) * (size_t)(n / CHOL_NB + 1) * CHOL_NB * CHOL_NB));
-    // the leaves write the lower triangles of their inverses only (k_potrf_leaf)
-    MCML_HIP(hipMemsetAsync(c.linv.p, 0, sizeof(double) * (size_t)((n + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB, c.stream));
-    MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf), (int)POTRF_LDS));
-    if (chol_blocked()) return potrf_blocked(c, A, lda, n, 0);
-    return potrf_rec(c, A, lda, 0, n);
-}
-
-// U (n x m) <- inv(L) U, L = A0[off.., off..]; needs the leaf inverses potrf_lower left in c.linv.
-// Recursive splitting: the update U2 -= L21 U1 is ONE product with K = n/2, n/4, ... (long-K GEMMs
-// at full MFMA efficiency) instead of n/128 products with K = 128.
-static int trsm_left_rec(Ctx& c, const double* A0, int lda, int off, int n, double* U, int ldu, int m)
-{
-    if (n <= CHOL_NB) {
-        const double* Linv = c.linv.d() + (size_t)(off / CHOL_NB) * CHOL_NB * CHOL_NB;
-        EpiAxpby epi{U, ldu, 1.0, 0.0};
-        // in place: a workgroup reads its whole column band (K = n <= 128) before it writes
-        return chol_gemm<false>(c.stream, n, m, n, Linv, CHOL_NB, U, ldu, epi, false, 2);
-    }
-    const int n1 = split128(n), n2 = n - n1;
-    MCML_TRY(trsm_left_rec(c, A0, lda, off, n1, U, ldu, m));
-    const double* L21 = A0 + (off + n1) + (size_t)off * lda;
-    double* U2 = U + n1;
-    EpiAxpby epi{U2, ldu, -1.0, 1.0};
-    static const bool big_dlds = getenv("GLMMR_MCML_TRSM_BIG") && !strcmp(getenv("GLMMR_MCML_TRSM_BIG"), "dlds");
-    if (big_dlds && n1 > CHOL_NB && dlds_applicable(n2, m, n1, L21, lda, n1 + 32, U, ldu))
-        MCML_TRY(launch_gemm_dlds(c.stream, n2, m, n1, L21, lda, U, ldu, epi));
-    else
-        MCML_TRY(chol_gemm<false>(c.stream, n2, m, n1, L21, lda, U, ldu, epi, false, 0));
-    return trsm_left_rec(c, A0, lda, off + n1, n2, U2, ldu, m);
-}
-
-int trsm_left_lower(Ctx& c, const double* L, int ldl, int n, double* U, int ldu, int m)
-{
-    // GLMMR_MCML_TRSM=rec: the recursive variant (long-K updates; measured 3-15 % slower at Q = 5000, m = 1024
-    // than the panel-by-panel one with the two-per-CU K = 128 tiles)
-    static const bool rec = getenv("GLMMR_MCML_TRSM") && !strcmp(getenv("GLMMR_MCML_TRSM"), "rec");
-    if (chol_blocked() && !(rec && m >= 64)) return trsm_left_blocked(c, L, ldl, n, U, ldu, m);
-    return trsm_left_rec(c, L, ldl, 0, n, U, ldu, m);
 }
 
 // ------------------------------------------------------------------ setup
@@ -1169,8 +1057,7 @@ int mvn_loglik_batch(Ctx& c, const double* thetas, int k, const double* Us, int 
     MCML_REQUIRE(k >= 1 && thetas && sums && rcs && m > 0 && Us, "mvn_ll batch: bad arguments");
     const CovSpec& cs = c.cov;
     const int R = cs.npar;
-    static const bool off = getenv("GLMMR_MCML_MVN_BATCH") && !strcmp(getenv("GLMMR_MCML_MVN_BATCH"), "0");
-    const bool batchable = !off && k > 1 && c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0 && chol_blocked();
+    const bool batchable = k > 1 && c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0;
     if (!batchable) {
         int first_rc = MCML_OK;
         for (int j = 0; j < k; ++j) {
@@ -1217,7 +1104,12 @@ int mvn_loglik_batch(Ctx& c, const double* thetas, int k, const double* Us, int 
             MCML_HIP(hipMemsetAsync(c.linv.p, 0, sizeof(double) * sL * kb, c.stream));
             MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf), (int)POTRF_LDS));
             Bat bt; bt.n = kb; bt.sA = sA; bt.sL = sL; bt.err = bflags;
-            MCML_TRY(potrf_graphed(c, c.Dbatch.d(), ld, dp, m, bt));
+            // A batch is launched EAGERLY with the two-stream fork-join of potrf_blocked (the leaf of step t+1 beside the
+            // bulk of step t): 13.4 ms per round of 8 at Q = 5000 and 1.95 ms at Q = 2000, against 14.4 / 2.21 ms for a
+            // one-chain graph (measured, then removed) -- a graph without a parallel branch cannot overlap the two, and one
+            // with a branch is subject to the executable lottery described at CholGraph.  The host keeps ahead easily (~250
+            // launches per round).  A round of one (the last round of k = 8 j + 1) is a single evaluation: it takes the graph.
+            MCML_TRY(kb > 1 ? potrf_blocked(c, c.Dbatch.d(), ld, dp, m, bt) : potrf_graphed(c, c.Dbatch.d(), ld, dp, m, bt));
             const int gx = (m + 255) / 256, gy = d < 64 ? d : 64;
             MCML_TRY(c.partials.ensure(sizeof(double) * (size_t)(gx * gy + 16)));
             for (int j = 0; j < kb; ++j) {
@@ -1279,53 +1171,35 @@ static int mvn_loglik_enqueue(Ctx& c, const double* theta, const double* Us, int
         MCML_HIP(hipGetLastError());
     }
     if (c.maxdim_large > 0) {
-        // blocked path: the m sample columns ride below the matrix as m extra rows (U', one sample per row), so
-        // the forward substitution happens inside the factorisation (potrf_blocked); recursive path: separate TRSM
-        const bool aug = chol_blocked();
-        if (aug) {
-            if (c.Dwork.rows < c.maxdim_large + 16 + m || c.Dwork.cols < c.maxdim_large + 16) {
-                MCML_TRY(c.Dwork.alloc(c.maxdim_large + 16 + m, c.maxdim_large + 16));
-                MCML_HIP(hipMemsetAsync(c.Dwork.d(), 0, sizeof(double) * (size_t)c.Dwork.ld * (c.maxdim_large + 16), c.stream));
-            }
-        } else {
-            MCML_TRY(c.Uwork.alloc(c.maxdim_large, m));
+        // the m sample columns ride below the matrix as m extra rows (U', one sample per row), so the forward
+        // substitution happens inside the factorisation (potrf_blocked)
+        if (c.Dwork.rows < c.maxdim_large + 16 + m || c.Dwork.cols < c.maxdim_large + 16) {
+            MCML_TRY(c.Dwork.alloc(c.maxdim_large + 16 + m, c.maxdim_large + 16));
+            MCML_HIP(hipMemsetAsync(c.Dwork.d(), 0, sizeof(double) * (size_t)c.Dwork.ld * (c.maxdim_large + 16), c.stream));
         }
         for (int b = 0; b < cs.B; ++b) {
             const CovBlock& blk = cs.blocks[b];
             if (blk.all_gr || blk.dim <= SMALL_BLOCK) continue;
             const int d = blk.dim;
-            dim3 g((d + 15) / 16, (d + 15) / 16);
             // a multiple of 16 (identity border): the extra rows and every panel stay 16-byte aligned and the last, ragged
             // panel still has a K the LDS-DMA kernel takes (5000 = 39 x 128 + 8 would fall back to the register-staged one)
-            const int dp = aug ? round_up(d, 16) : d;
-            g = dim3((dp + 63) / 64, (dp + 15) / 16);
-            hipLaunchKernelGGL(k_build_dense, g, dim3(256), 0, c.stream, c.Dwork.d(), c.Dwork.ld, b, dblk, dcov,
-                               cs.rows, c.d_data.d(), th, 0, dp);
+            const int dp = round_up(d, 16);
+            hipLaunchKernelGGL(k_build_dense, dim3((dp + 63) / 64, (dp + 15) / 16), dim3(256), 0, c.stream, c.Dwork.d(),
+                               c.Dwork.ld, b, dblk, dcov, cs.rows, c.d_data.d(), th, 0, dp);
             MCML_HIP(hipGetLastError());
-            const double* Z; int ldz, zr, zc;        // the solved samples: zr x zc, sum of squares wanted
-            if (aug) {
-                hipLaunchKernelGGL(k_transpose_in, dim3((d + 31) / 32, (m + 31) / 32), dim3(256), 0, c.stream,
-                                   Us + blk.matstart, ldu, d, m, c.Dwork.d() + dp, c.Dwork.ld);
-                if (dp > d)        // the border columns of the sample rows must be finite: they meet zeros only
-                    MCML_HIP(hipMemset2DAsync(c.Dwork.d() + dp + (size_t)d * c.Dwork.ld, sizeof(double) * c.Dwork.ld, 0, sizeof(double) * m, dp - d, c.stream));
-                MCML_HIP(hipGetLastError());
-                MCML_TRY(c.linv.ensure(sizeof(double) * (size_t)(dp / CHOL_NB + 1) * CHOL_NB * CHOL_NB));
-                MCML_HIP(hipMemsetAsync(c.linv.p, 0, sizeof(double) * (size_t)((dp + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB, c.stream));
-                MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf), (int)POTRF_LDS));
-                MCML_TRY(potrf_graphed(c, c.Dwork.d(), c.Dwork.ld, dp, m));
-                Z = c.Dwork.d() + dp; ldz = c.Dwork.ld; zr = m; zc = d;
-            } else {
-                MCML_TRY(potrf_lower(c, c.Dwork.d(), d, c.Dwork.ld));
-                int gy = m < 256 ? m : 256;
-                hipLaunchKernelGGL(k_copy_block, dim3((d + 255) / 256, gy), dim3(256), 0, c.stream, c.Uwork.d(),
-                                   c.Uwork.ld, Us + blk.matstart, ldu, d, m);
-                MCML_HIP(hipGetLastError());
-                MCML_TRY(trsm_left_lower(c, c.Dwork.d(), c.Dwork.ld, d, c.Uwork.d(), c.Uwork.ld, m));
-                Z = c.Uwork.d(); ldz = c.Uwork.ld; zr = d; zc = m;
-            }
-            int gx = (zr + 255) / 256, gy = zc < 64 ? zc : 64;
+            hipLaunchKernelGGL(k_transpose_in, dim3((d + 31) / 32, (m + 31) / 32), dim3(256), 0, c.stream,
+                               Us + blk.matstart, ldu, d, m, c.Dwork.d() + dp, c.Dwork.ld);
+            if (dp > d)        // the border columns of the sample rows must be finite: they meet zeros only
+                MCML_HIP(hipMemset2DAsync(c.Dwork.d() + dp + (size_t)d * c.Dwork.ld, sizeof(double) * c.Dwork.ld, 0, sizeof(double) * m, dp - d, c.stream));
+            MCML_HIP(hipGetLastError());
+            MCML_TRY(c.linv.ensure(sizeof(double) * (size_t)(dp / CHOL_NB + 1) * CHOL_NB * CHOL_NB));
+            MCML_HIP(hipMemsetAsync(c.linv.p, 0, sizeof(double) * (size_t)((dp + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB, c.stream));
+            MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf), (int)POTRF_LDS));
+            MCML_TRY(potrf_graphed(c, c.Dwork.d(), c.Dwork.ld, dp, m));
+            // the solved samples: m rows x d columns below the factor
+            const int gx = (m + 255) / 256, gy = d < 64 ? d : 64;
             MCML_TRY(c.partials.ensure(sizeof(double) * (size_t)(gx * gy + 16)));
-            hipLaunchKernelGGL(k_sumsq, dim3(gx, gy), dim3(256), 0, c.stream, Z, ldz, zr, zc, c.partials.d());
+            hipLaunchKernelGGL(k_sumsq, dim3(gx, gy), dim3(256), 0, c.stream, c.Dwork.d() + dp, c.Dwork.ld, m, d, c.partials.d());
             hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, c.partials.d(), gx * gy, 1.0, scal + 2, 0);
             hipLaunchKernelGGL(k_logdet, dim3(1), dim3(256), 0, c.stream, c.Dwork.d(), c.Dwork.ld, d, scal + 1);
             hipLaunchKernelGGL(k_finish_large, dim3(1), dim3(1), 0, c.stream, scal, d, m);

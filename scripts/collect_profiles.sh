@@ -47,7 +47,7 @@ for a in "5000 1024" "5000 128" "2000 256"; do $PY scripts/time_mvn_batch.py $a 
 $PY scripts/ab_sampler_gemm.py 5000 1024 512 256 128 > $O/sampler_products.txt 2>&1
 $PY scripts/ab_sampler_gemm.py 2000 256 >> $O/sampler_products.txt 2>&1
 echo "batch / products done"
-for g in 2 old 0; do for m in 1024 128; do GLMMR_MCML_CHOL_GRAPH=$g $PY scripts/time_mvn.py 5000 $m 12 2>/dev/null | sed "s/^/CHOL_GRAPH=$g  /" >> $O/mvn_graph_ab.txt; done; done
+for g in 2 0; do for m in 1024 128; do GLMMR_MCML_CHOL_GRAPH=$g $PY scripts/time_mvn.py 5000 $m 12 2>/dev/null | sed "s/^/CHOL_GRAPH=$g  /" >> $O/mvn_graph_ab.txt; done; done
 $PY scripts/rocpd_timeline.py $O/kt_mvn/m_results.db 260 > $O/mvn_timeline.txt 2>&1
 echo "few chains / graph A-B / timeline done"
 # keep the merge-back small: drop the raw traces

@@ -176,10 +176,10 @@ def test_streamed_and_mfma_products_agree_at_full_size(monkeypatch, chains):
 
 
 def test_graph_replay_of_the_factorisation_is_bit_identical_to_eager_launches():
-    """mvn_ll at Q = 2000, m = 192, five evaluations per mode: eager launches (GLMMR_MCML_CHOL_GRAPH=0), the graph of
-    the eager fork-join (=old) and the shipped graph captured from the two-chain schedule (default).  The first
-    evaluation is always eager and the second is the capture; every tile receives its updates in panel order from
-    kernels that accumulate k in order, so all fifteen values agree to the last bit."""
+    """mvn_ll at Q = 2000, m = 192, five evaluations per mode: eager launches (GLMMR_MCML_CHOL_GRAPH=0) and the shipped
+    graph captured from the two-chain schedule (default).  The first two evaluations are always eager and the third is
+    the capture; every tile receives its updates in panel order from kernels that accumulate k in order, so all ten
+    values agree to the last bit."""
     import json, os, subprocess, sys
     code = ("import json, numpy as np\n"
             "from glmmrmcml_amd import api, synth\n"
@@ -188,13 +188,13 @@ def test_graph_replay_of_the_factorisation_is_bit_identical_to_eager_launches():
             "ctx.set_u(np.asfortranarray(np.random.default_rng(1).standard_normal((2000, 192))))\n"
             "print(json.dumps([ctx.mvn_ll(d['theta'] * (1 + 0.02 * k)) for k in range(5)]))\n")
     out = {}
-    for mode in ("0", "old", "2"):
+    for mode in ("0", "2"):
         env = dict(os.environ, GLMMR_MCML_CHOL_GRAPH=mode)
         r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600,
                            cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         assert r.returncode == 0, r.stderr[-2000:]
         out[mode] = json.loads(r.stdout.strip().splitlines()[-1])
-    assert out["0"] == out["old"] == out["2"]
+    assert out["0"] == out["2"]
     assert len(set(out["2"])) == 5 and all(np.isfinite(out["2"]))
 
 
