@@ -324,6 +324,17 @@ class Context:
             d[k] = bool(d[k])
         return d
 
+    def sparse_plan(self, chains):
+        """the sparse chain-major operator as hmc_sample / log_prob_grad would run it with `chains` chains, valid after update_L (test hook,
+        include/glmmr_mcml_c.h glmmr_mcml_dbg_sparse_plan)"""
+        out = (C.c_longlong * 12)()
+        _lib.check(_lib.lib().glmmr_mcml_dbg_sparse_plan(self._h, int(chains), out))
+        keys = ("active", "factored", "W", "nnz", "nnz_z", "nnz_l", "nblk", "max_blk", "long_rows", "fused", "qrows", "ncb")
+        d = dict(zip(keys, (int(v) for v in out)))
+        for k in ("active", "factored", "long_rows"):
+            d[k] = bool(d[k])
+        return d
+
     def mcml_optim(self, start, trace=0, mcnr=False, maxfun=0, theta_batch=0):
         start = _f(start).ravel(); R = self.npar()
         b = np.zeros(self.P); t = np.zeros(R); sg = C.c_double()

@@ -2,6 +2,7 @@
 #include "../../include/glmmr_mcml_c.h"
 #include "ctx.h"
 #include <random>
+#include "sparse_plan.h"
 
 using namespace mcml;
 
@@ -200,6 +201,22 @@ extern "C" int glmmr_mcml_dbg_band_plan(glmmr_mcml_ctx* h, int which, int chains
     const int v[10] = {(which ? c.band_bwd : c.band_fwd) ? 1 : 0, bp.nbands, (int)bp.tiles, gn, nwg, nred, nslots,
                        paired, nempty, built};
     for (int i = 0; i < 10; ++i) out10[i] = v[i];
+    return MCML_OK;
+}
+
+// read-only: the form of the sparse (chain-major) ZL operator and the kernels the HMC sampler launches on it for `chains`
+// chains (ncb follows `chains`; nuts.h launches on the width of its active set) -- the decisions are the functions of sparse_plan.h that hmc.hip launches by
+extern "C" int glmmr_mcml_dbg_sparse_plan(glmmr_mcml_ctx* h, int chains, long long* out12)
+{
+    MCML_REQUIRE(h && chains >= 1 && out12, "dbg_sparse_plan: bad argument");
+    const Ctx& c = h->c;
+    const SparseZL& sp = c.sp;
+    for (int i = 0; i < 12; ++i) out12[i] = 0;
+    out12[0] = sp.active ? 1 : 0;
+    out12[10] = cm_qrows(c.Q); out12[11] = cm_chain_blocks(chains);
+    if (!sp.active) return MCML_OK;
+    out12[1] = sp.factored ? 1 : 0; out12[2] = sp.W; out12[3] = sp.nnz; out12[4] = sp.nnz_z; out12[5] = sp.nnz_l;
+    out12[6] = sp.nblk; out12[7] = sp.max_blk; out12[8] = cm_long_rows(c) ? 1 : 0; out12[9] = cm_fuse_width(c);
     return MCML_OK;
 }
 

@@ -540,17 +540,10 @@ static int hmc_forward(Ctx& c, const double* X, int ldx, double var_par, bool st
     return rc;
 }
 
-// GLMMR_MCML_CM_LFUSE=0: the factored operator's k_cm_Lcol and the next step's k_cm_Lrow as separate launches (the A/B switch)
-static bool cm_lfuse(const Ctx& c)
-{
-    const char* e = getenv("GLMMR_MCML_CM_LFUSE");          // read per hmc_sample call: a test compares the two in one process
-    const bool v = !(e && !strcmp(e, "0"));
-    return v && c.sp.factored && c.sp.nblk > 0 && c.sp.max_blk <= 16;
-}
-
-// next_lx (factored sparse operator, inside a trajectory): also leave LX = L * UP for the next step's forward product
+// next_lx (factored sparse operator, inside a trajectory; cm_fuse_width's 8 or 16, else 0): also leave LX = L * UP for the
+// next step's forward product, by k_cm_Lcol_Lrow of that width
 static int hmc_backward(Ctx& c, const double* Xs, double* G, int s, double var_par, int mode, bool chain = false,
-                        bool next_lx = false)
+                        int next_lx = 0)
 {
     HmcState& h = c.hmc;
     ChainArrays ca = chain_arrays(h);
@@ -566,8 +559,8 @@ static int hmc_backward(Ctx& c, const double* Xs, double* G, int s, double var_p
         double* out = f ? h.ZS.d() : G;
         const int m1 = f ? 2 : mode;
         const double post = glm_score_post(var_par, c.flink);
-        if ((f ? c.sp.nnz_z : c.sp.nnz) >= 24L * c.Q) {          // long rows: a workgroup per (random effect, 64 chains)
-            const int ncb = (h.Cw + 63) / 64;
+        if (cm_long_rows(c)) {                                   // long rows: a workgroup per (random effect, 64 chains)
+            const int ncb = cm_chain_blocks(h.Cw);
             hipLaunchKernelGGL(k_cm_backward_long, dim3((c.Q * ncb + 7) / 8 * 8), dim3(256), 0, c.stream, c.Q, h.Cw, h.V.ld,
                                ptr, ci, cv, h.S.d(), Xs, out, h.R.d(), h.UP.d(), ca.e, ca.steps, s, post, m1, ncb);
         } else {
@@ -578,7 +571,7 @@ static int hmc_backward(Ctx& c, const double* Xs, double* G, int s, double var_p
         }
         if (f && next_lx && mode == 1) {
             const dim3 grid((c.sp.nblk + 3) / 4, (h.Cw + 63) / 64);
-            if (c.sp.max_blk <= 8)
+            if (next_lx == 8)
                 hipLaunchKernelGGL((k_cm_Lcol_Lrow<8>), grid, dim3(256), 0, c.stream, c.sp.nblk, h.Cw, h.V.ld, c.sp.blk_ptr.as<int>(),
                                    c.L.d(), c.L.ld, h.ZS.d(), Xs, G, h.R.d(), h.UP.d(), ca.e, ca.steps, s, post, h.LX.d());
             else
@@ -768,7 +761,7 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
         }
     };
     bool pending_commit = false;                // sparse operator: the last decisions are applied by the next k_cm_propose
-    const bool lf = h.cm && cm_lfuse(c);        // factored operator: the backward pass of step s leaves LX for step s + 1
+    const int lf = h.cm ? cm_fuse_width(c) : 0; // factored operator: the backward pass of step s leaves LX for step s + 1
     const double t_setup = since(tc0);
     const auto tc1 = std::chrono::steady_clock::now();
     auto tp_prev = tc1;
@@ -831,7 +824,7 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
         int rc_traj = MCML_OK;
         for (int s = 0; s < maxs && rc_traj == MCML_OK; ++s) {
             rc_traj = hmc_forward(c, h.UP.d(), h.UP.ld, var_par, !h.cm && s == maxs - 1, s > 0, h.cm && s == maxs - 1, lf && s > 0);
-            if (rc_traj == MCML_OK) rc_traj = hmc_backward(c, h.UP.d(), h.GRADP.d(), s, var_par, 1, true, lf && s + 1 < maxs);
+            if (rc_traj == MCML_OK) rc_traj = hmc_backward(c, h.UP.d(), h.GRADP.d(), s, var_par, 1, true, s + 1 < maxs ? lf : 0);
         }
         c.prof.skip = false;
         mark(3, tt0);

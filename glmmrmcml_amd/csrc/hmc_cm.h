@@ -17,10 +17,9 @@
 #include "ctx.h"
 #include "glm.h"
 #include "rng.h"
+#include "sparse_plan.h"      // CM_ROWS, cm_qrows and the launch decisions hmc.hip shares with the test hook
 
 namespace mcml {
-
-constexpr int CM_ROWS = 64;       // rows per workgroup in the elementwise / partial-sum kernels (16 per wave)
 
 struct CmChain {                  // the per-chain scalars of hmc.hip::ChainArrays
     double *e, *ebar, *H, *lpcur, *K0;
@@ -413,10 +412,6 @@ __device__ __forceinline__ double cm_sum_chunks(const double* part, int nchunk, 
     __syncthreads();
     return ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
 }
-
-// rows of the random-effect-sized arrays per workgroup of the per-chain kernels: small chunks when Q is small, so
-// that config 4's 320 effects still spread over the chip
-__host__ __device__ inline int cm_qrows(int Q) { return Q <= 4096 ? 16 : CM_ROWS; }
 
 __global__ __launch_bounds__(256) void k_cm_init(double* V, int ldc, int Q, int C, CmChain ca, uint64_t seed,
                                                  uint32_t chain_offset, uint32_t iter_idx, const double* inj_init)

@@ -231,6 +231,15 @@ int glmmr_mcml_ctx_last_kernels(glmmr_mcml_ctx* ctx, int* fwd, int* bwd);
  * 1 paired / 0 streamed, bands with no nonzero K tile, 1 if a product has built this plan].  The plan a product has
  * built is reported as it is; otherwise the same decomposition is computed on the host (nothing is cached). */
 int glmmr_mcml_dbg_band_plan(glmmr_mcml_ctx* ctx, int which, int chains, int* out10);
+/* The sparse chain-major operator (csrc/hmc_cm.h) as the HMC sampler (hmc_sample, dbg_log_prob_grad) runs it with `chains`
+ * chains -- the No-U-Turn sampler launches on the width of its active set, which can be smaller --, read-only, valid after
+ * update_L: out12 = [sparse operator active, factored form ZL = Z * L, ELL width of ZL, nnz(ZL), nnz(Z), nnz(L),
+ * contiguous covariance blocks (0: not contiguous), largest block, 1 if the backward product takes the long-row kernel
+ * (nnz >= 24 Q of the operand it gathers through: Z' when factored, ZL' otherwise), width of the fused k_cm_Lcol_Lrow
+ * (8, 16, or 0: separate kernels; honours GLMMR_MCML_CM_LFUSE as the next hmc_sample call would), rows per chunk of the
+ * per-chain sums over the random effects, chain blocks of 64].  Entries 1-9 are 0 when the operator is not active.  The
+ * decisions are taken by the functions the launch code calls (csrc/sparse_plan.h). */
+int glmmr_mcml_dbg_sparse_plan(glmmr_mcml_ctx* ctx, int chains, long long* out12);
 /* Host wall-clock time per phase of the MCML iterations run by this process since the last reset (csrc/trace.h):
  * out8 (nullable) = [sample, beta-step, theta-step, refresh] ms, then the four phase counts.  enable / reset as above. */
 int glmmr_mcml_dbg_phase_ms(int enable, int reset, double* out8);

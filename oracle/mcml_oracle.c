@@ -773,6 +773,18 @@ int orc_hmc_chain(int n, int Q, const double *xb, const double *ZL, const double
                   double *samples, uint8_t *accept_flags, double *probs,
                   orc_hmc_diag *diag)
 {
+    return orc_hmc_chain_u(n, Q, xb, ZL, y, var_par, flink, o, seed, chain_id, iter_idx, inj_init, inj_mom,
+                           samples, accept_flags, probs, NULL, diag);
+}
+
+/* the same chain; unif (nullable): the uniform draw every proposal's acceptance probability was compared with */
+int orc_hmc_chain_u(int n, int Q, const double *xb, const double *ZL, const double *y,
+                    double var_par, int flink, const orc_hmc_opts *o,
+                    uint64_t seed, uint32_t chain_id, uint32_t iter_idx,
+                    const double *inj_init, const double *inj_mom,
+                    double *samples, uint8_t *accept_flags, double *probs, double *unif,
+                    orc_hmc_diag *diag)
+{
     double *u = (double *)malloc(sizeof(double) * (size_t)Q);
     double *up = (double *)malloc(sizeof(double) * (size_t)Q);
     double *r = (double *)malloc(sizeof(double) * (size_t)Q);
@@ -820,6 +832,7 @@ int orc_hmc_chain(int n, int Q, const double *xb, const double *ZL, const double
         if (acc) { memcpy(u, up, sizeof(double) * (size_t)Q); accept_count++; }
         if (accept_flags) accept_flags[it] = (uint8_t)acc;
         if (probs) probs[it] = prob;
+        if (unif) unif[it] = runif;
         if (adapt) {
             double f1 = 1.0 / (iter + 10);
             H = (1 - f1) * H + f1 * (o->target_accept - prob);

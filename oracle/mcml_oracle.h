@@ -96,6 +96,13 @@ int orc_hmc_chain(int n, int Q, const double *xb, const double *ZL, const double
                   uint8_t *accept_flags /* warmup+nsamp or NULL */,
                   double *probs /* warmup+nsamp or NULL */,
                   orc_hmc_diag *diag);
+/* the same chain; unif (warmup+nsamp or NULL): the uniform draw of every proposal's accept decision */
+int orc_hmc_chain_u(int n, int Q, const double *xb, const double *ZL, const double *y,
+                    double var_par, int flink, const orc_hmc_opts *o,
+                    uint64_t seed, uint32_t chain_id, uint32_t iter_idx,
+                    const double *inj_init, const double *inj_mom,
+                    double *samples, uint8_t *accept_flags, double *probs, double *unif,
+                    orc_hmc_diag *diag);
 
 /* ---- MCNR step (mcmloptim.h:198-236) ---- */
 int orc_mcnr(int n, int Q, int P, int m, const double *X, const double *Z, const double *y,

@@ -86,6 +86,9 @@ def lib():
         L.orc_hmc_chain.argtypes = [C.c_int, C.c_int, c_dp, c_dp, c_dp, C.c_double, C.c_int,
                                     C.POINTER(HmcOpts), C.c_uint64, C.c_uint32, C.c_uint32,
                                     c_dp, c_dp, c_dp, c_u8p, c_dp, C.POINTER(HmcDiag)]
+        L.orc_hmc_chain_u.argtypes = [C.c_int, C.c_int, c_dp, c_dp, c_dp, C.c_double, C.c_int,
+                                      C.POINTER(HmcOpts), C.c_uint64, C.c_uint32, C.c_uint32,
+                                      c_dp, c_dp, c_dp, c_u8p, c_dp, c_dp, C.POINTER(HmcDiag)]
         L.orc_mcnr.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, C.c_int,
                                c_dp, C.c_double, C.c_int, C.c_int, C.c_int,
                                c_dp, c_dp, c_dp, c_dp, c_dp]
@@ -220,7 +223,8 @@ def model_loglik(Z, xb, y, u, var_par, fl, ncols=None):
 def hmc_chain(xb, ZL, y, var_par, fl, warmup, nsamp, lambda_, max_steps, target_accept,
               seed, chain_id=0, iter_idx=0, adapt=100, inj_init=None, inj_mom=None):
     """one chain of mcmcRunHMC::sample (mhmcmc.h:121-157); returns whitened
-    samples Q x (nsamp+1), accept flags, probs, diag"""
+    samples Q x (nsamp+1), accept flags, probs, diag (diag["unif"]: the uniform draw every proposal's acceptance
+    probability was compared with)"""
     xb = _f(xb); ZL = _f(ZL); y = _f(y)
     n, Q = ZL.shape
     o = HmcOpts(warmup, nsamp, adapt, lambda_, max_steps, target_accept)
@@ -230,12 +234,13 @@ def hmc_chain(xb, ZL, y, var_par, fl, warmup, nsamp, lambda_, max_steps, target_
     diag = HmcDiag()
     ii = None if inj_init is None else _f(inj_init)
     im = None if inj_mom is None else _f(inj_mom)
-    rc = lib().orc_hmc_chain(n, Q, _d(xb), _d(ZL), _d(y), float(var_par), int(fl), C.byref(o),
-                             int(seed), int(chain_id), int(iter_idx), _d(ii), _d(im),
-                             _d(samples), flags.ctypes.data_as(c_u8p), _d(probs), C.byref(diag))
+    unif = np.zeros(warmup + nsamp)
+    rc = lib().orc_hmc_chain_u(n, Q, _d(xb), _d(ZL), _d(y), float(var_par), int(fl), C.byref(o),
+                               int(seed), int(chain_id), int(iter_idx), _d(ii), _d(im),
+                               _d(samples), flags.ctypes.data_as(c_u8p), _d(probs), _d(unif), C.byref(diag))
     if rc:
         raise RuntimeError("orc_hmc_chain rc=%d" % rc)
-    return samples, flags, probs, dict(accept=diag.accept, e=diag.e, ebar=diag.ebar, steps=diag.steps)
+    return samples, flags, probs, dict(accept=diag.accept, e=diag.e, ebar=diag.ebar, steps=diag.steps, unif=unif)
 
 
 def mcnr(X, Z, y, u, beta, var_par, family, link, ncols=None):

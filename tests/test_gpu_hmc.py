@@ -159,7 +159,9 @@ def test_sparse_and_dense_zl_operators_agree(monkeypatch):
                 diag, flags, probs = ctx.hmc_sample(d["beta"], 1.0, 15, 40, 0.4, 8, 0.9, seed=77, chains=20,
                                                     want_trace=True)
                 kinds = set(ctx.last_kernels())
-                assert kinds == {"sparse"} if mode != "dense" else kinds <= {"band", "dlds", "reg"}, (mode, kinds)
+                assert (kinds == {"sparse"}) if mode != "dense" else (kinds <= {"band", "dlds", "reg"}), (mode, kinds)
+                plan = ctx.sparse_plan(20)
+                assert plan["active"] == (mode != "dense") and plan["factored"] == (mode == "factored"), (mode, plan)
                 V = np.random.default_rng(5).normal(size=(d["Q"], 3)) * 0.5
                 lp, G = ctx.log_prob_grad(d["beta"], 1.0, V)
                 out[mode] = (ctx.get_u(), flags.copy(), probs.copy(), lp, G)
