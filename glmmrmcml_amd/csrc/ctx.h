@@ -225,7 +225,9 @@ struct Ctx {
     DevMat Dwork;               // maxdim x maxdim
     DevBuf linv;                // (maxdim/128 + 1) x 128 x 128
     DevBuf partials;            // reduction partials
-    DevBuf scalars;             // small device scalars: [0..15] results, [16] error flag (int)
+    DevBuf scalars;             // 64 small device scalars (doubles): [0..3] mvn_ll, [4] model log-likelihood, [8..15] sampler
+                                // diagnostics, [16] the "not positive definite" flag (int), [17..] sampler step counts (ints)
+    int* errflag() const { return reinterpret_cast<int*>(scalars.d() + 16); }
     int maxdim_large = 0;       // largest block that takes the blocked (dense) path
     int n_small = 0, n_diag_rows = 0;
     DevBuf small_ids;                           // ids of the small dense blocks (mvn_setup), for k_small_ll
@@ -262,7 +264,7 @@ struct Ctx {
     // side stream + events for the Cholesky look-ahead (mvn.hip potrf_blocked)
     hipStream_t aux = nullptr;      // high priority: the leaf of the eager fork-join
     hipStream_t aux_lo = nullptr;   // lowest priority: the bulk chain of the captured schedule
-    hipEvent_t ev_col = nullptr, ev_leaf = nullptr, ev_ps = nullptr, ev_b = nullptr;
+    hipEvent_t ev_col = nullptr, ev_leaf = nullptr;
     CholGraphCache chol_graphs;
     std::vector<hipEvent_t> ev_ring;                 // one event per dependency edge of the captured schedule (mvn.hip)
     DevMat Dbatch;                                   // mvn_loglik_batch: the candidates' matrices side by side
@@ -272,8 +274,6 @@ struct Ctx {
         comm_release_hook();
         if (ev_col) (void)hipEventDestroy(ev_col);
         if (ev_leaf) (void)hipEventDestroy(ev_leaf);
-        if (ev_ps) (void)hipEventDestroy(ev_ps);
-        if (ev_b) (void)hipEventDestroy(ev_b);
         if (aux) (void)hipStreamDestroy(aux);
         if (aux_lo) (void)hipStreamDestroy(aux_lo);
     }

@@ -27,25 +27,32 @@ namespace mcml {
 #define LOG_2PI 1.8378770664093454835606594728112   /* log(2*M_PI), mcmldmatrix.h:63,75 */
 
 // ------------------------------------------------------------------ reductions
-// out[0] = (accumulate ? out[0] : 0) + scale * sum(partials[0..n))
-__global__ __launch_bounds__(256) void k_sum_partials(const double* partials, int n, double scale,
-                                                      double* out, int accumulate)
+// out[0] = (accumulate ? out[0] : 0) + sum(partials[0..n))
+__global__ __launch_bounds__(256) void k_sum_partials(const double* partials, int n, double* out, int accumulate)
 {
     __shared__ double sh[4];
     double v = 0;
     for (int i = threadIdx.x; i < n; i += 256) v += partials[i];
     double r = block_sum(v, sh);
-    if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.0) + scale * r;
+    if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.0) + r;
 }
 
 int device_sum(Ctx& c, const double* partials, int n, double* dev_out)
 {
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, partials, n, 1.0, dev_out, 0);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, partials, n, dev_out, 0);
     MCML_HIP(hipGetLastError());
     return MCML_OK;
 }
 
 // ------------------------------------------------------------------ diagonal blocks
+// the variance of a row of an all-gr block: prod_k theta^2 (mcmldmatrix.h:61-65)
+__device__ __forceinline__ double diag_variance(const CovBlock& blk, const int32_t* cov, int rows, const ThetaArg& th)
+{
+    double val = 1.0;
+    for (int r = blk.r0; r < blk.r1; ++r) val = cov_term(1, 0.0, &th.v[cov[r + 4 * rows]], val);
+    return val;
+}
+
 // dd[k] = prod_k theta^2 ("dmat(k,k)*dmat(k,k)"), dc[k] = -0.5 log(dd) - 0.5 log(2 pi)
 __global__ void k_diag_prep(int Q, const int* rowblock, const CovBlock* blocks, const int32_t* cov,
                             int rows, ThetaArg th, double* dd, double* dc)
@@ -54,10 +61,7 @@ __global__ void k_diag_prep(int Q, const int* rowblock, const CovBlock* blocks, 
     if (k >= Q) return;
     int b = rowblock[k];
     if (b < 0) { dd[k] = 1.0; dc[k] = 0.0; return; }
-    CovBlock blk = blocks[b];
-    double val = 1.0;
-    for (int r = blk.r0; r < blk.r1; ++r) val = cov_term(1, 0.0, &th.v[cov[r + 4 * rows]], val);
-    double d = sqrt(val);           // the Cholesky factor of a diagonal block
+    double d = sqrt(diag_variance(blocks[b], cov, rows, th));   // the Cholesky factor of a diagonal block
     dd[k] = d * d;
     dc[k] = -0.5 * log(d * d) - 0.5 * LOG_2PI;
 }
@@ -156,31 +160,8 @@ __global__ __launch_bounds__(64) void k_small_ll(const double* U, int ldu, int m
 // (dpad > dim: rows / columns dim .. dpad are an identity border, so that an odd block can be factorised as an
 // even one -- every panel pointer stays 16-byte aligned; the border does not change L, the log-determinant or
 // the solves)
-// the candidate thetas of one round (mvn_loglik_batch): blockIdx.z picks the candidate and its matrix
-constexpr int MVN_MAXBATCH = 8;
-struct ThetaBatch { ThetaArg t[MVN_MAXBATCH]; };
-
-template <class TH>
 __device__ __forceinline__ void build_dense_body(double* A, int lda, int bidx, const CovBlock* blocks, const int32_t* cov,
-                                                 int rows, const double* data, const TH& th, int mirror, int dpad);
-
-__global__ __launch_bounds__(256) void k_build_dense_batch(double* A, int lda, size_t bsA, int bidx, const CovBlock* blocks,
-                                                           const int32_t* cov, int rows, const double* data,
-                                                           ThetaBatch tb, int dpad)
-{
-    build_dense_body(A + (size_t)blockIdx.z * bsA, lda, bidx, blocks, cov, rows, data, tb.t[blockIdx.z], 0, dpad);
-}
-
-__global__ __launch_bounds__(256) void k_build_dense(double* A, int lda, int bidx, const CovBlock* blocks,
-                                                     const int32_t* cov, int rows, const double* data,
-                                                     ThetaArg th, int mirror, int dpad)
-{
-    build_dense_body(A, lda, bidx, blocks, cov, rows, data, th, mirror, dpad);
-}
-
-template <class TH>
-__device__ __forceinline__ void build_dense_body(double* A, int lda, int bidx, const CovBlock* blocks, const int32_t* cov,
-                                                 int rows, const double* data, const TH& th, int mirror, int dpad)
+                                                 int rows, const double* data, const ThetaArg& th, int mirror, int dpad)
 {
     // a workgroup = 64 rows x 16 columns, a wave = the 64 rows of four columns: every store is 512 contiguous bytes
     // (16 x 16 tiles with 128-byte row groups ran 71 us for the 5000 x 5000 lower triangle)
@@ -196,6 +177,24 @@ __device__ __forceinline__ void build_dense_body(double* A, int lda, int bidx, c
         A[i + (size_t)j * lda] = v;
         if (mirror && i != j) A[j + (size_t)i * lda] = v;
     }
+}
+
+// the candidate thetas of one round (mvn_loglik_batch): blockIdx.z picks the candidate and its matrix
+constexpr int MVN_MAXBATCH = 8;
+struct ThetaBatch { ThetaArg t[MVN_MAXBATCH]; };
+
+__global__ __launch_bounds__(256) void k_build_dense_batch(double* A, int lda, size_t bsA, int bidx, const CovBlock* blocks,
+                                                           const int32_t* cov, int rows, const double* data,
+                                                           ThetaBatch tb, int dpad)
+{
+    build_dense_body(A + (size_t)blockIdx.z * bsA, lda, bidx, blocks, cov, rows, data, tb.t[blockIdx.z], 0, dpad);
+}
+
+__global__ __launch_bounds__(256) void k_build_dense(double* A, int lda, int bidx, const CovBlock* blocks,
+                                                     const int32_t* cov, int rows, const double* data,
+                                                     ThetaArg th, int mirror, int dpad)
+{
+    build_dense_body(A, lda, bidx, blocks, cov, rows, data, th, mirror, dpad);
 }
 
 // broadcast lane `src` (compile-time constant) of a double: two v_readlane_b32, no LDS round trip
@@ -272,22 +271,42 @@ __device__ __forceinline__ void potrf16_col(double (&a)[16], int ln, int& bad, d
 //   P3  wave 0: the three trailing tiles the next step's P1 reads (next diagonal tile + its 32 ride-along
 //       rows), then straight into P1 of step kt+1 with no workgroup barrier in between.
 constexpr int LEAF_NT = 512, LEAF_NW = LEAF_NT / 64;
+// LDS layout of the leaf, offsets in doubles: the 128 * 129 block first, then
+constexpr int LEAF_LS = CHOL_NB + 1;                 // row stride of the block
+constexpr int LEAF_XD = CHOL_NB * LEAF_LS;           // 128 reciprocal pivots = the diagonal of the inverse
+constexpr int LEAF_TT = LEAF_XD + CHOL_NB;           // 7 scratch tiles of 16 x 16 (one per wave 1..7)
+constexpr int LEAF_DUMMY = LEAF_TT + (LEAF_NW - 1) * 256;   // 64 doubles nobody reads (address-select stores)
+constexpr size_t POTRF_LDS = sizeof(double) * (LEAF_DUMMY + 64);
+// phase clocks (shader clock) of the profiling instance, see potrf_leaf_profile; the production instance has none
+template <bool PROF> struct LeafProf {};
+template <> struct LeafProf<true> {
+    unsigned long long* out = nullptr;               // ten slots, read by scripts/leaf_profile.py
+    unsigned long long ta = 0, tb = 0, tc = 0, q0 = 0, q1 = 0, q2 = 0, q3 = 0, t = 0, u = 0;
+    // the clock is a scalar read with no data dependence on the phase it closes: keep the compiler from moving it
+    __device__ static unsigned long long now() {
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned long long t = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+        return t;
+    }
+    __device__ void stamp(int i) const { if (threadIdx.x == 0) out[i] = now(); }
+};
 // workgroup barrier for LDS traffic only.  __syncthreads() also waits for vmcnt(0): with Linv stored to global
 // memory as the leaf goes, every barrier would wait for those stores to be acknowledged (~1-2 us each).
 __device__ __forceinline__ void leaf_sync()
 {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
+template <bool PROF>
 __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int n, double* Linv, int* errflag,
-                                                    unsigned long long* prof, size_t bsA = 0, size_t bsL = 0)
+                                                    size_t bsA, size_t bsL, LeafProf<PROF> prof)
 {
 #pragma clang fp contract(fast)      // the factorisation is not part of the bit-exact RNG / leapfrog contract
     // blockIdx.x: one of several matrices factorised side by side (mvn_loglik_batch), each with its own flag
     A += (size_t)blockIdx.x * bsA; Linv += (size_t)blockIdx.x * bsL; errflag += blockIdx.x;
-#define LEAF_T(i) do { if (prof && threadIdx.x == 0) prof[i] = __builtin_amdgcn_s_memtime(); } while (0)
-    LEAF_T(0);
+    if constexpr (PROF) prof.stamp(0);
     extern __shared__ __attribute__((aligned(16))) double S[];
-    constexpr int LS = 129;
+    constexpr int LS = LEAF_LS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, lk = lane >> 4;
     {   // load the lower triangle: thread = (row, column parity); 16 loads in flight per thread
@@ -305,12 +324,10 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
         }
     }
     __syncthreads();
-    LEAF_T(1);
-    unsigned long long ta = 0, tb = 0, tc = 0, t_, q0 = 0, q1 = 0, q2 = 0, q3 = 0, u_;
     const int ntile = (n + 15) >> 4;
-    double* xd = S + 128 * LS;            // 128 doubles: reciprocal pivots = diagonal of the inverse
-    double* Tt = xd + 128;                // 7 scratch tiles of 16 x 16 (one per wave 1..7)
-    double* dummy = Tt + 7 * 256;         // 64 doubles nobody reads (address-select stores)
+    double* xd = S + LEAF_XD;
+    double* Tt = S + LEAF_TT;
+    double* dummy = S + LEAF_DUMMY;
 
     // block row I of the inverse (waves 1..7: wave w owns column tile J = w - 1)
     auto inverse_row = [&](int I) {
@@ -381,14 +398,14 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
 
     for (int kt = 0; kt < ntile; ++kt) {
         const int kb = kt * 16;
-        t_ = __builtin_amdgcn_s_memtime();
+        if constexpr (PROF) prof.t = prof.u = prof.now();
         if (wave == 0) {
             // P1: lane < 16 tile row kb + lane; 16..31 identity row lane - 16; 32..63 panel row kb + 16 + (lane - 32)
             const int prow = kb + 16 + (lane - 32);
             const bool pvalid = lane >= 32 && prow < ntile * 16;
             int bad = 0; double yv = 1.0;
             double a[16];
-            u_ = __builtin_amdgcn_s_memtime();
+            if constexpr (PROF) prof.u = prof.now();
             // branch-free: one load per column from a clamped, always valid row; selects supply the identity
             // (padding rows of the tile, lanes 16-31) and zeros (padding rows of the panel)
             const int lrow = lane < 32 ? kb + l15 : (pvalid ? prow : 0);
@@ -401,7 +418,7 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
                 a[c] = use ? v : ((lane < 32 && l15 == c) ? 1.0 : 0.0);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            q0 += __builtin_amdgcn_s_memtime() - u_; u_ = __builtin_amdgcn_s_memtime();
+            if constexpr (PROF) { prof.q0 += prof.now() - prof.u; prof.u = prof.now(); }
             potrf16_col<0>(a, lane, bad, yv);  potrf16_col<1>(a, lane, bad, yv);
             potrf16_col<2>(a, lane, bad, yv);  potrf16_col<3>(a, lane, bad, yv);
             potrf16_col<4>(a, lane, bad, yv);  potrf16_col<5>(a, lane, bad, yv);
@@ -410,7 +427,7 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
             potrf16_col<10>(a, lane, bad, yv); potrf16_col<11>(a, lane, bad, yv);
             potrf16_col<12>(a, lane, bad, yv); potrf16_col<13>(a, lane, bad, yv);
             potrf16_col<14>(a, lane, bad, yv); potrf16_col<15>(a, lane, bad, yv);
-            q1 += __builtin_amdgcn_s_memtime() - u_; u_ = __builtin_amdgcn_s_memtime();
+            if constexpr (PROF) { prof.q1 += prof.now() - prof.u; prof.u = prof.now(); }
             // lanes 0-15 write row kb + l15 up to the diagonal (L), lanes 16-31 the SAME row above it (x[c] =
             // X_II[c][jj], c > jj: kept in the tile's upper part for the MFMA phases), lanes 32-63 their panel row.
             // Full leaves (n = 128) store through ADDRESS selects (a lane with nothing to store hits a dummy slot):
@@ -446,14 +463,16 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
                 }
             }
             if (bad && lane == 0) atomicExch(errflag, 1);
-            q2 += __builtin_amdgcn_s_memtime() - u_; u_ = __builtin_amdgcn_s_memtime();
+            if constexpr (PROF) { prof.q2 += prof.now() - prof.u; prof.u = prof.now(); }
         } else if (kt >= 1) {
             rest_update(kt - 1);
             inverse_row(kt - 1);
         }
         leaf_sync();
-        q3 += __builtin_amdgcn_s_memtime() - u_;
-        ta += __builtin_amdgcn_s_memtime() - t_; t_ = __builtin_amdgcn_s_memtime();
+        if constexpr (PROF) {
+            prof.q3 += prof.now() - prof.u;      // wave 0's wait at the barrier
+            prof.ta += prof.now() - prof.t; prof.t = prof.now();
+        }
         // P2: panel rows beyond the 32 that rode along: x = a inv(L11)' = a X_II' on the matrix cores
         for (int t = kt + 3 + wave; t < ntile; t += LEAF_NW) {
             const int r0 = t * 16;
@@ -472,7 +491,7 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
             for (int r = 0; r < 4; ++r) S[(r0 + lk + 4 * r) * LS + kb + l15] = acc[r];
         }
         leaf_sync();
-        tb += __builtin_amdgcn_s_memtime() - t_; t_ = __builtin_amdgcn_s_memtime();
+        if constexpr (PROF) { prof.tb += prof.now() - prof.t; prof.t = prof.now(); }
         // P3: wave 0 updates what its next P1 reads and goes on without a barrier; the other waves pick up the
         // rest of this step's trailing update at the top of the next iteration
         if (wave == 0) {
@@ -481,44 +500,24 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
             // wave's accesses in order; this keeps the compiler from moving them
             asm volatile("" ::: "memory");
         }
-        tc += __builtin_amdgcn_s_memtime() - t_;
+        if constexpr (PROF) prof.tc += prof.now() - prof.t;
     }
     leaf_sync();
-    if (prof && threadIdx.x == 0) { prof[2] = ta; prof[3] = tb; prof[4] = tc; }
-    LEAF_T(5);
+    if constexpr (PROF) prof.stamp(5);
     {   // write L
         const int i = tid & 127, j0 = tid >> 7;
         if (i < n)
             for (int j = j0; j <= i && j < n; j += LEAF_NT / 128) A[i + (size_t)j * lda] = S[i * LS + j];
     }
-    LEAF_T(6);
     // the last block row of the inverse (the earlier ones were done under the later steps' P1)
     if (wave >= 1) inverse_row(ntile - 1);
-    LEAF_T(9);
-    if (prof && threadIdx.x == 0) { prof[6] = q0; prof[7] = q1; prof[8] = q2; prof[1] = q3; }
-#undef LEAF_T
-}
-
-// debug: phase timestamps (shader clock) of one 128 x 128 leaf on a random SPD block
-int potrf_leaf_profile(Ctx& c, unsigned long long* host10)
-{
-    DevMat A; DevBuf prof;
-    MCML_TRY(A.alloc(128, 128));
-    MCML_TRY(prof.ensure(80));
-    MCML_TRY(c.linv.ensure(sizeof(double) * 2 * CHOL_NB * CHOL_NB));
-    std::vector<double> h((size_t)A.ld * 128, 0.0);
-    for (int j = 0; j < 128; ++j) for (int i = 0; i < 128; ++i) h[i + (size_t)j * A.ld] = (i == j ? 130.0 : 1.0 / (1 + abs(i - j)));
-    MCML_TRY(copy_h2d(A.d(), h.data(), sizeof(double) * h.size(), 0)); MCML_HIP(hipDeviceSynchronize());
-    MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf), (int)(sizeof(double) * (128 * 129 + 128 + 7 * 256 + 64))));
-    MCML_HIP(hipMemset(c.linv.p, 0, sizeof(double) * 2 * CHOL_NB * CHOL_NB));
-    for (int rep = 0; rep < 3; ++rep) {
-        MCML_TRY(copy_h2d(A.d(), h.data(), sizeof(double) * h.size(), 0)); MCML_HIP(hipDeviceSynchronize());
-        hipLaunchKernelGGL(k_potrf_leaf, dim3(1), dim3(LEAF_NT), sizeof(double) * (128 * 129 + 128 + 7 * 256 + 64), c.stream, A.d(), A.ld,
-                           128, c.linv.d(), c.scalars.as<int>() + 32, prof.as<unsigned long long>());
-        MCML_HIP(hipStreamSynchronize(c.stream));
+    if constexpr (PROF) {
+        prof.stamp(9);
+        if (threadIdx.x == 0) {
+            prof.out[1] = prof.q3; prof.out[2] = prof.ta; prof.out[3] = prof.tb; prof.out[4] = prof.tc;
+            prof.out[6] = prof.q0; prof.out[7] = prof.q1; prof.out[8] = prof.q2;
+        }
     }
-    MCML_HIP(hipMemcpy(host10, prof.p, 80, hipMemcpyDeviceToHost));
-    return MCML_OK;
 }
 
 // AT (cols x rows) = A' through a 32 x 33 LDS tile
@@ -584,30 +583,73 @@ __global__ void k_zero_upper(double* A, int lda, int n)
     if (i < n && j < n && i < j) A[i + (size_t)j * lda] = 0.0;
 }
 
-// LDS of k_potrf_leaf: the 128 x 129 block, the inverse's diagonal, 7 scratch tiles
-static constexpr size_t POTRF_LDS = sizeof(double) * (128 * 129 + 128 + 7 * 256 + 64);
+// Several matrices of the same shape factorised side by side (the candidate thetas of one theta-step round): every
+// launch of the schedule covers all of them (leaf: one workgroup per matrix; products: blockIdx.y), so the latency
+// chain of the late steps -- leaf, two single-block products, their gaps -- is paid once per round, not once per
+// candidate.  sA / sL: element strides from one matrix / one set of inverted diagonal blocks to the next.
+struct Bat { int n = 1; size_t sA = 0, sL = 0; int* err = nullptr; };   // err: one flag per matrix (null: the context's own)
 
-// The K = 128 panel GEMMs of the blocked solve (trsm_left_lower): deep-ring direct-to-LDS kernel
-// (dgemm_dl.h) when its contract holds, the register-staged kernel otherwise.
+// The K = 128 products of the blocked factorisation and of the blocked solve: deep-ring direct-to-LDS kernel
+// (dgemm_dl.h) when its contract holds, the register-staged kernel otherwise (one matrix, no shifted lower-only
+// update).
 //   inplace: 0 none, 1 = C aliases A (N <= 128), 2 = C aliases B (M <= 128)
 template <bool BNMAJOR>
 static int chol_gemm(hipStream_t s, int M, int N, int K, const double* A, int lda, const double* B, int ldb,
-                     const EpiAxpby& epi, bool lower_only, int inplace)
+                     const EpiAxpby& epi, bool lower_only, int tile, int inplace, int shift = 0, int nbatch = 1,
+                     size_t bsA = 0, size_t bsB = 0)
 {
     if (dl_applicable(M, N, K, A, lda, B, ldb, BNMAJOR))
-        return launch_gemm_dl<BNMAJOR>(s, M, N, K, A, lda, B, ldb, epi, lower_only, 0, inplace);
+        return launch_gemm_dl<BNMAJOR>(s, M, N, K, A, lda, B, ldb, epi, lower_only, tile, inplace, shift, nbatch, bsA, bsB);
+    MCML_REQUIRE(nbatch == 1, "potrf: a batch of factorisations needs the LDS-DMA kernel for every panel product");
+    MCML_REQUIRE(shift == 0 || !lower_only, "potrf: shifted lower-only update needs the LDS-DMA kernel");
     return launch_gemm<BNMAJOR>(s, M, N, K, A, lda, B, ldb, epi, lower_only, inplace ? inplace : -1);
 }
 
-// Right-looking blocked Cholesky: one 128-wide panel at a time -- leaf (factor + invert the diagonal
-// block in LDS), panel TRSM as a GEMM against the inverted block, SYRK of the trailing matrix.
-//
-// Look-ahead: the leaf is a single-workgroup, latency-bound kernel (~90 us) and the late
-// panels' GEMMs are small, so running them back to back leaves the chip idle most of the
-// time.  The trailing update is therefore split: the next panel's 128 columns are updated
-// first, the next leaf then runs on a high-priority side stream while the main stream updates
-// the rest of the trailing matrix (columns the leaf never touches).
+// size of c.linv for an n x n factorisation, in doubles: one inverted 128 x 128 diagonal block per panel
+static size_t linv_size(int n) { return (size_t)(n / CHOL_NB + 1) * CHOL_NB * CHOL_NB; }
 
+// what every run of leaves needs first: room for the inverted diagonal blocks of `nbatch` n x n matrices, zeroed (the
+// leaves write the lower triangles of their inverses only, k_potrf_leaf), and the leaf's LDS
+static int leaf_prepare(Ctx& c, int n, int nbatch)
+{
+    const size_t bytes = sizeof(double) * linv_size(n) * nbatch;
+    MCML_TRY(c.linv.ensure(bytes));
+    MCML_HIP(hipMemsetAsync(c.linv.p, 0, bytes, c.stream));
+    return ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf<false>), (int)POTRF_LDS);
+}
+
+// the launches and the step geometry both schedules of the factorisation (potrf_blocked, potrf_la2_capture) are made of
+struct PotrfLaunch {
+    Ctx& c; double* A; int lda; Bat bt; int* errflag;
+    PotrfLaunch(Ctx& c_, double* A_, int lda_, const Bat& b)
+        : c(c_), A(A_), lda(lda_), bt(b), errflag(b.err ? b.err : c_.errflag()) {}
+    double* linv(int k) const { return c.linv.d() + (size_t)(k / CHOL_NB) * CHOL_NB * CHOL_NB; }
+    // factorise + invert the nb x nb diagonal block at (k, k)
+    int leaf(hipStream_t s, int k, int nb) const {
+        hipLaunchKernelGGL(k_potrf_leaf<false>, dim3(bt.n), dim3(LEAF_NT), POTRF_LDS, s, A + k + (size_t)k * lda, lda, nb,
+                           linv(k), errflag, bt.sA, bt.sL, LeafProf<false>());
+        MCML_HIP(hipGetLastError());
+        return MCML_OK;
+    }
+    // C (M x N) = alpha A B' + beta C with B N-major, preferring the LDS-DMA kernel with a given tile
+    int gemm_nt(hipStream_t s, int M, int N, int K, const double* Ap, const double* Bp, int ldb, double* Cp,
+                double alpha, double beta, bool lower, int tile, int inplace, int shift) const {
+        EpiAxpby epi{Cp, lda, alpha, beta, bt.sA};
+        const size_t sB = (ldb == CHOL_NB) ? bt.sL : bt.sA;            // B is an inverted diagonal block, or part of the matrix
+        return chol_gemm<true>(s, M, N, K, Ap, lda, Bp, ldb, epi, lower, tile, inplace, shift, bt.n, bt.sA, sB);
+    }
+    // Step t of an n x n factorisation with `extra` rows carried below: the panel's first column k and width nb, the
+    // rem columns right of it, the R rows below its diagonal block A11 (R <= 0: nothing left to do), the R x nb panel
+    // A21 there, the nb2 rows of the next diagonal block (0 at the end), and the inverse leaf(k) left of A11.
+    struct Step { int k, nb, rem, R, nb2; double *A11, *A21; const double* Linv; };
+    Step step(int t, int n, int extra) const {
+        const int k = t * CHOL_NB, nb = (n - k < CHOL_NB) ? n - k : CHOL_NB, rem = n - k - nb;
+        double* A11 = A + k + (size_t)k * lda;
+        return Step{k, nb, rem, rem + extra, rem < CHOL_NB ? rem : CHOL_NB, A11, A11 + nb, linv(k)};
+    }
+};
+
+// side streams + events of the look-ahead (potrf_blocked) and of the captured schedule (potrf_la2_capture)
 static int lookahead_setup(Ctx& c)
 {
     if (c.aux) return MCML_OK;
@@ -617,18 +659,18 @@ static int lookahead_setup(Ctx& c)
     MCML_HIP(hipStreamCreateWithPriority(&c.aux_lo, hipStreamNonBlocking, lo));
     MCML_HIP(hipEventCreateWithFlags(&c.ev_col, hipEventDisableTiming));
     MCML_HIP(hipEventCreateWithFlags(&c.ev_leaf, hipEventDisableTiming));
-    MCML_HIP(hipEventCreateWithFlags(&c.ev_ps, hipEventDisableTiming));
-    MCML_HIP(hipEventCreateWithFlags(&c.ev_b, hipEventDisableTiming));
     return MCML_OK;
 }
 
-// Right-looking blocked Cholesky of the n x n lower triangle of A, 128-wide panels, with `extra` more ROWS
-// carried below the matrix (rows n .. n+extra of the same column-major array): they receive every panel
+// Right-looking blocked Cholesky of the n x n lower triangle of A, 128-wide panels -- leaf (factor + invert the
+// diagonal block in LDS), panel TRSM as a GEMM against the inverted block, SYRK of the trailing matrix -- with `extra`
+// more ROWS carried below the matrix (rows n .. n+extra of the same column-major array): they receive every panel
 // operation the rows of the matrix receive, i.e. X <- X inv(L)'.  With X = U' (the sample columns, one per
 // extra row) that is the forward substitution inv(L) U of mvn_ll, done inside the factorisation's own GEMMs
 // -- no separate TRSM pass, and the late panels, whose trailing matrices are tiny, still fill the chip.
 //
-// Step t, on the main stream: the ONE 128 x 128 panel block that becomes the next diagonal block's multiplier
+// Look-ahead (the leaf is a single-workgroup, latency-bound kernel and the late panels' GEMMs are small: back to back
+// they leave the chip idle most of the time).  Step t, on the main stream: the ONE 128 x 128 panel block that becomes the next diagonal block's multiplier
 // and that block's own update (two single-block products spread over 8 / 16 CUs); then, forked to a
 // high-priority side stream, leaf(t+1) -- while the main stream runs the bulk: the rest of panel t and the
 // whole trailing update except that block, one launch, lower tiles only, balanced over the XCDs.  The leaf
@@ -636,49 +678,21 @@ static int lookahead_setup(Ctx& c)
 // it never waits for a CU to drain.  The main stream joins the leaf before step t+1.  Period: two small GEMMs
 // + max(bulk, leaf).  (A freer two-queue schedule measured ~10 % faster live but
 // hung intermittently; it exists as a captured graph only -- see "the hang" above potrf_la2_capture.)
-// Several matrices of the same shape factorised side by side (the candidate thetas of one theta-step round): every
-// launch of the schedule covers all of them (leaf: one workgroup per matrix; products: blockIdx.y), so the latency
-// chain of the late steps -- leaf, two single-block products, their gaps -- is paid once per round, not once per
-// candidate.  sA / sL: element strides from one matrix / one set of inverted diagonal blocks to the next.
-struct Bat { int n = 1; size_t sA = 0, sL = 0; int* err = nullptr; };   // err: one flag per matrix (null: the context's own)
-
 static int potrf_blocked(Ctx& c, double* A, int lda, int n, int extra, Bat bt = Bat())
 {
-    int* errflag = bt.err ? bt.err : c.scalars.as<int>() + 32;
+    const PotrfLaunch L(c, A, lda, bt);
     const bool two = n > 2 * CHOL_NB;
     hipStream_t sM = c.stream, sL = c.stream;
     if (two) { MCML_TRY(lookahead_setup(c)); sL = c.aux; }
-    auto leaf = [&](hipStream_t s, int k, int nb) -> int {
-        hipLaunchKernelGGL(k_potrf_leaf, dim3(bt.n), dim3(LEAF_NT), POTRF_LDS, s, A + k + (size_t)k * lda, lda, nb,
-                           c.linv.d() + (size_t)(k / CHOL_NB) * CHOL_NB * CHOL_NB, errflag, nullptr, bt.sA, bt.sL);
-        MCML_HIP(hipGetLastError());
-        return MCML_OK;
-    };
-    // C (M x N) = alpha A B' + beta C with B N-major, preferring the LDS-DMA kernel with a given tile
-    auto gemm_nt = [&](int M, int N, int K, const double* Ap, const double* Bp, int ldb, double* Cp,
-                       double alpha, double beta, bool lower, int tile, int inplace, int shift) -> int {
-        EpiAxpby epi{Cp, lda, alpha, beta, bt.sA};
-        const size_t sB = (ldb == CHOL_NB) ? bt.sL : bt.sA;            // B is an inverted diagonal block, or part of the matrix
-        if (dl_applicable(M, N, K, Ap, lda, Bp, ldb, true))
-            return launch_gemm_dl<true>(sM, M, N, K, Ap, lda, Bp, ldb, epi, lower, tile, inplace, shift, bt.n, bt.sA, sB);
-        MCML_REQUIRE(bt.n == 1, "potrf: a batch of factorisations needs the LDS-DMA kernel for every panel product");
-        MCML_REQUIRE(shift == 0 || !lower, "potrf: shifted lower-only update needs the LDS-DMA kernel");
-        return launch_gemm<true>(sM, M, N, K, Ap, lda, Bp, ldb, epi, lower, inplace ? inplace : -1);
-    };
     const int nsteps = (n + CHOL_NB - 1) / CHOL_NB;
     constexpr int SPW = CHOL_NB * 8;                              // super-panel width: 8 panels
     const bool twolevel = bt.n > 1 && n > SPW + CHOL_NB;
-    MCML_TRY(leaf(sM, 0, n < CHOL_NB ? n : CHOL_NB));
+    MCML_TRY(L.leaf(sM, 0, n < CHOL_NB ? n : CHOL_NB));
     bool forked = false;
     for (int t = 0; t < nsteps; ++t) {
-        const int k = t * CHOL_NB;
-        const int nb = (n - k < CHOL_NB) ? n - k : CHOL_NB;
-        double* A11 = A + k + (size_t)k * lda;
-        const double* Linv = c.linv.d() + (size_t)t * CHOL_NB * CHOL_NB;
-        const int rem = n - k - nb, R = rem + extra;
+        const PotrfLaunch::Step s = L.step(t, n, extra);
+        const int k = s.k, nb = s.nb, rem = s.rem, R = s.R, nb2 = s.nb2;
         if (R <= 0) break;
-        double* A21 = A11 + nb;                                   // R x nb: the panel below the diagonal block
-        const int nb2 = rem < CHOL_NB ? rem : CHOL_NB;            // rows of the next diagonal block (0 at the end)
         if (forked) { MCML_HIP(hipStreamWaitEvent(sM, c.ev_leaf, 0)); forked = false; }   // leaf(t) done
         // Two levels of blocking for a BATCH (bt.n > 1), whose rounds are bound by the trailing updates, not by the chain:
         // inside a super-panel of 8 panels the K = 128 updates touch the super-panel's own columns only; the columns to
@@ -690,31 +704,31 @@ static int potrf_blocked(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
         const int inner = sp1 - (k + nb);                         // trailing columns this step's K = 128 update covers
         if (twolevel && inner == 0 && rem > 0) {
             // last panel of a super-panel: the whole panel, then everything to the right in one pass, then the next leaf
-            MCML_TRY(gemm_nt(R, nb, nb, A21, Linv, CHOL_NB, A21, 1.0, 0.0, false, 0, 1, 0));
+            MCML_TRY(L.gemm_nt(sM, R, nb, nb, s.A21, s.Linv, CHOL_NB, s.A21, 1.0, 0.0, false, 0, 1, 0));
             const double* Asp = A + sp1 + (size_t)sp0 * lda;      // rows below the super-panel, its columns
             double* Csp = A + sp1 + (size_t)sp1 * lda;
-            MCML_TRY(gemm_nt(R, rem, sp1 - sp0, Asp, Asp, lda, Csp, -1.0, 1.0, true, 0, 0, 0));
-            MCML_TRY(leaf(sM, k + nb, nb2));
+            MCML_TRY(L.gemm_nt(sM, R, rem, sp1 - sp0, Asp, Asp, lda, Csp, -1.0, 1.0, true, 0, 0, 0));
+            MCML_TRY(L.leaf(sM, k + nb, nb2));
             continue;
         }
         if (nb2 > 0) {
             // the next diagonal block: its multiplier, its update, its factorisation
-            MCML_TRY(gemm_nt(nb2, nb, nb, A21, Linv, CHOL_NB, A21, 1.0, 0.0, false, 7, 1, 0));
-            double* T = A11 + nb + (size_t)nb * lda;
-            MCML_TRY(gemm_nt(nb2, nb2, nb, A21, A21, lda, T, -1.0, 1.0, false, 8, 0, 0));
+            MCML_TRY(L.gemm_nt(sM, nb2, nb, nb, s.A21, s.Linv, CHOL_NB, s.A21, 1.0, 0.0, false, 7, 1, 0));
+            double* T = s.A11 + nb + (size_t)nb * lda;
+            MCML_TRY(L.gemm_nt(sM, nb2, nb2, nb, s.A21, s.A21, lda, T, -1.0, 1.0, false, 8, 0, 0));
             if (two) {
                 MCML_HIP(hipEventRecord(c.ev_col, sM));
                 MCML_HIP(hipStreamWaitEvent(sL, c.ev_col, 0));
             }
-            MCML_TRY(leaf(sL, k + nb, nb2));
+            MCML_TRY(L.leaf(sL, k + nb, nb2));
             if (two) { MCML_HIP(hipEventRecord(c.ev_leaf, sL)); forked = true; }
         }
         // the bulk: the rest of the panel, then the whole trailing update except the block above
         if (R - nb2 > 0)
-            MCML_TRY(gemm_nt(R - nb2, nb, nb, A21 + nb2, Linv, CHOL_NB, A21 + nb2, 1.0, 0.0, false, 0, 1, 0));
+            MCML_TRY(L.gemm_nt(sM, R - nb2, nb, nb, s.A21 + nb2, s.Linv, CHOL_NB, s.A21 + nb2, 1.0, 0.0, false, 0, 1, 0));
         if (rem > 0 && R - nb2 > 0) {
-            double* C2 = A11 + nb + nb2 + (size_t)nb * lda;       // rows nb2.. of the trailing matrix, all its columns
-            MCML_TRY(gemm_nt(R - nb2, twolevel ? inner : rem, nb, A21 + nb2, A21, lda, C2, -1.0, 1.0, true, 0, 0, nb2));
+            double* C2 = s.A11 + nb + nb2 + (size_t)nb * lda;     // rows nb2.. of the trailing matrix, all its columns
+            MCML_TRY(L.gemm_nt(sM, R - nb2, twolevel ? inner : rem, nb, s.A21 + nb2, s.A21, lda, C2, -1.0, 1.0, true, 0, 0, nb2));
         }
     }
     if (forked) MCML_HIP(hipStreamWaitEvent(sM, c.ev_leaf, 0));
@@ -734,8 +748,8 @@ static int potrf_blocked(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
 // updates: b(t) sits behind c(t-1) on the bulk queue (and must: column block t+2 was last written by c(t-1)), so the
 // critical chain has one step of slack against the bulk chain, which is what the early, throughput-bound steps use up;
 // in the late steps the bulk chain runs ahead and the three critical kernels sit back to back on one queue.
-// Every tile still receives its updates in panel order from kernels that accumulate k = 0..127 in order: the factor
-// is bit-identical to potrf_blocked's.
+// Every tile still receives its updates in panel order from kernels that accumulate k = 0..127 in order, launched by
+// the same PotrfLaunch from the same step geometry: the factor is bit-identical to potrf_blocked's.
 //
 // The hang (round 2: this structure as two LIVE streams, cross waits both ways, hung the process -- not the GPU -- on
 // three of ~20 boxes; no log of it was kept).  What the code says: the dependency structure is acyclic if every
@@ -761,65 +775,45 @@ static hipEvent_t ring_event(Ctx& c, size_t idx)
 }
 static int potrf_la2_capture(Ctx& c, double* A, int lda, int n, int extra, Bat bt = Bat())
 {
-    int* errflag = bt.err ? bt.err : c.scalars.as<int>() + 32;
+    const PotrfLaunch L(c, A, lda, bt);
     hipStream_t sC = c.stream, sB = c.aux_lo;
-    auto leaf = [&](int k, int nb) -> int {
-        hipLaunchKernelGGL(k_potrf_leaf, dim3(bt.n), dim3(LEAF_NT), POTRF_LDS, sC, A + k + (size_t)k * lda, lda, nb,
-                           c.linv.d() + (size_t)(k / CHOL_NB) * CHOL_NB * CHOL_NB, errflag, nullptr, bt.sA, bt.sL);
-        MCML_HIP(hipGetLastError());
-        return MCML_OK;
-    };
-    auto gemm_nt = [&](hipStream_t st, int M, int N, int K, const double* Ap, const double* Bp, int ldb, double* Cp,
-                       double alpha, double beta, bool lower, int tile, int inplace) -> int {
-        EpiAxpby epi{Cp, lda, alpha, beta, bt.sA};
-        const size_t sBb = (ldb == CHOL_NB) ? bt.sL : bt.sA;
-        if (dl_applicable(M, N, K, Ap, lda, Bp, ldb, true))
-            return launch_gemm_dl<true>(st, M, N, K, Ap, lda, Bp, ldb, epi, lower, tile, inplace, 0, bt.n, bt.sA, sBb);
-        MCML_REQUIRE(bt.n == 1, "potrf: a batch of factorisations needs the LDS-DMA kernel for every panel product");
-        return launch_gemm<true>(st, M, N, K, Ap, lda, Bp, ldb, epi, lower, inplace ? inplace : -1);
-    };
     const int nsteps = (n + CHOL_NB - 1) / CHOL_NB;
     // one event per dependency edge: 3 per step (leaf, P_small, b) + the first leaf + the join
     auto EV = [&](int step, int kind) -> hipEvent_t { return ring_event(c, (size_t)3 * (step + 1) + kind); };
     MCML_REQUIRE(ring_event(c, (size_t)3 * (nsteps + 2)) != nullptr, "potrf: could not create the capture's events");
-    MCML_TRY(leaf(0, n < CHOL_NB ? n : CHOL_NB));
+    MCML_TRY(L.leaf(sC, 0, n < CHOL_NB ? n : CHOL_NB));
     MCML_HIP(hipEventRecord(EV(-1, 0), sC));
     MCML_HIP(hipStreamWaitEvent(sB, EV(-1, 0), 0));                  // the side stream joins the capture; a(0) needs leaf(0)
     hipEvent_t last_b = nullptr;
     for (int t = 0; t < nsteps; ++t) {
-        const int k = t * CHOL_NB;
-        const int nb = (n - k < CHOL_NB) ? n - k : CHOL_NB;
-        double* A11 = A + k + (size_t)k * lda;
-        const double* Linv = c.linv.d() + (size_t)t * CHOL_NB * CHOL_NB;
-        const int rem = n - k - nb, R = rem + extra;
+        const PotrfLaunch::Step s = L.step(t, n, extra);
+        const int k = s.k, nb = s.nb, rem = s.rem, R = s.R, nb2 = s.nb2;
         if (R <= 0) break;
-        double* A21 = A11 + nb;
-        const int nb2 = rem < CHOL_NB ? rem : CHOL_NB;
         const int nb3 = (rem - nb2 < CHOL_NB) ? rem - nb2 : CHOL_NB;
         const int w = nb2 + nb3;                                      // columns b(t) covers
         // ---- critical chain
         if (nb2 > 0) {
             if (last_b) MCML_HIP(hipStreamWaitEvent(sC, last_b, 0));  // b(t-1)
-            MCML_TRY(gemm_nt(sC, nb2, nb, nb, A21, Linv, CHOL_NB, A21, 1.0, 0.0, false, 7, 1));
-            double* T = A11 + nb + (size_t)nb * lda;
-            MCML_TRY(gemm_nt(sC, nb2, nb2, nb, A21, A21, lda, T, -1.0, 1.0, false, 8, 0));
+            MCML_TRY(L.gemm_nt(sC, nb2, nb, nb, s.A21, s.Linv, CHOL_NB, s.A21, 1.0, 0.0, false, 7, 1, 0));
+            double* T = s.A11 + nb + (size_t)nb * lda;
+            MCML_TRY(L.gemm_nt(sC, nb2, nb2, nb, s.A21, s.A21, lda, T, -1.0, 1.0, false, 8, 0, 0));
             MCML_HIP(hipEventRecord(EV(t, 1), sC));
-            MCML_TRY(leaf(k + nb, nb2));
+            MCML_TRY(L.leaf(sC, k + nb, nb2));
             MCML_HIP(hipEventRecord(EV(t, 0), sC));
         }
         // ---- bulk chain
         const int Rb = R - nb2;
         if (Rb > 0) {
-            MCML_TRY(gemm_nt(sB, Rb, nb, nb, A21 + nb2, Linv, CHOL_NB, A21 + nb2, 1.0, 0.0, false, 0, 1));
+            MCML_TRY(L.gemm_nt(sB, Rb, nb, nb, s.A21 + nb2, s.Linv, CHOL_NB, s.A21 + nb2, 1.0, 0.0, false, 0, 1, 0));
             if (nb2 > 0) {
                 MCML_HIP(hipStreamWaitEvent(sB, EV(t, 1), 0));
-                double* Cb = A11 + nb + nb2 + (size_t)nb * lda;       // rows below block t+1, columns of blocks t+1, t+2
-                MCML_TRY(gemm_nt(sB, Rb, w, nb, A21 + nb2, A21, lda, Cb, -1.0, 1.0, false, 0, 0));
+                double* Cb = s.A11 + nb + nb2 + (size_t)nb * lda;     // rows below block t+1, columns of blocks t+1, t+2
+                MCML_TRY(L.gemm_nt(sB, Rb, w, nb, s.A21 + nb2, s.A21, lda, Cb, -1.0, 1.0, false, 0, 0, 0));
                 MCML_HIP(hipEventRecord(EV(t, 2), sB));
                 last_b = EV(t, 2);
                 if (rem - w > 0) {
-                    double* Cc = A11 + nb + w + (size_t)(nb + w) * lda;
-                    MCML_TRY(gemm_nt(sB, R - w, rem - w, nb, A21 + w, A21 + w, lda, Cc, -1.0, 1.0, true, 0, 0));
+                    double* Cc = s.A11 + nb + w + (size_t)(nb + w) * lda;
+                    MCML_TRY(L.gemm_nt(sB, R - w, rem - w, nb, s.A21 + w, s.A21 + w, lda, Cc, -1.0, 1.0, true, 0, 0, 0));
                 }
             }
         } else if (nb2 > 0) {
@@ -839,88 +833,93 @@ static int potrf_la2_capture(Ctx& c, double* A, int lda, int n, int extra, Bat b
 // call with a given key runs eagerly (function attributes, allocations), the second is captured (fork / join of the
 // look-ahead included: the side stream joins the capture through its event waits), later ones are one hipGraphLaunch.
 // The capture records potrf_la2_capture; GLMMR_MCML_CHOL_GRAPH=0 keeps the eager launches of potrf_blocked.
-// Single evaluations only (bt.n == 1): a batch runs potrf_blocked eagerly, see mvn_loglik_batch.
+// Single evaluations only (bt.n == 1): a batch runs potrf_blocked eagerly, see mvn_large_blocks.
 static bool chol_graph_on()
 {
     static const bool on = !(getenv("GLMMR_MCML_CHOL_GRAPH") && !strcmp(getenv("GLMMR_MCML_CHOL_GRAPH"), "0"));
     return on;
 }
+static bool graph_timer_begin(Ctx& c, CholGraph& g)
+{
+    if (!g.t0 && (hipEventCreate(&g.t0) != hipSuccess || hipEventCreate(&g.t1) != hipSuccess)) { (void)hipGetLastError(); return false; }
+    return hipEventRecord(g.t0, c.stream) == hipSuccess;
+}
+// Calibration of a fresh executable (see CholGraph): the previous replay's time is known by now -- every caller
+// synchronises for its result -- and an executable slower than the eager launches is instantiated again.
+static void calibrate(CholGraph& g)
+{
+    float ms = 0.f;
+    g.timed = false;
+    bool done = true;
+    const hipError_t ee = hipEventElapsedTime(&ms, g.t0, g.t1);
+    static const bool cal_trace = getenv("GLMMR_MCML_GRAPH_TRACE") != nullptr;
+    if (cal_trace) fprintf(stderr, "graph calibration: n=%d extra=%d trial %d: %.3f ms (eager %.3f, best %.3f) rc=%d\n", g.n, g.extra, g.tries, ms, g.eager_ms, g.best_ms, (int)ee);
+    if (ee == hipSuccess && g.eager_ms > 0.f && g.tmpl) {
+        // keep the fastest executable seen; try another instantiation unless this one clearly beats the eager
+        // launches or four have been tried
+        if (!g.best || ms < g.best_ms) {
+            if (g.best && g.best != g.exec) (void)hipGraphExecDestroy(g.best);
+            g.best = g.exec; g.best_ms = ms;
+        } else if (g.exec != g.best) (void)hipGraphExecDestroy(g.exec);
+        g.exec = g.best;
+        if (!(g.best_ms <= 0.93f * g.eager_ms) && g.tries < 3) {
+            hipGraphExec_t ex2 = nullptr;
+            if (hipGraphInstantiate(&ex2, g.tmpl, nullptr, nullptr, 0) == hipSuccess) { g.exec = ex2; ++g.tries; g.trial_launches = 0; done = false; }
+            else (void)hipGetLastError();
+        }
+    } else (void)hipGetLastError();
+    if (done) {
+        g.settled = true; g.best = nullptr;
+        if (g.tmpl) { (void)hipGraphDestroy(g.tmpl); g.tmpl = nullptr; }
+    }
+}
+// Records potrf_la2_capture and instantiates it into g.exec, ready for calibration.  Whatever goes wrong while
+// recording (nothing has run; e.g. the legacy default stream cannot be captured) leaves g.exec null.
+static int capture_and_instantiate(Ctx& c, CholGraph& g, double* A, int lda, int n, int extra, const Bat& bt)
+{
+    MCML_TRY(lookahead_setup(c));
+    if (hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return MCML_OK; }
+    const int rc = potrf_la2_capture(c, A, lda, n, extra, bt);
+    hipGraph_t graph = nullptr;
+    const hipError_t e = hipStreamEndCapture(c.stream, &graph);
+    if (rc != MCML_OK || e != hipSuccess || !graph || hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        (void)hipGetLastError();
+        g.exec = nullptr;
+        return MCML_OK;
+    }
+    g.tmpl = graph; g.tries = 0; g.settled = !(g.eager_ms > 0.f); g.timed = false; g.best = nullptr; g.best_ms = 0.f;
+    if (g.settled) { (void)hipGraphDestroy(g.tmpl); g.tmpl = nullptr; }
+    return MCML_OK;
+}
+// no graph for this key: the capture is never tried again
+static void eager_for_good(CholGraph& g) { g.seen = -(1 << 30); }
+
 static int potrf_graphed(Ctx& c, double* A, int lda, int n, int extra, Bat bt = Bat())
 {
     if (!chol_graph_on() || n <= 2 * CHOL_NB) return potrf_blocked(c, A, lda, n, extra, bt);
     CholGraph& g = c.chol_graphs.find(A, c.linv.d(), lda, n, extra);
-    auto timed_begin = [&]() -> bool {
-        if (!g.t0 && (hipEventCreate(&g.t0) != hipSuccess || hipEventCreate(&g.t1) != hipSuccess)) { (void)hipGetLastError(); return false; }
-        return hipEventRecord(g.t0, c.stream) == hipSuccess;
-    };
     if (g.exec) {
-        // calibration of a fresh executable (see CholGraph): the previous replay's time is known by now -- every caller
-        // synchronises for its result -- and an executable slower than the eager launches is instantiated again
-        if (!g.settled && g.timed) {
-            float ms = 0.f;
-            g.timed = false;
-            bool done = true;
-            const hipError_t ee = hipEventElapsedTime(&ms, g.t0, g.t1);
-            static const bool cal_trace = getenv("GLMMR_MCML_GRAPH_TRACE") != nullptr;
-            if (cal_trace) fprintf(stderr, "graph calibration: n=%d extra=%d trial %d: %.3f ms (eager %.3f, best %.3f) rc=%d\n", g.n, g.extra, g.tries, ms, g.eager_ms, g.best_ms, (int)ee);
-            if (ee == hipSuccess && g.eager_ms > 0.f && g.tmpl) {
-                // keep the fastest executable seen; try another instantiation unless this one clearly beats the eager
-                // launches or four have been tried
-                if (!g.best || ms < g.best_ms) {
-                    if (g.best && g.best != g.exec) (void)hipGraphExecDestroy(g.best);
-                    g.best = g.exec; g.best_ms = ms;
-                } else if (g.exec != g.best) (void)hipGraphExecDestroy(g.exec);
-                g.exec = g.best;
-                if (!(g.best_ms <= 0.93f * g.eager_ms) && g.tries < 3) {
-                    hipGraphExec_t ex2 = nullptr;
-                    if (hipGraphInstantiate(&ex2, g.tmpl, nullptr, nullptr, 0) == hipSuccess) { g.exec = ex2; ++g.tries; g.trial_launches = 0; done = false; }
-                    else (void)hipGetLastError();
-                }
-            } else (void)hipGetLastError();
-            if (done) {
-                g.settled = true; g.best = nullptr;
-                if (g.tmpl) { (void)hipGraphDestroy(g.tmpl); g.tmpl = nullptr; }
-            }
-        }
-        const bool tm = !g.settled && g.trial_launches >= 1 && timed_begin();
+        if (!g.settled && g.timed) calibrate(g);
+        const bool tm = !g.settled && g.trial_launches >= 1 && graph_timer_begin(c, g);
         MCML_HIP(hipGraphLaunch(g.exec, c.stream));
         if (tm) g.timed = hipEventRecord(g.t1, c.stream) == hipSuccess;
         ++g.trial_launches;
         return MCML_OK;
     }
     if (g.seen++ <= 1) {   // eager twice first (attributes, allocations): the second run's time is the calibration's yardstick
-        const bool tm = timed_begin();
+        const bool tm = graph_timer_begin(c, g);
         MCML_TRY(potrf_blocked(c, A, lda, n, extra, bt));
         if (tm && hipEventRecord(g.t1, c.stream) == hipSuccess && hipEventSynchronize(g.t1) == hipSuccess)
             (void)hipEventElapsedTime(&g.eager_ms, g.t0, g.t1);
         (void)hipGetLastError();
         return MCML_OK;
     }
-    MCML_TRY(lookahead_setup(c));
-    if (hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        (void)hipGetLastError();                                           // e.g. the legacy default stream: eager for good
-        g.seen = -(1 << 30);
+    MCML_TRY(capture_and_instantiate(c, g, A, lda, n, extra, bt));
+    if (!g.exec) {         // eager launches from now on, the error if that fails too
+        eager_for_good(g);
         return potrf_blocked(c, A, lda, n, extra, bt);
     }
-    const int rc = potrf_la2_capture(c, A, lda, n, extra, bt);
-    hipGraph_t graph = nullptr;
-    const hipError_t e = hipStreamEndCapture(c.stream, &graph);
-    if (rc != MCML_OK || e != hipSuccess || !graph) {
-        // whatever went wrong while recording (nothing has run): eager launches from now on, the error if that fails too
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();
-        g.seen = -(1 << 30);
-        return potrf_blocked(c, A, lda, n, extra, bt);
-    }
-    const hipError_t ei = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-    if (ei != hipSuccess) {
-        (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();
-        g.exec = nullptr; g.seen = -(1 << 30);
-        return potrf_blocked(c, A, lda, n, extra, bt);
-    }
-    g.tmpl = graph; g.tries = 0; g.settled = !(g.eager_ms > 0.f); g.timed = false; g.best = nullptr; g.best_ms = 0.f;
-    if (g.settled) { (void)hipGraphDestroy(g.tmpl); g.tmpl = nullptr; }
     g.trial_launches = 1;                     // this first launch is not timed (it carries the executable's upload)
     MCML_HIP(hipGraphLaunch(g.exec, c.stream));
     return MCML_OK;
@@ -929,11 +928,30 @@ static int potrf_graphed(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
 int potrf_lower(Ctx& c, double* A, int n, int lda)
 {
     MCML_REQUIRE(n > 0 && lda >= n && (lda & 1) == 0, "potrf: bad shape n=%d lda=%d", n, lda);
-    MCML_TRY(c.linv.ensure(sizeof(double) * (size_t)(n / CHOL_NB + 1) * CHOL_NB * CHOL_NB));
-    // the leaves write the lower triangles of their inverses only (k_potrf_leaf)
-    MCML_HIP(hipMemsetAsync(c.linv.p, 0, sizeof(double) * (size_t)((n + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB, c.stream));
-    MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf), (int)POTRF_LDS));
+    MCML_TRY(leaf_prepare(c, n, 1));
     return potrf_blocked(c, A, lda, n, 0);
+}
+
+// debug: phase timestamps (shader clock) of one 128 x 128 leaf on a random SPD block, from the kernel's profiling instance
+int potrf_leaf_profile(Ctx& c, unsigned long long* host10)
+{
+    DevMat A; DevBuf prof;
+    MCML_TRY(A.alloc(128, 128));
+    MCML_TRY(prof.ensure(80));
+    std::vector<double> h((size_t)A.ld * 128, 0.0);
+    for (int j = 0; j < 128; ++j) for (int i = 0; i < 128; ++i) h[i + (size_t)j * A.ld] = (i == j ? 130.0 : 1.0 / (1 + abs(i - j)));
+    MCML_TRY(leaf_prepare(c, 128, 1));
+    MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf<true>), (int)POTRF_LDS));
+    LeafProf<true> lp;
+    lp.out = prof.as<unsigned long long>();
+    for (int rep = 0; rep < 3; ++rep) {
+        MCML_TRY(copy_h2d(A.d(), h.data(), sizeof(double) * h.size(), 0)); MCML_HIP(hipDeviceSynchronize());
+        hipLaunchKernelGGL(k_potrf_leaf<true>, dim3(1), dim3(LEAF_NT), POTRF_LDS, c.stream, A.d(), A.ld, 128, c.linv.d(),
+                           c.errflag(), (size_t)0, (size_t)0, lp);
+        MCML_HIP(hipStreamSynchronize(c.stream));
+    }
+    MCML_HIP(hipMemcpy(host10, prof.p, 80, hipMemcpyDeviceToHost));
+    return MCML_OK;
 }
 
 // U (n x m) <- inv(L) U, L lower n x n; needs the leaf inverses potrf_lower left in c.linv.  Panel by panel: the
@@ -947,13 +965,13 @@ int trsm_left_lower(Ctx& c, const double* L, int ldl, int n, double* U, int ldu,
         double* Uk = U + k;
         {
             EpiAxpby epi{Uk, ldu, 1.0, 0.0};
-            MCML_TRY(chol_gemm<false>(c.stream, nb, m, nb, Linv, CHOL_NB, Uk, ldu, epi, false, 2));
+            MCML_TRY(chol_gemm<false>(c.stream, nb, m, nb, Linv, CHOL_NB, Uk, ldu, epi, false, 0, 2));
         }
         const int rem = n - k - nb;
         if (rem <= 0) break;
         const double* L21 = L + (k + nb) + (size_t)k * ldl;
         EpiAxpby epi{Uk + nb, ldu, -1.0, 1.0};
-        MCML_TRY(chol_gemm<false>(c.stream, rem, m, nb, L21, ldl, Uk, ldu, epi, false, 0));
+        MCML_TRY(chol_gemm<false>(c.stream, rem, m, nb, L21, ldl, Uk, ldu, epi, false, 0, 0));
     }
     return MCML_OK;
 }
@@ -996,7 +1014,7 @@ int mvn_setup(Ctx& c)
         MCML_HIP(hipMemsetAsync(c.Dwork.d(), 0, sizeof(double) * (size_t)c.Dwork.ld * c.maxdim_large, c.stream));
         // room for a whole round of candidates (mvn_loglik_batch) from the start: growing the buffer later would change
         // the pointer the single evaluation's captured graph is keyed on
-        MCML_TRY(c.linv.ensure(sizeof(double) * (size_t)(round_up(c.maxdim_large, 16) / CHOL_NB + 1) * CHOL_NB * CHOL_NB * MVN_MAXBATCH));
+        MCML_TRY(c.linv.ensure(sizeof(double) * linv_size(round_up(c.maxdim_large, 16)) * MVN_MAXBATCH));
     }
     MCML_HIP(hipStreamSynchronize(c.stream));
     return MCML_OK;
@@ -1013,10 +1031,10 @@ static int theta_arg(const Ctx& c, const double* theta, ThetaArg& th)
 static int check_errflag(Ctx& c, const char* what)
 {
     int flag = 0;
-    MCML_TRY(copy_d2h(&flag, c.scalars.as<int>() + 32, sizeof(int), c.stream));
+    MCML_TRY(copy_d2h(&flag, c.errflag(), sizeof(int), c.stream));
     MCML_HIP(hipStreamSynchronize(c.stream));
     if (flag) {
-        MCML_HIP(hipMemsetAsync(c.scalars.as<int>() + 32, 0, sizeof(int), c.stream));
+        MCML_HIP(hipMemsetAsync(c.errflag(), 0, sizeof(int), c.stream));
         set_error("%s: covariance block is not positive definite", what);
         return MCML_ENOTPD;
     }
@@ -1036,97 +1054,62 @@ int mvn_loglik_sum(Ctx& c, const double* theta, double* sum_out)
     return mvn_loglik_sum_on(c, theta, c.U.d(), c.U.ld, c.mcols, sum_out);
 }
 
-static int mvn_loglik_enqueue(Ctx& c, const double* theta, const double* Us, int ldu, int m);
-
-int mvn_loglik_sum_on(Ctx& c, const double* theta, const double* Us, int ldu, int m, double* sum_out)
+// The large blocks of D for kb >= 1 candidate thetas th[0..kb), enqueued.  W holds the kb matrices side by side
+// (matrix j = columns [j * dmax, (j + 1) * dmax), sized by the caller); the m sample columns ride below each matrix as
+// m extra rows (U', one sample per row), so the forward substitution happens inside the factorisation (potrf_blocked).
+// Candidate j's terms are added to scal[j * sstride] (scal[j * sstride + 1 .. 2]: log-determinant and sum of squares
+// of the block at hand); a failed pivot raises flags[j].
+//
+// A batch (kb > 1) is launched EAGERLY with the two-stream fork-join of potrf_blocked (the leaf of step t+1 beside the
+// bulk of step t): 13.4 ms per round of 8 at Q = 5000 and 1.95 ms at Q = 2000, against 14.4 / 2.21 ms for a
+// one-chain graph (measured, then removed) -- a graph without a parallel branch cannot overlap the two, and one
+// with a branch is subject to the executable lottery described at CholGraph.  The host keeps ahead easily (~250
+// launches per round).  kb = 1 (a single evaluation, or the last round of k = 8 j + 1 candidates) takes the graph.
+static int mvn_large_blocks(Ctx& c, DevMat& W, int kb, const ThetaArg* th, const double* Us, int ldu, int m,
+                            double* scal, int sstride, int* flags)
 {
-    MCML_TRY(mvn_loglik_enqueue(c, theta, Us, ldu, m));
-    MCML_TRY(copy_d2h(sum_out, c.scalars.d(), sizeof(double), c.stream));
-    MCML_TRY(check_errflag(c, "mvn_ll"));
-    return MCML_OK;
-}
-
-// k candidate thetas in ONE pass of the factorisation's schedule.  A single evaluation of a large dense block is a
-// latency chain (40 steps of leaf + two single-block products, ~70 us each, on a handful of CUs; 0.24 of the FP64 MFMA
-// peak at Q = 5000); with the k matrices side by side in one workspace every launch covers all of them, so the chain
-// is paid once per round.  (Measured dead end: the k evaluations as k independent streams / graphs -- "lanes" -- do
-// not overlap on this stack: 3.6 ms per evaluation alone, 4.1 / 4.8 / 5.0 ms each with 2 / 4 / 8 lanes, worse with
-// more hardware queues.)  Models whose D has diagonal or small blocks besides, and k = 1, take the single path.
-int mvn_loglik_batch(Ctx& c, const double* thetas, int k, const double* Us, int ldu, int m, double* sums, int* rcs)
-{
-    MCML_REQUIRE(k >= 1 && thetas && sums && rcs && m > 0 && Us, "mvn_ll batch: bad arguments");
     const CovSpec& cs = c.cov;
-    const int R = cs.npar;
-    const bool batchable = k > 1 && c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0;
-    if (!batchable) {
-        int first_rc = MCML_OK;
-        for (int j = 0; j < k; ++j) {
-            rcs[j] = mvn_loglik_sum_on(c, thetas + (size_t)j * R, Us, ldu, m, sums + j);
-            if (rcs[j] != MCML_OK && rcs[j] != MCML_ENOTPD && first_rc == MCML_OK) first_rc = rcs[j];
+    const int32_t* dcov = c.d_cov.as<int32_t>();
+    const CovBlock* dblk = c.d_blocks.as<CovBlock>();
+    const int ld = W.ld, dmax = round_up(c.maxdim_large, 16);
+    Bat bt; bt.n = kb; bt.sA = (size_t)ld * dmax; bt.sL = linv_size(dmax); bt.err = flags;
+    ThetaBatch tb;
+    memset(&tb, 0, sizeof tb);
+    for (int j = 0; j < kb; ++j) tb.t[j] = th[j];
+    for (int b = 0; b < cs.B; ++b) {
+        const CovBlock& blk = cs.blocks[b];
+        if (blk.all_gr || blk.dim <= SMALL_BLOCK) continue;
+        const int d = blk.dim;
+        // a multiple of 16 (identity border): the extra rows and every panel stay 16-byte aligned and the last, ragged
+        // panel still has a K the LDS-DMA kernel takes (5000 = 39 x 128 + 8 would fall back to the register-staged one)
+        const int dp = round_up(d, 16);
+        const dim3 gb((dp + 63) / 64, (dp + 15) / 16, kb);
+        if (kb == 1)
+            hipLaunchKernelGGL(k_build_dense, gb, dim3(256), 0, c.stream, W.d(), ld, b, dblk, dcov, cs.rows, c.d_data.d(),
+                               th[0], 0, dp);
+        else
+            hipLaunchKernelGGL(k_build_dense_batch, gb, dim3(256), 0, c.stream, W.d(), ld, bt.sA, b, dblk, dcov, cs.rows,
+                               c.d_data.d(), tb, dp);
+        hipLaunchKernelGGL(k_transpose_in, dim3((d + 31) / 32, (m + 31) / 32, kb), dim3(256), 0, c.stream,
+                           Us + blk.matstart, ldu, d, m, W.d() + dp, ld, bt.sA);
+        MCML_HIP(hipGetLastError());
+        if (dp > d)          // the border columns of the sample rows must be finite: they meet zeros only
+            for (int j = 0; j < kb; ++j)
+                MCML_HIP(hipMemset2DAsync(W.d() + j * bt.sA + dp + (size_t)d * ld, sizeof(double) * ld, 0, sizeof(double) * m, dp - d, c.stream));
+        MCML_TRY(leaf_prepare(c, dmax, kb));
+        MCML_TRY(kb > 1 ? potrf_blocked(c, W.d(), ld, dp, m, bt) : potrf_graphed(c, W.d(), ld, dp, m, bt));
+        // the solved samples: m rows x d columns below each factor
+        const int gx = (m + 255) / 256, gy = d < 64 ? d : 64;
+        MCML_TRY(c.partials.ensure(sizeof(double) * (size_t)(gx * gy + 16)));
+        for (int j = 0; j < kb; ++j) {
+            double* sj = scal + (size_t)j * sstride;
+            const double* Aj = W.d() + j * bt.sA;
+            hipLaunchKernelGGL(k_sumsq, dim3(gx, gy), dim3(256), 0, c.stream, Aj + dp, ld, m, d, c.partials.d());
+            hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, c.partials.d(), gx * gy, sj + 2, 0);
+            hipLaunchKernelGGL(k_logdet, dim3(1), dim3(256), 0, c.stream, Aj, ld, d, sj + 1);
+            hipLaunchKernelGGL(k_finish_large, dim3(1), dim3(1), 0, c.stream, sj, d, m);
         }
-        return first_rc;
-    }
-    for (int j0 = 0; j0 < k; j0 += MVN_MAXBATCH) {
-        const int kb = (k - j0 < MVN_MAXBATCH) ? k - j0 : MVN_MAXBATCH;
-        ThetaBatch tb;
-        memset(&tb, 0, sizeof tb);
-        for (int j = 0; j < kb; ++j)
-            for (int i = 0; i < R; ++i) tb.t[j].v[i] = thetas[(size_t)(j0 + j) * R + i];
-        const int dmax = round_up(c.maxdim_large, 16);
-        // kb matrices side by side: matrix j = columns [j * dmax, (j + 1) * dmax), the m sample rows below each
-        if (c.Dbatch.rows < dmax + m || c.Dbatch.cols < kb * dmax) {
-            MCML_TRY(c.Dbatch.alloc(dmax + m, MVN_MAXBATCH * dmax));
-            MCML_HIP(hipMemsetAsync(c.Dbatch.d(), 0, sizeof(double) * (size_t)c.Dbatch.ld * MVN_MAXBATCH * dmax, c.stream));
-        }
-        const int ld = c.Dbatch.ld;
-        const size_t sA = (size_t)ld * dmax;
-        const int nst = dmax / CHOL_NB + 1;
-        const size_t sL = (size_t)nst * CHOL_NB * CHOL_NB;
-        MCML_TRY(c.linv.ensure(sizeof(double) * sL * MVN_MAXBATCH));
-        // results: 4 doubles per candidate, then one "not positive definite" flag (int) per candidate -- a buffer of
-        // their own (c.scalars is shared with the sampler's diagnostics)
-        MCML_TRY(c.bscal.ensure(sizeof(double) * 5 * MVN_MAXBATCH));
-        MCML_HIP(hipMemsetAsync(c.bscal.p, 0, sizeof(double) * 5 * MVN_MAXBATCH, c.stream));
-        int* bflags = reinterpret_cast<int*>(c.bscal.d() + 4 * MVN_MAXBATCH);
-        const int32_t* dcov = c.d_cov.as<int32_t>();
-        const CovBlock* dblk = c.d_blocks.as<CovBlock>();
-        for (int b = 0; b < cs.B; ++b) {
-            const CovBlock& blk = cs.blocks[b];
-            const int d = blk.dim, dp = round_up(d, 16);
-            hipLaunchKernelGGL(k_build_dense_batch, dim3((dp + 63) / 64, (dp + 15) / 16, kb), dim3(256), 0, c.stream,
-                               c.Dbatch.d(), ld, sA, b, dblk, dcov, cs.rows, c.d_data.d(), tb, dp);
-            hipLaunchKernelGGL(k_transpose_in, dim3((d + 31) / 32, (m + 31) / 32, kb), dim3(256), 0, c.stream,
-                               Us + blk.matstart, ldu, d, m, c.Dbatch.d() + dp, ld, sA);
-            MCML_HIP(hipGetLastError());
-            if (dp > d)          // the border columns of the sample rows must be finite: they meet zeros only
-                for (int j = 0; j < kb; ++j)
-                    MCML_HIP(hipMemset2DAsync(c.Dbatch.d() + j * sA + dp + (size_t)d * ld, sizeof(double) * ld, 0, sizeof(double) * m, dp - d, c.stream));
-            MCML_HIP(hipMemsetAsync(c.linv.p, 0, sizeof(double) * sL * kb, c.stream));
-            MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf), (int)POTRF_LDS));
-            Bat bt; bt.n = kb; bt.sA = sA; bt.sL = sL; bt.err = bflags;
-            // A batch is launched EAGERLY with the two-stream fork-join of potrf_blocked (the leaf of step t+1 beside the
-            // bulk of step t): 13.4 ms per round of 8 at Q = 5000 and 1.95 ms at Q = 2000, against 14.4 / 2.21 ms for a
-            // one-chain graph (measured, then removed) -- a graph without a parallel branch cannot overlap the two, and one
-            // with a branch is subject to the executable lottery described at CholGraph.  The host keeps ahead easily (~250
-            // launches per round).  A round of one (the last round of k = 8 j + 1) is a single evaluation: it takes the graph.
-            MCML_TRY(kb > 1 ? potrf_blocked(c, c.Dbatch.d(), ld, dp, m, bt) : potrf_graphed(c, c.Dbatch.d(), ld, dp, m, bt));
-            const int gx = (m + 255) / 256, gy = d < 64 ? d : 64;
-            MCML_TRY(c.partials.ensure(sizeof(double) * (size_t)(gx * gy + 16)));
-            for (int j = 0; j < kb; ++j) {
-                double* scal = c.bscal.d() + 4 * j;
-                const double* Aj = c.Dbatch.d() + j * sA;
-                hipLaunchKernelGGL(k_sumsq, dim3(gx, gy), dim3(256), 0, c.stream, Aj + dp, ld, m, d, c.partials.d());
-                hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, c.partials.d(), gx * gy, 1.0, scal + 2, 0);
-                hipLaunchKernelGGL(k_logdet, dim3(1), dim3(256), 0, c.stream, Aj, ld, d, scal + 1);
-                hipLaunchKernelGGL(k_finish_large, dim3(1), dim3(1), 0, c.stream, scal, d, m);
-            }
-            MCML_HIP(hipGetLastError());
-        }
-        double hs[4 * MVN_MAXBATCH]; int hf[MVN_MAXBATCH];
-        MCML_TRY(copy_d2h(hs, c.bscal.p, sizeof(double) * 4 * kb, c.stream));
-        MCML_TRY(copy_d2h(hf, bflags, sizeof(int) * kb, c.stream));
-        MCML_HIP(hipStreamSynchronize(c.stream));
-        for (int j = 0; j < kb; ++j) { sums[j0 + j] = hs[4 * j]; rcs[j0 + j] = hf[j] ? MCML_ENOTPD : MCML_OK; }
+        MCML_HIP(hipGetLastError());
     }
     return MCML_OK;
 }
@@ -1155,56 +1138,77 @@ static int mvn_loglik_enqueue(Ctx& c, const double* theta, const double* Us, int
         int gy = 65536 / (int)grid.x; if (gy > m) gy = m; if (gy > 64) gy = 64; if (gy < 1) gy = 1;
         grid.y = gy;
         hipLaunchKernelGGL(k_diag_ll, grid, dim3(256), 0, c.stream, Us, ldu, Q, m, drb, dd, dc, part);
-        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, part, (int)(grid.x * grid.y), 1.0, scal, 1);
+        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, part, (int)(grid.x * grid.y), scal, 1);
         MCML_HIP(hipGetLastError());
     }
     if (c.n_small > 0) {
-        // the block ids were uploaded once by mvn_setup: nothing here needs the host to wait (this was a host
-        // synchronisation per evaluation, 40 of them in a theta-step of config 4)
+        // the block ids were uploaded once by mvn_setup: nothing here needs the host to wait
         int ny = (m + 63) / 64; if (ny > 16) ny = 16;
         DevBuf& wb = c.scratch;      // scratch that outlives the launch
         MCML_TRY(wb.ensure(sizeof(double) * (size_t)c.n_small * ny + 1024));
         double* part = wb.d();
         hipLaunchKernelGGL(k_small_ll, dim3((unsigned)c.n_small, ny), dim3(64), 0, c.stream, Us, ldu, m,
-                           c.small_ids.as<int>(), dblk, dcov, cs.rows, c.d_data.d(), th, part, c.scalars.as<int>() + 32);
-        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, part, c.n_small * ny, 1.0, scal, 1);
+                           c.small_ids.as<int>(), dblk, dcov, cs.rows, c.d_data.d(), th, part, c.errflag());
+        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, part, c.n_small * ny, scal, 1);
         MCML_HIP(hipGetLastError());
     }
     if (c.maxdim_large > 0) {
-        // the m sample columns ride below the matrix as m extra rows (U', one sample per row), so the forward
-        // substitution happens inside the factorisation (potrf_blocked)
         if (c.Dwork.rows < c.maxdim_large + 16 + m || c.Dwork.cols < c.maxdim_large + 16) {
             MCML_TRY(c.Dwork.alloc(c.maxdim_large + 16 + m, c.maxdim_large + 16));
             MCML_HIP(hipMemsetAsync(c.Dwork.d(), 0, sizeof(double) * (size_t)c.Dwork.ld * (c.maxdim_large + 16), c.stream));
         }
-        for (int b = 0; b < cs.B; ++b) {
-            const CovBlock& blk = cs.blocks[b];
-            if (blk.all_gr || blk.dim <= SMALL_BLOCK) continue;
-            const int d = blk.dim;
-            // a multiple of 16 (identity border): the extra rows and every panel stay 16-byte aligned and the last, ragged
-            // panel still has a K the LDS-DMA kernel takes (5000 = 39 x 128 + 8 would fall back to the register-staged one)
-            const int dp = round_up(d, 16);
-            hipLaunchKernelGGL(k_build_dense, dim3((dp + 63) / 64, (dp + 15) / 16), dim3(256), 0, c.stream, c.Dwork.d(),
-                               c.Dwork.ld, b, dblk, dcov, cs.rows, c.d_data.d(), th, 0, dp);
-            MCML_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_transpose_in, dim3((d + 31) / 32, (m + 31) / 32), dim3(256), 0, c.stream,
-                               Us + blk.matstart, ldu, d, m, c.Dwork.d() + dp, c.Dwork.ld);
-            if (dp > d)        // the border columns of the sample rows must be finite: they meet zeros only
-                MCML_HIP(hipMemset2DAsync(c.Dwork.d() + dp + (size_t)d * c.Dwork.ld, sizeof(double) * c.Dwork.ld, 0, sizeof(double) * m, dp - d, c.stream));
-            MCML_HIP(hipGetLastError());
-            MCML_TRY(c.linv.ensure(sizeof(double) * (size_t)(dp / CHOL_NB + 1) * CHOL_NB * CHOL_NB));
-            MCML_HIP(hipMemsetAsync(c.linv.p, 0, sizeof(double) * (size_t)((dp + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB, c.stream));
-            MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&k_potrf_leaf), (int)POTRF_LDS));
-            MCML_TRY(potrf_graphed(c, c.Dwork.d(), c.Dwork.ld, dp, m));
-            // the solved samples: m rows x d columns below the factor
-            const int gx = (m + 255) / 256, gy = d < 64 ? d : 64;
-            MCML_TRY(c.partials.ensure(sizeof(double) * (size_t)(gx * gy + 16)));
-            hipLaunchKernelGGL(k_sumsq, dim3(gx, gy), dim3(256), 0, c.stream, c.Dwork.d() + dp, c.Dwork.ld, m, d, c.partials.d());
-            hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c.stream, c.partials.d(), gx * gy, 1.0, scal + 2, 0);
-            hipLaunchKernelGGL(k_logdet, dim3(1), dim3(256), 0, c.stream, c.Dwork.d(), c.Dwork.ld, d, scal + 1);
-            hipLaunchKernelGGL(k_finish_large, dim3(1), dim3(1), 0, c.stream, scal, d, m);
-            MCML_HIP(hipGetLastError());
+        MCML_TRY(mvn_large_blocks(c, c.Dwork, 1, &th, Us, ldu, m, scal, 4, c.errflag()));
+    }
+    return MCML_OK;
+}
+
+int mvn_loglik_sum_on(Ctx& c, const double* theta, const double* Us, int ldu, int m, double* sum_out)
+{
+    MCML_TRY(mvn_loglik_enqueue(c, theta, Us, ldu, m));
+    MCML_TRY(copy_d2h(sum_out, c.scalars.d(), sizeof(double), c.stream));
+    MCML_TRY(check_errflag(c, "mvn_ll"));
+    return MCML_OK;
+}
+
+// k candidate thetas in ONE pass of the factorisation's schedule.  A single evaluation of a large dense block is a
+// latency chain (40 steps of leaf + two single-block products, ~70 us each, on a handful of CUs; 0.24 of the FP64 MFMA
+// peak at Q = 5000); with the k matrices side by side in one workspace every launch covers all of them, so the chain
+// is paid once per round.  (Measured dead end: the k evaluations as k independent streams / graphs -- "lanes" -- do
+// not overlap on this stack: 3.6 ms per evaluation alone, 4.1 / 4.8 / 5.0 ms each with 2 / 4 / 8 lanes, worse with
+// more hardware queues.)  Models whose D has diagonal or small blocks besides, and k = 1, take the single path.
+int mvn_loglik_batch(Ctx& c, const double* thetas, int k, const double* Us, int ldu, int m, double* sums, int* rcs)
+{
+    MCML_REQUIRE(k >= 1 && thetas && sums && rcs && m > 0 && Us, "mvn_ll batch: bad arguments");
+    const int R = c.cov.npar;
+    const bool batchable = k > 1 && c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0;
+    if (!batchable) {
+        int first_rc = MCML_OK;
+        for (int j = 0; j < k; ++j) {
+            rcs[j] = mvn_loglik_sum_on(c, thetas + (size_t)j * R, Us, ldu, m, sums + j);
+            if (rcs[j] != MCML_OK && rcs[j] != MCML_ENOTPD && first_rc == MCML_OK) first_rc = rcs[j];
         }
+        return first_rc;
+    }
+    for (int j0 = 0; j0 < k; j0 += MVN_MAXBATCH) {
+        const int kb = (k - j0 < MVN_MAXBATCH) ? k - j0 : MVN_MAXBATCH;
+        ThetaArg th[MVN_MAXBATCH];
+        for (int j = 0; j < kb; ++j) MCML_TRY(theta_arg(c, thetas + (size_t)(j0 + j) * R, th[j]));
+        const int dmax = round_up(c.maxdim_large, 16);
+        if (c.Dbatch.rows < dmax + m || c.Dbatch.cols < kb * dmax) {
+            MCML_TRY(c.Dbatch.alloc(dmax + m, MVN_MAXBATCH * dmax));
+            MCML_HIP(hipMemsetAsync(c.Dbatch.d(), 0, sizeof(double) * (size_t)c.Dbatch.ld * MVN_MAXBATCH * dmax, c.stream));
+        }
+        // results: 4 doubles per candidate, then one "not positive definite" flag (int) per candidate -- a buffer of
+        // their own (c.scalars is shared with the sampler's diagnostics)
+        MCML_TRY(c.bscal.ensure(sizeof(double) * 5 * MVN_MAXBATCH));
+        MCML_HIP(hipMemsetAsync(c.bscal.p, 0, sizeof(double) * 5 * MVN_MAXBATCH, c.stream));
+        int* bflags = reinterpret_cast<int*>(c.bscal.d() + 4 * MVN_MAXBATCH);
+        MCML_TRY(mvn_large_blocks(c, c.Dbatch, kb, th, Us, ldu, m, c.bscal.d(), 4, bflags));
+        double hs[4 * MVN_MAXBATCH]; int hf[MVN_MAXBATCH];
+        MCML_TRY(copy_d2h(hs, c.bscal.p, sizeof(double) * 4 * kb, c.stream));
+        MCML_TRY(copy_d2h(hf, bflags, sizeof(int) * kb, c.stream));
+        MCML_HIP(hipStreamSynchronize(c.stream));
+        for (int j = 0; j < kb; ++j) { sums[j0 + j] = hs[4 * j]; rcs[j0 + j] = hf[j] ? MCML_ENOTPD : MCML_OK; }
     }
     return MCML_OK;
 }
@@ -1217,9 +1221,7 @@ __global__ void k_diag_fill(double* L, int ldl, int Q, const int* rowblock, cons
     if (k >= Q) return;
     int b = rowblock[k];
     if (b < 0) return;
-    CovBlock blk = blocks[b];
-    double val = 1.0;
-    for (int r = blk.r0; r < blk.r1; ++r) val = cov_term(1, 0.0, &th.v[cov[r + 4 * rows]], val);
+    const double val = diag_variance(blocks[b], cov, rows, th);
     L[k + (size_t)k * ldl] = chol ? sqrt(val) : val;
 }
 
