@@ -63,6 +63,26 @@ def phase_ms(enable=True, reset=False):
     return {k: float(out[i]) for i, k in enumerate(("sample", "beta_step", "theta_step", "refresh"))}
 
 
+_TRAJ = {"step": 0, "component": 1}
+
+
+def set_default_trajectory(mode):
+    """the trajectory mode new contexts start with ("step" or "component"), the contexts the one-shot exports create
+    included (include/glmmr_mcml_c.h glmmr_mcml_set_default_trajectory)"""
+    _lib.check(_lib.lib().glmmr_mcml_set_default_trajectory(_TRAJ[mode]))
+
+
+def get_default_trajectory():
+    return {v: k for k, v in _TRAJ.items()}[_lib.lib().glmmr_mcml_get_default_trajectory()]
+
+
+def traj_launches():
+    """k_cm_traj launches of this process so far, over all contexts (test hook, glmmr_mcml_dbg_traj_launches)"""
+    f = _lib.lib().glmmr_mcml_dbg_traj_launches
+    f.restype = C.c_longlong
+    return int(f())
+
+
 def rccl_unique_id():
     """128 opaque bytes from ncclGetUniqueId: made on rank 0, handed to every rank's Context.comm_init_rccl"""
     buf = (C.c_ubyte * 128)()
@@ -308,7 +328,7 @@ class Context:
 
     def last_kernels(self):
         """kernel family of the sampler's last (forward, backward) product"""
-        names = {-1: None, 0: "skinny", 1: "band", 2: "dlds", 3: "reg", 4: "sparse"}
+        names = {-1: None, 0: "skinny", 1: "band", 2: "dlds", 3: "reg", 4: "sparse", 5: "component"}
         f = C.c_int(); b = C.c_int()
         _lib.check(_lib.lib().glmmr_mcml_ctx_last_kernels(self._h, C.byref(f), C.byref(b)))
         return names[f.value], names[b.value]
@@ -332,6 +352,23 @@ class Context:
         keys = ("active", "factored", "W", "nnz", "nnz_z", "nnz_l", "nblk", "max_blk", "long_rows", "fused", "qrows", "ncb")
         d = dict(zip(keys, (int(v) for v in out)))
         for k in ("active", "factored", "long_rows"):
+            d[k] = bool(d[k])
+        return d
+
+    def set_trajectory(self, mode):
+        """how hmc_sample runs a trajectory on the sparse operator: "step" (a forward and a backward launch per leapfrog
+        step) or "component" (csrc/hmc_traj.h: one launch per proposal, where the component plan is feasible)"""
+        _lib.check(_lib.lib().glmmr_mcml_ctx_set_trajectory(self._h, _TRAJ[mode]))
+
+    def component_plan(self, chains):
+        """the component-local trajectory path as the next hmc_sample with `chains` chains would take it, valid after
+        update_L (test hook, include/glmmr_mcml_c.h glmmr_mcml_dbg_component_plan)"""
+        out = (C.c_longlong * 11)()
+        _lib.check(_lib.lib().glmmr_mcml_dbg_component_plan(self._h, int(chains), out))
+        keys = ("requested", "feasible", "used", "ncomp", "max_vars", "max_rows", "empty_comps", "nitems", "waves_per_item",
+                "cap_vars", "lds_bytes_per_workgroup")
+        d = dict(zip(keys, (int(v) for v in out)))
+        for k in ("requested", "feasible", "used"):
             d[k] = bool(d[k])
         return d
 

@@ -1,6 +1,7 @@
 // cabi.hip -- the extern "C" boundary (include/glmmr_mcml_c.h).
 #include "../../include/glmmr_mcml_c.h"
 #include "ctx.h"
+#include <atomic>
 #include <random>
 #include "sparse_plan.h"
 
@@ -14,6 +15,20 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
 int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nuts_opts* o, uint64_t seed, uint32_t iter_idx,
                 int* depth_out, int* nleap_out, double* eps_out, double* accept_out, glmmr_mcml_nuts_diag* diag,
                 int* ncols_out);
+}
+
+// process-wide default of Ctx::traj_mode: -1 until first asked, then GLMMR_MCML_TRAJ=component|step (read once) or 0
+static std::atomic<int> g_default_traj{-1};
+static int default_trajectory()
+{
+    int v = g_default_traj.load();
+    if (v < 0) {
+        const char* e = getenv("GLMMR_MCML_TRAJ");
+        int unset = -1;
+        g_default_traj.compare_exchange_strong(unset, (e && !strcmp(e, "component")) ? 1 : 0);     // a set_default that raced us wins
+        v = g_default_traj.load();
+    }
+    return v;
 }
 
 static int flink_of(const char* family, const char* link)
@@ -69,6 +84,7 @@ extern "C" int glmmr_mcml_ctx_create(const glmmr_mcml_problem* p, const glmmr_mc
         if (e != hipSuccess) { set_error("hipStreamCreate: %s", hipGetErrorString(e)); return fail(MCML_EHIP); }
         c.own_stream = true;
     }
+    c.traj_mode = default_trajectory();
     c.rank = o ? o->rank : 0;
     c.world = (o && o->world > 0) ? o->world : 1;
     c.reduce = o ? (reduce_fn)o->reduce : nullptr;
@@ -217,6 +233,43 @@ extern "C" int glmmr_mcml_dbg_sparse_plan(glmmr_mcml_ctx* h, int chains, long lo
     if (!sp.active) return MCML_OK;
     out12[1] = sp.factored ? 1 : 0; out12[2] = sp.W; out12[3] = sp.nnz; out12[4] = sp.nnz_z; out12[5] = sp.nnz_l;
     out12[6] = sp.nblk; out12[7] = sp.max_blk; out12[8] = cm_long_rows(c) ? 1 : 0; out12[9] = cm_fuse_width(c);
+    return MCML_OK;
+}
+
+extern "C" int glmmr_mcml_set_default_trajectory(int mode)
+{
+    MCML_REQUIRE(mode == 0 || mode == 1, "set_default_trajectory: mode must be 0 (per step) or 1 (component)");
+    g_default_traj.store(mode);
+    return MCML_OK;
+}
+
+extern "C" int glmmr_mcml_get_default_trajectory(void) { return default_trajectory(); }
+
+namespace mcml { long long cm_traj_launch_count(); }
+extern "C" long long glmmr_mcml_dbg_traj_launches(void) { return cm_traj_launch_count(); }
+
+extern "C" int glmmr_mcml_ctx_set_trajectory(glmmr_mcml_ctx* h, int mode)
+{
+    MCML_REQUIRE(h && (mode == 0 || mode == 1), "set_trajectory: mode must be 0 (per step) or 1 (component)");
+    h->c.traj_mode = mode;
+    return MCML_OK;
+}
+
+// read-only: the component-local trajectory path as the next hmc_sample call with `chains` chains would take it
+extern "C" int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* h, int chains, long long* out11)
+{
+    MCML_REQUIRE(h && chains >= 1 && out11, "dbg_component_plan: bad argument");
+    const Ctx& c = h->c;
+    const ComponentPlan& p = c.cp.plan;
+    for (int i = 0; i < 11; ++i) out11[i] = 0;
+    out11[0] = c.traj_mode; out11[9] = CP_MAX_VARS;
+    if (!c.sp.active) return MCML_OK;
+    const bool feasible = c.cp.ready && p.feasible;
+    out11[1] = feasible ? 1 : 0; out11[2] = (feasible && c.traj_mode == 1) ? 1 : 0;
+    out11[3] = p.ncomp; out11[4] = p.max_vars; out11[5] = p.max_rows; out11[6] = p.empty_comps;
+    if (!feasible) return MCML_OK;
+    const int waves = cp_waves(p, cp_forced_waves());
+    out11[7] = p.nitems(); out11[8] = waves; out11[10] = cp_lds_bytes(p.max_vars, waves);
     return MCML_OK;
 }
 

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "covspec.h"
 #include "band_plan.h"
+#include "component_plan.h"
 
 namespace mcml {
 
@@ -17,7 +18,7 @@ constexpr int SMALL_BLOCK = 32;  // blocks up to this size are factorised one wa
 typedef int (*reduce_fn)(void* user, double* dev_buf, int n);
 
 // kernel family that served an HMC product (glmmr_mcml_ctx_last_kernels)
-enum { KERNEL_SKINNY = 0, KERNEL_BAND = 1, KERNEL_DLDS = 2, KERNEL_REG = 3, KERNEL_SPARSE = 4 };
+enum { KERNEL_SKINNY = 0, KERNEL_BAND = 1, KERNEL_DLDS = 2, KERNEL_REG = 3, KERNEL_SPARSE = 4, KERNEL_COMPONENT = 5 };
 
 // the sampler's step-count read-back (hmc.hip hmc_sample): a ring of host memory mapped into the device, written by
 // k_max_steps with (proposal sequence number << 32 | count), read by the host with plain loads; lives as long as the context
@@ -46,6 +47,7 @@ struct HmcState {
     DevBuf cm_part, cm_acc;     // chain-major path: partial sums (ll | lp | kin | ss), accept flags
     DevBuf cm_part_fwd;         // ... and the log-density partials the last forward product of a trajectory leaves (one per workgroup)
     DevMat LX, ZS;              // factored operator (SparseZL::factored): L X and Z' S, C x Q
+    DevBuf cp_part;             // component-local trajectories (hmc_traj.h): K0 | ll | lp | kin, one per (work item, chain)
 };
 
 // No-U-Turn sampler (nuts.h): edges, tree, node under construction and one stored node per tree level (Q x C each),
@@ -75,6 +77,14 @@ struct SparseZL {
     DevBuf row_end;                            // one past the last row of column q of L (= end of q's block)
     DevBuf blk_ptr;                            // first row of every covariance block, B + 1 entries (k_cm_Lcol_Lrow)
     int nblk = 0, max_blk = 0;
+};
+
+// the components of ZL's coupling graph and the work items of the trajectory kernel (component_plan.h, hmc_traj.h): the
+// pattern is fixed per model (built by sparse_zl_setup), the values follow L (model_update_L)
+struct ComponentDev {
+    ComponentPlan plan;
+    bool ready = false;                        // the device copies below are there
+    DevBuf item_ptr, var_ptr, vars, slot_ptr, slot_quarter, slot_i, slot_src, slot_d;
 };
 
 // HIP-event timing of the dominant kernels, on the stream they are launched on
@@ -196,6 +206,8 @@ struct Ctx {
     DevBuf z_idx, z_val;        // n x z_width (column-major)
     std::vector<int> h_zidx; std::vector<double> h_zval;   // host copy of the same
     SparseZL sp;
+    ComponentDev cp;
+    int traj_mode = 0;          // 0: a launch per leapfrog step; 1: component-local trajectories where feasible (hmc_traj.h)
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT
     bool l_foreign = false;     // L came from the caller (set_L), not from theta: it need not have the block pattern the
                                 // sparse ZL operator assumes; cleared as soon as L is regenerated from theta (mvn_gen_L)

@@ -14,6 +14,7 @@
 // log_prob(u) and log_grad(u) of the current state are cached from the step that
 // produced it instead of being recomputed (the reference recomputes them,
 // :64,82): same numbers, 2*steps GEMMs per proposal instead of 2*steps + 4.
+#include <atomic>
 #include <chrono>
 #include "../../include/glmmr_mcml_c.h"
 #include "ctx.h"
@@ -25,6 +26,7 @@
 #include "reduce.h"
 #include "rng.h"
 #include "hmc_cm.h"
+#include "hmc_traj.h"
 
 namespace mcml {
 
@@ -423,6 +425,46 @@ __global__ void k_hmc_diag(ChainArrays ca, int C, double* out)
 }
 
 // ------------------------------------------------------------------ host
+// component-local trajectories (hmc_traj.h): asked for, the sparse operator is active and every component fits the kernel
+static bool cm_traj_used(const Ctx& c) { return c.traj_mode == 1 && c.sp.active && c.cp.ready && c.cp.plan.feasible; }
+
+// k_cm_traj launches of this process, over all contexts (glmmr_mcml_dbg_traj_launches: the contexts the one-shot exports
+// create cannot be asked which kernels they ran)
+static std::atomic<long long> g_traj_launches{0};
+long long cm_traj_launch_count() { return g_traj_launches.load(); }
+
+// one proposal's trajectories of every (component, chain): ONE launch whatever the step counts
+static int cm_traj_launch(Ctx& c, const TrajArgs& a)
+{
+    const ComponentDev& cp = c.cp;
+    const CpDev m{cp.item_ptr.as<int>(), cp.var_ptr.as<int>(), cp.vars.as<int>(), cp.slot_ptr.as<int>(), cp.slot_quarter.as<int>(),
+                  cp.slot_i.as<int>(), cp.slot_d.d()};
+    const int waves = cp_waves(cp.plan, cp_forced_waves());
+    const int lds = cp_lds_bytes(cp.plan.max_vars, waves);
+    const dim3 grid(cp.plan.nitems(), cm_chain_blocks(a.C));
+#define MCML_TRAJ(FL)                                                                                                        \
+    do {                                                                                                                     \
+        if (waves == 4) {                                                                                                    \
+            MCML_TRY(ensure_dynamic_lds((const void*)k_cm_traj<FL, 4>, cp_lds_bytes(CP_MAX_VARS, 4)));                      \
+            hipLaunchKernelGGL((k_cm_traj<FL, 4>), grid, dim3(256), lds, c.stream, m, a);                                  \
+        } else {                                                                                                             \
+            MCML_TRY(ensure_dynamic_lds((const void*)k_cm_traj<FL, 1>, cp_lds_bytes(CP_MAX_VARS, 1)));                      \
+            hipLaunchKernelGGL((k_cm_traj<FL, 1>), grid, dim3(64), lds, c.stream, m, a);                                   \
+        }                                                                                                                    \
+    } while (0)
+    switch (c.flink) {
+    case 1: MCML_TRAJ(1); break;
+    case 3: MCML_TRAJ(3); break;
+    case 7: MCML_TRAJ(7); break;
+    case 12: MCML_TRAJ(12); break;
+    default: MCML_TRAJ(0); break;
+    }
+#undef MCML_TRAJ
+    MCML_HIP(hipGetLastError());
+    ++g_traj_launches;                           // launches that were actually enqueued
+    return MCML_OK;
+}
+
 static int hmc_alloc(Ctx& c, int C)
 {
     HmcState& h = c.hmc;
@@ -438,6 +480,7 @@ static int hmc_alloc(Ctx& c, int C)
         MCML_TRY(h.cm_part.ensure(sizeof(double) * (nchn + 3 * nchq + 4) * (size_t)h.V.ld));
         MCML_TRY(h.cm_acc.ensure(sizeof(int) * (size_t)round_up(C, 64)));
         if (c.sp.factored) { MCML_TRY(h.LX.alloc(C, c.Q)); MCML_TRY(h.ZS.alloc(C, c.Q)); }
+        if (cm_traj_used(c)) MCML_TRY(h.cp_part.ensure(sizeof(double) * 4 * (size_t)c.cp.plan.nitems() * h.V.ld));
         return MCML_OK;
     }
     MCML_TRY(h.V.alloc(c.Q, C)); MCML_TRY(h.R.alloc(c.Q, C)); MCML_TRY(h.UP.alloc(c.Q, C));
@@ -717,6 +760,16 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
     MCML_HIP(hipGetLastError());
     MCML_TRY(hmc_eval_state(c, var_par));
     if (C == 1 && o->warmup == 0) store(0, 0);
+    // component-local trajectories: one launch per proposal instead of the loop over the steps below
+    const bool traj = h.cm && cm_traj_used(c);
+    double* tpart = traj ? h.cp_part.d() : nullptr;
+    const size_t tstride = traj ? (size_t)c.cp.plan.nitems() * h.V.ld : 0;
+    if (traj) {                                 // xb follows beta: the records' copy of it
+        const int ns = c.cp.plan.nslots;
+        hipLaunchKernelGGL(k_cp_fill_xy, dim3((ns + 255) / 256), dim3(256), 0, c.stream, ns, c.cp.slot_i.as<int>(), c.xb.d(),
+                           c.y.d(), c.cp.slot_d.d());
+        MCML_HIP(hipGetLastError());
+    }
 
     int* d_maxs = c.scalars.as<int>() + 34;
     // The number of leapfrog iterations to launch is the largest step count over the chains, a device
@@ -761,6 +814,22 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
         }
     };
     bool pending_commit = false;                // sparse operator: the last decisions are applied by the next k_cm_propose
+    // the accepted chains' V <- UP, GRAD <- GRADP: folded into the next proposal's first pass unless V is read
+    // before that (a draw is stored after this proposal, or it is the last one)
+    auto commit_cm = [&](int it) {
+        const bool stores_now = (C == 1) ? (it >= o->warmup - 1) : (it >= o->warmup);
+        if (it + 1 < total && !stores_now) pending_commit = true;
+        else hipLaunchKernelGGL(k_cm_commit, dim3((C + 63) / 64, nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.UP.d(),
+                                h.GRADP.d(), h.V.ld, Q, C, h.cm_acc.as<int>());
+    };
+    auto store_draw = [&](int it) {
+        int col = -1, stride = 0;
+        if (C == 1) {
+            if (it == o->warmup - 1) col = 0;                      // samples.col(0) = u_, :142
+            else if (it >= o->warmup) col = it - o->warmup + 1;    // samples.col(i+1) = u_, :147
+        } else if (it >= o->warmup) { col = it - o->warmup; stride = d; }
+        if (col >= 0) store(stride, col);
+    };
     const int lf = h.cm ? cm_fuse_width(c) : 0; // factored operator: the backward pass of step s leaves LX for step s + 1
     const double t_setup = since(tc0);
     const auto tc1 = std::chrono::steady_clock::now();
@@ -772,6 +841,30 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
         const auto tp0 = std::chrono::steady_clock::now();
         if (it > 0 && timing) { const double d = since(tp_prev); if (d > t_slowest) t_slowest = d; }
         tp_prev = tp0;
+        if (traj) {
+            TrajArgs a{h.V.d(), h.GRAD.d(), h.UP.d(), h.GRADP.d(), h.V.ld, C, Q, cm_chain(ca), seed, (uint32_t)o->chain_offset,
+                       iter_idx, it, p_mom, pending_commit ? h.cm_acc.as<int>() : nullptr, o->lambda, o->max_steps, c.flink,
+                       var_par, glm_score_post(var_par, c.flink), tpart, tpart + tstride, tpart + 2 * tstride,
+                       tpart + 3 * tstride, h.V.ld, c.cp.plan.max_vars};
+            pending_commit = false;
+            c.prof.skip = (it & 3) != 0;
+            const int slot = c.prof.begin(c.stream, 0);     // counted (and timed) under the forward product's slot
+            const int rc = cm_traj_launch(c, a);
+            c.prof.end(c.stream, slot);
+            c.prof.skip = false;
+            c.prof.unchain();
+            MCML_TRY(rc);
+            const int ni = c.cp.plan.nitems();
+            hipLaunchKernelGGL((k_cm_accept_fin<true>), dim3((C + 63) / 64), dim3(256), 0, c.stream, tpart + tstride, tpart + 2 * tstride,
+                               tpart + 3 * tstride, ni, ni, h.V.ld, C, cm_chain(ca), o->target_accept,
+                               (it < o->warmup) && (it < o->adapt) ? 1 : 0, it, flags_out ? d_flags.as<uint8_t>() : nullptr,
+                               probs_out ? d_probs.d() : nullptr, h.cm_acc.as<int>(), tpart, ni, o->lambda, o->max_steps);
+            commit_cm(it);
+            store_draw(it);
+            MCML_HIP(hipGetLastError());
+            c.last_kernel[0] = c.last_kernel[1] = KERNEL_COMPONENT;
+            continue;
+        }
         if (h.cm) {
             const CmParts p = cm_parts(c);
             hipLaunchKernelGGL(k_cm_propose, dim3((C + 63) / 64, p.nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(),
@@ -835,27 +928,17 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
         if (h.cm) {
             const CmParts p = cm_parts(c);
             MCML_TRY(cm_logprob_partials(c, h.UP.d(), h.R.d(), var_par, true));
-            hipLaunchKernelGGL(k_cm_accept_fin, dim3((C + 63) / 64), dim3(256), 0, c.stream, h.cm_part_fwd.d(), p.lp, p.kin,
+            hipLaunchKernelGGL((k_cm_accept_fin<false>), dim3((C + 63) / 64), dim3(256), 0, c.stream, h.cm_part_fwd.d(), p.lp, p.kin,
                                cm_fwd_chunks(c), p.nchq, p.ldp, C, cm_chain(ca), o->target_accept, adapt, it,
                                flags_out ? d_flags.as<uint8_t>() : nullptr, probs_out ? d_probs.d() : nullptr,
-                               h.cm_acc.as<int>());
-            // the accepted chains' V <- UP, GRAD <- GRADP: folded into the next proposal's first pass unless V is read
-            // before that (a draw is stored after this proposal, or it is the last one)
-            const bool stores_now = (C == 1) ? (it >= o->warmup - 1) : (it >= o->warmup);
-            if (it + 1 < total && !stores_now) pending_commit = true;
-            else hipLaunchKernelGGL(k_cm_commit, dim3((C + 63) / 64, p.nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.UP.d(),
-                                    h.GRADP.d(), h.V.ld, Q, C, h.cm_acc.as<int>());
+                               h.cm_acc.as<int>(), (const double*)nullptr, 0, 0.0, 0);
+            commit_cm(it);
         } else
         MCML_FL_DISPATCH(c.flink, k_hmc_accept, dim3(C), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(), h.UP.d(),
                            h.GRADP.d(), h.V.ld, Q, h.MU.d(), h.MU.ld, n, c.y.d(), var_par, c.flink, ca,
                            o->target_accept, adapt, it, C, flags_out ? d_flags.as<uint8_t>() : nullptr,
                            probs_out ? d_probs.d() : nullptr);
-        int col = -1, stride = 0;
-        if (C == 1) {
-            if (it == o->warmup - 1) col = 0;                      // samples.col(0) = u_, :142
-            else if (it >= o->warmup) col = it - o->warmup + 1;    // samples.col(i+1) = u_, :147
-        } else if (it >= o->warmup) { col = it - o->warmup; stride = d; }
-        if (col >= 0) store(stride, col);
+        store_draw(it);
         MCML_HIP(hipGetLastError());
         mark(4, ta0);
     }

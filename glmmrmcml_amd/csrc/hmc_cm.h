@@ -533,17 +533,32 @@ __global__ __launch_bounds__(256) void k_cm_propose_fin(const double* part_ss, i
 }
 
 // new_proposal, second part (mhmcmc.h:80-117): the decision of every chain
+// TRAJ: after the component-local trajectory kernel (hmc_traj.h), whose partials are one per work item and which has no
+// k_cm_propose_fin before it: K0, the step count and the leapfrog total are set here too, from the step size the
+// trajectory ran with (part_k0, nchunk_k0, lambda, max_steps are read in this form only)
+template <bool TRAJ>
 __global__ __launch_bounds__(256) void k_cm_accept_fin(const double* part_ll, const double* part_lp, const double* part_kin,
                                                        int nchunk_n, int nchunk_q, int ldp, int C, CmChain ca,
                                                        double target_accept, int adapt, int it, uint8_t* flags,
-                                                       double* probs, int* accflag)
+                                                       double* probs, int* accflag, const double* part_k0, int nchunk_k0,
+                                                       double lambda, int max_steps)
 {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
     const int cc = c < C ? c : 0;
     const double a = cm_sum_chunks(part_ll, nchunk_n, ldp, cc);
     const double b = cm_sum_chunks(part_lp, nchunk_q, ldp, cc);
     const double kin = cm_sum_chunks(part_kin, nchunk_q, ldp, cc);
+    double k0 = 0.0;
+    if constexpr (TRAJ) k0 = cm_sum_chunks(part_k0, nchunk_k0, ldp, cc);
     if (threadIdx.x >= 64 || c >= C) return;
+    if constexpr (TRAJ) {                                         // k_cm_propose_fin
+        ca.K0[c] = 0.5 * k0;
+        double st = round(lambda / ca.e[c]);
+        if (!(st >= 1.0)) st = 1.0;
+        if (st > (double)max_steps) st = (double)max_steps;
+        ca.steps[c] = (int)st;
+        ca.leap[c] += (long long)st;
+    }
     const double l2 = a + b;
     const double lprt = 0.5 * kin, lpr = ca.K0[c], l1 = ca.lpcur[c];
     const double prob = fmin(1.0, exp(-l1 + lpr + l2 - lprt));

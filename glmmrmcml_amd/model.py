@@ -239,8 +239,22 @@ class ModelMCML:
         return dict(par=list(names), est=est, SE=SE, lower=est - _Z975 * SE, upper=est + _Z975 * SE)
 
     # ---- MCML ----------------------------------------------------------------------------------------------------
-    def MCML(self, y, start=None, se_method="approx", method="mcnr", sim_lik_step=False, verbose=True, tol=1e-2,
-             max_iter=30, sparse=False, sampler="full", options=None, seed=0, chains=1):
+    def MCML(self, y, *args, trajectory=None, **kwargs):
+        """_mcml below (its arguments, unchanged); trajectory ("step" / "component", None = leave the backend's default
+        alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  It becomes the backend's
+        process-wide default for the duration of the call -- the contexts the exports create inherit it -- and the previous
+        default is restored; do not run two fits with different choices in one process at the same time."""
+        if trajectory is None:
+            return self._mcml(y, *args, **kwargs)
+        prev = self._be.get_default_trajectory()
+        self._be.set_default_trajectory(trajectory)
+        try:
+            return self._mcml(y, *args, **kwargs)
+        finally:
+            self._be.set_default_trajectory(prev)
+
+    def _mcml(self, y, start=None, se_method="approx", method="mcnr", sim_lik_step=False, verbose=True, tol=1e-2,
+              max_iter=30, sparse=False, sampler="full", options=None, seed=0, chains=1):
         """ModelMCML$MCML (R6ModelExtMCML.R:103-594).  sampler: "full" = the usestan = FALSE branch (mcml_full);
         "stepwise" = the usestan = TRUE loop with mcmc_sample standing in for Stan, "nuts" = the same loop with
         gen_u_samples (the build's No-U-Turn sampler, csrc/nuts.h) in Stan's place.  seed / chains are the build's

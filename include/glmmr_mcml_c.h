@@ -223,7 +223,8 @@ int glmmr_mcml_ctx_profile(glmmr_mcml_ctx* ctx, int enable, int reset, double* o
 int glmmr_mcml_ctx_profile_launches(glmmr_mcml_ctx* ctx, long long* fwd, long long* bwd);
 /* kernel family that served the sampler's last forward / backward product: 0 streamed few-column kernel
  * (dgemm_skinny.h), 1 banded FP64 MFMA kernel (dgemm_band.h), 2 dense direct-to-LDS MFMA kernel (dgemm_dlds.h),
- * 3 register-staged MFMA kernel (dgemm_mfma.h), 4 sparse chain-major operator (hmc_cm.h); -1 none yet */
+ * 3 register-staged MFMA kernel (dgemm_mfma.h), 4 sparse chain-major operator (hmc_cm.h), 5 component-local trajectory
+ * kernel (hmc_traj.h, both entries); -1 none yet */
 int glmmr_mcml_ctx_last_kernels(glmmr_mcml_ctx* ctx, int* fwd, int* bwd);
 /* The banded kernel's work decomposition (csrc/band_plan.h) for `chains` columns of the sampler's forward (which = 0) or
  * backward (which = 1) product, read-only: out10 = [banded kernel selected for this operand, bands of 80 rows, K tiles
@@ -240,6 +241,25 @@ int glmmr_mcml_dbg_band_plan(glmmr_mcml_ctx* ctx, int which, int chains, int* ou
  * per-chain sums over the random effects, chain blocks of 64].  Entries 1-9 are 0 when the operator is not active.  The
  * decisions are taken by the functions the launch code calls (csrc/sparse_plan.h). */
 int glmmr_mcml_dbg_sparse_plan(glmmr_mcml_ctx* ctx, int chains, long long* out12);
+/* How hmc_sample runs a trajectory on the sparse operator: 0 = a forward and a backward launch per leapfrog step (the
+ * default), 1 = component-local trajectories (csrc/hmc_traj.h: one launch per proposal, every connected component of the
+ * coupling graph of ZL in LDS) where feasible -- the sparse operator active and no component above the kernel's cap;
+ * otherwise, and for the No-U-Turn sampler, the dense operators and the Laplace fits, the call changes nothing. */
+int glmmr_mcml_ctx_set_trajectory(glmmr_mcml_ctx* ctx, int mode);
+/* The mode new contexts start with, the ones the one-shot exports create included.  Initially GLMMR_MCML_TRAJ=component|step
+ * from the environment (read once), else 0.  The value is one atomic per process: a caller that flips it round a call
+ * (ModelMCML.MCML(trajectory=...)) must not run another fit in the same process at the same time. */
+int glmmr_mcml_set_default_trajectory(int mode);
+int glmmr_mcml_get_default_trajectory(void);
+/* The component plan (csrc/component_plan.h) as the next hmc_sample call with `chains` chains would use it, read-only, valid
+ * after update_L: out11 = [mode requested, feasible, used (= requested and feasible), components, most variables in one,
+ * most observations in one, components without an observation, work items, waves per work item (1 or 4; honours
+ * GLMMR_MCML_TRAJ_WAVES=1|4, the A/B switch of the two kernel forms, read per call), the cap on variables, LDS bytes
+ * per workgroup].  Entries 1-8 and 10 are 0 when the sparse operator is not active; 7, 8, 10 when not feasible. */
+int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* ctx, int chains, long long* out11);
+/* k_cm_traj launches of this process so far, over all contexts: tells whether a context that a one-shot export created
+ * internally took the component path. */
+long long glmmr_mcml_dbg_traj_launches(void);
 /* Host wall-clock time per phase of the MCML iterations run by this process since the last reset (csrc/trace.h):
  * out8 (nullable) = [sample, beta-step, theta-step, refresh] ms, then the four phase counts.  enable / reset as above. */
 int glmmr_mcml_dbg_phase_ms(int enable, int reset, double* out8);
