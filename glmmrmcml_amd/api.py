@@ -76,6 +76,43 @@ def get_default_trajectory():
     return {v: k for k, v in _TRAJ.items()}[_lib.lib().glmmr_mcml_get_default_trajectory()]
 
 
+_LA_OP = {"dense": 0, "component": 1}
+_LA_OP_NAME = {v: k for k, v in _LA_OP.items()}
+
+
+def set_default_la_operator(mode):
+    """the operator of the Laplace fits new contexts start with ("dense" or "component"), the contexts mcml_la /
+    mcml_la_nr create included (include/glmmr_mcml_c.h glmmr_mcml_set_default_la_operator)"""
+    _lib.check(_lib.lib().glmmr_mcml_set_default_la_operator(_LA_OP[mode]))
+
+
+def get_default_la_operator():
+    return _LA_OP_NAME[_lib.lib().glmmr_mcml_get_default_la_operator()]
+
+
+def la_component_launches():
+    """k_lac_factor launches of this process so far, over all contexts (test hook, glmmr_mcml_dbg_la_component_launches)"""
+    f = _lib.lib().glmmr_mcml_dbg_la_component_launches
+    f.restype = C.c_longlong
+    return int(f())
+
+
+class _default_la_operator:
+    """operator=None leaves the process default alone; otherwise it is set for the duration of a call and restored"""
+
+    def __init__(self, operator):
+        self.operator = operator
+
+    def __enter__(self):
+        if self.operator is not None:
+            self.prev = get_default_la_operator()
+            set_default_la_operator(self.operator)
+
+    def __exit__(self, *a):
+        if self.operator is not None:
+            set_default_la_operator(self.prev)
+
+
 def traj_launches():
     """k_cm_traj launches of this process so far, over all contexts (test hook, glmmr_mcml_dbg_traj_launches)"""
     f = _lib.lib().glmmr_mcml_dbg_traj_launches
@@ -372,6 +409,19 @@ class Context:
             d[k] = bool(d[k])
         return d
 
+    def set_la_operator(self, mode):
+        """how mcml_la / la_probe run on this context: "dense" (the dense ZL and M = ZL' W ZL + I) or "component"
+        (csrc/la_comp.h: M one connected component at a time on the sparse operator, where the component plan is feasible)"""
+        _lib.check(_lib.lib().glmmr_mcml_ctx_set_la_operator(self._h, _LA_OP[mode]))
+
+    def la_plan(self):
+        """what was asked for and what the last Laplace call on this context ran (test hook, include/glmmr_mcml_c.h
+        glmmr_mcml_dbg_la_plan)"""
+        out = (C.c_longlong * 8)()
+        _lib.check(_lib.lib().glmmr_mcml_dbg_la_plan(self._h, out))
+        return dict(requested=_LA_OP_NAME[int(out[0])], operator=_LA_OP_NAME[int(out[1])], ncomp=int(out[2]),
+                    max_vars=int(out[3]), max_rows=int(out[4]), launches=int(out[5]), dense_bytes=int(out[6]))
+
     def mcml_optim(self, start, trace=0, mcnr=False, maxfun=0, theta_batch=0):
         start = _f(start).ravel(); R = self.npar()
         b = np.zeros(self.P); t = np.zeros(R); sg = C.c_double()
@@ -415,8 +465,17 @@ class Context:
         return dict(beta=b, theta=t, sigma=sg.value, converged=bool(conv.value), iters=it.value,
                     accept_rate=d.accept_rate, mean_e=d.mean_e, leapfrog_total=d.leapfrog_total)
 
-    def mcml_la(self, start, usehess=False, tol=1e-3, verbose=False, trace=0, maxiter=10, nr=False, maxfun=0):
-        """mcml_la / mcml_la_nr on the resident model (src/mcml_la.cpp:28-290)"""
+    def mcml_la(self, start, usehess=False, tol=1e-3, verbose=False, trace=0, maxiter=10, nr=False, maxfun=0,
+                operator=None):
+        """mcml_la / mcml_la_nr on the resident model (src/mcml_la.cpp:28-290); operator ("dense" / "component", None =
+        the context's setting): set_la_operator for this call only"""
+        if operator is not None:
+            prev = self.la_plan()["requested"]
+            self.set_la_operator(operator)
+            try:
+                return self.mcml_la(start, usehess, tol, verbose, trace, maxiter, nr, maxfun)
+            finally:
+                self.set_la_operator(prev)
         start = _f(start).ravel(); R = self.npar()
         b = np.zeros(self.P); t = np.zeros(R); sg = C.c_double(); conv = C.c_int(); it = C.c_int()
         se = np.zeros(start.size); u = np.zeros(self.Q)
@@ -500,17 +559,20 @@ def _la_call(fn, cov, data, eff_range, Z, X, y, family, link, start, usehess, to
 
 
 def mcml_la(cov, data, eff_range, Z, X, y, family, link, start, usehess=False, tol=1e-3, verbose=True, trace=0,
-            maxiter=10, maxfun=0):
-    """mcml_la(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:28-155)"""
-    return _la_call(_lib.lib().glmmr_mcml_la, cov, data, eff_range, Z, X, y, family, link, start, usehess, tol,
-                    verbose, trace, maxiter, maxfun)
+            maxiter=10, maxfun=0, operator=None):
+    """mcml_la(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:28-155).  operator ("dense" / "component",
+    None = the process default): the default operator of the Laplace fits for the duration of the call"""
+    with _default_la_operator(operator):
+        return _la_call(_lib.lib().glmmr_mcml_la, cov, data, eff_range, Z, X, y, family, link, start, usehess, tol,
+                        verbose, trace, maxiter, maxfun)
 
 
 def mcml_la_nr(cov, data, eff_range, Z, X, y, family, link, start, usehess=False, tol=1e-3, verbose=True, trace=0,
-               maxiter=10, maxfun=0):
-    """mcml_la_nr(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:174-290)"""
-    return _la_call(_lib.lib().glmmr_mcml_la_nr, cov, data, eff_range, Z, X, y, family, link, start, usehess, tol,
-                    verbose, trace, maxiter, maxfun)
+               maxiter=10, maxfun=0, operator=None):
+    """mcml_la_nr(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:174-290); operator as mcml_la"""
+    with _default_la_operator(operator):
+        return _la_call(_lib.lib().glmmr_mcml_la_nr, cov, data, eff_range, Z, X, y, family, link, start, usehess, tol,
+                        verbose, trace, maxiter, maxfun)
 
 
 def mcmc_sample(Z, L, X, y, beta, family, link, warmup, nsamp, lambda_, var_par=1, trace=0, refresh=500,

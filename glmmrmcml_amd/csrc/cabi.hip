@@ -31,6 +31,20 @@ static int default_trajectory()
     return v;
 }
 
+// the same for Ctx::la_mode: GLMMR_MCML_LA=component|dense (read once) or 0
+static std::atomic<int> g_default_la{-1};
+static int default_la_operator()
+{
+    int v = g_default_la.load();
+    if (v < 0) {
+        const char* e = getenv("GLMMR_MCML_LA");
+        int unset = -1;
+        g_default_la.compare_exchange_strong(unset, (e && !strcmp(e, "component")) ? 1 : 0);
+        v = g_default_la.load();
+    }
+    return v;
+}
+
 static int flink_of(const char* family, const char* link)
 {
     // mcmlmodel.h:74-87 string_to_case
@@ -85,6 +99,7 @@ extern "C" int glmmr_mcml_ctx_create(const glmmr_mcml_problem* p, const glmmr_mc
         c.own_stream = true;
     }
     c.traj_mode = default_trajectory();
+    c.la_mode = default_la_operator();
     c.rank = o ? o->rank : 0;
     c.world = (o && o->world > 0) ? o->world : 1;
     c.reduce = o ? (reduce_fn)o->reduce : nullptr;
@@ -270,6 +285,36 @@ extern "C" int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* h, int chains, long
     if (!feasible) return MCML_OK;
     const int waves = cp_waves(p, cp_forced_waves());
     out11[7] = p.nitems(); out11[8] = waves; out11[10] = cp_lds_bytes(p.max_vars, waves);
+    return MCML_OK;
+}
+
+extern "C" int glmmr_mcml_set_default_la_operator(int mode)
+{
+    MCML_REQUIRE(mode == 0 || mode == 1, "set_default_la_operator: mode must be 0 (dense) or 1 (component)");
+    g_default_la.store(mode);
+    return MCML_OK;
+}
+
+extern "C" int glmmr_mcml_get_default_la_operator(void) { return default_la_operator(); }
+
+extern "C" int glmmr_mcml_ctx_set_la_operator(glmmr_mcml_ctx* h, int mode)
+{
+    MCML_REQUIRE(h && (mode == 0 || mode == 1), "set_la_operator: mode must be 0 (dense) or 1 (component)");
+    h->c.la_mode = mode;
+    return MCML_OK;
+}
+
+namespace mcml { long long la_component_launch_count(); }
+extern "C" long long glmmr_mcml_dbg_la_component_launches(void) { return la_component_launch_count(); }
+
+// read-only: what was asked for and what the last Laplace call on this context did
+extern "C" int glmmr_mcml_dbg_la_plan(glmmr_mcml_ctx* h, long long* out8)
+{
+    MCML_REQUIRE(h && out8, "dbg_la_plan: null argument");
+    const Ctx& c = h->c;
+    const ComponentPlan& p = c.cp.plan;
+    const long long v[8] = {c.la_mode, c.la_last_op, p.ncomp, p.max_vars, p.max_rows, c.la_launches, c.la_dense_bytes, 0};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
     return MCML_OK;
 }
 

@@ -209,6 +209,9 @@ struct Ctx {
     ComponentDev cp;
     int traj_mode = 0;          // 0: a launch per leapfrog step; 1: component-local trajectories where feasible (hmc_traj.h)
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT
+    int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (la_comp.h)
+    int la_last_op = 0;         // what the last Laplace call ran (0 dense, 1 component), its k_lac_factor launches and the
+    long long la_launches = 0, la_dense_bytes = 0;   // bytes of M + ZLTW + ZL + ZLT it allocated / worked on (dbg_la_plan)
     bool l_foreign = false;     // L came from the caller (set_L), not from theta: it need not have the block pattern the
                                 // sparse ZL operator assumes; cleared as soon as L is regenerated from theta (mvn_gen_L)
     CovSpec cov;
@@ -325,6 +328,7 @@ int allreduce_host(Ctx& c, double* vals, int n);             // comm.hip
 int model_update_beta(Ctx& c, const double* beta);          // xb = X beta
 int model_update_zu(Ctx& c);                                // ZU = Z U (cached)
 int model_update_L(Ctx& c);                                 // ZL = Z L, ZLT (dense) or the ELL/CSR pair (sparse)
+int model_sparse_setup(Ctx& c);                             // the sparse ZL pattern and the component plan, if not built yet
 int model_loglik_sum(Ctx& c, double var_par, double* sum_out);
 int model_mcnr_stats(Ctx& c, double var_par, double* stats /* P*P + P + 2 */);
 int mcnr_finish(int P, const double* stats, const double* beta, double* beta_out, double* sigma_out);

@@ -5,7 +5,9 @@
 //   state     mcmlModel ctor, update_W(i, useL), log_grad(v, usezl=false) mcmlmodel.h:51-134,156-168
 // Every objective evaluation runs on the device (Z, X, y, L, ZL resident) and returns one
 // scalar; the Q x Q x n product ZL' W ZL and its Cholesky use the same MFMA GEMM / potrf as
-// the MCML path, the vector-sized pieces are plain streaming kernels.
+// the MCML path, the vector-sized pieces are plain streaming kernels.  Opt-in (glmmr_mcml_ctx_set_la_operator, DESIGN.md
+// 5.5): on a block-structured design the same statements run on the sparse ZL operator and factorise M component by
+// component (la_comp.h); nothing of size Q x n or Q x Q is then built per evaluation.
 //
 // Reference behaviour reproduced on purpose (also restated in oracle/la.py):
 //   * v = u column 0 is the whitened effect, yet update_W(useL = false) forms Z v and
@@ -21,11 +23,17 @@
 #include "ctx.h"
 #include "dgemm_mfma.h"
 #include "glm.h"
+#include "la_comp.h"
 #include "optim.h"
 #include "reduce.h"
+#include <atomic>
 #include <cmath>
 
 namespace mcml {
+
+// k_lac_factor launches of this process, over all contexts (glmmr_mcml_dbg_la_component_launches)
+static std::atomic<long long> g_lac_launches{0};
+long long la_component_launch_count() { return g_lac_launches.load(); }
 
 static bool la_is_gaussian(int flink) { return flink == 7 || flink == 8; }
 static bool la_has_var_par(int flink) { return flink == 7 || flink == 8 || flink == 12; }
@@ -186,8 +194,21 @@ struct LaFit {
     DevBuf v, W, zv, tmpn, tmpn2, tmpn3, tmpq, tmpq2, part, small;
     DevMat M, ZLTW, D0;
     std::vector<double> hv;                         // host copy of v
+    bool comp = false;                              // the component operator (la_comp.h) instead of the dense ZL / M
+    DevBuf lac_ld;                                  // its per-component log-determinants
+    size_t zl_bytes0 = 0;                           // what c.ZL + c.ZLT held when the call began
 
-    LaFit(Ctx& ctx) : c(ctx), n(ctx.n), Q(ctx.Q), P(ctx.P), R(ctx.cov.npar), flink(ctx.flink), link_code(ctx.link_code) {}
+    LaFit(Ctx& ctx) : c(ctx), n(ctx.n), Q(ctx.Q), P(ctx.P), R(ctx.cov.npar), flink(ctx.flink), link_code(ctx.link_code)
+    {
+        zl_bytes0 = c.ZL.buf.bytes + c.ZLT.buf.bytes;
+        c.la_last_op = 0; c.la_launches = 0; c.la_dense_bytes = 0;
+    }
+    // glmmr_mcml_dbg_la_plan: the dense matrices this call allocated (component) or worked on (dense)
+    ~LaFit()
+    {
+        const size_t zl = c.ZL.buf.bytes + c.ZLT.buf.bytes;
+        c.la_dense_bytes = (long long)(M.buf.bytes + ZLTW.buf.bytes + (comp ? zl - zl_bytes0 : zl));
+    }
 
     int nblk() const { int b = (n + 255) / 256; return b > 1024 ? 1024 : (b < 1 ? 1 : b); }
 
@@ -210,7 +231,15 @@ struct LaFit {
         MCML_TRY(part.ensure(sizeof(double) * 1100));
         MCML_TRY(small.ensure(sizeof(double) * (size_t)(P * P + P + 16)));
         MCML_HIP(hipMemsetAsync(v.p, 0, sizeof(double) * (size_t)(Q + 64), c.stream));
-        c.no_sparse_zl = true;                                    // this path works on the dense ZL
+        // the component operator: asked for, and the model has the sparse ZL with a feasible component plan (L always
+        // comes from theta here: gen_L).  Otherwise, silently, the dense ZL as ever
+        if (c.la_mode == 1) {
+            MCML_TRY(model_sparse_setup(c));
+            comp = c.sp.possible && c.cp.ready && c.cp.plan.feasible;
+        }
+        if (comp) MCML_TRY(lac_ld.ensure(sizeof(double) * (size_t)c.cp.plan.ncomp));
+        c.la_last_op = comp ? 1 : 0;
+        c.no_sparse_zl = !comp;                                   // the dense path works on the dense ZL
         // D_ = L L' at the starting theta (mcmlmodel.h:71); genD(chol = false) gives it directly
         MCML_TRY(mvn_gen_L(c, theta.data(), false));
         MCML_TRY(D0.alloc(Q, Q));
@@ -226,6 +255,7 @@ struct LaFit {
     {
         MCML_TRY(mvn_gen_L(c, th, true));
         MCML_TRY(model_update_L(c));
+        MCML_REQUIRE(!comp || c.sp.active, "mcml_la: the sparse ZL operator did not follow L");
         model_L_valid = false;
         return MCML_OK;
     }
@@ -251,6 +281,12 @@ struct LaFit {
     // out = ZL v from the current c.ZLT (Q x n): column i of ZLT is row i of ZL
     int zl_times_v(double* out)
     {
+        if (comp) {
+            hipLaunchKernelGGL(k_lac_rows_times_v, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.sp.ell_col.as<int>(),
+                               c.sp.ell_val.d(), n, c.sp.W, v.d(), out);
+            MCML_HIP(hipGetLastError());
+            return MCML_OK;
+        }
         hipLaunchKernelGGL(k_la_gemv_t, dim3((n + 3) / 4), dim3(256), 0, c.stream, c.ZLT.d(), c.ZLT.ld, Q, n, v.d(), out,
                            1.0, 0.0);
         MCML_HIP(hipGetLastError());
@@ -258,6 +294,12 @@ struct LaFit {
     }
     int z_times_v(double* out)
     {
+        if (comp) {
+            hipLaunchKernelGGL(k_lac_rows_times_v, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.z_idx.as<int>(),
+                               c.z_val.d(), n, c.z_width, v.d(), out);
+            MCML_HIP(hipGetLastError());
+            return MCML_OK;
+        }
         hipLaunchKernelGGL(k_la_gemv_n, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.Z.d(), c.Z.ld, n, Q, v.d(), out);
         MCML_HIP(hipGetLastError());
         return MCML_OK;
@@ -317,8 +359,39 @@ struct LaFit {
         MCML_HIP(hipGetLastError());
         return MCML_OK;
     }
+    // every M_c built and factorised from the current record values and W (la_comp.h); with g, x = M^-1 g as well
+    int lac_factor(const double* g, double* x)
+    {
+        const ComponentDev& cp = c.cp;
+        LacArgs a{cp.var_ptr.as<int>(), cp.vars.as<int>(), cp.slot_ptr.as<int>(), cp.slot_i.as<int>(), cp.slot_d.d(), W.d(),
+                  cp.plan.ncomp, g, x, lac_ld.d(), c.errflag()};
+        hipLaunchKernelGGL(k_lac_factor, dim3((cp.plan.ncomp + LAC_WAVES - 1) / LAC_WAVES), dim3(64 * LAC_WAVES), 0, c.stream, a);
+        MCML_HIP(hipGetLastError());
+        ++c.la_launches; ++g_lac_launches;
+        return MCML_OK;
+    }
+    // a non-positive pivot of some M_c, as potrf_lower_checked reports one of M; synchronises the stream
+    int lac_check()
+    {
+        int flag = 0;
+        MCML_TRY(copy_d2h(&flag, c.errflag(), sizeof(int), c.stream));
+        MCML_HIP(hipStreamSynchronize(c.stream));
+        if (flag) {
+            MCML_HIP(hipMemsetAsync(c.errflag(), 0, sizeof(int), c.stream));
+            set_error("mcml_la: ZL' W ZL + I is not positive definite");
+            return MCML_ENOTPD;
+        }
+        return MCML_OK;
+    }
     int logdet_M(double* out)
     {
+        if (comp) {
+            MCML_TRY(lac_factor(nullptr, nullptr));
+            hipLaunchKernelGGL(k_la_sum, dim3(1), dim3(256), 0, c.stream, lac_ld.d(), c.cp.plan.ncomp, small.d() + 2);
+            MCML_HIP(hipGetLastError());
+            MCML_TRY(copy_d2h(out, small.d() + 2, sizeof(double), c.stream));
+            return lac_check();
+        }
         MCML_TRY(build_M());
         int rc = potrf_lower_checked(c, M.d(), Q, M.ld);
         if (rc) return rc;
@@ -438,15 +511,26 @@ struct LaFit {
         std::vector<double> st((size_t)P * P + P), resid(n);
         MCML_TRY(copy_d2h(st.data(), small.p, sizeof(double) * st.size(), c.stream));
         MCML_TRY(copy_d2h(resid.data(), tmpn2.p, sizeof(double) * (size_t)n, c.stream));
-        // vgrad = -D0 v + post * ZL' score
-        hipLaunchKernelGGL(k_la_gemv_t, dim3((Q + 3) / 4), dim3(256), 0, c.stream, c.ZL.d(), c.ZL.ld, n, Q, tmpn.d(), tmpq.d(),
-                           glm_score_post(var_par, flink), 0.0);
-        hipLaunchKernelGGL(k_la_gemv_t, dim3((Q + 3) / 4), dim3(256), 0, c.stream, D0.d(), D0.ld, Q, Q, v.d(), tmpq.d(), -1.0, 1.0);
-        MCML_HIP(hipGetLastError());
-        // vincr = (ZL' W ZL + I)^-1 vgrad
-        MCML_TRY(build_M());
-        MCML_TRY(potrf_lower_checked(c, M.d(), Q, M.ld));
-        MCML_TRY(potrs_lower_vec(c, M.d(), M.ld, Q, tmpq.d(), tmpq2.d()));
+        if (comp) {
+            // vgrad = -D0 v + post * ZL' score (D0 by covariance blocks), vincr = M^-1 vgrad component by component
+            hipLaunchKernelGGL(k_lac_vgrad, dim3((Q + 255) / 256), dim3(256), 0, c.stream, c.sp.csr_ptr.as<int>(),
+                               c.sp.csr_i.as<int>(), c.sp.csr_val.d(), tmpn.d(), glm_score_post(var_par, flink), D0.d(), D0.ld,
+                               c.sp.row_start.as<int>(), c.sp.row_end.as<int>(), v.d(), Q, tmpq2.d());
+            MCML_HIP(hipGetLastError());
+            MCML_TRY(lac_factor(tmpq2.d(), tmpq.d()));
+            MCML_TRY(lac_check());
+        } else {
+            // vgrad = -D0 v + post * ZL' score
+            hipLaunchKernelGGL(k_la_gemv_t, dim3((Q + 3) / 4), dim3(256), 0, c.stream, c.ZL.d(), c.ZL.ld, n, Q, tmpn.d(),
+                               tmpq.d(), glm_score_post(var_par, flink), 0.0);
+            hipLaunchKernelGGL(k_la_gemv_t, dim3((Q + 3) / 4), dim3(256), 0, c.stream, D0.d(), D0.ld, Q, Q, v.d(), tmpq.d(),
+                               -1.0, 1.0);
+            MCML_HIP(hipGetLastError());
+            // vincr = (ZL' W ZL + I)^-1 vgrad
+            MCML_TRY(build_M());
+            MCML_TRY(potrf_lower_checked(c, M.d(), Q, M.ld));
+            MCML_TRY(potrs_lower_vec(c, M.d(), M.ld, Q, tmpq.d(), tmpq2.d()));
+        }
         hipLaunchKernelGGL(k_la_axpy, dim3((Q + 255) / 256), dim3(256), 0, c.stream, v.d(), tmpq.d(), 1.0, Q);
         MCML_HIP(hipGetLastError());
         MCML_TRY(get_v());                                        // also synchronises st / resid
@@ -589,7 +673,8 @@ struct LaFit {
     }
 };
 
-// the Laplace path forces the dense ZL and leaves c.L at an arbitrary theta: restore / invalidate on every exit
+// the Laplace path forces the dense ZL (unless it runs the component operator) and leaves c.L at an arbitrary theta:
+// restore / invalidate on every exit
 struct LaScope {
     Ctx& c;
     explicit LaScope(Ctx& ctx) : c(ctx) {}

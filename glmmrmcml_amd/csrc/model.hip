@@ -287,6 +287,13 @@ static int sparse_zl_setup(Ctx& c)
     return MCML_OK;
 }
 
+int model_sparse_setup(Ctx& c)
+{
+    MCML_REQUIRE(c.n > 0, "sparse_setup: no model");
+    if (!c.sp.built) MCML_TRY(sparse_zl_setup(c));
+    return MCML_OK;
+}
+
 // ZL_ = Z * L (mcmlmodel.h:104-106): dense with its transpose (so that both HMC products read
 // their A operand M-contiguous), or the ELL/CSR pair when ZL is sparse
 int model_update_L(Ctx& c)

@@ -388,7 +388,20 @@ class ModelMCML:
                        re_samps=dsamps, iter=it, warnings=warnings, theta=theta)
 
     # ---- LA ------------------------------------------------------------------------------------------------------
-    def LA(self, y, start=None, method="nloptim", use_hess=False, verbose=False, maxfun=0):
+    def LA(self, y, *args, operator=None, **kwargs):
+        """_la below (its arguments, unchanged); operator ("dense" / "component", None = leave the backend's default
+        alone): how the Laplace fit forms and factorises ZL' W ZL + I (csrc/la_comp.h).  It becomes the backend's default
+        for the duration of the call and is restored afterwards"""
+        if operator is None:
+            return self._la(y, *args, **kwargs)
+        prev = self._be.get_default_la_operator()
+        self._be.set_default_la_operator(operator)
+        try:
+            return self._la(y, *args, **kwargs)
+        finally:
+            self._be.set_default_la_operator(prev)
+
+    def _la(self, y, start=None, method="nloptim", use_hess=False, verbose=False, maxfun=0):
         """ModelMCML$LA (R6ModelExtMCML.R:627-845): mcml_la ("nloptim") or mcml_la_nr ("nr"), tol fixed at 1e-2"""
         if method not in ("nloptim", "nr"):
             raise ValueError("method should be either nr or nloptim")

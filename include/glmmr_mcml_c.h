@@ -260,6 +260,22 @@ int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* ctx, int chains, long long* ou
 /* k_cm_traj launches of this process so far, over all contexts: tells whether a context that a one-shot export created
  * internally took the component path. */
 long long glmmr_mcml_dbg_traj_launches(void);
+/* The operator of the Laplace fits (glmmr_mcml_ctx_la, glmmr_mcml_la, glmmr_mcml_la_nr): 0 = the dense ZL and the dense
+ * Q x Q matrix M = ZL' W ZL + I (the default), 1 = the component operator (csrc/la_comp.h): on the sparse ZL operator, M
+ * built, factorised and solved one connected component of ZL's coupling graph at a time -- where the sparse operator is
+ * possible and no component is above the kernel's cap; otherwise the call changes nothing. */
+int glmmr_mcml_ctx_set_la_operator(glmmr_mcml_ctx* ctx, int mode);
+/* The mode new contexts start with, the ones glmmr_mcml_la / glmmr_mcml_la_nr create included.  Initially
+ * GLMMR_MCML_LA=component|dense from the environment (read once), else 0.  One atomic per process, as the trajectory default. */
+int glmmr_mcml_set_default_la_operator(int mode);
+int glmmr_mcml_get_default_la_operator(void);
+/* out8 = [mode requested, operator the last Laplace call on this context ran (0 dense, 1 component), components, most
+ * variables in one, most observations in one (0 until the sparse operator has been set up), k_lac_factor launches of that
+ * call, bytes of M + ZLTW + ZL + ZLT that call allocated (component) or worked on (dense), 0] */
+int glmmr_mcml_dbg_la_plan(glmmr_mcml_ctx* ctx, long long* out8);
+/* k_lac_factor launches of this process so far, over all contexts: tells whether a context that glmmr_mcml_la /
+ * glmmr_mcml_la_nr created internally took the component operator. */
+long long glmmr_mcml_dbg_la_component_launches(void);
 /* Host wall-clock time per phase of the MCML iterations run by this process since the last reset (csrc/trace.h):
  * out8 (nullable) = [sample, beta-step, theta-step, refresh] ms, then the four phase counts.  enable / reset as above. */
 int glmmr_mcml_dbg_phase_ms(int enable, int reset, double* out8);
