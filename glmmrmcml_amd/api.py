@@ -76,12 +76,12 @@ def get_default_trajectory():
     return {v: k for k, v in _TRAJ.items()}[_lib.lib().glmmr_mcml_get_default_trajectory()]
 
 
-_LA_OP = {"dense": 0, "component": 1}
+_LA_OP = {"dense": 0, "component": 1, "component_wide": 2}
 _LA_OP_NAME = {v: k for k, v in _LA_OP.items()}
 
 
 def set_default_la_operator(mode):
-    """the operator of the Laplace fits new contexts start with ("dense" or "component"), the contexts mcml_la /
+    """the operator of the Laplace fits new contexts start with ("dense", "component" or "component_wide"), the contexts mcml_la /
     mcml_la_nr create included (include/glmmr_mcml_c.h glmmr_mcml_set_default_la_operator)"""
     _lib.check(_lib.lib().glmmr_mcml_set_default_la_operator(_LA_OP[mode]))
 
@@ -410,17 +410,20 @@ class Context:
         return d
 
     def set_la_operator(self, mode):
-        """how mcml_la / la_probe run on this context: "dense" (the dense ZL and M = ZL' W ZL + I) or "component"
-        (csrc/la_comp.h: M one connected component at a time on the sparse operator, where the component plan is feasible)"""
+        """how mcml_la / la_probe run on this context: "dense" (the dense ZL and M = ZL' W ZL + I), "component"
+        (csrc/la_comp.h: M one connected component at a time on the sparse operator, a wave each, where no component has
+        more than 32 variables) or "component_wide" (the same up to 128 variables per component: a wave each, or a workgroup
+        each where a component has more than 32 variables or 128 observations and more; GLMMR_MCML_LA_WAVES=1|4 forces a
+        form).  Where the asked-for operator cannot run, the dense one does"""
         _lib.check(_lib.lib().glmmr_mcml_ctx_set_la_operator(self._h, _LA_OP[mode]))
 
     def la_plan(self):
         """what was asked for and what the last Laplace call on this context ran (test hook, include/glmmr_mcml_c.h
-        glmmr_mcml_dbg_la_plan)"""
+        glmmr_mcml_dbg_la_plan); waves: per component in that call, 0 (dense), 1 or 4"""
         out = (C.c_longlong * 8)()
         _lib.check(_lib.lib().glmmr_mcml_dbg_la_plan(self._h, out))
         return dict(requested=_LA_OP_NAME[int(out[0])], operator=_LA_OP_NAME[int(out[1])], ncomp=int(out[2]),
-                    max_vars=int(out[3]), max_rows=int(out[4]), launches=int(out[5]), dense_bytes=int(out[6]))
+                    max_vars=int(out[3]), max_rows=int(out[4]), launches=int(out[5]), dense_bytes=int(out[6]), waves=int(out[7]))
 
     def mcml_optim(self, start, trace=0, mcnr=False, maxfun=0, theta_batch=0):
         start = _f(start).ravel(); R = self.npar()
@@ -467,8 +470,8 @@ class Context:
 
     def mcml_la(self, start, usehess=False, tol=1e-3, verbose=False, trace=0, maxiter=10, nr=False, maxfun=0,
                 operator=None):
-        """mcml_la / mcml_la_nr on the resident model (src/mcml_la.cpp:28-290); operator ("dense" / "component", None =
-        the context's setting): set_la_operator for this call only"""
+        """mcml_la / mcml_la_nr on the resident model (src/mcml_la.cpp:28-290); operator ("dense" / "component" /
+        "component_wide", None = the context's setting): set_la_operator for this call only"""
         if operator is not None:
             prev = self.la_plan()["requested"]
             self.set_la_operator(operator)
@@ -560,8 +563,8 @@ def _la_call(fn, cov, data, eff_range, Z, X, y, family, link, start, usehess, to
 
 def mcml_la(cov, data, eff_range, Z, X, y, family, link, start, usehess=False, tol=1e-3, verbose=True, trace=0,
             maxiter=10, maxfun=0, operator=None):
-    """mcml_la(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:28-155).  operator ("dense" / "component",
-    None = the process default): the default operator of the Laplace fits for the duration of the call"""
+    """mcml_la(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:28-155).  operator ("dense" / "component" /
+    "component_wide", None = the process default): the default operator of the Laplace fits for the duration of the call"""
     with _default_la_operator(operator):
         return _la_call(_lib.lib().glmmr_mcml_la, cov, data, eff_range, Z, X, y, family, link, start, usehess, tol,
                         verbose, trace, maxiter, maxfun)
@@ -569,7 +572,8 @@ def mcml_la(cov, data, eff_range, Z, X, y, family, link, start, usehess=False, t
 
 def mcml_la_nr(cov, data, eff_range, Z, X, y, family, link, start, usehess=False, tol=1e-3, verbose=True, trace=0,
                maxiter=10, maxfun=0, operator=None):
-    """mcml_la_nr(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:174-290); operator as mcml_la"""
+    """mcml_la_nr(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:174-290); operator ("dense" / "component" /
+    "component_wide") as mcml_la"""
     with _default_la_operator(operator):
         return _la_call(_lib.lib().glmmr_mcml_la_nr, cov, data, eff_range, Z, X, y, family, link, start, usehess, tol,
                         verbose, trace, maxiter, maxfun)

@@ -31,7 +31,7 @@ static int default_trajectory()
     return v;
 }
 
-// the same for Ctx::la_mode: GLMMR_MCML_LA=component|dense (read once) or 0
+// the same for Ctx::la_mode: GLMMR_MCML_LA=component|component_wide|dense (read once) or 0
 static std::atomic<int> g_default_la{-1};
 static int default_la_operator()
 {
@@ -39,7 +39,7 @@ static int default_la_operator()
     if (v < 0) {
         const char* e = getenv("GLMMR_MCML_LA");
         int unset = -1;
-        g_default_la.compare_exchange_strong(unset, (e && !strcmp(e, "component")) ? 1 : 0);
+        g_default_la.compare_exchange_strong(unset, (e && !strcmp(e, "component")) ? 1 : (e && !strcmp(e, "component_wide")) ? 2 : 0);
         v = g_default_la.load();
     }
     return v;
@@ -290,7 +290,7 @@ extern "C" int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* h, int chains, long
 
 extern "C" int glmmr_mcml_set_default_la_operator(int mode)
 {
-    MCML_REQUIRE(mode == 0 || mode == 1, "set_default_la_operator: mode must be 0 (dense) or 1 (component)");
+    MCML_REQUIRE(mode >= 0 && mode <= 2, "set_default_la_operator: mode must be 0 (dense), 1 (component) or 2 (component_wide)");
     g_default_la.store(mode);
     return MCML_OK;
 }
@@ -299,7 +299,7 @@ extern "C" int glmmr_mcml_get_default_la_operator(void) { return default_la_oper
 
 extern "C" int glmmr_mcml_ctx_set_la_operator(glmmr_mcml_ctx* h, int mode)
 {
-    MCML_REQUIRE(h && (mode == 0 || mode == 1), "set_la_operator: mode must be 0 (dense) or 1 (component)");
+    MCML_REQUIRE(h && mode >= 0 && mode <= 2, "set_la_operator: mode must be 0 (dense), 1 (component) or 2 (component_wide)");
     h->c.la_mode = mode;
     return MCML_OK;
 }
@@ -313,7 +313,7 @@ extern "C" int glmmr_mcml_dbg_la_plan(glmmr_mcml_ctx* h, long long* out8)
     MCML_REQUIRE(h && out8, "dbg_la_plan: null argument");
     const Ctx& c = h->c;
     const ComponentPlan& p = c.cp.plan;
-    const long long v[8] = {c.la_mode, c.la_last_op, p.ncomp, p.max_vars, p.max_rows, c.la_launches, c.la_dense_bytes, 0};
+    const long long v[8] = {c.la_mode, c.la_last_op, p.ncomp, p.max_vars, p.max_rows, c.la_launches, c.la_dense_bytes, c.la_waves};
     for (int i = 0; i < 8; ++i) out8[i] = v[i];
     return MCML_OK;
 }

@@ -20,6 +20,10 @@ constexpr int CP_LDS_BYTES_PER_CU = 160 * 1024;
 constexpr int CP_MAX_VARS = 32;
 static_assert(CP_MAX_VARS >= 16 && CP_MAX_VARS < 48, "the fallback tests rely on a sparse design above the cap");
 static_assert(CP_MAX_VARS * 3 * 512 * 3 <= CP_LDS_BYTES_PER_CU && CP_MAX_VARS * 6 * 512 + 8192 <= CP_LDS_BYTES_PER_CU, "LDS budget");
+// The Laplace kernels (la_comp.h) keep only the nv x nv matrix of a component in LDS: the workgroup form takes up to
+// CP_WIDE_MAX_VARS variables (about 146 KB at the cap, one workgroup per CU).  The trajectory kernel keeps CP_MAX_VARS.
+constexpr int CP_WIDE_MAX_VARS = 128;
+static_assert(CP_WIDE_MAX_VARS >= CP_MAX_VARS, "a plan the trajectory kernel takes has records");
 constexpr int CP_SLOT = 4;            // entries of ZL per metadata record (one batch of scalar loads)
 constexpr int CP_TARGET_ITEMS = 1024; // work items aimed at when components are packed (a guess, not measured)
 // the four-wave form (a workgroup per component and chain block, the observations split over its waves) is taken when
@@ -33,7 +37,8 @@ inline int cp_lds_bytes(int max_vars, int waves) { return waves == 4 ? max_vars 
 struct ComponentPlan {
     int n = 0, Q = 0, W = 0;
     int ncomp = 0, max_vars = 0, max_rows = 0, empty_comps = 0;
-    bool feasible = false;
+    bool feasible = false;                        // max_vars <= CP_MAX_VARS: the trajectory kernel's work items are built
+    bool records = false;                         // max_vars <= CP_WIDE_MAX_VARS: the record arrays are built
     std::vector<int> comp_of_var, local_of_var;   // Q
     std::vector<int> var_ptr, vars;               // ncomp + 1, Q: the global variables of a component, ascending
     std::vector<int> row_ptr, rows;               // ncomp + 1, n: its observations, ascending
@@ -109,8 +114,9 @@ inline void component_plan_build(int n, int Q, int W, const std::vector<int>& co
         p.empty_comps += rcnt[c] == 0;
     }
     p.feasible = p.ncomp > 0 && p.max_vars <= CP_MAX_VARS;
-    if (!p.feasible) return;
-    // records
+    p.records = p.ncomp > 0 && p.max_vars <= CP_WIDE_MAX_VARS;
+    if (!p.records) return;
+    // records: read by the trajectory kernel and by the Laplace kernels
     p.slot_ptr.assign(p.ncomp + 1, 0);
     p.slot_quarter.assign(5 * (size_t)p.ncomp, 0);
     for (int c = 0; c < p.ncomp; ++c) {
@@ -133,6 +139,7 @@ inline void component_plan_build(int n, int Q, int W, const std::vector<int>& co
     }
     p.nslots = (int)(p.slot_i.size() / 8);
     p.slot_ptr[p.ncomp] = p.nslots;
+    if (!p.feasible) return;
     // work items: consecutive components, packed until an item costs what the costliest component does or the total spread
     // over CP_TARGET_ITEMS items, whichever is more -- so that a one-variable component rides with its neighbours
     auto cost = [&](int c) { return (long)(p.slot_ptr[c + 1] - p.slot_ptr[c]) + 2L * (p.var_ptr[c + 1] - p.var_ptr[c]); };

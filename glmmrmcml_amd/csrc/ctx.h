@@ -209,8 +209,10 @@ struct Ctx {
     ComponentDev cp;
     int traj_mode = 0;          // 0: a launch per leapfrog step; 1: component-local trajectories where feasible (hmc_traj.h)
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT
-    int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (la_comp.h)
-    int la_last_op = 0;         // what the last Laplace call ran (0 dense, 1 component), its k_lac_factor launches and the
+    int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (la_comp.h); 2 the same up
+                                // to CP_WIDE_MAX_VARS variables per component, a wave or a workgroup each
+    int la_last_op = 0;         // what the last Laplace call ran (0 dense, 1 component, 2 component_wide), its waves per
+    int la_waves = 0;           // component (0 dense, 1, 4), its k_lac_factor / k_lac_factor_wg launches and the
     long long la_launches = 0, la_dense_bytes = 0;   // bytes of M + ZLTW + ZL + ZLT it allocated / worked on (dbg_la_plan)
     bool l_foreign = false;     // L came from the caller (set_L), not from theta: it need not have the block pattern the
                                 // sparse ZL operator assumes; cleared as soon as L is regenerated from theta (mvn_gen_L)

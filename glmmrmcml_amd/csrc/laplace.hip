@@ -7,7 +7,8 @@
 // scalar; the Q x Q x n product ZL' W ZL and its Cholesky use the same MFMA GEMM / potrf as
 // the MCML path, the vector-sized pieces are plain streaming kernels.  Opt-in (glmmr_mcml_ctx_set_la_operator, DESIGN.md
 // 5.5): on a block-structured design the same statements run on the sparse ZL operator and factorise M component by
-// component (la_comp.h); nothing of size Q x n or Q x Q is then built per evaluation.
+// component (la_comp.h: a wave per component up to CP_MAX_VARS variables under "component", a wave or a workgroup up to
+// CP_WIDE_MAX_VARS under "component_wide"); nothing of size Q x n or Q x Q is then built per evaluation.
 //
 // Reference behaviour reproduced on purpose (also restated in oracle/la.py):
 //   * v = u column 0 is the whitened effect, yet update_W(useL = false) forms Z v and
@@ -31,7 +32,7 @@
 
 namespace mcml {
 
-// k_lac_factor launches of this process, over all contexts (glmmr_mcml_dbg_la_component_launches)
+// k_lac_factor / k_lac_factor_wg launches of this process, over all contexts (glmmr_mcml_dbg_la_component_launches)
 static std::atomic<long long> g_lac_launches{0};
 long long la_component_launch_count() { return g_lac_launches.load(); }
 
@@ -195,13 +196,14 @@ struct LaFit {
     DevMat M, ZLTW, D0;
     std::vector<double> hv;                         // host copy of v
     bool comp = false;                              // the component operator (la_comp.h) instead of the dense ZL / M
+    int waves = 0;                                  // its form: 1 k_lac_factor, 4 k_lac_factor_wg; 0 with the dense operator
     DevBuf lac_ld;                                  // its per-component log-determinants
     size_t zl_bytes0 = 0;                           // what c.ZL + c.ZLT held when the call began
 
     LaFit(Ctx& ctx) : c(ctx), n(ctx.n), Q(ctx.Q), P(ctx.P), R(ctx.cov.npar), flink(ctx.flink), link_code(ctx.link_code)
     {
         zl_bytes0 = c.ZL.buf.bytes + c.ZLT.buf.bytes;
-        c.la_last_op = 0; c.la_launches = 0; c.la_dense_bytes = 0;
+        c.la_last_op = 0; c.la_waves = 0; c.la_launches = 0; c.la_dense_bytes = 0;
     }
     // glmmr_mcml_dbg_la_plan: the dense matrices this call allocated (component) or worked on (dense)
     ~LaFit()
@@ -231,14 +233,19 @@ struct LaFit {
         MCML_TRY(part.ensure(sizeof(double) * 1100));
         MCML_TRY(small.ensure(sizeof(double) * (size_t)(P * P + P + 16)));
         MCML_HIP(hipMemsetAsync(v.p, 0, sizeof(double) * (size_t)(Q + 64), c.stream));
-        // the component operator: asked for, and the model has the sparse ZL with a feasible component plan (L always
-        // comes from theta here: gen_L).  Otherwise, silently, the dense ZL as ever
-        if (c.la_mode == 1) {
+        // the component operator: asked for, and the model has the sparse ZL with a component plan its kernel takes (L
+        // always comes from theta here: gen_L).  Otherwise, silently, the dense ZL as ever.  "component" is the one-wave
+        // kernel and its cap; "component_wide" takes components up to CP_WIDE_MAX_VARS and picks the form (lac_waves)
+        if (c.la_mode == 1 || c.la_mode == 2) {
             MCML_TRY(model_sparse_setup(c));
-            comp = c.sp.possible && c.cp.ready && c.cp.plan.feasible;
+            comp = c.sp.possible && c.cp.ready && (c.la_mode == 2 ? c.cp.plan.records : c.cp.plan.feasible);
         }
-        if (comp) MCML_TRY(lac_ld.ensure(sizeof(double) * (size_t)c.cp.plan.ncomp));
-        c.la_last_op = comp ? 1 : 0;
+        if (comp) {
+            MCML_TRY(lac_ld.ensure(sizeof(double) * (size_t)c.cp.plan.ncomp));
+            waves = c.la_mode == 2 ? lac_waves(c.cp.plan, lac_forced_waves()) : 1;
+        }
+        c.la_last_op = comp ? c.la_mode : 0;
+        c.la_waves = waves;
         c.no_sparse_zl = !comp;                                   // the dense path works on the dense ZL
         // D_ = L L' at the starting theta (mcmlmodel.h:71); genD(chol = false) gives it directly
         MCML_TRY(mvn_gen_L(c, theta.data(), false));
@@ -365,7 +372,13 @@ struct LaFit {
         const ComponentDev& cp = c.cp;
         LacArgs a{cp.var_ptr.as<int>(), cp.vars.as<int>(), cp.slot_ptr.as<int>(), cp.slot_i.as<int>(), cp.slot_d.d(), W.d(),
                   cp.plan.ncomp, g, x, lac_ld.d(), c.errflag()};
-        hipLaunchKernelGGL(k_lac_factor, dim3((cp.plan.ncomp + LAC_WAVES - 1) / LAC_WAVES), dim3(64 * LAC_WAVES), 0, c.stream, a);
+        if (waves == 4) {
+            MCML_TRY(ensure_dynamic_lds((const void*)k_lac_factor_wg, lacw_lds_bytes(CP_WIDE_MAX_VARS)));
+            hipLaunchKernelGGL(k_lac_factor_wg, dim3(cp.plan.ncomp), dim3(LACW_THREADS), lacw_lds_bytes(cp.plan.max_vars), c.stream, a,
+                               cp.plan.max_vars);
+        } else {
+            hipLaunchKernelGGL(k_lac_factor, dim3((cp.plan.ncomp + LAC_WAVES - 1) / LAC_WAVES), dim3(64 * LAC_WAVES), 0, c.stream, a);
+        }
         MCML_HIP(hipGetLastError());
         ++c.la_launches; ++g_lac_launches;
         return MCML_OK;

@@ -268,7 +268,7 @@ static int sparse_zl_setup(Ctx& c)
         ComponentDev& cp = c.cp;
         component_plan_build(n, Q, W, col, width, cp.plan);
         cp.ready = false;
-        if (cp.plan.feasible) {
+        if (cp.plan.records) {                 // item_ptr stays empty above CP_MAX_VARS: only the Laplace kernels run there
             const ComponentPlan& p = cp.plan;
             auto up = [&](DevBuf& b, const std::vector<int>& v) -> int {
                 MCML_TRY(b.ensure(sizeof(int) * (v.size() + 8)));

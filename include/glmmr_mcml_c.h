@@ -263,17 +263,22 @@ long long glmmr_mcml_dbg_traj_launches(void);
 /* The operator of the Laplace fits (glmmr_mcml_ctx_la, glmmr_mcml_la, glmmr_mcml_la_nr): 0 = the dense ZL and the dense
  * Q x Q matrix M = ZL' W ZL + I (the default), 1 = the component operator (csrc/la_comp.h): on the sparse ZL operator, M
  * built, factorised and solved one connected component of ZL's coupling graph at a time -- where the sparse operator is
- * possible and no component is above the kernel's cap; otherwise the call changes nothing. */
+ * possible and no component is above the kernel's cap of 32 variables (a wave per component); otherwise the call changes
+ * nothing.  2 = "component_wide": the same operator for components of up to 128 variables, a wave per component
+ * (k_lac_factor) where none has more than 32 variables and none 128 observations or more, else a workgroup of four waves
+ * per component (k_lac_factor_wg, M_c in dynamically sized LDS); GLMMR_MCML_LA_WAVES=1|4, read per call, forces a form
+ * (1 is ignored above 32 variables).  Above 128 variables, or without the sparse operator, the dense path as under 1. */
 int glmmr_mcml_ctx_set_la_operator(glmmr_mcml_ctx* ctx, int mode);
 /* The mode new contexts start with, the ones glmmr_mcml_la / glmmr_mcml_la_nr create included.  Initially
- * GLMMR_MCML_LA=component|dense from the environment (read once), else 0.  One atomic per process, as the trajectory default. */
+ * GLMMR_MCML_LA=component|component_wide|dense from the environment (read once), else 0.  One atomic per process, as the trajectory default. */
 int glmmr_mcml_set_default_la_operator(int mode);
 int glmmr_mcml_get_default_la_operator(void);
-/* out8 = [mode requested, operator the last Laplace call on this context ran (0 dense, 1 component), components, most
- * variables in one, most observations in one (0 until the sparse operator has been set up), k_lac_factor launches of that
- * call, bytes of M + ZLTW + ZL + ZLT that call allocated (component) or worked on (dense), 0] */
+/* out8 = [mode requested, operator the last Laplace call on this context ran (0 dense, 1 component, 2 component_wide),
+ * components, most variables in one, most observations in one (0 until the sparse operator has been set up), k_lac_factor /
+ * k_lac_factor_wg launches of that call, bytes of M + ZLTW + ZL + ZLT that call allocated (component) or worked on
+ * (dense), waves per component in that call (0 dense, 1, 4)] */
 int glmmr_mcml_dbg_la_plan(glmmr_mcml_ctx* ctx, long long* out8);
-/* k_lac_factor launches of this process so far, over all contexts: tells whether a context that glmmr_mcml_la /
+/* k_lac_factor / k_lac_factor_wg launches of this process so far, over all contexts: tells whether a context that glmmr_mcml_la /
  * glmmr_mcml_la_nr created internally took the component operator. */
 long long glmmr_mcml_dbg_la_component_launches(void);
 /* Host wall-clock time per phase of the MCML iterations run by this process since the last reset (csrc/trace.h):

@@ -12,6 +12,13 @@ figures that are reported) and one on this tree's library, each under a time lim
 object (profiles/la_component_timing.json).
 
     python scripts/time_la_component.py --parent-lib PATH [--configs cfg5,cfg4] [--reps 3] [--limit 560] [--out FILE]
+
+--wide times the third operator, "component_wide" (k_lac_factor_wg), by the same protocol in ONE worker on this tree's
+library (profiles/la_component_wide_timing.json): config 4 with dense / component / component_wide alternating -- the
+baseline is "component", the parent commit's kernel, in the same process -- and synth.cluster_rct(100, 40, 10) (n = 40000,
+Q = 4100, 100 components of 41 variables and 400 observations: above the cap of "component") with dense / component_wide.
+
+    python scripts/time_la_component.py --wide [--reps 3] [--limit 560] [--out FILE]
 """
 import argparse
 import json
@@ -30,11 +37,13 @@ def worker(args):
     from glmmrmcml_amd import _lib, api, synth
     assert torch.cuda.is_available(), "needs the GPU"
     has_switch = hasattr(_lib.lib(), "glmmr_mcml_ctx_set_la_operator")
-    specs = {"cfg5": lambda: synth.longitudinal(2000, 10), "cfg4": lambda: synth.stepped_wedge(40, 8, 50)}
-    modes = ["dense", "component"] if has_switch else ["dense"]
+    specs = {"cfg5": lambda: synth.longitudinal(2000, 10), "cfg4": lambda: synth.stepped_wedge(40, 8, 50),
+             "cfg4_wide": lambda: synth.stepped_wedge(40, 8, 50), "rct41_wide": lambda: synth.cluster_rct(100, 40, 10)}
+    modes_of = {"cfg4_wide": ["dense", "component", "component_wide"], "rct41_wide": ["dense", "component_wide"]}
     out = {"device": torch.cuda.get_device_name(0), "library": _lib.LIB_PATH, "has_switch": has_switch, "reps": args.reps}
     for key in args.configs.split(","):
         d = specs[key]()
+        modes = modes_of.get(key, ["dense", "component"]) if has_switch else ["dense"]
         calls, fits = [], {}
         with api.Context(d["cov"], d["data"], d["eff_range"], d["Z"], d["X"], d["y"], d["family"], d["link"]) as ctx:
             for rep in range(args.reps + 1):                    # rep 0: untimed, first-time work of each operator
@@ -53,7 +62,7 @@ def worker(args):
                         if has_switch:
                             p = ctx.la_plan()
                             assert p["operator"] == mode, p
-                            rec.update(launches=p["launches"], dense_bytes=p["dense_bytes"])
+                            rec.update(launches=p["launches"], dense_bytes=p["dense_bytes"], waves=p.get("waves"))
                         calls.append(rec)
             res = dict(n=int(d["n"]), Q=int(d["Q"]), calls=calls)
             if has_switch:
@@ -64,11 +73,11 @@ def worker(args):
             res[mode + "_ms"] = ms
             res[mode + "_ms_median"] = ms[len(ms) // 2]
             res[mode + "_fit"] = dict(beta=fits[mode]["beta"].tolist(), theta=fits[mode]["theta"].tolist())
-        if has_switch:                                           # faster and different is not faster
-            a, b = fits["dense"], fits["component"]
-            res["component_vs_dense_max_abs_diff"] = dict(beta=float(np.abs(a["beta"] - b["beta"]).max()),
-                                                          theta=float(np.abs(a["theta"] - b["theta"]).max()),
-                                                          u=float(np.abs(a["u"] - b["u"]).max()))
+        for mode in modes[1:]:                                   # faster and different is not faster
+            a, b = fits["dense"], fits[mode]
+            res[mode + "_vs_dense_max_abs_diff"] = dict(beta=float(np.abs(a["beta"] - b["beta"]).max()),
+                                                        theta=float(np.abs(a["theta"] - b["theta"]).max()),
+                                                        u=float(np.abs(a["u"] - b["u"]).max()))
         out[key] = res
     print("WORKER " + json.dumps(out))
 
@@ -86,6 +95,37 @@ def run_worker(args, lib):
     return json.loads(next(l for l in p.stdout.splitlines() if l.startswith("WORKER "))[7:])
 
 
+def wide(args):
+    args.configs = "cfg4_wide,rct41_wide"
+    br = run_worker(args, None)
+    out = {"device": br["device"], "call": "Context.mcml_la(start, nr=True, maxiter=1, maxfun=20)", "reps": args.reps,
+           "clock": "host wall clock around the call, device synchronised before and after",
+           "order": "one process: one untimed call of each operator, then the operators alternating on one context"}
+    for key in args.configs.split(","):
+        r = br[key]
+        modes = [m for m in ("dense", "component", "component_wide") if m + "_ms" in r]
+        e = dict(n=r["n"], Q=r["Q"], plan=r["plan"])
+        for m in modes:
+            e[m + "_ms"] = r[m + "_ms"]
+            e[m + "_ms_median"] = r[m + "_ms_median"]
+            e[m + "_waves"] = sorted({c["waves"] for c in r["calls"] if c["mode"] == m})
+            e[m + "_launches_per_call"] = [c["launches"] for c in r["calls"] if c["mode"] == m]
+            e[m + "_dense_bytes"] = [c["dense_bytes"] for c in r["calls"] if c["mode"] == m]
+        base = "component" if "component" in modes else "dense"
+        e["baseline"] = base
+        e[base + "_over_component_wide"] = round(r[base + "_ms_median"] / r["component_wide_ms_median"], 2)
+        # faster beyond the run-to-run spread: the slowest repetition of the one under the fastest of the other
+        e["component_wide_faster_beyond_spread"] = max(r["component_wide_ms"]) < min(r[base + "_ms"])
+        for m in modes[1:]:
+            e[m + "_vs_dense_max_abs_diff"] = r[m + "_vs_dense_max_abs_diff"]
+        out[key] = e
+    txt = json.dumps(out, indent=1)
+    print(txt)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(txt + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="cfg5,cfg4")
@@ -94,9 +134,12 @@ def main():
     ap.add_argument("--limit", type=int, default=560, help="seconds a worker may take")
     ap.add_argument("--out", default=None)
     ap.add_argument("--worker", action="store_true")
+    ap.add_argument("--wide", action="store_true", help="time component_wide on this tree's library alone")
     args = ap.parse_args()
     if args.worker:
         return worker(args)
+    if args.wide:
+        return wide(args)
     if not args.parent_lib:
         raise SystemExit("--parent-lib: the dense figures come from the parent commit's library")
     parent = run_worker(args, args.parent_lib)                    # a failure or a time limit ends the run here
