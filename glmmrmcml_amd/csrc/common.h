@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace mcml {
@@ -55,17 +56,22 @@ const char* last_error();
 // (kernel, device) -- a process may hold contexts on several GPUs
 int ensure_dynamic_lds(const void* kernel, int bytes);
 
-// launch KERNEL<FL>: the common families get their own instantiation (1 poisson/log, 3 binomial/logit, 7 gaussian/identity)
-#define MCML_FL_DISPATCH(FLINK, KERNEL, ...)                                          \
-    do {                                                                              \
-        switch (FLINK) {                                                              \
-        case 1: hipLaunchKernelGGL((KERNEL<1>), __VA_ARGS__); break;                  \
-        case 3: hipLaunchKernelGGL((KERNEL<3>), __VA_ARGS__); break;                  \
-        case 7: hipLaunchKernelGGL((KERNEL<7>), __VA_ARGS__); break;                  \
-        default: hipLaunchKernelGGL((KERNEL<0>), __VA_ARGS__); break;                 \
-        }                                                                             \
-    } while (0)
-
+// Family / link dispatch: f(std::integral_constant<int, FL>) with FL = flink where flink is one of CODES..., the codes the
+// call site's kernel has an instantiation of its own for (1 poisson/log, 3 binomial/logit, 7 gaussian/identity, 12
+// beta/logit), else FL = 0, the instantiation that reads the code at run time.  -> what f returns (an error code), MCML_OK
+// where it returns nothing.  dispatch_flink<1, 3, 7>(flink, [&](auto FL) { hipLaunchKernelGGL((k<FL()>), ...); });
+template <int... CODES, class F>
+inline int dispatch_flink(int flink, F&& f)
+{
+    int rc = MCML_OK;
+    auto call = [&](auto FL) {
+        if constexpr (std::is_void_v<decltype(f(FL))>) f(FL);
+        else rc = f(FL);
+        return true;
+    };
+    if (!((flink == CODES && call(std::integral_constant<int, CODES>{})) || ...)) call(std::integral_constant<int, 0>{});
+    return rc;
+}
 
 static inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
 static inline size_t round_up_sz(size_t x, size_t a) { return (x + a - 1) / a * a; }

@@ -6,6 +6,7 @@
 #include "covspec.h"
 #include "band_plan.h"
 #include "component_plan.h"
+#include "step_ahead.h"
 
 namespace mcml {
 
@@ -21,9 +22,10 @@ typedef int (*reduce_fn)(void* user, double* dev_buf, int n);
 enum { KERNEL_SKINNY = 0, KERNEL_BAND = 1, KERNEL_DLDS = 2, KERNEL_REG = 3, KERNEL_SPARSE = 4, KERNEL_COMPONENT = 5 };
 
 // the sampler's step-count read-back (hmc.hip hmc_sample): a ring of host memory mapped into the device, written by
-// k_max_steps with (proposal sequence number << 32 | count), read by the host with plain loads; lives as long as the context
+// k_max_steps with (proposal sequence number << 32 | count), read by the host with plain loads (StepAhead, step_ahead.h);
+// lives as long as the context
 struct StepRing {
-    static constexpr int SLOTS = 8;
+    static constexpr int SLOTS = StepAhead::SLOTS;
     unsigned long long* h = nullptr;    // host address
     unsigned long long* d = nullptr;    // the same memory as the device sees it
     unsigned seq = 0;                   // sequence number of the last proposal launched

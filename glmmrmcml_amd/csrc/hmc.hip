@@ -14,6 +14,7 @@
 // log_prob(u) and log_grad(u) of the current state are cached from the step that
 // produced it instead of being recomputed (the reference recomputes them,
 // :64,82): same numbers, 2*steps GEMMs per proposal instead of 2*steps + 4.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include "../../include/glmmr_mcml_c.h"
@@ -442,24 +443,16 @@ static int cm_traj_launch(Ctx& c, const TrajArgs& a)
     const int waves = cp_waves(cp.plan, cp_forced_waves());
     const int lds = cp_lds_bytes(cp.plan.max_vars, waves);
     const dim3 grid(cp.plan.nitems(), cm_chain_blocks(a.C));
-#define MCML_TRAJ(FL)                                                                                                        \
-    do {                                                                                                                     \
-        if (waves == 4) {                                                                                                    \
-            MCML_TRY(ensure_dynamic_lds((const void*)k_cm_traj<FL, 4>, cp_lds_bytes(CP_MAX_VARS, 4)));                      \
-            hipLaunchKernelGGL((k_cm_traj<FL, 4>), grid, dim3(256), lds, c.stream, m, a);                                  \
-        } else {                                                                                                             \
-            MCML_TRY(ensure_dynamic_lds((const void*)k_cm_traj<FL, 1>, cp_lds_bytes(CP_MAX_VARS, 1)));                      \
-            hipLaunchKernelGGL((k_cm_traj<FL, 1>), grid, dim3(64), lds, c.stream, m, a);                                   \
-        }                                                                                                                    \
-    } while (0)
-    switch (c.flink) {
-    case 1: MCML_TRAJ(1); break;
-    case 3: MCML_TRAJ(3); break;
-    case 7: MCML_TRAJ(7); break;
-    case 12: MCML_TRAJ(12); break;
-    default: MCML_TRAJ(0); break;
-    }
-#undef MCML_TRAJ
+    MCML_TRY((dispatch_flink<1, 3, 7, 12>(c.flink, [&](auto FL) {
+        if (waves == 4) {
+            MCML_TRY(ensure_dynamic_lds((const void*)k_cm_traj<FL(), 4>, cp_lds_bytes(CP_MAX_VARS, 4)));
+            hipLaunchKernelGGL((k_cm_traj<FL(), 4>), grid, dim3(256), lds, c.stream, m, a);
+        } else {
+            MCML_TRY(ensure_dynamic_lds((const void*)k_cm_traj<FL(), 1>, cp_lds_bytes(CP_MAX_VARS, 1)));
+            hipLaunchKernelGGL((k_cm_traj<FL(), 1>), grid, dim3(64), lds, c.stream, m, a);
+        }
+        return (int)MCML_OK;
+    })));
     MCML_HIP(hipGetLastError());
     ++g_traj_launches;                           // launches that were actually enqueued
     return MCML_OK;
@@ -470,12 +463,12 @@ static int hmc_alloc(Ctx& c, int C)
     HmcState& h = c.hmc;
     h.C = C; h.Cw = C;
     h.cm = c.sp.active;
+    // chain-major state (sparse operator, hmc_cm.h): the "rows" of a DevMat are the chains
+    auto mat = [&](DevMat& m, int len) { return h.cm ? m.alloc(C, len) : m.alloc(len, C); };
+    for (DevMat* m : {&h.V, &h.R, &h.UP, &h.GRAD, &h.GRADP}) MCML_TRY(mat(*m, c.Q));
+    MCML_TRY(mat(h.MU, c.n)); MCML_TRY(mat(h.S, c.n));
+    MCML_TRY(h.chain.ensure(sizeof(double) * (size_t)round_up(C, 16) * 8));
     if (h.cm) {
-        // chain-major (hmc_cm.h): "rows" of the DevMat are the chains
-        MCML_TRY(h.V.alloc(C, c.Q)); MCML_TRY(h.R.alloc(C, c.Q)); MCML_TRY(h.UP.alloc(C, c.Q));
-        MCML_TRY(h.GRAD.alloc(C, c.Q)); MCML_TRY(h.GRADP.alloc(C, c.Q));
-        MCML_TRY(h.MU.alloc(C, c.n)); MCML_TRY(h.S.alloc(C, c.n));
-        MCML_TRY(h.chain.ensure(sizeof(double) * (size_t)round_up(C, 16) * 8));
         const size_t nchn = (size_t)(c.n + CM_ROWS - 1) / CM_ROWS, nchq = (size_t)(c.Q + cm_qrows(c.Q) - 1) / cm_qrows(c.Q);
         MCML_TRY(h.cm_part.ensure(sizeof(double) * (nchn + 3 * nchq + 4) * (size_t)h.V.ld));
         MCML_TRY(h.cm_acc.ensure(sizeof(int) * (size_t)round_up(C, 64)));
@@ -483,10 +476,6 @@ static int hmc_alloc(Ctx& c, int C)
         if (cm_traj_used(c)) MCML_TRY(h.cp_part.ensure(sizeof(double) * 4 * (size_t)c.cp.plan.nitems() * h.V.ld));
         return MCML_OK;
     }
-    MCML_TRY(h.V.alloc(c.Q, C)); MCML_TRY(h.R.alloc(c.Q, C)); MCML_TRY(h.UP.alloc(c.Q, C));
-    MCML_TRY(h.GRAD.alloc(c.Q, C)); MCML_TRY(h.GRADP.alloc(c.Q, C));
-    MCML_TRY(h.MU.alloc(c.n, C)); MCML_TRY(h.S.alloc(c.n, C));
-    MCML_TRY(h.chain.ensure(sizeof(double) * (size_t)round_up(C, 16) * 8));
     // padding rows of the operands the GEMMs read must hold finite values
     MCML_HIP(hipMemsetAsync(h.V.d(), 0, sizeof(double) * (size_t)h.V.ld * C, c.stream));
     MCML_HIP(hipMemsetAsync(h.UP.d(), 0, sizeof(double) * (size_t)h.UP.ld * C, c.stream));
@@ -508,36 +497,46 @@ static bool use_skinny()                       // GLMMR_MCML_SKINNY=0: the MFMA 
     return !(e && !strcmp(e, "0"));
 }
 
-// MU = xb + ZL * X ; S = score
+// The dense product of one direction (dir 0: forward, A = ZL; 1: backward, A = ZL') with the h.Cw columns of B, by the
+// first kernel family that applies.
+struct DenseOp { BandPlan& plan; bool band; int M, K; const DevMat& A; };
 template <class Epi>
-static int hmc_forward_launch(Ctx& c, const double* X, int ldx, const Epi& epi)
+static int dense_product(Ctx& c, int dir, const DenseOp& a, const double* B, int ldb, const Epi& epi)
 {
-    HmcState& h = c.hmc;
+    const int N = c.hmc.Cw, lda = a.A.ld;
+    const double* A = a.A.d();
     // at most 16 chains (chains = 1: the reference's layout; the tail of a NUTS doubling): an HBM-bound stream, not an MFMA tile
     // c.last_kernel[]: which kernel family served the product (tests assert the path they mean to compare)
-    if (use_skinny() && skinny_applicable(c.plan_fwd, c.n, c.Q, h.Cw, c.ZL.ld)) {
-        c.last_kernel[0] = KERNEL_SKINNY;
-        return launch_skinny(c.stream, c.plan_fwd, h.Cw, c.ZL.d(), c.ZL.ld, X, ldx, epi);
+    if (use_skinny() && skinny_applicable(a.plan, a.M, a.K, N, lda)) {
+        c.last_kernel[dir] = KERNEL_SKINNY;
+        return launch_skinny(c.stream, a.plan, N, A, lda, B, ldb, epi);
     }
-    if (c.band_fwd && dlds_applicable(c.n, h.Cw, c.Q, c.ZL.d(), c.ZL.ld, c.ZL.cols_alloc, X, ldx)) {
-        c.last_kernel[0] = KERNEL_BAND;
-        return launch_gemm_band(c.stream, c.plan_fwd, h.Cw, c.ZL.d(), c.ZL.ld, X, ldx, epi);
+    if (a.band && dlds_applicable(a.M, N, a.K, A, lda, a.A.cols_alloc, B, ldb)) {
+        c.last_kernel[dir] = KERNEL_BAND;
+        return launch_gemm_band(c.stream, a.plan, N, A, lda, B, ldb, epi);
     }
-    if (use_dlds() && dlds_applicable(c.n, h.Cw, c.Q, c.ZL.d(), c.ZL.ld, c.ZL.cols_alloc, X, ldx)) {
-        c.last_kernel[0] = KERNEL_DLDS;
-        return launch_gemm_dlds(c.stream, c.n, h.Cw, c.Q, c.ZL.d(), c.ZL.ld, X, ldx, epi);
+    if (use_dlds() && dlds_applicable(a.M, N, a.K, A, lda, a.A.cols_alloc, B, ldb)) {
+        c.last_kernel[dir] = KERNEL_DLDS;
+        return launch_gemm_dlds(c.stream, a.M, N, a.K, A, lda, B, ldb, epi);
     }
-    c.last_kernel[0] = KERNEL_REG;
-    return launch_gemm<false>(c.stream, c.n, h.Cw, c.Q, c.ZL.d(), c.ZL.ld, X, ldx, epi);
+    c.last_kernel[dir] = KERNEL_REG;
+    return launch_gemm<false>(c.stream, a.M, N, a.K, A, lda, B, ldb, epi);
 }
 
-// want_ll (sparse operator only): leave the per-chain partial sums of log f(y | MU) in h.cm_part_fwd instead of MU
-// lx_ready (factored sparse operator only): LX = L X is already there, left by k_cm_Lcol_Lrow of the previous leapfrog step
-static int hmc_forward(Ctx& c, const double* X, int ldx, double var_par, bool store_mu = true, bool chain = false,
-                       bool want_ll = false, bool lx_ready = false)
+// what a product of the sampler is asked for besides its operands
+enum : unsigned {
+    PROD_STORE_MU = 1,   // forward: write the linear predictor MU too (see EpiForwardT)
+    PROD_CHAIN = 2,      // the launch depends on the one before it (profiler: no marker in between)
+    PROD_WANT_LL = 4,    // forward, sparse operator only: leave the per-chain partial sums of log f(y | MU) in h.cm_part_fwd instead of MU
+    PROD_LX_READY = 8,   // forward, factored sparse operator only: LX = L X is already there, left by k_cm_Lcol_Lrow of the previous leapfrog step
+};
+
+// MU = xb + ZL * X ; S = score
+static int hmc_forward(Ctx& c, const double* X, int ldx, double var_par, unsigned flags = PROD_STORE_MU)
 {
     HmcState& h = c.hmc;
-    const int slot = c.prof.begin(c.stream, 0, chain);
+    const int store_mu = (flags & PROD_STORE_MU) ? 1 : 0;
+    const int slot = c.prof.begin(c.stream, 0, (flags & PROD_CHAIN) != 0);
     int rc;
     if (h.cm) {
         c.last_kernel[0] = KERNEL_SPARSE;
@@ -546,52 +545,40 @@ static int hmc_forward(Ctx& c, const double* X, int ldx, double var_par, bool st
         // factored operator: LX = L X first, then the rows of Z gather from LX
         int W = c.sp.W; const int* col = c.sp.ell_col.as<int>(); const double* val = c.sp.ell_val.d(); const double* Xin = X;
         if (c.sp.factored) {
-            if (!lx_ready)
+            if (!(flags & PROD_LX_READY))
             hipLaunchKernelGGL(k_cm_Lrow, dim3((c.Q + 3) / 4, (h.Cw + 63) / 64), dim3(256), 0, c.stream, c.Q, h.Cw, h.V.ld,
                                c.sp.row_start.as<int>(), c.L.d(), c.L.ld, X, h.LX.d());
             W = c.z_width; col = c.z_idx.as<int>(); val = c.z_val.d(); Xin = h.LX.d();
         }
         double* pll = nullptr;
-        if (want_ll) {
+        if (flags & PROD_WANT_LL) {
             MCML_TRY(h.cm_part_fwd.ensure(sizeof(double) * (size_t)grid.x * h.V.ld));
             pll = h.cm_part_fwd.d();
         }
-#define MCML_CMF(FL) hipLaunchKernelGGL((k_cm_forward<FL>), grid, dim3(256), 0, c.stream, c.n, h.Cw, h.V.ld, W, col, val, Xin, \
-                                        c.xb.d(), c.y.d(), c.flink, var_par, store_mu ? 1 : 0, h.MU.d(), h.S.d(), rpw, pll, h.V.ld)
-        switch (c.flink) {
-        case 1: MCML_CMF(1); break;
-        case 3: MCML_CMF(3); break;
-        case 7: MCML_CMF(7); break;
-        case 12: MCML_CMF(12); break;
-        default: MCML_CMF(0); break;
-        }
-#undef MCML_CMF
+        dispatch_flink<1, 3, 7, 12>(c.flink, [&](auto FL) {
+            hipLaunchKernelGGL((k_cm_forward<FL()>), grid, dim3(256), 0, c.stream, c.n, h.Cw, h.V.ld, W, col, val, Xin, c.xb.d(),
+                               c.y.d(), c.flink, var_par, store_mu, h.MU.d(), h.S.d(), rpw, pll, h.V.ld);
+        });
         rc = (hipGetLastError() == hipSuccess) ? MCML_OK : MCML_EHIP;
-    } else {
-#define MCML_FWD(FL) rc = hmc_forward_launch(c, X, ldx, EpiForwardT<FL>{h.MU.d(), h.S.d(), h.MU.ld, c.xb.d(), c.y.d(), c.flink, \
-                                                                        store_mu ? 1 : 0, var_par})
-        switch (c.flink) {
-        case 1: MCML_FWD(1); break;
-        case 3: MCML_FWD(3); break;
-        case 7: MCML_FWD(7); break;
-        case 12: MCML_FWD(12); break;
-        default: MCML_FWD(0); break;
-        }
-#undef MCML_FWD
-    }
+    } else
+        rc = dispatch_flink<1, 3, 7, 12>(c.flink, [&](auto FL) {
+            return dense_product(c, 0, DenseOp{c.plan_fwd, c.band_fwd, c.n, c.Q, c.ZL}, X, ldx,
+                                 EpiForwardT<FL()>{h.MU.d(), h.S.d(), h.MU.ld, c.xb.d(), c.y.d(), c.flink, store_mu, var_par});
+        });
     c.prof.end(c.stream, slot);
     return rc;
 }
 
+// flags: PROD_CHAIN only
 // next_lx (factored sparse operator, inside a trajectory; cm_fuse_width's 8 or 16, else 0): also leave LX = L * UP for the
 // next step's forward product, by k_cm_Lcol_Lrow of that width
-static int hmc_backward(Ctx& c, const double* Xs, double* G, int s, double var_par, int mode, bool chain = false,
+static int hmc_backward(Ctx& c, const double* Xs, double* G, int s, double var_par, int mode, unsigned flags = 0,
                         int next_lx = 0)
 {
     HmcState& h = c.hmc;
     ChainArrays ca = chain_arrays(h);
     EpiBackward epi{Xs, G, h.R.d(), h.UP.d(), h.V.ld, ca.e, ca.steps, s, glm_score_post(var_par, c.flink), mode};
-    const int slot = c.prof.begin(c.stream, 1, chain);
+    const int slot = c.prof.begin(c.stream, 1, (flags & PROD_CHAIN) != 0);
     int rc;
     if (h.cm) {
         // factored operator: T = Z' S (mode 2: the raw sums), then g = -x + post * L' T with the leapfrog update
@@ -614,34 +601,17 @@ static int hmc_backward(Ctx& c, const double* Xs, double* G, int s, double var_p
         }
         if (f && next_lx && mode == 1) {
             const dim3 grid((c.sp.nblk + 3) / 4, (h.Cw + 63) / 64);
-            if (next_lx == 8)
-                hipLaunchKernelGGL((k_cm_Lcol_Lrow<8>), grid, dim3(256), 0, c.stream, c.sp.nblk, h.Cw, h.V.ld, c.sp.blk_ptr.as<int>(),
-                                   c.L.d(), c.L.ld, h.ZS.d(), Xs, G, h.R.d(), h.UP.d(), ca.e, ca.steps, s, post, h.LX.d());
-            else
-                hipLaunchKernelGGL((k_cm_Lcol_Lrow<16>), grid, dim3(256), 0, c.stream, c.sp.nblk, h.Cw, h.V.ld, c.sp.blk_ptr.as<int>(),
-                                   c.L.d(), c.L.ld, h.ZS.d(), Xs, G, h.R.d(), h.UP.d(), ca.e, ca.steps, s, post, h.LX.d());
+            hipLaunchKernelGGL(next_lx == 8 ? k_cm_Lcol_Lrow<8> : k_cm_Lcol_Lrow<16>, grid, dim3(256), 0, c.stream, c.sp.nblk, h.Cw,
+                               h.V.ld, c.sp.blk_ptr.as<int>(), c.L.d(), c.L.ld, h.ZS.d(), Xs, G, h.R.d(), h.UP.d(), ca.e, ca.steps, s,
+                               post, h.LX.d());
         } else if (f)
             hipLaunchKernelGGL(k_cm_Lcol, dim3((c.Q + 3) / 4, (h.Cw + 63) / 64), dim3(256), 0, c.stream, c.Q, h.Cw, h.V.ld,
                                c.sp.row_end.as<int>(), c.L.d(), c.L.ld, h.ZS.d(), Xs, G, h.R.d(), h.UP.d(), ca.e, ca.steps, s,
                                post, mode);
         rc = (hipGetLastError() == hipSuccess) ? MCML_OK : MCML_EHIP;
         c.last_kernel[1] = KERNEL_SPARSE;
-        c.prof.end(c.stream, slot);
-        return rc;
-    }
-    if (use_skinny() && skinny_applicable(c.plan_bwd, c.Q, c.n, h.Cw, c.ZLT.ld)) {
-        c.last_kernel[1] = KERNEL_SKINNY;
-        rc = launch_skinny(c.stream, c.plan_bwd, h.Cw, c.ZLT.d(), c.ZLT.ld, h.S.d(), h.S.ld, epi);
-    } else if (c.band_bwd && dlds_applicable(c.Q, h.Cw, c.n, c.ZLT.d(), c.ZLT.ld, c.ZLT.cols_alloc, h.S.d(), h.S.ld)) {
-        c.last_kernel[1] = KERNEL_BAND;
-        rc = launch_gemm_band(c.stream, c.plan_bwd, h.Cw, c.ZLT.d(), c.ZLT.ld, h.S.d(), h.S.ld, epi);
-    } else if (use_dlds() && dlds_applicable(c.Q, h.Cw, c.n, c.ZLT.d(), c.ZLT.ld, c.ZLT.cols_alloc, h.S.d(), h.S.ld)) {
-        c.last_kernel[1] = KERNEL_DLDS;
-        rc = launch_gemm_dlds(c.stream, c.Q, h.Cw, c.n, c.ZLT.d(), c.ZLT.ld, h.S.d(), h.S.ld, epi);
-    } else {
-        c.last_kernel[1] = KERNEL_REG;
-        rc = launch_gemm<false>(c.stream, c.Q, h.Cw, c.n, c.ZLT.d(), c.ZLT.ld, h.S.d(), h.S.ld, epi);
-    }
+    } else
+        rc = dense_product(c, 1, DenseOp{c.plan_bwd, c.band_bwd, c.Q, c.n, c.ZLT}, h.S.d(), h.S.ld, epi);
     c.prof.end(c.stream, slot);
     return rc;
 }
@@ -663,24 +633,29 @@ static CmParts cm_parts(const Ctx& c)
     return p;
 }
 // partial sums of log f(y | MU) + log N(X; 0, 1) (+ R^2) of every chain
-// skip_ll: the observation part came out of the last forward product (hmc_forward want_ll); only the prior / kinetic part runs
+// skip_ll: the observation part came out of the last forward product (PROD_WANT_LL); only the prior / kinetic part runs
 static int cm_logprob_partials(Ctx& c, const double* X, const double* R, double var_par, bool skip_ll = false)
 {
     HmcState& h = c.hmc;
     const CmParts p = cm_parts(c);
     const int nchn = skip_ll ? 0 : p.nchn;
     const dim3 grid((h.Cw + 63) / 64, nchn + p.nchq);
-#define MCML_LP_LAUNCH(FL) hipLaunchKernelGGL((k_cm_logprob_partials<FL>), grid, dim3(256), 0, c.stream, h.MU.d(), X, R, h.V.ld, \
-                       c.n, c.Q, h.Cw, c.y.d(), var_par, c.flink, nchn, p.ll, p.lp, p.kin, p.ldp)
-    switch (c.flink) {                       // the common families get their own instantiation
-    case 1: MCML_LP_LAUNCH(1); break;        // poisson / log
-    case 3: MCML_LP_LAUNCH(3); break;        // binomial / logit
-    case 7: MCML_LP_LAUNCH(7); break;        // gaussian / identity
-    default: MCML_LP_LAUNCH(0); break;
-    }
-#undef MCML_LP_LAUNCH
+    dispatch_flink<1, 3, 7>(c.flink, [&](auto FL) {
+        hipLaunchKernelGGL((k_cm_logprob_partials<FL()>), grid, dim3(256), 0, c.stream, h.MU.d(), X, R, h.V.ld, c.n, c.Q, h.Cw,
+                           c.y.d(), var_par, c.flink, nchn, p.ll, p.lp, p.kin, p.ldp);
+    });
     MCML_HIP(hipGetLastError());
     return MCML_OK;
+}
+
+// column-major state: lp[c] = log_prob of column c of X with the linear predictor in h.MU, for the first ncols columns
+static void hmc_lp0_launch(Ctx& c, const DevMat& X, int ncols, double var_par, double* lp)
+{
+    const HmcState& h = c.hmc;
+    dispatch_flink<1, 3, 7>(c.flink, [&](auto FL) {
+        hipLaunchKernelGGL((k_hmc_lp0<FL()>), dim3(ncols), dim3(256), 0, c.stream, h.MU.d(), h.MU.ld, c.n, X.d(), X.ld, c.Q,
+                           c.y.d(), var_par, c.flink, lp);
+    });
 }
 
 // log_prob and log_grad of every column of the current V
@@ -689,17 +664,247 @@ static int hmc_eval_state(Ctx& c, double var_par)
     HmcState& h = c.hmc;
     ChainArrays ca = chain_arrays(h);
     // sparse operator: the observation part of the log density comes out of the forward product (MU is not stored)
-    MCML_TRY(hmc_forward(c, h.V.d(), h.V.ld, var_par, !h.cm, false, h.cm));
+    MCML_TRY(hmc_forward(c, h.V.d(), h.V.ld, var_par, h.cm ? PROD_WANT_LL : PROD_STORE_MU));
     if (h.cm) {
         const CmParts p = cm_parts(c);
         MCML_TRY(cm_logprob_partials(c, h.V.d(), nullptr, var_par, true));
         hipLaunchKernelGGL(k_cm_lp0_fin, dim3((h.C + 63) / 64), dim3(256), 0, c.stream, h.cm_part_fwd.d(), p.lp,
                            cm_fwd_chunks(c), p.nchq, p.ldp, h.C, ca.lpcur);
     } else
-    MCML_FL_DISPATCH(c.flink, k_hmc_lp0, dim3(h.C), dim3(256), 0, c.stream, h.MU.d(), h.MU.ld, c.n, h.V.d(), h.V.ld, c.Q,
-                       c.y.d(), var_par, c.flink, ca.lpcur);
+        hmc_lp0_launch(c, h.V, h.C, var_par, ca.lpcur);
     MCML_HIP(hipGetLastError());
     return hmc_backward(c, h.V.d(), h.GRAD.d(), 0, var_par, 0);
+}
+
+// ---- pieces the two samplers (hmc_sample here, nuts_sample in nuts.h) share ----
+// initialise_u (mhmcmc.h:47-59): the state V (init, Q x C column-major on the device, or fresh normal draws) and the per-chain arrays
+static int sampler_init_state(Ctx& c, uint64_t seed, uint32_t chain_offset, uint32_t iter_idx, const double* init)
+{
+    HmcState& h = c.hmc;
+    const ChainArrays ca = chain_arrays(h);
+    if (h.cm)
+        hipLaunchKernelGGL(k_cm_init, dim3((h.C + 63) / 64, cm_parts(c).nchq), dim3(256), 0, c.stream, h.V.d(), h.V.ld, c.Q, h.C,
+                           cm_chain(ca), seed, chain_offset, iter_idx, init);
+    else
+        hipLaunchKernelGGL(k_hmc_init, dim3(h.C), dim3(256), 0, c.stream, h.V.d(), h.V.ld, c.Q, ca, seed, chain_offset, iter_idx,
+                           init);
+    MCML_HIP(hipGetLastError());
+    return MCML_OK;
+}
+
+// the current state of every chain c becomes sample column c * stride + col
+static void store_columns(Ctx& c, const DevMat& samp, int stride, int col)
+{
+    const HmcState& h = c.hmc;
+    if (h.cm)      // SAMP[k + (c * stride + col) * lds] = V[c + k * ldc]
+        hipLaunchKernelGGL(k_cm_transpose, dim3((c.Q + 31) / 32, (h.C + 31) / 32), dim3(256), 0, c.stream, h.V.d(), h.V.ld, c.Q,
+                           h.C, samp.d(), (size_t)samp.ld, (size_t)(stride > 0 ? stride : 1), col);
+    else
+        hipLaunchKernelGGL(k_hmc_store, dim3(h.C), dim3(256), 0, c.stream, h.V.d(), h.V.ld, c.Q, samp.d(), samp.ld, stride, col);
+}
+
+// c.U = L * samples  (mhmcmc.h:155; gen_u_samples.R:66); the caller sets c.niter
+static int samples_to_U(Ctx& c, const DevMat& samp, int ncols)
+{
+    const int Q = c.Q;
+    MCML_TRY(c.U.alloc(Q, ncols));
+    MCML_HIP(hipMemsetAsync(c.U.d(), 0, sizeof(double) * (size_t)c.U.ld * ncols, c.stream));
+    if (c.sp.active && c.sp.row_start.p) {
+        int gy = ncols < 1024 ? ncols : 1024;
+        hipLaunchKernelGGL(k_blockdiag_LV, dim3((Q + 255) / 256, gy), dim3(256), 0, c.stream, Q, ncols,
+                           c.sp.row_start.as<int>(), c.L.d(), c.L.ld, samp.d(), samp.ld, c.U.d(), c.U.ld);
+        MCML_HIP(hipGetLastError());
+    } else {
+        EpiAxpby epi{c.U.d(), c.U.ld, 1.0, 0.0};
+        MCML_TRY(launch_gemm<false>(c.stream, Q, ncols, Q, c.L.d(), c.L.ld, samp.d(), samp.ld, epi));
+    }
+    c.mcols = ncols;
+    c.zu_valid = false; c.uall_valid = false;
+    return MCML_OK;
+}
+
+// ---- hmc_sample in parts ----
+// GLMMR_MCML_HMC_TIMING=1: host wall-clock of a call's segments on stderr (set-up | proposals | tail), and of the slowest
+// proposal's enqueue -- to tell a slow call's cause from outside (run-to-run jitter)
+struct HmcTiming {
+    using Clock = std::chrono::steady_clock;
+    enum { PROPOSE, LOOK_AHEAD, TRAJECTORY, ACCEPT, NSEG };     // the segments of a proposal's enqueue
+    const bool on = enabled();
+    Clock::time_point t_phase = Clock::now(), t_mark = t_phase, t_prop = t_phase;
+    double setup = 0, loop = 0, sync = 0, slowest = 0, seg[NSEG] = {};   // seg: the slowest enqueue of each segment
+    int n_sync = 0, nprop = 0;
+
+    static bool enabled() { static const bool v = getenv("GLMMR_MCML_HMC_TIMING") != nullptr; return v; }
+    static double since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
+    static double now_ms() { return std::chrono::duration<double, std::milli>(Clock::now().time_since_epoch()).count(); }
+    double phase_end() { const double d = since(t_phase); t_phase = Clock::now(); return d; }   // set-up -> loop -> tail
+    void proposal()                                 // a proposal's enqueue begins (and the one before it has ended)
+    {
+        if (!on) return;
+        if (nprop++ > 0) slowest = std::max(slowest, since(t_prop));
+        t_prop = t_mark = Clock::now();
+    }
+    void start() { if (on) t_mark = Clock::now(); }                                // a segment begins ...
+    void mark(int k) { if (on) { seg[k] = std::max(seg[k], since(t_mark)); t_mark = Clock::now(); } }   // ... ends, the next begins
+    void waited() { if (on) { sync += since(t_mark); ++n_sync; } }                 // ... was a stream synchronisation
+    void print(int total) const
+    {
+        if (on)
+            fprintf(stderr, "hmc_sample: set-up %.2f ms | %d proposals %.2f ms enqueue (%d synchronous, %.2f ms waiting; slowest proposal %.2f ms: propose %.2f, count look-ahead %.2f, trajectory %.2f, accept %.2f) | tail %.2f ms\n",
+                    setup, total, loop, n_sync, sync, slowest, seg[PROPOSE], seg[LOOK_AHEAD], seg[TRAJECTORY], seg[ACCEPT], since(t_phase));
+    }
+};
+
+// what the proposals of one hmc_sample call share; constant over the call but for pending_commit
+struct HmcCall {
+    const glmmr_mcml_hmc_opts* o; double var_par; uint64_t seed; uint32_t iter_idx;
+    int C, d, total;                      // chains, draws per chain, proposals
+    ChainArrays ca;
+    const double* mom; uint8_t* flags; double* probs;   // device, or null: injected momenta; accept flags / probabilities out
+    const DevMat* samp;                   // the draws
+    int lf;                               // factored operator: the backward pass of step s leaves LX for step s + 1 (cm_fuse_width)
+    double* tpart; size_t tstride;        // component trajectories: K0 | ll | lp | kin partial sums, tstride doubles each
+    StepRing* ring; int* d_maxs;          // the step-count read-back
+    bool pending_commit;                  // sparse operator: the last decisions are applied by the next proposal's first kernel
+    int adapt(int it) const { return (it < o->warmup) && (it < o->adapt); }     // mhmcmc.h:131-136
+};
+
+// sparse operator: the accepted chains' V <- UP, GRAD <- GRADP: folded into the next proposal's first pass unless V is read
+// before that (a draw is stored after this proposal, or it is the last one)
+static void commit_cm(Ctx& c, HmcCall& k, int it)
+{
+    HmcState& h = c.hmc;
+    const bool stores_now = (k.C == 1) ? (it >= k.o->warmup - 1) : (it >= k.o->warmup);
+    if (it + 1 < k.total && !stores_now) k.pending_commit = true;
+    else hipLaunchKernelGGL(k_cm_commit, dim3((k.C + 63) / 64, cm_parts(c).nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(),
+                            h.UP.d(), h.GRADP.d(), h.V.ld, c.Q, k.C, h.cm_acc.as<int>());
+}
+
+static void store_draw(Ctx& c, const HmcCall& k, int it)
+{
+    const int warmup = k.o->warmup;
+    int col = -1, stride = 0;
+    if (k.C == 1) {
+        if (it == warmup - 1) col = 0;                      // samples.col(0) = u_, :142
+        else if (it >= warmup) col = it - warmup + 1;       // samples.col(i+1) = u_, :147
+    } else if (it >= warmup) { col = it - warmup; stride = k.d; }
+    if (col >= 0) store_columns(c, *k.samp, stride, col);
+}
+
+// The proposal's first kernels are on the stream: the leapfrog steps of every chain.  As many iterations are launched as the
+// read-ahead answers -- the cap while it speculates, else the largest step count over the chains, waited for; the chains'
+// own counts mask the rest
+static int leapfrog_steps(Ctx& c, const HmcCall& k, StepAhead& ahead, HmcTiming& t, int it)
+{
+    HmcState& h = c.hmc;
+    StepRing& ring = *k.ring;
+    const unsigned seq = ++ring.seq;
+    const int slot = (int)(seq % StepRing::SLOTS);
+    hipLaunchKernelGGL(k_max_steps, dim3(1), dim3(256), 0, c.stream, k.ca.steps, k.C, k.d_maxs, ring.d + slot, seq);
+    MCML_HIP(hipGetLastError());
+    t.mark(HmcTiming::PROPOSE);
+    int maxs = ahead.launched(seq, HmcTiming::now_ms);
+    if (maxs != StepAhead::SYNCHRONISE) t.mark(HmcTiming::LOOK_AHEAD);
+    else {
+        t.start();
+        MCML_HIP(hipStreamSynchronize(c.stream));
+        t.waited();
+        maxs = ahead.synchronised(seq);
+        MCML_REQUIRE(maxs != StepAhead::NOT_ARRIVED, "hmc: the step count of proposal %d did not arrive (token %llx, expected sequence %u)", it, ring.h[slot], seq);
+        MCML_REQUIRE(maxs != StepAhead::OUT_OF_ORDER, "hmc: step-count ring out of order");
+    }
+    MCML_REQUIRE(maxs >= 1 && maxs <= k.o->max_steps, "hmc: step count %d out of range", maxs);
+    // kernel timing (bench.py's roofline): every marker between two dependent launches costs ~2.5 us of idle GPU,
+    // so one proposal in four is timed -- still hundreds of launches per MCML iteration behind the average
+    c.prof.skip = (it & 3) != 0;
+    t.start();
+    int rc = MCML_OK;
+    for (int s = 0; s < maxs && rc == MCML_OK; ++s) {
+        const bool last = s == maxs - 1;
+        rc = hmc_forward(c, h.UP.d(), h.UP.ld, k.var_par, (s > 0 ? PROD_CHAIN : 0) | (last ? (h.cm ? PROD_WANT_LL : PROD_STORE_MU) : 0) |
+                                                              (k.lf && s > 0 ? PROD_LX_READY : 0));
+        if (rc == MCML_OK) rc = hmc_backward(c, h.UP.d(), h.GRADP.d(), s, k.var_par, 1, PROD_CHAIN, last ? 0 : k.lf);
+    }
+    c.prof.skip = false;
+    t.mark(HmcTiming::TRAJECTORY);
+    MCML_TRY(rc);
+    c.prof.unchain();
+    return MCML_OK;
+}
+
+// One proposal of every chain (new_proposal, mhmcmc.h:62-117), per back end.  dense ZL, column-major state:
+static int propose_dense(Ctx& c, HmcCall& k, StepAhead& ahead, HmcTiming& t, int it)
+{
+    HmcState& h = c.hmc;
+    const glmmr_mcml_hmc_opts* o = k.o;
+    hipLaunchKernelGGL(k_hmc_propose, dim3(k.C), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(), h.UP.d(),
+                       h.V.ld, c.Q, k.ca, o->lambda, o->max_steps, k.seed, (uint32_t)o->chain_offset, k.iter_idx, it,
+                       k.mom, k.C);
+    MCML_TRY(leapfrog_steps(c, k, ahead, t, it));
+    dispatch_flink<1, 3, 7>(c.flink, [&](auto FL) {
+        hipLaunchKernelGGL((k_hmc_accept<FL()>), dim3(k.C), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(), h.UP.d(),
+                           h.GRADP.d(), h.V.ld, c.Q, h.MU.d(), h.MU.ld, c.n, c.y.d(), k.var_par, c.flink, k.ca,
+                           o->target_accept, k.adapt(it), it, k.C, k.flags, k.probs);
+    });
+    store_draw(c, k, it);
+    MCML_HIP(hipGetLastError());
+    t.mark(HmcTiming::ACCEPT);
+    return MCML_OK;
+}
+
+// sparse ZL operator, chain-major state (hmc_cm.h), a launch pair per leapfrog step:
+static int propose_cm(Ctx& c, HmcCall& k, StepAhead& ahead, HmcTiming& t, int it)
+{
+    HmcState& h = c.hmc;
+    const glmmr_mcml_hmc_opts* o = k.o;
+    const CmParts p = cm_parts(c);
+    const CmChain cc = cm_chain(k.ca);
+    const dim3 chains((k.C + 63) / 64);
+    hipLaunchKernelGGL(k_cm_propose, dim3(chains.x, p.nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(),
+                       h.UP.d(), h.V.ld, c.Q, k.C, cc, k.seed, (uint32_t)o->chain_offset, k.iter_idx, it, k.mom,
+                       p.ss, p.ldp, k.pending_commit ? h.cm_acc.as<int>() : nullptr, h.GRADP.d());
+    k.pending_commit = false;
+    hipLaunchKernelGGL(k_cm_propose_fin, chains, dim3(256), 0, c.stream, p.ss, p.nchq, p.ldp, k.C, cc, o->lambda, o->max_steps);
+    MCML_TRY(leapfrog_steps(c, k, ahead, t, it));
+    MCML_TRY(cm_logprob_partials(c, h.UP.d(), h.R.d(), k.var_par, true));
+    hipLaunchKernelGGL((k_cm_accept_fin<false>), chains, dim3(256), 0, c.stream, h.cm_part_fwd.d(), p.lp, p.kin,
+                       cm_fwd_chunks(c), p.nchq, p.ldp, k.C, cc, o->target_accept, k.adapt(it), it, k.flags, k.probs,
+                       h.cm_acc.as<int>(), (const double*)nullptr, 0, 0.0, 0);
+    commit_cm(c, k, it);
+    store_draw(c, k, it);
+    MCML_HIP(hipGetLastError());
+    t.mark(HmcTiming::ACCEPT);
+    return MCML_OK;
+}
+
+// component-local trajectories (hmc_traj.h): one launch instead of the loop over the steps, no step count to read
+static int propose_component(Ctx& c, HmcCall& k, int it)
+{
+    HmcState& h = c.hmc;
+    const glmmr_mcml_hmc_opts* o = k.o;
+    const CmChain cc = cm_chain(k.ca);
+    double* const tpart = k.tpart; const size_t tstride = k.tstride;
+    TrajArgs a{h.V.d(), h.GRAD.d(), h.UP.d(), h.GRADP.d(), h.V.ld, k.C, c.Q, cc, k.seed, (uint32_t)o->chain_offset,
+               k.iter_idx, it, k.mom, k.pending_commit ? h.cm_acc.as<int>() : nullptr, o->lambda, o->max_steps, c.flink,
+               k.var_par, glm_score_post(k.var_par, c.flink), tpart, tpart + tstride, tpart + 2 * tstride,
+               tpart + 3 * tstride, h.V.ld, c.cp.plan.max_vars};
+    k.pending_commit = false;
+    c.prof.skip = (it & 3) != 0;
+    const int slot = c.prof.begin(c.stream, 0);     // counted (and timed) under the forward product's slot
+    const int rc = cm_traj_launch(c, a);
+    c.prof.end(c.stream, slot);
+    c.prof.skip = false;
+    c.prof.unchain();
+    MCML_TRY(rc);
+    const int ni = c.cp.plan.nitems();
+    hipLaunchKernelGGL((k_cm_accept_fin<true>), dim3((k.C + 63) / 64), dim3(256), 0, c.stream, tpart + tstride, tpart + 2 * tstride,
+                       tpart + 3 * tstride, ni, ni, h.V.ld, k.C, cc, o->target_accept, k.adapt(it), it, k.flags, k.probs,
+                       h.cm_acc.as<int>(), tpart, ni, o->lambda, o->max_steps);
+    commit_cm(c, k, it);
+    store_draw(c, k, it);
+    MCML_HIP(hipGetLastError());
+    c.last_kernel[0] = c.last_kernel[1] = KERNEL_COMPONENT;
+    return MCML_OK;
 }
 
 int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed,
@@ -714,260 +919,69 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
     const int d = (C == 1) ? o->nsamp : (o->nsamp + C - 1) / C;   // draws per chain
     const int total = o->warmup + d;
     const int ncols = (C == 1) ? d + 1 : C * d;                   // mhmcmc.h:126: Q x (nsamp+1)
-    const int Q = c.Q, n = c.n;
+    const int Q = c.Q;
     HmcState& h = c.hmc;
-    // GLMMR_MCML_HMC_TIMING=1: host wall-clock of this call's segments on stderr (set-up | proposals | tail), and of the slowest
-    // proposal's enqueue -- to tell a slow call's cause from outside (run-to-run jitter)
-    static const bool timing = getenv("GLMMR_MCML_HMC_TIMING") != nullptr;
-    const auto tc0 = std::chrono::steady_clock::now();
-    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    HmcTiming t;
     MCML_TRY(model_update_beta(c, beta));
     MCML_TRY(hmc_alloc(c, C));
-    ChainArrays ca = chain_arrays(h);
     DevMat samp;
     MCML_TRY(samp.alloc(Q, ncols));
     MCML_HIP(hipMemsetAsync(samp.d(), 0, sizeof(double) * (size_t)samp.ld * ncols, c.stream));
 
     DevBuf d_init, d_mom, d_flags, d_probs;
-    const double* p_init = nullptr; const double* p_mom = nullptr;
     if (inj_init) {
         MCML_TRY(d_init.ensure(sizeof(double) * (size_t)Q * C));
         MCML_TRY(copy_h2d(d_init.p, inj_init, sizeof(double) * (size_t)Q * C, c.stream));
-        p_init = d_init.d();
     }
     if (inj_mom) {
         MCML_TRY(d_mom.ensure(sizeof(double) * (size_t)Q * C * total));
         MCML_TRY(copy_h2d(d_mom.p, inj_mom, sizeof(double) * (size_t)Q * C * total, c.stream));
-        p_mom = d_mom.d();
     }
     if (flags_out) MCML_TRY(d_flags.ensure((size_t)C * total));
     if (probs_out) MCML_TRY(d_probs.ensure(sizeof(double) * (size_t)C * total));
 
-    const int nchq = (Q + cm_qrows(Q) - 1) / cm_qrows(Q);
-    auto store = [&](int stride, int col) {
-        if (h.cm)      // SAMP[k + (c * stride + col) * lds] = V[c + k * ldc]
-            hipLaunchKernelGGL(k_cm_transpose, dim3((Q + 31) / 32, (C + 31) / 32), dim3(256), 0, c.stream, h.V.d(), h.V.ld, Q, C,
-                               samp.d(), (size_t)samp.ld, (size_t)(stride > 0 ? stride : 1), col);
-        else
-            hipLaunchKernelGGL(k_hmc_store, dim3(C), dim3(256), 0, c.stream, h.V.d(), h.V.ld, Q, samp.d(), samp.ld, stride, col);
-    };
-    if (h.cm)
-        hipLaunchKernelGGL(k_cm_init, dim3((C + 63) / 64, nchq), dim3(256), 0, c.stream, h.V.d(), h.V.ld, Q, C, cm_chain(ca), seed,
-                           (uint32_t)o->chain_offset, iter_idx, p_init);
-    else
-    hipLaunchKernelGGL(k_hmc_init, dim3(C), dim3(256), 0, c.stream, h.V.d(), h.V.ld, Q, ca, seed,
-                       (uint32_t)o->chain_offset, iter_idx, p_init);
-    MCML_HIP(hipGetLastError());
-    MCML_TRY(hmc_eval_state(c, var_par));
-    if (C == 1 && o->warmup == 0) store(0, 0);
-    // component-local trajectories: one launch per proposal instead of the loop over the steps below
+    // the step-count read-back: step_ahead.h.  GLMMR_MCML_HMC_SPEC=0 disables the speculation
+    static const bool spec_allowed = !(getenv("GLMMR_MCML_HMC_SPEC") && atoi(getenv("GLMMR_MCML_HMC_SPEC")) == 0);
+    StepRing& ring = h.ring;
+    if (!ring.h) {
+        MCML_HIP(hipHostMalloc((void**)&ring.h, sizeof(unsigned long long) * StepRing::SLOTS, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(ring.h, 0, sizeof(unsigned long long) * StepRing::SLOTS);
+        MCML_HIP(hipHostGetDevicePointer((void**)&ring.d, ring.h, 0));
+    }
+    StepAhead ahead(ring.h, ring.seq, o->max_steps, spec_allowed);
+
+    // component-local trajectories: one launch per proposal instead of the loop over the steps
     const bool traj = h.cm && cm_traj_used(c);
-    double* tpart = traj ? h.cp_part.d() : nullptr;
-    const size_t tstride = traj ? (size_t)c.cp.plan.nitems() * h.V.ld : 0;
+    HmcCall k{o, var_par, seed, iter_idx, C, d, total, chain_arrays(h), d_mom.d(), d_flags.as<uint8_t>(), d_probs.d(), &samp,
+              h.cm ? cm_fuse_width(c) : 0, traj ? h.cp_part.d() : nullptr, traj ? (size_t)c.cp.plan.nitems() * h.V.ld : 0,
+              &ring, c.scalars.as<int>() + 34, false};
+
+    MCML_TRY(sampler_init_state(c, seed, (uint32_t)o->chain_offset, iter_idx, d_init.d()));
+    MCML_TRY(hmc_eval_state(c, var_par));
+    if (C == 1 && o->warmup == 0) store_columns(c, samp, 0, 0);
     if (traj) {                                 // xb follows beta: the records' copy of it
         const int ns = c.cp.plan.nslots;
         hipLaunchKernelGGL(k_cp_fill_xy, dim3((ns + 255) / 256), dim3(256), 0, c.stream, ns, c.cp.slot_i.as<int>(), c.xb.d(),
                            c.y.d(), c.cp.slot_d.d());
         MCML_HIP(hipGetLastError());
     }
-
-    int* d_maxs = c.scalars.as<int>() + 34;
-    // The number of leapfrog iterations to launch is the largest step count over the chains, a device
-    // value.  Reading it back costs a host synchronisation per proposal (~50 us of idle GPU).  While
-    // the step counts observed so far sit at the cap (lambda / e >= max_steps, the usual regime), the
-    // cap itself is launched without waiting -- iterations beyond a chain's own count are masked
-    // no-ops, so results are identical -- and the true value comes back on its own: k_max_steps stores
-    // (proposal sequence number, count) into a ring of host memory mapped into the device (StepRing,
-    // ctx.h), which the host reads with plain loads; an observation below the cap switches back to the
-    // exact, synchronous path.  GLMMR_MCML_HMC_SPEC=0 disables the speculation.
-    // (Until round 3 the read-back was a hipMemcpyAsync into a pinned ring allocated per call plus an
-    // event per slot: in about one process in four ONE such enqueue stalled for 65-70 ms inside the
-    // runtime -- config 4's "slow first repetition", DESIGN.md 6 -- and every call paid a hipHostMalloc,
-    // four event creations and their release.  The loop now makes no HIP call besides kernel launches
-    // and, on the synchronous path, the stream synchronisation.)
-    static const bool spec_allowed = !(getenv("GLMMR_MCML_HMC_SPEC") && atoi(getenv("GLMMR_MCML_HMC_SPEC")) == 0);
-    constexpr int RING = StepRing::SLOTS, AHEAD = 4;      // the host runs at most AHEAD proposals ahead of the last count it has seen
-    StepRing& ring = h.ring;
-    if (!ring.h) {
-        MCML_HIP(hipHostMalloc((void**)&ring.h, sizeof(unsigned long long) * RING, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(ring.h, 0, sizeof(unsigned long long) * RING);
-        MCML_HIP(hipHostGetDevicePointer((void**)&ring.d, ring.h, 0));
-    }
-    int seen_maxs = -1;                         // latest step count actually observed
-    const unsigned seq0 = ring.seq + 1;          // sequence number of this call's first proposal
-    unsigned seen_seq = seq0 - 1;                // newest proposal of this call whose count has arrived
-    // Speculating costs a whole masked leapfrog step whenever the true count is below the cap (config 5: 290 us against ~30 us
-    // for the wait it saves), so it needs evidence: SPEC_STREAK consecutive proposals at the cap, and the first count below it
-    // ends it.  (With "the last count seen was at the cap" as the only condition a model whose longest chain hovers round the
-    // cap flipped between the two paths by the timing of the read-back: config 5 measured 337-386 ms per iteration from one
-    // process to the next on one box.)
-    constexpr int SPEC_STREAK = 8;
-    int streak = 0;                              // consecutive proposals observed at the cap
-    auto observe = [&](unsigned sq, int v) { seen_seq = sq; seen_maxs = v; streak = (v == o->max_steps) ? streak + 1 : 0; };
-    auto harvest = [&]() {                       // the counts that have arrived, in proposal order (at most AHEAD + 1 are outstanding)
-        for (;;) {
-            const unsigned want = seen_seq + 1;
-            if ((int)(ring.seq - want) < 0) return;                  // nothing launched beyond what has been seen
-            const unsigned long long tok = __atomic_load_n(ring.h + (want % RING), __ATOMIC_ACQUIRE);
-            if ((unsigned)(tok >> 32) != want) return;               // not there yet
-            observe(want, (int)(unsigned)tok);
-        }
-    };
-    bool pending_commit = false;                // sparse operator: the last decisions are applied by the next k_cm_propose
-    // the accepted chains' V <- UP, GRAD <- GRADP: folded into the next proposal's first pass unless V is read
-    // before that (a draw is stored after this proposal, or it is the last one)
-    auto commit_cm = [&](int it) {
-        const bool stores_now = (C == 1) ? (it >= o->warmup - 1) : (it >= o->warmup);
-        if (it + 1 < total && !stores_now) pending_commit = true;
-        else hipLaunchKernelGGL(k_cm_commit, dim3((C + 63) / 64, nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.UP.d(),
-                                h.GRADP.d(), h.V.ld, Q, C, h.cm_acc.as<int>());
-    };
-    auto store_draw = [&](int it) {
-        int col = -1, stride = 0;
-        if (C == 1) {
-            if (it == o->warmup - 1) col = 0;                      // samples.col(0) = u_, :142
-            else if (it >= o->warmup) col = it - o->warmup + 1;    // samples.col(i+1) = u_, :147
-        } else if (it >= o->warmup) { col = it - o->warmup; stride = d; }
-        if (col >= 0) store(stride, col);
-    };
-    const int lf = h.cm ? cm_fuse_width(c) : 0; // factored operator: the backward pass of step s leaves LX for step s + 1
-    const double t_setup = since(tc0);
-    const auto tc1 = std::chrono::steady_clock::now();
-    auto tp_prev = tc1;
-    double t_sync = 0, t_slowest = 0; int n_sync = 0;
-    double seg[5] = {0, 0, 0, 0, 0};   // slowest enqueue of: [0] propose launches, [1] count look-ahead (speculative path), [3] trajectory launches, [4] accept / commit / store
-    auto mark = [&](int k, std::chrono::steady_clock::time_point t) { if (timing) { const double d = since(t); if (d > seg[k]) seg[k] = d; } };
+    t.setup = t.phase_end();
     for (int it = 0; it < total; ++it) {
-        const auto tp0 = std::chrono::steady_clock::now();
-        if (it > 0 && timing) { const double d = since(tp_prev); if (d > t_slowest) t_slowest = d; }
-        tp_prev = tp0;
-        if (traj) {
-            TrajArgs a{h.V.d(), h.GRAD.d(), h.UP.d(), h.GRADP.d(), h.V.ld, C, Q, cm_chain(ca), seed, (uint32_t)o->chain_offset,
-                       iter_idx, it, p_mom, pending_commit ? h.cm_acc.as<int>() : nullptr, o->lambda, o->max_steps, c.flink,
-                       var_par, glm_score_post(var_par, c.flink), tpart, tpart + tstride, tpart + 2 * tstride,
-                       tpart + 3 * tstride, h.V.ld, c.cp.plan.max_vars};
-            pending_commit = false;
-            c.prof.skip = (it & 3) != 0;
-            const int slot = c.prof.begin(c.stream, 0);     // counted (and timed) under the forward product's slot
-            const int rc = cm_traj_launch(c, a);
-            c.prof.end(c.stream, slot);
-            c.prof.skip = false;
-            c.prof.unchain();
-            MCML_TRY(rc);
-            const int ni = c.cp.plan.nitems();
-            hipLaunchKernelGGL((k_cm_accept_fin<true>), dim3((C + 63) / 64), dim3(256), 0, c.stream, tpart + tstride, tpart + 2 * tstride,
-                               tpart + 3 * tstride, ni, ni, h.V.ld, C, cm_chain(ca), o->target_accept,
-                               (it < o->warmup) && (it < o->adapt) ? 1 : 0, it, flags_out ? d_flags.as<uint8_t>() : nullptr,
-                               probs_out ? d_probs.d() : nullptr, h.cm_acc.as<int>(), tpart, ni, o->lambda, o->max_steps);
-            commit_cm(it);
-            store_draw(it);
-            MCML_HIP(hipGetLastError());
-            c.last_kernel[0] = c.last_kernel[1] = KERNEL_COMPONENT;
-            continue;
-        }
-        if (h.cm) {
-            const CmParts p = cm_parts(c);
-            hipLaunchKernelGGL(k_cm_propose, dim3((C + 63) / 64, p.nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(),
-                               h.UP.d(), h.V.ld, Q, C, cm_chain(ca), seed, (uint32_t)o->chain_offset, iter_idx, it, p_mom,
-                               p.ss, p.ldp, pending_commit ? h.cm_acc.as<int>() : nullptr, h.GRADP.d());
-            pending_commit = false;
-            hipLaunchKernelGGL(k_cm_propose_fin, dim3((C + 63) / 64), dim3(256), 0, c.stream, p.ss, p.nchq, p.ldp, C,
-                               cm_chain(ca), o->lambda, o->max_steps);
-        } else
-        hipLaunchKernelGGL(k_hmc_propose, dim3(C), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(), h.UP.d(),
-                           h.V.ld, Q, ca, o->lambda, o->max_steps, seed, (uint32_t)o->chain_offset, iter_idx, it,
-                           p_mom, C);
-        const unsigned seq = ++ring.seq;
-        const int slot = (int)(seq % RING);
-        hipLaunchKernelGGL(k_max_steps, dim3(1), dim3(256), 0, c.stream, ca.steps, C, d_maxs, ring.d + slot, seq);
-        MCML_HIP(hipGetLastError());
-        mark(0, tp0);
-        const auto tq0 = std::chrono::steady_clock::now();
-        harvest();
-        int maxs = 0;
-        bool spec = spec_allowed && streak >= SPEC_STREAK;
-        if (spec) {
-            // bounded look-ahead: a count below the cap must be noticed within AHEAD proposals (in the dense path a masked
-            // step is a full product).  Plain loads of host memory; a count that does not arrive falls back to the wait below
-            const auto tw0 = std::chrono::steady_clock::now();
-            while ((int)(seq - seen_seq) > AHEAD) {
-                harvest();
-                if ((int)(seq - seen_seq) > AHEAD && since(tw0) > 2000.0) { spec = false; break; }
-            }
-            if (spec && streak < SPEC_STREAK) spec = false;
-        }
-        if (spec) {
-            maxs = o->max_steps;
-            mark(1, tq0);
-        } else {
-            const auto ts0 = std::chrono::steady_clock::now();
-            MCML_HIP(hipStreamSynchronize(c.stream));
-            if (timing) { t_sync += since(ts0); ++n_sync; }
-            const unsigned long long tok = __atomic_load_n(ring.h + slot, __ATOMIC_ACQUIRE);
-            MCML_REQUIRE((unsigned)(tok >> 32) == seq, "hmc: the step count of proposal %d did not arrive (token %llx, expected sequence %u)", it, tok, seq);
-            maxs = (int)(unsigned)tok;
-            harvest();                                               // everything up to and including this proposal, in order
-            MCML_REQUIRE(seen_seq == seq && seen_maxs == maxs, "hmc: step-count ring out of order");
-        }
-        MCML_REQUIRE(maxs >= 1 && maxs <= o->max_steps, "hmc: step count %d out of range", maxs);
-        // kernel timing (bench.py's roofline): every marker between two dependent launches costs ~2.5 us of idle GPU,
-        // so one proposal in four is timed -- still hundreds of launches per MCML iteration behind the average
-        c.prof.skip = (it & 3) != 0;
-        const auto tt0 = std::chrono::steady_clock::now();
-        int rc_traj = MCML_OK;
-        for (int s = 0; s < maxs && rc_traj == MCML_OK; ++s) {
-            rc_traj = hmc_forward(c, h.UP.d(), h.UP.ld, var_par, !h.cm && s == maxs - 1, s > 0, h.cm && s == maxs - 1, lf && s > 0);
-            if (rc_traj == MCML_OK) rc_traj = hmc_backward(c, h.UP.d(), h.GRADP.d(), s, var_par, 1, true, s + 1 < maxs ? lf : 0);
-        }
-        c.prof.skip = false;
-        mark(3, tt0);
-        const auto ta0 = std::chrono::steady_clock::now();
-        MCML_TRY(rc_traj);
-        c.prof.unchain();
-        const int adapt = (it < o->warmup) && (it < o->adapt);     // mhmcmc.h:131-136
-        if (h.cm) {
-            const CmParts p = cm_parts(c);
-            MCML_TRY(cm_logprob_partials(c, h.UP.d(), h.R.d(), var_par, true));
-            hipLaunchKernelGGL((k_cm_accept_fin<false>), dim3((C + 63) / 64), dim3(256), 0, c.stream, h.cm_part_fwd.d(), p.lp, p.kin,
-                               cm_fwd_chunks(c), p.nchq, p.ldp, C, cm_chain(ca), o->target_accept, adapt, it,
-                               flags_out ? d_flags.as<uint8_t>() : nullptr, probs_out ? d_probs.d() : nullptr,
-                               h.cm_acc.as<int>(), (const double*)nullptr, 0, 0.0, 0);
-            commit_cm(it);
-        } else
-        MCML_FL_DISPATCH(c.flink, k_hmc_accept, dim3(C), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(), h.UP.d(),
-                           h.GRADP.d(), h.V.ld, Q, h.MU.d(), h.MU.ld, n, c.y.d(), var_par, c.flink, ca,
-                           o->target_accept, adapt, it, C, flags_out ? d_flags.as<uint8_t>() : nullptr,
-                           probs_out ? d_probs.d() : nullptr);
-        store_draw(it);
-        MCML_HIP(hipGetLastError());
-        mark(4, ta0);
+        t.proposal();
+        if (traj) MCML_TRY(propose_component(c, k, it));
+        else if (h.cm) MCML_TRY(propose_cm(c, k, ahead, t, it));
+        else MCML_TRY(propose_dense(c, k, ahead, t, it));
     }
-    const double t_loop = since(tc1);
-    const auto tc2 = std::chrono::steady_clock::now();
-    // return (L * samples)  (mhmcmc.h:155)
-    MCML_TRY(c.U.alloc(Q, ncols));
-    MCML_HIP(hipMemsetAsync(c.U.d(), 0, sizeof(double) * (size_t)c.U.ld * ncols, c.stream));
-    if (c.sp.active && c.sp.row_start.p) {
-        int gy = ncols < 1024 ? ncols : 1024;
-        hipLaunchKernelGGL(k_blockdiag_LV, dim3((Q + 255) / 256, gy), dim3(256), 0, c.stream, Q, ncols,
-                           c.sp.row_start.as<int>(), c.L.d(), c.L.ld, samp.d(), samp.ld, c.U.d(), c.U.ld);
-        MCML_HIP(hipGetLastError());
-    } else {
-        EpiAxpby epi{c.U.d(), c.U.ld, 1.0, 0.0};
-        MCML_TRY(launch_gemm<false>(c.stream, Q, ncols, Q, c.L.d(), c.L.ld, samp.d(), samp.ld, epi));
-    }
-    c.mcols = ncols;
-    c.niter = (C == 1) ? d : ncols;                                // mcmlmodel.h:73 vs mhmcmc.h:126 (D5)
-    c.zu_valid = false; c.uall_valid = false;
+    t.loop = t.phase_end();
+    MCML_TRY(samples_to_U(c, samp, ncols));     // return (L * samples)  (mhmcmc.h:155)
+    c.niter = (C == 1) ? d : ncols;             // mcmlmodel.h:73 vs mhmcmc.h:126 (D5)
     if (flags_out) MCML_TRY(copy_d2h(flags_out, d_flags.p, (size_t)C * total, c.stream));
     if (probs_out) MCML_TRY(copy_d2h(probs_out, d_probs.p, sizeof(double) * (size_t)C * total, c.stream));
     double dg[6] = {0, 0, 0, 0, 0, 0};
-    hipLaunchKernelGGL(k_hmc_diag, dim3(1), dim3(64), 0, c.stream, ca, C, c.scalars.d() + 8);
+    hipLaunchKernelGGL(k_hmc_diag, dim3(1), dim3(64), 0, c.stream, k.ca, C, c.scalars.d() + 8);
     MCML_TRY(copy_d2h(dg, c.scalars.d() + 8, sizeof dg, c.stream));
     MCML_HIP(hipStreamSynchronize(c.stream));
-    if (timing)
-        fprintf(stderr, "hmc_sample: set-up %.2f ms | %d proposals %.2f ms enqueue (%d synchronous, %.2f ms waiting; slowest proposal %.2f ms: propose %.2f, count look-ahead %.2f, trajectory %.2f, accept %.2f) | tail %.2f ms\n",
-                t_setup, total, t_loop, n_sync, t_sync, t_slowest, seg[0], seg[1], seg[3], seg[4], since(tc2));
+    t.print(total);
     c.prof.collect();
     if (diag) {
         diag->accept_rate = dg[0] / ((double)C * total);

@@ -386,8 +386,10 @@ int model_loglik_sum(Ctx& c, double var_par, double* sum_out)
     MCML_TRY(model_update_zu(c));
     int gx = (c.n + 255) / 256, gy = c.niter < 64 ? c.niter : 64;
     MCML_TRY(c.partials.ensure(sizeof(double) * (size_t)(gx * gy + 16)));
-    MCML_FL_DISPATCH(c.flink, k_loglik, dim3(gx, gy), dim3(256), 0, c.stream, c.ZU.d(), c.ZU.ld, c.n, c.niter,
-                       c.xb.d(), c.y.d(), var_par, c.flink, c.partials.d());
+    dispatch_flink<1, 3, 7>(c.flink, [&](auto FL) {
+        hipLaunchKernelGGL((k_loglik<FL()>), dim3(gx, gy), dim3(256), 0, c.stream, c.ZU.d(), c.ZU.ld, c.n, c.niter, c.xb.d(),
+                           c.y.d(), var_par, c.flink, c.partials.d());
+    });
     MCML_HIP(hipGetLastError());
     MCML_TRY(device_sum(c, c.partials.d(), gx * gy, c.scalars.d() + 4));
     MCML_TRY(copy_d2h(sum_out, c.scalars.d() + 4, sizeof(double), c.stream));
@@ -517,10 +519,12 @@ int model_mcnr_stats(Ctx& c, double var_par, double* stats)
     double* pw = sig + round_up(m + 16, 32);
     double* pwu = pw + (size_t)nchunks * ldp;
     MCML_TRY(c.reduce_buf.ensure(sizeof(double) * (size_t)ns));
-    MCML_FL_DISPATCH(c.flink, k_mcnr_col, dim3(m), dim3(256), 0, c.stream, c.ZU.d(), c.ZU.ld, n, c.xb.d(), c.y.d(),
-                     c.link_code, sig);
-    MCML_FL_DISPATCH(c.flink, k_mcnr_row, dim3((n + 255) / 256, nchunks), dim3(256), 0, c.stream, c.ZU.d(), c.ZU.ld, n, m,
-                     c.xb.d(), c.y.d(), c.flink, c.link_code, nvar_par, pw, pwu, ldp);
+    dispatch_flink<1, 3, 7>(c.flink, [&](auto FL) {
+        hipLaunchKernelGGL((k_mcnr_col<FL()>), dim3(m), dim3(256), 0, c.stream, c.ZU.d(), c.ZU.ld, n, c.xb.d(), c.y.d(),
+                           c.link_code, sig);
+        hipLaunchKernelGGL((k_mcnr_row<FL()>), dim3((n + 255) / 256, nchunks), dim3(256), 0, c.stream, c.ZU.d(), c.ZU.ld, n, m,
+                           c.xb.d(), c.y.d(), c.flink, c.link_code, nvar_par, pw, pwu, ldp);
+    });
     hipLaunchKernelGGL(k_mcnr_rowsum, dim3((n + 63) / 64), dim3(64), 0, c.stream, pw, pwu, ldp, n, nchunks, wsum, wusum);
     hipLaunchKernelGGL(k_mcnr_fin, dim3(ns), dim3(256), 0, c.stream, c.X.d(), c.X.ld, n, P, wsum, wusum, sig, m,
                        c.reduce_buf.d());

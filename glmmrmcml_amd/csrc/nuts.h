@@ -574,30 +574,29 @@ struct NutsRun {
     long long leapfrogs = 0;
 
     template <class K, class... A> void vec(K k, A... a) { hipLaunchKernelGGL(k, vgrid, dim3(256), 0, c.stream, a...); }
+    // run.vec(K<CM>, ...) with CM the layout of the state
+#define NUTS_VEC(run, K, ...) ((run).h.cm ? (run).vec(K<true>, __VA_ARGS__) : (run).vec(K<false>, __VA_ARGS__))
 
     // gradient and log density of WX = h.UP for every chain: GRADP, nc.lp_new
     int eval_new()
     {
-        MCML_TRY(hmc_forward(c, h.UP.d(), h.UP.ld, var_par, true));
+        MCML_TRY(hmc_forward(c, h.UP.d(), h.UP.ld, var_par));
         if (h.cm) {
             const CmParts p = cm_parts(c);
             MCML_TRY(cm_logprob_partials(c, h.UP.d(), nullptr, var_par));
             hipLaunchKernelGGL(k_cm_lp0_fin, dim3((h.Cw + 63) / 64), dim3(256), 0, c.stream, p.ll, p.lp, p.nchn, p.nchq, p.ldp,
                                h.Cw, nc.lp_new);
         } else
-            MCML_FL_DISPATCH(c.flink, k_hmc_lp0, dim3(h.Cw), dim3(256), 0, c.stream, h.MU.d(), h.MU.ld, c.n, h.UP.d(), h.UP.ld, Q,
-                               c.y.d(), var_par, c.flink, nc.lp_new);
+            hmc_lp0_launch(c, h.UP, h.Cw, var_par, nc.lp_new);
         MCML_HIP(hipGetLastError());
         return hmc_backward(c, h.UP.d(), h.GRADP.d(), 0, var_par, 0);
     }
     // one leapfrog step of every growing chain, leaf bookkeeping with tz merges to follow
     int leaf(int tz)
     {
-        if (h.cm) vec(k_nuts_leap_pre<true>, nv, h.UP.d(), h.R.d(), ld, Q, C, nc);
-        else vec(k_nuts_leap_pre<false>, nv, h.UP.d(), h.R.d(), ld, Q, C, nc);
+        NUTS_VEC(*this, k_nuts_leap_pre, nv, h.UP.d(), h.R.d(), ld, Q, C, nc);
         MCML_TRY(eval_new());
-        if (h.cm) vec(k_nuts_leap_post<true>, h.UP.d(), h.R.d(), h.GRADP.d(), nv, ld, Q, C, nc, part, pstride, ldp);
-        else vec(k_nuts_leap_post<false>, h.UP.d(), h.R.d(), h.GRADP.d(), nv, ld, Q, C, nc, part, pstride, ldp);
+        NUTS_VEC(*this, k_nuts_leap_post, h.UP.d(), h.R.d(), h.GRADP.d(), nv, ld, Q, C, nc, part, pstride, ldp);
         hipLaunchKernelGGL(k_nuts_leaf_fin, dim3((C + 63) / 64), dim3(256), 0, c.stream, part, nchunk, ldp, C, nc, tz);
         MCML_HIP(hipGetLastError());
         ++leapfrogs;
@@ -619,8 +618,7 @@ struct NutsRun {
         h.Cw = C;
         MCML_TRY(hmc_eval_state(c, var_par));                          // lpcur, GRAD at V
         ChainArrays ca = chain_arrays(h);
-        if (h.cm) vec(k_nuts_begin<true>, h.V.d(), h.GRAD.d(), nv, ld, Q, C, seed, chain_offset, it, stream, part, pstride, ldp);
-        else vec(k_nuts_begin<false>, h.V.d(), h.GRAD.d(), nv, ld, Q, C, seed, chain_offset, it, stream, part, pstride, ldp);
+        NUTS_VEC(*this, k_nuts_begin, h.V.d(), h.GRAD.d(), nv, ld, Q, C, seed, chain_offset, it, stream, part, pstride, ldp);
         hipLaunchKernelGGL(k_nuts_begin_fin, dim3((C + 63) / 64), dim3(256), 0, c.stream, part, nchunk, ldp, C, nc, ca.lpcur);
         MCML_HIP(hipGetLastError());
         return MCML_OK;
@@ -641,16 +639,14 @@ struct NutsRun {
         for (int j = 0; j < max_depth; ++j) {
             MCML_TRY(pack(nact));
             hipLaunchKernelGGL(k_nuts_begin_doubling, dim3((C + 255) / 256), dim3(256), 0, c.stream, C, nc, 0);
-            if (h.cm) vec(k_nuts_save_adj<true>, nv, ld, Q, C, nc);
-            else vec(k_nuts_save_adj<false>, nv, ld, Q, C, nc);
+            NUTS_VEC(*this, k_nuts_save_adj, nv, ld, Q, C, nc);
             const int nleaf = 1 << j;
             for (int n = 0; n < nleaf; ++n) {
                 int tz = 0;
                 while ((n >> tz) & 1) ++tz;                            // merges this leaf completes
                 MCML_TRY(leaf(tz));
                 for (int l = 0; l < tz; ++l) {
-                    if (h.cm) vec(k_nuts_merge<true>, Srho[l], Spb[l], Spe[l], Sth[l], nv, nc.choose + (size_t)l * nc.Cp, ld, Q, C, nc, part, pstride, ldp);
-                    else vec(k_nuts_merge<false>, Srho[l], Spb[l], Spe[l], Sth[l], nv, nc.choose + (size_t)l * nc.Cp, ld, Q, C, nc, part, pstride, ldp);
+                    NUTS_VEC(*this, k_nuts_merge, Srho[l], Spb[l], Spe[l], Sth[l], nv, nc.choose + (size_t)l * nc.Cp, ld, Q, C, nc, part, pstride, ldp);
                     hipLaunchKernelGGL(k_nuts_merge_fin, dim3((C + 63) / 64), dim3(256), 0, c.stream, part, pstride, nchunk, ldp, C, nc);
                 }
                 // push: the node under construction becomes the stored node of level tz (all growing chains agree)
@@ -664,8 +660,7 @@ struct NutsRun {
                 }
             }
             hipLaunchKernelGGL(k_nuts_end_doubling, dim3((C + 255) / 256), dim3(256), 0, c.stream, C, nc, j);
-            if (h.cm) vec(k_nuts_tree_update<true>, Srho[j], Spb[j], Sth[j], nv, ld, Q, C, nc, part, pstride, ldp);
-            else vec(k_nuts_tree_update<false>, Srho[j], Spb[j], Sth[j], nv, ld, Q, C, nc, part, pstride, ldp);
+            NUTS_VEC(*this, k_nuts_tree_update, Srho[j], Spb[j], Sth[j], nv, ld, Q, C, nc, part, pstride, ldp);
             hipLaunchKernelGGL(k_nuts_tree_fin, dim3((C + 63) / 64), dim3(256), 0, c.stream, part, pstride, nchunk, ldp, C, nc, max_depth);
             MCML_HIP(hipGetLastError());
             int na = 0;
@@ -674,8 +669,7 @@ struct NutsRun {
             nact = na;
         }
         h.Cw = C;
-        if (h.cm) vec(k_nuts_commit<true>, nv.Tth, h.V.d(), ld, Q, C);
-        else vec(k_nuts_commit<false>, nv.Tth, h.V.d(), ld, Q, C);
+        NUTS_VEC(*this, k_nuts_commit, nv.Tth, h.V.d(), ld, Q, C);
         MCML_HIP(hipGetLastError());
         return MCML_OK;
     }
@@ -723,7 +717,6 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
     HmcState& h = c.hmc;
     MCML_TRY(model_update_beta(c, beta));
     MCML_TRY(hmc_alloc(c, C));
-    ChainArrays ca = chain_arrays(h);
     NutsState& ns = c.nuts;
     const int nvec = 16 + 4 * (max_depth + 1);
     const bool diag_metric = o->metric == 0;
@@ -759,21 +752,13 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
     if (accept_out) MCML_TRY(d_acc.ensure(sizeof(double) * (size_t)C * total));
 
     // the HMC sampler's initialisation sets up the per-chain arrays; the state itself is then Stan's uniform(-2, 2)
-    const int nchq = (Q + cm_qrows(Q) - 1) / cm_qrows(Q);
-    if (h.cm)
-        hipLaunchKernelGGL(k_cm_init, dim3((C + 63) / 64, nchq), dim3(256), 0, c.stream, h.V.d(), h.V.ld, Q, C, cm_chain(ca), seed,
-                           (uint32_t)o->chain_offset, iter_idx, (const double*)nullptr);
-    else
-        hipLaunchKernelGGL(k_hmc_init, dim3(C), dim3(256), 0, c.stream, h.V.d(), h.V.ld, Q, ca, seed, (uint32_t)o->chain_offset,
-                           iter_idx, (const double*)nullptr);
-    if (h.cm) r.vec(k_nuts_init_uniform<true>, h.V.d(), r.ld, Q, C, seed, (uint32_t)o->chain_offset, 16u * iter_idx + 6u);
-    else r.vec(k_nuts_init_uniform<false>, h.V.d(), r.ld, Q, C, seed, (uint32_t)o->chain_offset, 16u * iter_idx + 6u);
+    MCML_TRY(sampler_init_state(c, seed, (uint32_t)o->chain_offset, iter_idx, nullptr));
+    NUTS_VEC(r, k_nuts_init_uniform, h.V.d(), r.ld, Q, C, seed, (uint32_t)o->chain_offset, 16u * iter_idx + 6u);
     hipLaunchKernelGGL(k_nuts_chain_init, dim3((C + 255) / 256), dim3(256), 0, c.stream, C, r.nc, eps0, seed,
                        (uint32_t)o->chain_offset, iter_idx);
     MCML_HIP(hipGetLastError());
     // unit metric to start with (Stan's diag_e starts from ones too), Welford state cleared
-    if (h.cm) r.vec(k_nuts_metric<true>, r.nv, r.ld, Q, C, 0.0, 1);
-    else r.vec(k_nuts_metric<false>, r.nv, r.ld, Q, C, 0.0, 1);
+    NUTS_VEC(r, k_nuts_metric, r.nv, r.ld, Q, C, 0.0, 1);
     MCML_TRY(r.find_stepsize());
     long long heur_leaps = r.leapfrogs;
     // windowed_adaptation (stan/mcmc/windowed_adaptation.hpp): all integer bookkeeping, the same for every chain
@@ -796,7 +781,6 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
     } win(o->warmup);
     int wsamp = 0;
 
-    long long sum_leap_chain = 0;                                     // filled from the device at the end
     for (int it = 0; it < total; ++it) {
         MCML_TRY(r.transition((uint32_t)it, max_depth));
         const int adapt = it < o->warmup, last = it == o->warmup - 1;
@@ -806,14 +790,12 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
         if (adapt && diag_metric) {                                      // var_adaptation::learn_variance
             if (win.in_window()) {
                 ++wsamp;
-                if (h.cm) r.vec(k_nuts_welford<true>, h.V.d(), r.nv, r.ld, Q, C, (double)wsamp);
-                else r.vec(k_nuts_welford<false>, h.V.d(), r.nv, r.ld, Q, C, (double)wsamp);
+                NUTS_VEC(r, k_nuts_welford, h.V.d(), r.nv, r.ld, Q, C, (double)wsamp);
             }
             const bool update = win.at_end();
             if (update) {
                 win.compute_next();
-                if (h.cm) r.vec(k_nuts_metric<true>, r.nv, r.ld, Q, C, (double)wsamp, 0);
-                else r.vec(k_nuts_metric<false>, r.nv, r.ld, Q, C, (double)wsamp, 0);
+                NUTS_VEC(r, k_nuts_metric, r.nv, r.ld, Q, C, (double)wsamp, 0);
                 wsamp = 0;
             }
             ++win.counter;
@@ -824,30 +806,11 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
                 heur_leaps += r.leapfrogs - before;
             }
         }
-        if (it >= o->warmup) {
-            const int col = it - o->warmup;
-            if (h.cm)
-                hipLaunchKernelGGL(k_cm_transpose, dim3((Q + 31) / 32, (C + 31) / 32), dim3(256), 0, c.stream, h.V.d(), h.V.ld, Q, C,
-                                   samp.d(), (size_t)samp.ld, (size_t)d, col);
-            else
-                hipLaunchKernelGGL(k_hmc_store, dim3(C), dim3(256), 0, c.stream, h.V.d(), h.V.ld, Q, samp.d(), samp.ld, d, col);
-        }
+        if (it >= o->warmup) store_columns(c, samp, d, it - o->warmup);
         MCML_HIP(hipGetLastError());
     }
-    (void)sum_leap_chain;
-    // u = L * gamma (gen_u_samples.R:66)
-    MCML_TRY(c.U.alloc(Q, ncols));
-    MCML_HIP(hipMemsetAsync(c.U.d(), 0, sizeof(double) * (size_t)c.U.ld * ncols, c.stream));
-    if (c.sp.active && c.sp.row_start.p) {
-        int gy = ncols < 1024 ? ncols : 1024;
-        hipLaunchKernelGGL(k_blockdiag_LV, dim3((Q + 255) / 256, gy), dim3(256), 0, c.stream, Q, ncols, c.sp.row_start.as<int>(),
-                           c.L.d(), c.L.ld, samp.d(), samp.ld, c.U.d(), c.U.ld);
-        MCML_HIP(hipGetLastError());
-    } else {
-        EpiAxpby epi{c.U.d(), c.U.ld, 1.0, 0.0};
-        MCML_TRY(launch_gemm<false>(c.stream, Q, ncols, Q, c.L.d(), c.L.ld, samp.d(), samp.ld, epi));
-    }
-    c.mcols = ncols; c.niter = ncols; c.zu_valid = false; c.uall_valid = false;
+    MCML_TRY(samples_to_U(c, samp, ncols));                              // u = L * gamma (gen_u_samples.R:66)
+    c.niter = ncols;
     if (depth_out) MCML_TRY(copy_d2h(depth_out, d_depth.p, sizeof(int) * (size_t)C * total, c.stream));
     if (nleap_out) MCML_TRY(copy_d2h(nleap_out, d_nleap.p, sizeof(int) * (size_t)C * total, c.stream));
     if (eps_out) MCML_TRY(copy_d2h(eps_out, d_eps.p, sizeof(double) * (size_t)C * total, c.stream));
@@ -866,5 +829,7 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
     if (ncols_out) *ncols_out = ncols;
     return MCML_OK;
 }
+
+#undef NUTS_VEC
 
 }  // namespace mcml
