@@ -1,6 +1,6 @@
 // band_plan.h -- host side of dgemm_band.h: tile constants and the work decomposition of the banded
-// HMC products (paired bands, or the flattened (band, K tile) space cut into equal runs with a
-// fixed-order second stage).  Kept apart from the kernels so that ctx.h stays light.
+// HMC products (whole bands dealt into balanced groups, or the flattened (band, K tile) space cut into
+// equal runs with a fixed-order second stage).  Kept apart from the kernels so that ctx.h stays light.
 #pragma once
 #include "common.h"
 #include <algorithm>
@@ -26,7 +26,7 @@ struct BandRed { int band, s0, s1, pad; };
 // ---- host: the decomposition ------------------------------------------------------------
 struct BandPlanDev {
     int gn = 0, nwg = 0, nred = 0, nslots = 0;
-    int paired = 0;                       // decompose() chose the paired form (else streamed)
+    int paired = 0;                       // decompose() chose whole bands, no partial sums (else streamed)
     DevBuf items, wg_ptr, red, part;
 };
 
@@ -53,30 +53,59 @@ struct BandPlan {
         skinny.reset();
     }
 
-    // target_wg: workgroups the launch should have in all (one per CU).  Returns true for the paired form.
+    // target_wg: workgroups the launch should have in all (one per CU).  Returns true for the whole-band form.  The
+    // plan is a function of (kr, nbands, gn, target_wg) alone.
     static bool decompose(const std::vector<int>& kr, int nbands, int gn, int target_wg, std::vector<BandItem>& items,
                           std::vector<int>& wg_ptr, std::vector<BandRed>& red, int& nslots)
     {
         items.clear(); wg_ptr.clear(); red.clear(); nslots = 0;
+        // Cost of an item in half K tiles, both forms: 2 per K tile + OVH (ring fill, barrier, epilogue or partial
+        // store).  Per-workgroup phase stamps (scripts/band_clocks.py 5000 128 1 48) put a second item at about one
+        // K tile: with OVH = 5 the two-item workgroups ended 8 us before the single-item ones and only 249 of 256 CUs
+        // were used at n = 5000, 128 chains; OVH = 3 fills all 256 and the longest run drops from 21 to 20 K tiles.
+        constexpr long OVH = 3;
         const int npairs = (nbands + 1) / 2;
-        if ((long)npairs * gn * 5 >= (long)target_wg * 4) {          // paired fills >= 80% of the CUs: no partial sums
-            for (int p = 0; p < npairs; ++p) {
+        if ((long)npairs * gn * 5 >= (long)target_wg * 4) {          // mirror pairs would fill >= 80% of the CUs: no partial sums
+            // Whole bands, one group of them per workgroup.  The launch is one wave of workgroups, so it lasts as long
+            // as its costliest group: deal the bands, costliest first (ties: lowest band), each into the least loaded
+            // of G groups (ties: lowest group) -- longest-processing-time greedy.  An empty band costs OVH and still
+            // gets its item: its epilogue has to run.  The first G bands open the groups in order, so group g and
+            // g + 1 start on adjacent long bands and the groups that share an XCD stay roughly in step on B.
+            auto cost = [&](int b) { return 2L * (kr[2 * b + 1] - kr[2 * b]) + OVH; };
+            int G = target_wg / gn; if (G > nbands) G = nbands; if (G < 1) G = 1;
+            std::vector<int> order(nbands);
+            for (int b = 0; b < nbands; ++b) order[b] = b;
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost(a) > cost(b); });
+            std::vector<long> load(G, 0);
+            std::vector<std::vector<int>> group(G);
+            for (int b : order) {
+                const int g = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+                group[g].push_back(b); load[g] += cost(b);
+            }
+            // against band p with its mirror nbands-1-p (equal K steps when the ranges are exactly linear in the band):
+            // waves of workgroups x costliest group; the mirror pairs stay only where they are strictly better
+            long pair_max = 0;
+            for (int p = 0; p < npairs; ++p)
+                pair_max = std::max(pair_max, cost(p) + (nbands - 1 - p > p ? cost(nbands - 1 - p) : 0));
+            auto waves = [&](int groups) { return ((long)groups * gn + target_wg - 1) / target_wg; };
+            if (waves(npairs) * pair_max < waves(G) * *std::max_element(load.begin(), load.end())) {
+                group.assign(npairs, std::vector<int>());
+                for (int p = 0; p < npairs; ++p) {
+                    group[p].push_back(p);
+                    if (nbands - 1 - p > p) group[p].push_back(nbands - 1 - p);
+                }
+            }
+            for (std::vector<int>& g : group) {
+                std::sort(g.begin(), g.end());
                 wg_ptr.push_back((int)items.size());
-                items.push_back({p, kr[2 * p], kr[2 * p + 1], -1});
-                const int q = nbands - 1 - p;
-                if (q > p) items.push_back({q, kr[2 * q], kr[2 * q + 1], -1});
+                for (int b : g) items.push_back({b, kr[2 * b], kr[2 * b + 1], -1});
             }
             wg_ptr.push_back((int)items.size());
             return true;
         }
-        // Streamed: walk the bands in order and fill one workgroup after another up to a cost cap.  Cost in
-        // half K tiles: 2 per K tile + OVH per item (ring fill, barrier, epilogue or partial store).  Per-workgroup
-        // phase stamps (scripts/band_clocks.py 5000 128 1 48) put a second item at about one K tile: with OVH = 5
-        // the two-item workgroups ended 8 us before the single-item ones and only 249 of 256 CUs were used at
-        // n = 5000, 128 chains; OVH = 3 fills all 256 and the longest run drops from 21 to 20 K tiles.  The cap is
+        // Streamed: walk the bands in order and fill one workgroup after another up to a cost cap.  The cap is
         // the smallest one whose greedy fill needs at most nwg workgroups (bisection).
         int nwg = target_wg / gn; if (nwg < 1) nwg = 1;
-        constexpr long OVH = 3;
         auto fill = [&](long cap, bool emit) -> int {
             int used = 1; long room = cap;
             if (emit) wg_ptr.push_back(0);

@@ -8,12 +8,16 @@
 // range only.  Skipping exact zeros does not change any sum (0*x adds nothing for finite x).
 //
 // Work decomposition (BandPlan, built on the host per number of column tiles):
-//   * paired: a workgroup owns band p and its mirror nbands-1-p of one column tile, back to
-//     back, so for a triangular operand every workgroup executes the same number of K steps:
+//   * whole bands (BandPlanDev::paired): a workgroup owns a group of whole bands of one column
+//     tile, back to back.  The launch is one wave of workgroups, as long as its costliest group,
+//     so the bands are dealt costliest first into the least loaded of 256 / (column tiles) groups:
 //     63 bands x 8 column tiles -> 32 x 8 = 256 workgroups (one per CU) for the 5000 x 1024
-//     products.  No partial sums.
+//     products, the longest of them 158 K steps forward and 157 backward, the mean rounded up
+//     (band p with its mirror nbands-1-p, the earlier rule: 161 and 160, because the 80-row
+//     bands' K ranges round up to whole 32-wide tiles and the last band has 40 rows).  A group
+//     holds one, two, three or more bands.  No partial sums, every band one ordered K loop.
 //   * streamed (few column tiles: a rank of the chain-sharded job holds 1024/8 = 128 chains = ONE
-//     column tile, which paired would run on 32 of the 256 CUs): the (band, K tile) iteration
+//     column tile, which whole bands would run on 32 of the 256 CUs): the (band, K tile) iteration
 //     space of a column tile is flattened and cut into equal runs of K tiles, one run per
 //     workgroup, ~256 workgroups in all.  A run may end one band and start the next.  A band
 //     covered by one run is finished by that workgroup; a band cut into several pieces has each

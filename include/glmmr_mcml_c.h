@@ -229,7 +229,7 @@ int glmmr_mcml_ctx_last_kernels(glmmr_mcml_ctx* ctx, int* fwd, int* bwd);
 /* The banded kernel's work decomposition (csrc/band_plan.h) for `chains` columns of the sampler's forward (which = 0) or
  * backward (which = 1) product, read-only: out10 = [banded kernel selected for this operand, bands of 80 rows, K tiles
  * multiplied, column tiles, workgroups per column tile, split bands (k_band_reduce blocks), partial slots,
- * 1 paired / 0 streamed, bands with no nonzero K tile, 1 if a product has built this plan].  The plan a product has
+ * 1 whole bands in balanced groups, no partial sums ("paired") / 0 streamed, bands with no nonzero K tile, 1 if a product has built this plan].  The plan a product has
  * built is reported as it is; otherwise the same decomposition is computed on the host (nothing is cached). */
 int glmmr_mcml_dbg_band_plan(glmmr_mcml_ctx* ctx, int which, int chains, int* out10);
 /* The sparse chain-major operator (csrc/hmc_cm.h) as the HMC sampler (hmc_sample, dbg_log_prob_grad) runs it with `chains`
