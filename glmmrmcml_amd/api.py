@@ -76,6 +76,20 @@ def get_default_trajectory():
     return {v: k for k, v in _TRAJ.items()}[_lib.lib().glmmr_mcml_get_default_trajectory()]
 
 
+_DRAWS = {"hmc": 0, "exact": 1}
+_DRAWS_NAME = {v: k for k, v in _DRAWS.items()}
+
+
+def set_default_draws(mode):
+    """what hmc_sample draws on new contexts ("hmc" or "exact"), the contexts the one-shot exports create included
+    (include/glmmr_mcml_c.h glmmr_mcml_set_default_draws)"""
+    _lib.check(_lib.lib().glmmr_mcml_set_default_draws(_DRAWS[mode]))
+
+
+def get_default_draws():
+    return _DRAWS_NAME[_lib.lib().glmmr_mcml_get_default_draws()]
+
+
 _LA_OP = {"dense": 0, "component": 1, "component_wide": 2}
 _LA_OP_NAME = {v: k for k, v in _LA_OP.items()}
 
@@ -365,7 +379,7 @@ class Context:
 
     def last_kernels(self):
         """kernel family of the sampler's last (forward, backward) product"""
-        names = {-1: None, 0: "skinny", 1: "band", 2: "dlds", 3: "reg", 4: "sparse", 5: "component"}
+        names = {-1: None, 0: "skinny", 1: "band", 2: "dlds", 3: "reg", 4: "sparse", 5: "component", 6: "exact"}
         f = C.c_int(); b = C.c_int()
         _lib.check(_lib.lib().glmmr_mcml_ctx_last_kernels(self._h, C.byref(f), C.byref(b)))
         return names[f.value], names[b.value]
@@ -408,6 +422,43 @@ class Context:
         for k in ("requested", "feasible", "used"):
             d[k] = bool(d[k])
         return d
+
+    def set_draws(self, mode):
+        """what hmc_sample draws: "hmc" (trajectories) or "exact" (csrc/hmc_exact.h: the conditional distribution of the
+        whitened effects directly, where it is Gaussian -- gaussian / identity on the dense ZL operator; elsewhere the
+        request changes nothing)"""
+        _lib.check(_lib.lib().glmmr_mcml_ctx_set_draws(self._h, _DRAWS[mode]))
+
+    def draws_plan(self):
+        """the exact path as the next hmc_sample would (not) take it (test hook, include/glmmr_mcml_c.h
+        glmmr_mcml_dbg_draws_plan)"""
+        out = (C.c_int * 4)()
+        _lib.check(_lib.lib().glmmr_mcml_dbg_draws_plan(self._h, out))
+        return dict(requested=_DRAWS_NAME[int(out[0])], applicable=bool(out[1]), Q=int(out[2]), m_bytes=int(out[3]))
+
+    def exact_sample(self, beta, var_par, nsamp, seed, chains=1, chain_offset=0, iter_idx=0, inj_z=None):
+        """exact conditional draws whatever set_draws says (McmlError where the path does not apply); the samples have
+        hmc_sample's shape.  inj_z (Q x columns) replaces the generated standard normals"""
+        beta = _f(beta).ravel()
+        o = HmcOpts(0, nsamp, 0, 1.0, 1, 0.9, chains, chain_offset)
+        d = HmcDiag()
+        iz = None if inj_z is None else _f(inj_z)
+        want = nsamp + 1 if chains == 1 else chains * -(-nsamp // chains)
+        if iz is not None and iz.shape != (self.Q, want):
+            raise ValueError("inj_z must be Q x %d" % want)
+        ncols = C.c_int()
+        _lib.check(_lib.lib().glmmr_mcml_ctx_exact_sample(
+            self._h, _p(beta), C.c_double(var_par), C.byref(o), C.c_uint64(seed), C.c_uint32(iter_idx), _p(iz),
+            C.byref(d), C.byref(ncols)))
+        self.mcols = ncols.value
+        return dict(accept_rate=d.accept_rate, mean_e=d.mean_e, min_e=d.min_e, max_e=d.max_e,
+                    max_steps_used=d.max_steps_used, leapfrog_total=d.leapfrog_total)
+
+    def exact_phases(self, enable=True):
+        """HIP-event ms of the phases of the last exact call recorded; enable: record the following calls"""
+        out = np.zeros(5)
+        _lib.check(_lib.lib().glmmr_mcml_dbg_exact_phases(self._h, int(enable), _p(out)))
+        return dict(zip(("m_build", "factorisation", "rhs_fill", "transposed_solve", "lv"), (float(v) for v in out)))
 
     def set_la_operator(self, mode):
         """how mcml_la / la_probe run on this context: "dense" (the dense ZL and M = ZL' W ZL + I), "component"

@@ -1,6 +1,7 @@
 // cabi.hip -- the extern "C" boundary (include/glmmr_mcml_c.h).
 #include "../../include/glmmr_mcml_c.h"
 #include "ctx.h"
+#include <algorithm>
 #include <atomic>
 #include <random>
 #include "sparse_plan.h"
@@ -15,6 +16,9 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
 int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nuts_opts* o, uint64_t seed, uint32_t iter_idx,
                 int* depth_out, int* nleap_out, double* eps_out, double* accept_out, glmmr_mcml_nuts_diag* diag,
                 int* ncols_out);
+bool hmc_exact_applicable(const Ctx& c);
+int hmc_exact_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed, uint32_t iter_idx,
+                     const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out);
 }
 
 // process-wide default of Ctx::traj_mode: -1 until first asked, then GLMMR_MCML_TRAJ=component|step (read once) or 0
@@ -27,6 +31,20 @@ static int default_trajectory()
         int unset = -1;
         g_default_traj.compare_exchange_strong(unset, (e && !strcmp(e, "component")) ? 1 : 0);     // a set_default that raced us wins
         v = g_default_traj.load();
+    }
+    return v;
+}
+
+// the same for Ctx::draws_mode: GLMMR_MCML_DRAWS=exact|hmc (read once) or 0
+static std::atomic<int> g_default_draws{-1};
+static int default_draws()
+{
+    int v = g_default_draws.load();
+    if (v < 0) {
+        const char* e = getenv("GLMMR_MCML_DRAWS");
+        int unset = -1;
+        g_default_draws.compare_exchange_strong(unset, (e && !strcmp(e, "exact")) ? 1 : 0);
+        v = g_default_draws.load();
     }
     return v;
 }
@@ -100,6 +118,7 @@ extern "C" int glmmr_mcml_ctx_create(const glmmr_mcml_problem* p, const glmmr_mc
     }
     c.traj_mode = default_trajectory();
     c.la_mode = default_la_operator();
+    c.draws_mode = default_draws();
     c.rank = o ? o->rank : 0;
     c.world = (o && o->world > 0) ? o->world : 1;
     c.reduce = o ? (reduce_fn)o->reduce : nullptr;
@@ -286,6 +305,86 @@ extern "C" int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* h, int chains, long
     const int waves = cp_waves(p, cp_forced_waves());
     out11[7] = p.nitems(); out11[8] = waves; out11[10] = cp_lds_bytes(p.max_vars, waves);
     return MCML_OK;
+}
+
+extern "C" int glmmr_mcml_set_default_draws(int mode)
+{
+    MCML_REQUIRE(mode == 0 || mode == 1, "set_default_draws: mode must be 0 (hmc) or 1 (exact)");
+    g_default_draws.store(mode);
+    return MCML_OK;
+}
+
+extern "C" int glmmr_mcml_get_default_draws(void) { return default_draws(); }
+
+extern "C" int glmmr_mcml_ctx_set_draws(glmmr_mcml_ctx* h, int mode)
+{
+    MCML_REQUIRE(h && (mode == 0 || mode == 1), "set_draws: mode must be 0 (hmc) or 1 (exact)");
+    h->c.draws_mode = mode;
+    return MCML_OK;
+}
+
+// read-only: the exact path as the next hmc_sample call would (not) take it
+extern "C" int glmmr_mcml_dbg_draws_plan(glmmr_mcml_ctx* h, int* out4)
+{
+    MCML_REQUIRE(h && out4, "dbg_draws_plan: null argument");
+    const Ctx& c = h->c;
+    const long long bytes = (long long)sizeof(double) * pad_ld(c.Q) * c.Q;
+    out4[0] = c.draws_mode; out4[1] = hmc_exact_applicable(c) ? 1 : 0; out4[2] = c.Q;
+    out4[3] = bytes > 0x7fffffffLL ? 0x7fffffff : (int)bytes;
+    return MCML_OK;
+}
+
+extern "C" int glmmr_mcml_ctx_exact_sample(glmmr_mcml_ctx* h, const double* beta, double var_par,
+                                           const glmmr_mcml_hmc_opts* opts, uint64_t seed, uint32_t iter_idx,
+                                           const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out)
+{
+    MCML_REQUIRE(h && beta && opts, "exact_sample: null argument");
+    MCML_HIP(hipSetDevice(h->c.device));
+    return hmc_exact_sample(h->c, beta, var_par, opts, seed, iter_idx, inj_z, diag, ncols_out);
+}
+
+extern "C" int glmmr_mcml_dbg_exact_phases(glmmr_mcml_ctx* h, int enable, double* out5)
+{
+    MCML_REQUIRE(h, "dbg_exact_phases: null context");
+    if (out5) for (int i = 0; i < 5; ++i) out5[i] = h->c.exact.ms[i];
+    h->c.exact.prof = enable != 0;
+    return MCML_OK;
+}
+
+// scripts/time_exact_gaussian.py: HIP-event time (median of `reps`) of the transposed solve and / or of the forward solve of
+// the factor the last exact call left, on a copy of the context's m sample columns
+extern "C" int glmmr_mcml_dbg_trsm_compare(glmmr_mcml_ctx* h, int m, int reps, double* trans_ms, double* fwd_ms)
+{
+    MCML_REQUIRE(h && m > 0 && reps > 0 && reps <= 64, "dbg_trsm_compare: bad argument");
+    Ctx& c = h->c;
+    MCML_HIP(hipSetDevice(c.device));
+    MCML_REQUIRE(c.last_kernel[0] == KERNEL_EXACT && c.exact.M.d() && c.exact.M.rows == c.Q && c.U.d() && c.mcols >= m,
+                 "dbg_trsm_compare: the last sampler call on this context must be an exact one with at least %d columns", m);
+    DevMat T;
+    MCML_TRY(T.alloc(c.Q, m));
+    hipEvent_t e0, e1;
+    MCML_HIP(hipEventCreate(&e0)); MCML_HIP(hipEventCreate(&e1));
+    int rc = MCML_OK;
+    for (int which = 0; which < 2 && rc == MCML_OK; ++which) {
+        double* out = which ? fwd_ms : trans_ms;
+        if (!out) continue;
+        std::vector<float> ms;
+        for (int r = 0; r < reps && rc == MCML_OK; ++r) {
+            if (hipMemcpy2DAsync(T.d(), sizeof(double) * T.ld, c.U.d(), sizeof(double) * c.U.ld, sizeof(double) * c.Q, m,
+                                 hipMemcpyDeviceToDevice, c.stream) != hipSuccess) { rc = MCML_EHIP; break; }
+            (void)hipEventRecord(e0, c.stream);
+            rc = which ? trsm_left_lower(c, c.exact.M.d(), c.exact.M.ld, c.Q, T.d(), T.ld, m)
+                       : trsm_left_lower_trans(c, c.exact.M.d(), c.exact.M.ld, c.Q, T.d(), T.ld, m);
+            (void)hipEventRecord(e1, c.stream);
+            if (hipEventSynchronize(e1) != hipSuccess) rc = MCML_EHIP;
+            float t = 0;
+            if (rc == MCML_OK && hipEventElapsedTime(&t, e0, e1) == hipSuccess) ms.push_back(t);
+        }
+        if (rc == MCML_OK && !ms.empty()) { std::sort(ms.begin(), ms.end()); *out = ms[ms.size() / 2]; }
+    }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (rc == MCML_EHIP) set_error("dbg_trsm_compare: HIP call failed");
+    return rc;
 }
 
 extern "C" int glmmr_mcml_set_default_la_operator(int mode)

@@ -19,7 +19,8 @@ constexpr int SMALL_BLOCK = 32;  // blocks up to this size are factorised one wa
 typedef int (*reduce_fn)(void* user, double* dev_buf, int n);
 
 // kernel family that served an HMC product (glmmr_mcml_ctx_last_kernels)
-enum { KERNEL_SKINNY = 0, KERNEL_BAND = 1, KERNEL_DLDS = 2, KERNEL_REG = 3, KERNEL_SPARSE = 4, KERNEL_COMPONENT = 5 };
+enum { KERNEL_SKINNY = 0, KERNEL_BAND = 1, KERNEL_DLDS = 2, KERNEL_REG = 3, KERNEL_SPARSE = 4, KERNEL_COMPONENT = 5,
+       KERNEL_EXACT = 6 };   // 6: no product pair at all, the exact conditional draw (hmc_exact.h)
 
 // the sampler's step-count read-back (hmc.hip hmc_sample): a ring of host memory mapped into the device, written by
 // k_max_steps with (proposal sequence number << 32 | count), read by the host with plain loads (StepAhead, step_ahead.h);
@@ -197,6 +198,15 @@ struct CholGraphCache {
     }
 };
 
+// exact conditional draws (hmc_exact.h): M = I + ZL' ZL / sigma^2 and its factor, the Q x ncols right-hand sides / draws, the
+// Q-vector b -> w; kept between calls (Q x Q: 200 MB at Q = 5000).  prof: HIP events around the phases of the next calls
+struct ExactState {
+    DevMat M, T;
+    DevBuf b;
+    bool prof = false;
+    double ms[5] = {0, 0, 0, 0, 0};   // M build | factorisation | right-hand side + fill | transposed solve | L V, of the last call
+};
+
 struct Ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -210,6 +220,8 @@ struct Ctx {
     SparseZL sp;
     ComponentDev cp;
     int traj_mode = 0;          // 0: a launch per leapfrog step; 1: component-local trajectories where feasible (hmc_traj.h)
+    int draws_mode = 0;         // hmc_sample: 0 HMC trajectories; 1 exact conditional draws where the target is Gaussian (hmc_exact.h)
+    ExactState exact;
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT
     int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (la_comp.h); 2 the same up
                                 // to CP_WIDE_MAX_VARS variables per component, a wave or a workgroup each
@@ -325,6 +337,13 @@ int potrf_lower_checked(Ctx& c, double* A, int n, int lda);                  // 
 // x <- (L L')^-1 x for one vector, L from the LAST potrf_lower (its diagonal-block inverses are in c.linv)
 int potrs_lower_vec(Ctx& c, const double* L, int ldl, int n, double* x, double* tmp);
 int trsm_left_lower(Ctx& c, const double* L, int ldl, int n, double* U, int ldu, int m);
+// T <- R^-T T (the transposed solve of the same factor, all m columns at once)
+int trsm_left_lower_trans(Ctx& c, const double* R, int ldr, int n, double* T, int ldt, int m);
+
+// ---- laplace.hip ----
+// M (Q x Q) = ZL' diag(W) ZL + I from the current c.ZL / c.ZLT.  W null: W = w0 for every observation, ZLT is multiplied as it
+// is (ZLTW is not touched).  lower_only: the tiles strictly above the diagonal are left zero
+int build_M_dense(Ctx& c, const double* W, double w0, DevMat& M, DevMat& ZLTW, bool lower_only);
 
 // ---- model.hip ----
 int model_setup(Ctx& c, const double* Z, const double* X, const double* y);

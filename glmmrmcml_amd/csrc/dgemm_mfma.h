@@ -4,9 +4,10 @@
 //
 //   C(M x N) = epilogue( A(M x K) * B(K x N) )
 //
-// A is column-major (M contiguous).  B is either K-major (column-major K x N,
-// as the Q x m sample matrices are) or N-major (B^T stored column-major, as the
-// L21 panels of the Cholesky update are).  All operands f64.
+// A is column-major (M contiguous), or -- ATRANS -- read transposed in place: A(i, k) = A[k + i*lda], K
+// contiguous, as the R21' panels of the transposed triangular solve are (mvn.hip trsm_left_lower_trans).
+// B is either K-major (column-major K x N, as the Q x m sample matrices are) or N-major (B^T stored
+// column-major, as the L21 panels of the Cholesky update are).  All operands f64.
 //
 // CDNA4 mapping (one 256-thread workgroup = 4 waves = one wave per SIMD):
 //   * v_mfma_f64_16x16x4_f64, 64-lane waves, operands swapped so that the MFMA's
@@ -20,7 +21,10 @@
 //     MFMAs of the current one.
 //   * LDS rows padded so that the two 16-lane halves of a ds_read_b64 land in
 //     disjoint bank halves (A rows: stride = 16 mod 32 doubles; K-major B rows:
-//     18 doubles).
+//     18 doubles).  A transposed A is staged like a K-major B -- 16-byte loads along K, one LDS row of
+//     18 doubles per row of the product -- and the transposition is the fragment read's indexing: lane
+//     (l15, lk) reads double (16 i + l15) * 18 + 4 ks + lk, i.e. slot 18 l15 + lk mod 32, 32 distinct
+//     slots per 32-lane half.
 //   * blockIdx -> tile map is XCD-aware: each XCD (blockIdx % 8) owns a
 //     contiguous band of row tiles, so the A band and the B panels it shares
 //     stay in that XCD's L2.
@@ -36,7 +40,7 @@ constexpr int GEMM_BK = 16;
 
 struct GemmP {
     int M, N, K;
-    const double* A; int lda;   // A[i + k*lda]
+    const double* A; int lda;   // A[i + k*lda];  ATRANS: A[k + i*lda]
     const double* B; int ldb;   // K-major: B[k + j*ldb];  N-major: B[j + k*ldb]
     int gm, gn;                 // tile grid
     int lower_only;             // skip tiles that lie strictly above the diagonal
@@ -45,13 +49,13 @@ struct GemmP {
 };
 
 // WTM x WTN: 16x16 MFMA tiles per wave; WM x WN: waves per workgroup.
-template <int WTM, int WTN, int WM, int WN, bool BNMAJOR, int BK = 16>
+template <int WTM, int WTN, int WM, int WN, bool BNMAJOR, int BK = 16, bool ATRANS = false>
 struct GemmCfg {
     static constexpr int THREADS = 64 * WM * WN;
     static constexpr int BM = 16 * WTM * WM, BN = 16 * WTN * WN;
-    static constexpr int SA = BM + 16;
+    static constexpr int SA = ATRANS ? (BK + 2) : (BM + 16);
     static constexpr int SB = BNMAJOR ? (BN + 16) : (BK + 2);
-    static constexpr int A_TILE = BK * SA;
+    static constexpr int A_TILE = ATRANS ? BM * SA : BK * SA;
     static constexpr int B_TILE = BNMAJOR ? BK * SB : BN * SB;
     static constexpr size_t LDS_BYTES = sizeof(double) * 2 * (A_TILE + B_TILE);
     // 16-byte staging loads per thread (ceil)
@@ -101,10 +105,10 @@ struct EpiAxpby {   // C = alpha*A*B + beta*C
     }
 };
 
-template <int WTM, int WTN, int WM, int WN, bool BNMAJOR, int BK, bool STAGGER, int INNER, class Epi>
+template <int WTM, int WTN, int WM, int WN, bool BNMAJOR, int BK, bool STAGGER, int INNER, class Epi, bool ATRANS = false>
 __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi epi)
 {
-    using Cfg = GemmCfg<WTM, WTN, WM, WN, BNMAJOR, BK>;
+    using Cfg = GemmCfg<WTM, WTN, WM, WN, BNMAJOR, BK, ATRANS>;
     constexpr int BM = Cfg::BM, BN = Cfg::BN, SA = Cfg::SA, SB = Cfg::SB, NT = Cfg::THREADS;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     double* As = smem;
@@ -134,11 +138,19 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
     for (int i = 0; i < Cfg::A_LD; ++i) {
         int idx = tid + i * NT;
         if (Cfg::A_VEC % NT != 0 && idx >= Cfg::A_VEC) idx = Cfg::A_VEC - 1;
-        const int kr = idx / (BM / 2), mp = idx - kr * (BM / 2);
-        const int m = m0 + 2 * mp;
-        const bool okm = m < p.M;
-        oka |= (okm ? 1u : 0u) << i; kra[i] = kr;
-        pa[i] = p.A + (okm ? m : 0) + (size_t)kr * p.lda;
+        if (ATRANS) {     // one row of the product per BK / 2 loads, as the columns of a K-major B
+            const int mrow = idx / (BK / 2), kp = idx - mrow * (BK / 2);
+            const int m = m0 + mrow;
+            const bool okm = m < p.M;
+            oka |= (okm ? 1u : 0u) << i; kra[i] = 2 * kp;
+            pa[i] = p.A + 2 * kp + (size_t)(okm ? m : 0) * p.lda;
+        } else {
+            const int kr = idx / (BM / 2), mp = idx - kr * (BM / 2);
+            const int m = m0 + 2 * mp;
+            const bool okm = m < p.M;
+            oka |= (okm ? 1u : 0u) << i; kra[i] = kr;
+            pa[i] = p.A + (okm ? m : 0) + (size_t)kr * p.lda;
+        }
     }
 #pragma unroll
     for (int j = 0; j < Cfg::B_LD; ++j) {
@@ -158,9 +170,11 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
             pb[j] = p.B + 2 * kp + (size_t)(okn ? n : 0) * p.ldb;
         }
     }
-    const size_t stepA = (size_t)BK * p.lda;
+    const size_t stepA = ATRANS ? (size_t)BK : (size_t)BK * p.lda;
     const size_t stepB = BNMAJOR ? (size_t)BK * p.ldb : (size_t)BK;
     unsigned kva = 0, kvb0 = 0, kvb1 = 0;   // bit i: load i of the tile in flight lies inside K
+    unsigned kva1 = 0;                      // ATRANS: the same for the second double of A's load i
+    (void)kva1;
 
     // full = the whole tile lies inside K (every K step but possibly the last)
     auto load_tiles = [&](int k0, bool full) {
@@ -170,12 +184,15 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
 #pragma unroll
             for (int j = 0; j < Cfg::B_LD; ++j) rb[j] = *reinterpret_cast<const d2*>(pb[j]);
             kva = kvb0 = kvb1 = ~0u;
+            if (ATRANS) kva1 = ~0u;
         } else {
             kva = kvb0 = kvb1 = 0;
+            if (ATRANS) kva1 = 0;
 #pragma unroll
             for (int i = 0; i < Cfg::A_LD; ++i) {
                 const bool v = (k0 + kra[i] < p.K);
                 kva |= (v ? 1u : 0u) << i;
+                if (ATRANS) kva1 |= ((k0 + kra[i] + 1 < p.K) ? 1u : 0u) << i;
                 ra[i] = v ? *reinterpret_cast<const d2*>(pa[i]) : d2{0.0, 0.0};
             }
 #pragma unroll
@@ -198,9 +215,17 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
         for (int i = 0; i < Cfg::A_LD; ++i) {
             int idx = tid + i * NT;
             if (Cfg::A_VEC % NT == 0 || idx < Cfg::A_VEC) {
-                int kr = idx / (BM / 2), mp = idx - kr * (BM / 2);
-                d2 v = ((oka & kva) >> i & 1u) ? ra[i] : d2{0.0, 0.0};
-                *reinterpret_cast<d2*>(as + kr * SA + 2 * mp) = v;
+                if (ATRANS) {
+                    int mrow = idx / (BK / 2), kp = idx - mrow * (BK / 2);
+                    d2 v;
+                    v[0] = ((oka & kva) >> i & 1u) ? ra[i][0] : 0.0;
+                    v[1] = ((oka & kva1) >> i & 1u) ? ra[i][1] : 0.0;
+                    *reinterpret_cast<d2*>(as + mrow * SA + 2 * kp) = v;
+                } else {
+                    int kr = idx / (BM / 2), mp = idx - kr * (BM / 2);
+                    d2 v = ((oka & kva) >> i & 1u) ? ra[i] : d2{0.0, 0.0};
+                    *reinterpret_cast<d2*>(as + kr * SA + 2 * mp) = v;
+                }
             }
         }
 #pragma unroll
@@ -230,7 +255,8 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
     const int nk = (p.K + BK - 1) / BK;
     const int l15 = lane & 15, lk = lane >> 4;
     auto compute = [&](int cur) {
-        const double* as = As + cur * Cfg::A_TILE + wr * 16 * WTM + l15;
+        const double* as = ATRANS ? (As + cur * Cfg::A_TILE + (wr * 16 * WTM + l15) * SA)
+                                  : (As + cur * Cfg::A_TILE + wr * 16 * WTM + l15);
         const double* bs = BNMAJOR ? (Bs + cur * Cfg::B_TILE + wc * 16 * WTN + l15)
                                    : (Bs + cur * Cfg::B_TILE + (wc * 16 * WTN + l15) * SB);
         if constexpr (INNER == 2) {
@@ -240,7 +266,7 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
             for (int ks = 0; ks < BK / 4; ++ks) {
                 const int kk = 4 * ks + lk;
 #pragma unroll
-                for (int i = 0; i < WTM; ++i) a[ks][i] = as[kk * SA + 16 * i];
+                for (int i = 0; i < WTM; ++i) a[ks][i] = ATRANS ? as[16 * i * SA + kk] : as[kk * SA + 16 * i];
 #pragma unroll
                 for (int j = 0; j < WTN; ++j) b[ks][j] = BNMAJOR ? bs[kk * SB + 16 * j] : bs[16 * j * SB + kk];
             }
@@ -258,7 +284,7 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
                 const int kk = 4 * ks + lk;
                 double a[WTM], b[WTN];
 #pragma unroll
-                for (int i = 0; i < WTM; ++i) a[i] = as[kk * SA + 16 * i];
+                for (int i = 0; i < WTM; ++i) a[i] = ATRANS ? as[16 * i * SA + kk] : as[kk * SA + 16 * i];
 #pragma unroll
                 for (int j = 0; j < WTN; ++j) b[j] = BNMAJOR ? bs[kk * SB + 16 * j] : bs[16 * j * SB + kk];
 #pragma unroll
@@ -352,16 +378,16 @@ static inline TileChoice pick_tile(int M, int N, int K = 1 << 30)
     return best;
 }
 
-template <int WTM, int WTN, int WM, int WN, bool BNMAJOR, int BK, bool STAGGER, int INNER, class Epi>
+template <int WTM, int WTN, int WM, int WN, bool BNMAJOR, int BK, bool STAGGER, int INNER, class Epi, bool ATRANS = false>
 static inline int launch_gemm_tile(hipStream_t s, GemmP p, const Epi& epi)
 {
-    using Cfg = GemmCfg<WTM, WTN, WM, WN, BNMAJOR, BK>;
+    using Cfg = GemmCfg<WTM, WTN, WM, WN, BNMAJOR, BK, ATRANS>;
     p.gm = (p.M + Cfg::BM - 1) / Cfg::BM;
     p.gn = (p.N + Cfg::BN - 1) / Cfg::BN;
     MCML_TRY(ensure_dynamic_lds(
-        reinterpret_cast<const void*>(&dgemm_mfma_kernel<WTM, WTN, WM, WN, BNMAJOR, BK, STAGGER, INNER, Epi>),
+        reinterpret_cast<const void*>(&dgemm_mfma_kernel<WTM, WTN, WM, WN, BNMAJOR, BK, STAGGER, INNER, Epi, ATRANS>),
         (int)Cfg::LDS_BYTES));
-    hipLaunchKernelGGL((dgemm_mfma_kernel<WTM, WTN, WM, WN, BNMAJOR, BK, STAGGER, INNER, Epi>), dim3(p.gm * p.gn),
+    hipLaunchKernelGGL((dgemm_mfma_kernel<WTM, WTN, WM, WN, BNMAJOR, BK, STAGGER, INNER, Epi, ATRANS>), dim3(p.gm * p.gn),
                        dim3(Cfg::THREADS), Cfg::LDS_BYTES, s, p, epi);
     MCML_HIP(hipGetLastError());
     return MCML_OK;
@@ -376,14 +402,18 @@ static inline int gemm_row_slots(int M, int tile_id)
 
 // Host-side shape contract of the kernel (checked before every launch: a
 // faulting kernel can take the whole node down).
-static inline int check_gemm_args(const GemmP& p)
+// atrans: A is read as A[k + i*lda], i < M, in 16-byte loads along K: the pair that holds k = K - 1 of an odd K also
+// touches k = K, so a column of the operand is round_up(K, 2) doubles the caller owns (never used: it is zeroed on the
+// way to LDS).  Rows i >= M of a ragged tile are not read (their loads point at row 0).
+static inline int check_gemm_args(const GemmP& p, bool atrans = false)
 {
     MCML_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "dgemm: empty shape %dx%dx%d", p.M, p.N, p.K);
     MCML_REQUIRE(p.A && p.B, "dgemm: null operand");
     MCML_REQUIRE((p.lda & 1) == 0 && (p.ldb & 1) == 0, "dgemm: odd leading dimension");
     MCML_REQUIRE(((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.B & 15) == 0,
                  "dgemm: operand not 16-byte aligned");
-    MCML_REQUIRE(p.lda >= p.M, "dgemm: lda %d < M %d", p.lda, p.M);
+    if (atrans) MCML_REQUIRE(p.lda >= p.K + (p.K & 1), "dgemm: transposed A: lda %d < K %d rounded up to even", p.lda, p.K);
+    else MCML_REQUIRE(p.lda >= p.M, "dgemm: lda %d < M %d", p.lda, p.M);
     return MCML_OK;
 }
 
@@ -413,6 +443,25 @@ static inline int launch_gemm(hipStream_t s, int M, int N, int K, const double* 
     case 14: return launch_gemm_tile<5, 2, 2, 4, BNMAJOR, 16, false, 2, Epi>(s, p, epi);
     case 15: return launch_gemm_tile<5, 2, 2, 4, BNMAJOR, 16, false, 1, Epi>(s, p, epi);
     default: return launch_gemm_tile<2, 2, 2, 2, BNMAJOR, 16, false, 0, Epi>(s, p, epi);
+    }
+}
+
+// C = epilogue(A' B) with A read transposed in place (A(i, k) = A[k + i*lda]) and B K-major: the tiles pick_tile
+// chooses among, K step 16.  The caller owns round_up(K, 2) doubles of each of A's M columns and of B's N columns.
+template <class Epi>
+static inline int launch_gemm_at(hipStream_t s, int M, int N, int K, const double* A, int lda, const double* B, int ldb,
+                                 const Epi& epi, int force_tile = -1)
+{
+    GemmP p{M, N, K, A, lda, B, ldb, 0, 0, 0};
+    MCML_TRY(check_gemm_args(p, true));
+    MCML_REQUIRE(ldb >= K + (K & 1), "dgemm: ldb %d too small", ldb);
+    int id = force_tile >= 0 ? force_tile : pick_tile(M, N, K).id;
+    if (id == 6) id = 0;
+    switch (id) {
+    case 0: return launch_gemm_tile<5, 2, 2, 4, false, 16, false, 0, Epi, true>(s, p, epi);
+    case 1: return launch_gemm_tile<4, 2, 2, 4, false, 16, false, 0, Epi, true>(s, p, epi);
+    case 2: return launch_gemm_tile<4, 2, 2, 2, false, 16, false, 0, Epi, true>(s, p, epi);
+    default: return launch_gemm_tile<2, 2, 2, 2, false, 16, false, 0, Epi, true>(s, p, epi);
     }
 }
 

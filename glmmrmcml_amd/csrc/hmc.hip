@@ -723,6 +723,20 @@ static int samples_to_U(Ctx& c, const DevMat& samp, int ncols)
     return MCML_OK;
 }
 
+}  // namespace mcml
+
+#include "hmc_exact.h"      // exact conditional draws (gaussian / identity): ends in samples_to_U like the samplers here
+
+namespace mcml {
+
+// the exact path from outside this file (cabi.hip: the direct entry point and the plan hook)
+bool hmc_exact_applicable(const Ctx& c) { return exact_applicable(c); }
+int hmc_exact_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed, uint32_t iter_idx,
+                     const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out)
+{
+    return exact_gaussian_sample(c, beta, var_par, o, seed, iter_idx, inj_z, nullptr, nullptr, diag, ncols_out);
+}
+
 // ---- hmc_sample in parts ----
 // GLMMR_MCML_HMC_TIMING=1: host wall-clock of a call's segments on stderr (set-up | proposals | tail), and of the slowest
 // proposal's enqueue -- to tell a slow call's cause from outside (run-to-run jitter)
@@ -915,6 +929,10 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
     MCML_REQUIRE(o && o->warmup >= 0 && o->nsamp > 0 && o->max_steps >= 1 && o->lambda > 0,
                  "hmc: bad options");
     MCML_REQUIRE(beta, "hmc: beta is null");
+    // exact conditional draws: asked for (Ctx::draws_mode) and the target is the Gaussian hmc_exact.h draws from; anywhere else the
+    // request changes nothing
+    if (c.draws_mode == 1 && exact_applicable(c))
+        return exact_gaussian_sample(c, beta, var_par, o, seed, iter_idx, nullptr, flags_out, probs_out, diag, ncols_out);
     const int C = o->chains > 0 ? o->chains : 1;
     const int d = (C == 1) ? o->nsamp : (o->nsamp + C - 1) / C;   // draws per chain
     const int total = o->warmup + d;

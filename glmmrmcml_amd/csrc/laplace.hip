@@ -184,6 +184,31 @@ int potrs_lower_vec(Ctx& c, const double* L, int ldl, int n, double* x, double* 
     return MCML_OK;
 }
 
+// M = ZL' diag(W) ZL + I from the current c.ZL / c.ZLT (ctx.h): the Laplace fits' M with their per-observation weights, the
+// exact conditional draws' (hmc_exact.h) with the constant 1 / sigma^2, which is the product's alpha
+int build_M_dense(Ctx& c, const double* W, double w0, DevMat& M, DevMat& ZLTW, bool lower_only)
+{
+    const int n = c.n, Q = c.Q;
+    MCML_TRY(M.alloc(Q, Q));
+    const double* A = c.ZLT.d(); int lda = c.ZLT.ld;
+    if (W) {
+        MCML_TRY(ZLTW.alloc(Q, n, 32));
+        if ((size_t)ZLTW.cols_alloc > (size_t)n)
+            MCML_HIP(hipMemsetAsync(ZLTW.at(0, n), 0, sizeof(double) * (size_t)ZLTW.ld * (ZLTW.cols_alloc - n), c.stream));
+        int gy = n < 1024 ? n : 1024;
+        hipLaunchKernelGGL(k_la_scale_cols, dim3((Q + 255) / 256, gy), dim3(256), 0, c.stream, c.ZLT.d(), c.ZLT.ld, Q, n,
+                           W, ZLTW.d(), ZLTW.ld);
+        MCML_HIP(hipGetLastError());
+        A = ZLTW.d(); lda = ZLTW.ld;
+    }
+    if (lower_only) MCML_HIP(hipMemsetAsync(M.d(), 0, sizeof(double) * (size_t)M.ld * Q, c.stream));
+    EpiAxpby epi{M.d(), M.ld, W ? 1.0 : w0, 0.0};
+    MCML_TRY(launch_gemm<false>(c.stream, Q, Q, n, A, lda, c.ZL.d(), c.ZL.ld, epi, lower_only));
+    hipLaunchKernelGGL(k_la_add_identity, dim3((Q + 255) / 256), dim3(256), 0, c.stream, M.d(), M.ld, Q);
+    MCML_HIP(hipGetLastError());
+    return MCML_OK;
+}
+
 // ------------------------------------------------------------------ state
 struct LaFit {
     Ctx& c;
@@ -350,22 +375,7 @@ struct LaFit {
     }
 
     // M = ZL' W ZL + I from the current c.ZL / c.ZLT
-    int build_M()
-    {
-        MCML_TRY(M.alloc(Q, Q));
-        MCML_TRY(ZLTW.alloc(Q, n, 32));
-        if ((size_t)ZLTW.cols_alloc > (size_t)n)
-            MCML_HIP(hipMemsetAsync(ZLTW.at(0, n), 0, sizeof(double) * (size_t)ZLTW.ld * (ZLTW.cols_alloc - n), c.stream));
-        int gy = n < 1024 ? n : 1024;
-        hipLaunchKernelGGL(k_la_scale_cols, dim3((Q + 255) / 256, gy), dim3(256), 0, c.stream, c.ZLT.d(), c.ZLT.ld, Q, n,
-                           W.d(), ZLTW.d(), ZLTW.ld);
-        MCML_HIP(hipGetLastError());
-        EpiAxpby epi{M.d(), M.ld, 1.0, 0.0};
-        MCML_TRY(launch_gemm<false>(c.stream, Q, Q, n, ZLTW.d(), ZLTW.ld, c.ZL.d(), c.ZL.ld, epi));
-        hipLaunchKernelGGL(k_la_add_identity, dim3((Q + 255) / 256), dim3(256), 0, c.stream, M.d(), M.ld, Q);
-        MCML_HIP(hipGetLastError());
-        return MCML_OK;
-    }
+    int build_M() { return build_M_dense(c, W.d(), 1.0, M, ZLTW, false); }
     // every M_c built and factorised from the current record values and W (la_comp.h); with g, x = M^-1 g as well
     int lac_factor(const double* g, double* x)
     {

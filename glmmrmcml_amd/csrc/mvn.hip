@@ -976,6 +976,31 @@ int trsm_left_lower(Ctx& c, const double* L, int ldl, int n, double* U, int ldu,
     return MCML_OK;
 }
 
+// T (n x m) <- inv(R)' T, R lower n x n; needs the leaf inverses potrf_lower left in c.linv.  Panels from the last to the
+// first: the diagonal block against its inverse transposed, then the rows above -= R21' T_k with K = nb <= 128.  Both
+// products read their A operand transposed in place (dgemm_mfma.h ATRANS: A(i, p) = R[k + p, i] is K-contiguous), so no
+// transposed copy of the factor is made.  A column of R and of T is read up to row round_up(n, 2) - 1.
+int trsm_left_lower_trans(Ctx& c, const double* R, int ldr, int n, double* T, int ldt, int m)
+{
+    MCML_REQUIRE(R && T && n > 0 && m > 0, "trsm_left_lower_trans: empty operand");
+    MCML_REQUIRE(ldr >= n + (n & 1) && ldt >= n + (n & 1) && (ldr & 1) == 0 && (ldt & 1) == 0,
+                 "trsm_left_lower_trans: bad leading dimensions %d, %d for n = %d", ldr, ldt, n);
+    MCML_REQUIRE(c.linv.bytes >= sizeof(double) * linv_size(n), "trsm_left_lower_trans: no factorisation of this size before it");
+    for (int k = (n - 1) / CHOL_NB * CHOL_NB; k >= 0; k -= CHOL_NB) {
+        const int nb = (n - k < CHOL_NB) ? n - k : CHOL_NB;
+        const double* Linv = c.linv.d() + (size_t)(k / CHOL_NB) * CHOL_NB * CHOL_NB;
+        double* Tk = T + k;
+        {
+            EpiAxpby epi{Tk, ldt, 1.0, 0.0};               // in place: one 128-row tile holds all of T_k's rows (tile 2)
+            MCML_TRY(launch_gemm_at(c.stream, nb, m, nb, Linv, CHOL_NB, Tk, ldt, epi, 2));
+        }
+        if (k == 0) break;
+        EpiAxpby epi{T, ldt, -1.0, 1.0};
+        MCML_TRY(launch_gemm_at(c.stream, k, m, nb, R + k, ldr, Tk, ldt, epi));
+    }
+    return MCML_OK;
+}
+
 // ------------------------------------------------------------------ setup
 int mvn_setup(Ctx& c)
 {

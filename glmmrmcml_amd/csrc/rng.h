@@ -138,7 +138,11 @@ __host__ __device__ static inline double rng_ppnd16(double p)
 }
 
 // standard normal addressed by (seed; element, global chain id, proposal, tag)
-// tag: 0 initial state, 2 momentum; + 16 * MCML iteration
+// tag + 16 * MCML iteration:
+//   0 initial state (k_hmc_init)           2 momentum (k_hmc_propose)
+//   3 seed of a chain's accept stream (chain_minstd_seed, without the iteration term)
+//   4, 5, 6 the No-U-Turn sampler (nuts.h: a transition, the step-size search, the initial values)
+//   8 the z of an exact conditional draw (hmc_exact.h k_exact_fill; `prop` = the draw's index within its chain)
 __host__ __device__ static inline double rng_normal(uint64_t seed, uint32_t elem, uint32_t chain,
                                                     uint32_t prop, uint32_t tag)
 {

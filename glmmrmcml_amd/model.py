@@ -239,19 +239,28 @@ class ModelMCML:
         return dict(par=list(names), est=est, SE=SE, lower=est - _Z975 * SE, upper=est + _Z975 * SE)
 
     # ---- MCML ----------------------------------------------------------------------------------------------------
-    def MCML(self, y, *args, trajectory=None, **kwargs):
+    def MCML(self, y, *args, trajectory=None, draws=None, **kwargs):
         """_mcml below (its arguments, unchanged); trajectory ("step" / "component", None = leave the backend's default
-        alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  It becomes the backend's
-        process-wide default for the duration of the call -- the contexts the exports create inherit it -- and the previous
-        default is restored; do not run two fits with different choices in one process at the same time."""
-        if trajectory is None:
-            return self._mcml(y, *args, **kwargs)
-        prev = self._be.get_default_trajectory()
-        self._be.set_default_trajectory(trajectory)
+        alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  draws ("hmc" / "exact",
+        None = leave the default alone): what the HMC sampler's call returns -- "exact" draws the conditional distribution of
+        the random effects directly where it is Gaussian (gaussian / identity on the dense operator, csrc/hmc_exact.h) and
+        changes nothing elsewhere; `sampler` below picks the route, not this.  Either becomes the backend's process-wide
+        default for the duration of the call -- the contexts the exports create inherit it -- and the previous default is
+        restored; do not run two fits with different choices in one process at the same time."""
+        prev_t = prev_d = None
+        if trajectory is not None:
+            prev_t = self._be.get_default_trajectory()
+            self._be.set_default_trajectory(trajectory)
         try:
+            if draws is not None:
+                prev_d = self._be.get_default_draws()
+                self._be.set_default_draws(draws)
             return self._mcml(y, *args, **kwargs)
         finally:
-            self._be.set_default_trajectory(prev)
+            if prev_d is not None:
+                self._be.set_default_draws(prev_d)
+            if prev_t is not None:
+                self._be.set_default_trajectory(prev_t)
 
     def _mcml(self, y, start=None, se_method="approx", method="mcnr", sim_lik_step=False, verbose=True, tol=1e-2,
               max_iter=30, sparse=False, sampler="full", options=None, seed=0, chains=1):

@@ -224,7 +224,7 @@ int glmmr_mcml_ctx_profile_launches(glmmr_mcml_ctx* ctx, long long* fwd, long lo
 /* kernel family that served the sampler's last forward / backward product: 0 streamed few-column kernel
  * (dgemm_skinny.h), 1 banded FP64 MFMA kernel (dgemm_band.h), 2 dense direct-to-LDS MFMA kernel (dgemm_dlds.h),
  * 3 register-staged MFMA kernel (dgemm_mfma.h), 4 sparse chain-major operator (hmc_cm.h), 5 component-local trajectory
- * kernel (hmc_traj.h, both entries); -1 none yet */
+ * kernel (hmc_traj.h, both entries), 6 no product pair: exact conditional draws (hmc_exact.h, both entries); -1 none yet */
 int glmmr_mcml_ctx_last_kernels(glmmr_mcml_ctx* ctx, int* fwd, int* bwd);
 /* The banded kernel's work decomposition (csrc/band_plan.h) for `chains` columns of the sampler's forward (which = 0) or
  * backward (which = 1) product, read-only: out10 = [banded kernel selected for this operand, bands of 80 rows, K tiles
@@ -260,6 +260,36 @@ int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* ctx, int chains, long long* ou
 /* k_cm_traj launches of this process so far, over all contexts: tells whether a context that a one-shot export created
  * internally took the component path. */
 long long glmmr_mcml_dbg_traj_launches(void);
+/* What glmmr_mcml_ctx_hmc_sample draws: 0 = HMC trajectories (the default), 1 = exact conditional draws (csrc/hmc_exact.h).
+ * For gaussian / identity the density HMC targets in the whitened effects is v | y ~ N(mu*, M^-1) with
+ * M = I + ZL' ZL / sigma^2 and M mu* = ZL' (y - X beta) / sigma^2; mode 1 draws from it directly -- one Q x Q product, one
+ * Cholesky factorisation, one transposed triangular solve for all columns -- instead of simulating it.  The output has
+ * hmc_sample's shape (for one chain column 0 is just another draw); warmup, lambda, max_steps, target_accept, adapt, inj_init
+ * and inj_mom are ignored, flags_out is all 1, probs_out all 1.0, diag is accept_rate 1, step sizes 0, no leapfrog steps.
+ * The draws are independent and follow their own RNG addressing (csrc/rng.h tag 8): a different, exact estimator of the same
+ * conditional distribution, not the HMC draws.  Honoured where the model is gaussian / identity AND the context runs the
+ * dense ZL operator; for every other family / link (gaussian / log included), on the sparse operator and for the No-U-Turn
+ * sampler the call changes nothing. */
+int glmmr_mcml_ctx_set_draws(glmmr_mcml_ctx* ctx, int mode);
+/* The mode new contexts start with, the ones the one-shot exports create included.  Initially GLMMR_MCML_DRAWS=exact|hmc from
+ * the environment (read once), else 0.  One atomic per process, as the trajectory default. */
+int glmmr_mcml_set_default_draws(int mode);
+int glmmr_mcml_get_default_draws(void);
+/* out4 = [mode requested, 1 if the exact path applies to the context as it is now (gaussian / identity, dense operator, L
+ * set), Q, bytes of the Q x Q matrix M the path keeps on the device] */
+int glmmr_mcml_dbg_draws_plan(glmmr_mcml_ctx* ctx, int* out4);
+/* The exact path whatever the mode; MCML_EUNSUPPORTED (-2) where it does not apply.  opts: nsamp, chains and chain_offset are
+ * used.  inj_z (nullable, Q x ncols column-major, ncols = glmmr_mcml_sample_cols(nsamp, chains)) replaces the generated
+ * standard normals (tests). */
+int glmmr_mcml_ctx_exact_sample(glmmr_mcml_ctx* ctx, const double* beta, double var_par, const glmmr_mcml_hmc_opts* opts,
+                                uint64_t seed, uint32_t iter_idx, const double* inj_z, glmmr_mcml_hmc_diag* diag,
+                                int* ncols_out);
+/* HIP-event times of the phases of the exact path: enable != 0 records them on the following calls; out5 (nullable) = ms of
+ * the last recorded call's [M build, factorisation, right-hand side and fill, transposed solve, L V] */
+int glmmr_mcml_dbg_exact_phases(glmmr_mcml_ctx* ctx, int enable, double* out5);
+/* HIP-event ms (median of reps) of the transposed solve R^-T T (trans_ms) and / or the forward solve R^-1 T (fwd_ms) with
+ * the factor the last exact call on this context left, on a copy of its first m sample columns; either pointer nullable */
+int glmmr_mcml_dbg_trsm_compare(glmmr_mcml_ctx* ctx, int m, int reps, double* trans_ms, double* fwd_ms);
 /* The operator of the Laplace fits (glmmr_mcml_ctx_la, glmmr_mcml_la, glmmr_mcml_la_nr): 0 = the dense ZL and the dense
  * Q x Q matrix M = ZL' W ZL + I (the default), 1 = the component operator (csrc/la_comp.h): on the sparse ZL operator, M
  * built, factorised and solved one connected component of ZL's coupling graph at a time -- where the sparse operator is
