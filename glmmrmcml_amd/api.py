@@ -134,6 +134,22 @@ def traj_launches():
     return int(f())
 
 
+def dbg_dgemm_at(A, B, C0, K, alpha=1.0, beta=0.0, tile=-1):
+    """alpha A[:K]' B[:K] + beta C0 through the transposed-A operand form of the GEMM (test hook, include/glmmr_mcml_c.h
+    glmmr_mcml_dbg_dgemm_at).  A (K2 x M) and B (K2 x N) hold K2 = round_up(K, 2) rows and go to the device as they are: row
+    K of an odd K is the pad row the kernel must ignore.  C0 = None: in place, the product overwrites the first M = K rows
+    of B, which are returned."""
+    A = np.array(A, dtype=np.float64, order="F"); B = np.array(B, dtype=np.float64, order="F")
+    K2 = K + (K & 1)
+    assert A.shape[0] == K2 and B.shape[0] == K2, "operands hold round_up(K, 2) rows"
+    M, N = A.shape[1], B.shape[1]
+    out = B if C0 is None else np.array(C0, dtype=np.float64, order="F")
+    assert C0 is None or out.shape == (M, N)
+    _lib.check(_lib.lib().glmmr_mcml_dbg_dgemm_at(M, N, int(K), _p(A), K2, _p(B), K2, C.c_double(alpha), C.c_double(beta),
+                                                  _p(out), out.shape[0], int(tile)))
+    return out[:M]
+
+
 def rccl_unique_id():
     """128 opaque bytes from ncclGetUniqueId: made on rank 0, handed to every rank's Context.comm_init_rccl"""
     buf = (C.c_ubyte * 128)()
@@ -270,6 +286,42 @@ class Context:
         th = np.ascontiguousarray(np.atleast_2d(np.asarray(thetas, dtype=np.float64)))     # row j = candidate j = column-major R x k
         out = np.zeros(th.shape[0])
         _lib.check(_lib.lib().glmmr_mcml_ctx_mvn_ll_batch(self._h, _p(th), th.shape[0], _p(out)))
+        return out
+
+    def mvn_workspace(self, cand=-1):
+        """(L, X, dims): what the last mvn_ll call (cand = -1) or candidate `cand` of the last mvn_ll_batch call left in its
+        workspace for the last large block -- the d x d array holding the factor, the m x d solved sample rows below it,
+        dims = (d, round_up(d, 16), m, leading dimension) (test hook, include/glmmr_mcml_c.h glmmr_mcml_dbg_mvn_workspace)"""
+        f = _lib.lib().glmmr_mcml_dbg_mvn_workspace
+        dims = (C.c_int * 4)()
+        _lib.check(f(self._h, int(cand), None, 0, None, 0, dims))
+        d, m = dims[0], dims[2]
+        L = np.zeros((d, d), order="F"); X = np.zeros((m, d), order="F")
+        _lib.check(f(self._h, int(cand), _p(L), d, _p(X), m, dims))
+        return L, X, tuple(dims)
+
+    def dbg_chol(self, A, B=None, linv=True):
+        """The dense Cholesky stack on the caller's matrix (test hook, include/glmmr_mcml_c.h glmmr_mcml_dbg_chol): A (n x n) is
+        uploaded as given, upper triangle included.  -> dict(A = the whole array as the device left it, fwd / trans / potrs =
+        inv(L) B, inv(L)' B, inv(L L') B, each solved on its own copy of B (absent without B), linv = the ceil(n / 128)
+        inverted diagonal blocks, nblk x 128 x 128 with [k, i, j] = entry (i, j) of block k).  Raises McmlError (code -3) if A
+        is not positive definite."""
+        A = np.array(A, dtype=np.float64, order="F")
+        n = A.shape[0]
+        assert A.shape == (n, n)
+        out = dict(A=A)
+        m = 0
+        if B is not None:
+            B = _f(B).reshape(n, -1, order="F")
+            m = B.shape[1]
+            for k in ("fwd", "trans", "potrs"):
+                out[k] = np.zeros((n, m), order="F")
+        nblk = (n + 127) // 128
+        li = np.zeros((nblk, 128, 128)) if linv else None
+        _lib.check(_lib.lib().glmmr_mcml_dbg_chol(self._h, n, _p(A), n, m, _p(B), n, _p(out.get("fwd")), _p(out.get("trans")),
+                                                  _p(out.get("potrs")), _p(li)))
+        if linv:
+            out["linv"] = li.transpose(0, 2, 1)         # the blocks are column-major on the device
         return out
 
     def gen_D(self, theta, chol=False):

@@ -981,3 +981,67 @@ extern "C" int glmmr_mcml_gen_u_samples(const double* Z, const double* L, const 
     MCML_TRY(glmmr_mcml_ctx_nuts_sample(g.h, beta, sigma, &no, seed, 0, nullptr, nullptr, nullptr, nullptr, nullptr, ncols));
     return glmmr_mcml_get_u(g.h, samples, lds);
 }
+
+// ------------------------------------------------------------------------- test hooks of the dense Cholesky stack
+// The n x n host array A goes to the device AS GIVEN (upper triangle included), potrf_lower_checked factorises it, then every
+// solve runs on a fresh copy of B (n x m) against that factor: trsm_left_lower -> Xfwd, trsm_left_lower_trans -> Ytrans,
+// potrs_lower_vec column by column -> Zpotrs (each n x m with leading dimension ldb; null: skipped).  A receives the whole
+// array as the device left it, Linv (nullable) the ceil(n / 128) inverted 128 x 128 diagonal blocks of c.linv.
+extern "C" int glmmr_mcml_dbg_chol(glmmr_mcml_ctx* h, int n, double* A, int lda, int m, const double* B, int ldb,
+                                   double* Xfwd, double* Ytrans, double* Zpotrs, double* Linv)
+{
+    MCML_REQUIRE(h && A && n > 0 && lda >= n && m >= 0, "dbg_chol: bad argument");
+    MCML_REQUIRE(m == 0 || (B && ldb >= n), "dbg_chol: bad right-hand sides");
+    Ctx& c = h->c;
+    MCML_HIP(hipSetDevice(c.device));
+    MCML_REQUIRE(c.scalars.d(), "dbg_chol: the context has no covariance set up");
+    DevMat dA, dB, T;
+    DevBuf tmp;
+    MCML_TRY(upload_matrix(dA, A, n, n, lda, c.stream));
+    MCML_TRY(potrf_lower_checked(c, dA.d(), n, dA.ld));
+    MCML_TRY(download_matrix(A, lda, dA.d(), dA.ld, n, n, c.stream));
+    if (Linv) {
+        MCML_TRY(copy_d2h(Linv, c.linv.d(), sizeof(double) * (size_t)((n + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB, c.stream));
+        MCML_HIP(hipStreamSynchronize(c.stream));
+    }
+    if (m == 0) return MCML_OK;
+    MCML_TRY(upload_matrix(dB, B, n, m, ldb, c.stream));
+    MCML_TRY(T.alloc(n, m));
+    MCML_TRY(tmp.ensure(sizeof(double) * CHOL_NB));
+    for (int which = 0; which < 3; ++which) {
+        double* out = which == 0 ? Xfwd : which == 1 ? Ytrans : Zpotrs;
+        if (!out) continue;
+        MCML_HIP(hipMemcpyAsync(T.d(), dB.d(), sizeof(double) * (size_t)dB.ld * m, hipMemcpyDeviceToDevice, c.stream));
+        if (which == 0) MCML_TRY(trsm_left_lower(c, dA.d(), dA.ld, n, T.d(), T.ld, m));
+        else if (which == 1) MCML_TRY(trsm_left_lower_trans(c, dA.d(), dA.ld, n, T.d(), T.ld, m));
+        else for (int j = 0; j < m; ++j) MCML_TRY(potrs_lower_vec(c, dA.d(), dA.ld, n, T.d() + (size_t)j * T.ld, tmp.d()));
+        MCML_TRY(download_matrix(out, ldb, T.d(), T.ld, n, m, c.stream));
+    }
+    return MCML_OK;
+}
+
+// What the last mvn_ll call (cand = -1: c.Dwork) or the last mvn_ll_batch call (cand >= 0: matrix `cand` of c.Dbatch) left in
+// its workspace for the context's last large block: the d x d array holding the factor -> L, the m x d solved sample rows
+// below it -> X (either may be null); dims = {d, round_up(d, 16), m, the workspace's leading dimension}.
+extern "C" int glmmr_mcml_dbg_mvn_workspace(glmmr_mcml_ctx* h, int cand, double* L, int ldl, double* X, int ldx, int* dims)
+{
+    MCML_REQUIRE(h && dims && cand >= -1, "dbg_mvn_workspace: bad argument");
+    Ctx& c = h->c;
+    MCML_HIP(hipSetDevice(c.device));
+    const Ctx::MvnWs& w = c.mvn_ws[cand >= 0];
+    const DevMat& W = cand >= 0 ? c.Dbatch : c.Dwork;
+    MCML_REQUIRE(w.kb > 0 && W.d(), "dbg_mvn_workspace: no %s call on this context before it", cand >= 0 ? "mvn_ll_batch" : "mvn_ll");
+    MCML_REQUIRE(cand < w.kb, "dbg_mvn_workspace: candidate %d of %d", cand, w.kb);
+    dims[0] = w.d; dims[1] = w.dp; dims[2] = w.m; dims[3] = w.ld;
+    MCML_HIP(hipStreamSynchronize(c.stream));
+    const double* Wj = W.d() + (cand > 0 ? (size_t)cand * w.ld * round_up(c.maxdim_large, 16) : 0);
+    if (L) {
+        MCML_REQUIRE(ldl >= w.d, "dbg_mvn_workspace: ldl %d < %d", ldl, w.d);
+        MCML_TRY(download_matrix(L, ldl, Wj, w.ld, w.d, w.d, c.stream));
+    }
+    if (X) {
+        MCML_REQUIRE(ldx >= w.m, "dbg_mvn_workspace: ldx %d < %d", ldx, w.m);
+        MCML_TRY(download_matrix(X, ldx, Wj + w.dp, w.ld, w.m, w.d, c.stream));
+    }
+    return MCML_OK;
+}

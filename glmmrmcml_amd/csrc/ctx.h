@@ -300,6 +300,9 @@ struct Ctx {
     std::vector<hipEvent_t> ev_ring;                 // one event per dependency edge of the captured schedule (mvn.hip)
     DevMat Dbatch;                                   // mvn_loglik_batch: the candidates' matrices side by side
     DevBuf bscal;                                    // ... and their result scalars (4 per candidate)
+    // tests (glmmr_mcml_dbg_mvn_workspace): what mvn_large_blocks last left in Dwork [0] / Dbatch [1] -- the block's
+    // dimension d, round_up(d, 16), the sample rows m, the leading dimension, the number of matrices (0: no call yet)
+    struct MvnWs { int d = 0, dp = 0, m = 0, ld = 0, kb = 0; } mvn_ws[2];
     ~Ctx() {
         for (hipEvent_t e : ev_ring) if (e) (void)hipEventDestroy(e);
         comm_release_hook();

@@ -1,5 +1,6 @@
 // debug_hooks.hip -- C-ABI test/bench hooks for the GEMM building block
-// (declared in include/glmmr_mcml_c.h under "test hooks").
+// (declared in include/glmmr_mcml_c.h under "test hooks").  The hooks of the dense Cholesky stack built on it --
+// glmmr_mcml_dbg_chol, glmmr_mcml_dbg_mvn_workspace -- need a context and live in cabi.hip; glmmr_mcml_dbg_dgemm_at is here.
 #include "dgemm_mfma.h"
 #include "dgemm_dl.h"
 #include "dgemm_band.h"
@@ -50,6 +51,35 @@ extern "C" int glmmr_mcml_dbg_dgemm(int M, int N, int K, const double* A, int ld
                       : launch_gemm<false>(s, M, N, K, dA.d(), dA.ld, dB.d(), dB.ld, epi, lower_only != 0, force_tile);
     MCML_TRY(rc);
     MCML_TRY(download_matrix(C, ldc, dC.d(), dC.ld, M, N, s));
+    return MCML_OK;
+}
+
+// C (M x N) = alpha A' B + beta C through launch_gemm_at (dgemm_mfma.h ATRANS): A is K x M column-major.  round_up(K, 2)
+// rows of A and of B are uploaded exactly as the host passes them -- the pad row k = K of an odd K is the caller's, who may
+// poison it.  C == B (the same host pointer, M == K): the product is written over B in place, as trsm_left_lower_trans does
+// with a diagonal block.
+extern "C" int glmmr_mcml_dbg_dgemm_at(int M, int N, int K, const double* A, int lda, const double* B, int ldb,
+                                       double alpha, double beta, double* C, int ldc, int force_tile)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_error("no HIP device: libglmmr_mcml_hip has no CPU fallback");
+        return MCML_ENODEVICE;
+    }
+    MCML_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C, "dbg_dgemm_at: bad argument");
+    const int K2 = round_up(K, 2);
+    MCML_REQUIRE(lda >= K2 && ldb >= K2 && ldc >= M, "dbg_dgemm_at: a column of A and of B holds round_up(K, 2) = %d doubles", K2);
+    hipStream_t s = nullptr;
+    DevMat dA, dB, dC;
+    MCML_TRY(upload_matrix(dA, A, K2, M, lda, s));
+    MCML_TRY(upload_matrix(dB, B, K2, N, ldb, s));
+    const bool inplace = C == B;
+    MCML_REQUIRE(!inplace || (M == K && M <= 128 && ldc == ldb), "dbg_dgemm_at: in place needs M == K <= 128");
+    if (!inplace) MCML_TRY(upload_matrix(dC, C, M, N, ldc, s));
+    const DevMat& out = inplace ? dB : dC;
+    EpiAxpby epi{out.d(), out.ld, alpha, beta};
+    MCML_TRY(launch_gemm_at(s, M, N, K, dA.d(), dA.ld, dB.d(), dB.ld, epi, force_tile));
+    MCML_TRY(download_matrix(C, ldc, out.d(), out.ld, M, N, s));
     return MCML_OK;
 }
 

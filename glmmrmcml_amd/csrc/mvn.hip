@@ -925,6 +925,9 @@ static int potrf_graphed(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
     return MCML_OK;
 }
 
+// In-place factorisation of the lower triangle of A.  The strict upper triangle is never read, by this or by the solves
+// below (the leaf loads i >= j only, every operand panel lies below a diagonal block, a diagonal tile's update rewrites its own
+// upper half from itself): it may hold anything, NaN included, and comes back changed (tests/test_gpu_chol_solve.py).
 int potrf_lower(Ctx& c, double* A, int n, int lda)
 {
     MCML_REQUIRE(n > 0 && lda >= n && (lda & 1) == 0, "potrf: bad shape n=%d lda=%d", n, lda);
@@ -1108,6 +1111,7 @@ static int mvn_large_blocks(Ctx& c, DevMat& W, int kb, const ThetaArg* th, const
         // a multiple of 16 (identity border): the extra rows and every panel stay 16-byte aligned and the last, ragged
         // panel still has a K the LDS-DMA kernel takes (5000 = 39 x 128 + 8 would fall back to the register-staged one)
         const int dp = round_up(d, 16);
+        c.mvn_ws[&W == &c.Dbatch] = Ctx::MvnWs{d, dp, m, ld, kb};
         const dim3 gb((dp + 63) / 64, (dp + 15) / 16, kb);
         if (kb == 1)
             hipLaunchKernelGGL(k_build_dense, gb, dim3(256), 0, c.stream, W.d(), ld, b, dblk, dcov, cs.rows, c.d_data.d(),

@@ -434,6 +434,25 @@ int glmmr_mcml_dbg_dgemm(int M, int N, int K, const double* A, int lda, const do
                          int lower_only, int force_tile /* -1 = auto; 0.. tiles of the register-staged kernel; 20..25 the
                                                            Cholesky's deep-ring kernel; 40 the sampler's dense direct-to-LDS
                                                            kernel (dgemm_dlds_asm_kernel) */);
+/* C (M x N) = alpha A' B + beta C through the transposed-A operand form of the register-staged kernel (launch_gemm_at,
+ * the products of trsm_left_lower_trans): A is K x M column-major.  round_up(K, 2) rows of A and of B are uploaded exactly as
+ * passed -- the pad row k = K of an odd K belongs to the caller, who may poison it.  C == B (same pointer, M == K <= 128):
+ * in place.  force_tile: -1 = auto, 0..2 the tiles of launch_gemm_at, anything else its 64 x 64 default */
+int glmmr_mcml_dbg_dgemm_at(int M, int N, int K, const double* A, int lda, const double* B, int ldb, double alpha,
+                            double beta, double* C, int ldc, int force_tile);
+/* The dense Cholesky stack on a matrix of the caller's choosing.  A (n x n) is uploaded AS GIVEN, upper triangle included,
+ * and factorised (potrf_lower_checked; GLMMR_MCML_ENOTPD is returned as such and the context stays usable); then each solve
+ * runs on its own fresh copy of B (n x m) against that factor: trsm_left_lower -> Xfwd, trsm_left_lower_trans -> Ytrans,
+ * potrs_lower_vec on each column -> Zpotrs (n x m, leading dimension ldb; a null pointer skips that solve).  A receives
+ * the whole n x n array as the device left it, Linv (nullable) the ceil(n / 128) inverted 128 x 128 diagonal blocks.
+ * A context made from a covariance alone suffices. */
+int glmmr_mcml_dbg_chol(glmmr_mcml_ctx* ctx, int n, double* A, int lda, int m, const double* B, int ldb, double* Xfwd,
+                        double* Ytrans, double* Zpotrs, double* Linv);
+/* What the last mvn_ll call (cand = -1) or the last mvn_ll_batch call (its candidate cand >= 0; of a batch of more than 8,
+ * the last 8) left in its workspace for the context's last large block: the d x d array holding the factor -> L (leading
+ * dimension ldl), the m x d solved sample rows below it -> X (ldx); either may be null.  dims = {d, round_up(d, 16), m,
+ * the workspace's leading dimension}.  An error if no such call came before. */
+int glmmr_mcml_dbg_mvn_workspace(glmmr_mcml_ctx* ctx, int cand, double* L, int ldl, double* X, int ldx, int* dims);
 /* mcmlModel::log_prob / log_grad (mcmlmodel.h:138-279) of every column of V (Q x ncols) */
 int glmmr_mcml_dbg_log_prob_grad(glmmr_mcml_ctx* ctx, const double* beta, double var_par, const double* V,
                                  int ncols, double* lp, double* G);
