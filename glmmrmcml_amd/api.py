@@ -53,7 +53,7 @@ class NutsOpts(C.Structure):
 class NutsDiag(C.Structure):
     _fields_ = [("mean_e", C.c_double), ("min_e", C.c_double), ("max_e", C.c_double), ("divergent", C.c_longlong),
                 ("treedepth_hits", C.c_longlong), ("batched_leapfrogs", C.c_longlong),
-                ("stepsize_search_leapfrogs", C.c_longlong)]
+                ("stepsize_search_leapfrogs", C.c_longlong), ("packs", C.c_longlong)]
 
 
 def phase_ms(enable=True, reset=False):
@@ -408,7 +408,8 @@ class Context:
             None if tr is None else _p(tr["eps"]), None if tr is None else _p(tr["accept"]), C.byref(d), C.byref(ncols)))
         self.mcols = ncols.value
         diag = dict(mean_e=d.mean_e, min_e=d.min_e, max_e=d.max_e, divergent=d.divergent, treedepth_hits=d.treedepth_hits,
-                    batched_leapfrogs=d.batched_leapfrogs, stepsize_search_leapfrogs=d.stepsize_search_leapfrogs)
+                    batched_leapfrogs=d.batched_leapfrogs, stepsize_search_leapfrogs=d.stepsize_search_leapfrogs,
+                    packs=d.packs)
         return (diag, tr) if want_trace else diag
 
     # -- drivers on the resident context

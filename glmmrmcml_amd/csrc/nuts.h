@@ -571,7 +571,7 @@ struct NutsRun {
     double* Srho[NUTS_MAXD + 1]; double* Spb[NUTS_MAXD + 1]; double* Spe[NUTS_MAXD + 1]; double* Sth[NUTS_MAXD + 1];
     int C, Q, ld, nchunk, ldp; size_t pstride; double* part; dim3 vgrid; double var_par;
     uint64_t seed; uint32_t chain_offset, iter_idx;
-    long long leapfrogs = 0;
+    long long leapfrogs = 0, packs = 0;
 
     template <class K, class... A> void vec(K k, A... a) { hipLaunchKernelGGL(k, vgrid, dim3(256), 0, c.stream, a...); }
     // run.vec(K<CM>, ...) with CM the layout of the state
@@ -611,6 +611,7 @@ struct NutsRun {
         int cw = round_up(nact, g);
         if (!h.cm && nact <= SK_NUSE) cw = nact;                       // few enough for the streamed products (dgemm_skinny.h)
         h.Cw = cw < C ? cw : C;
+        ++packs;
         return MCML_OK;
     }
     int begin(uint32_t it, uint32_t stream)
@@ -825,6 +826,7 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
         diag->divergent = (long long)dg[3]; diag->treedepth_hits = (long long)dg[4];
         diag->batched_leapfrogs = r.leapfrogs - heur_leaps;
         diag->stepsize_search_leapfrogs = heur_leaps;
+        diag->packs = r.packs;
     }
     if (ncols_out) *ncols_out = ncols;
     return MCML_OK;

@@ -175,6 +175,8 @@ typedef struct glmmr_mcml_nuts_diag {
     long long treedepth_hits;                /* transitions stopped by max_treedepth */
     long long batched_leapfrogs;             /* leapfrog steps launched (each advances every growing chain) */
     long long stepsize_search_leapfrogs;
+    long long packs;                         /* times the growing chains were packed into the leading columns: every round of a
+                                                step-size search, every doubling, every re-pack at a checkpoint inside one */
 } glmmr_mcml_nuts_diag;
 
 /* Fills the context's samples with L * gamma like glmmr_mcml_ctx_hmc_sample.  depth_out / nleap_out (int) and
