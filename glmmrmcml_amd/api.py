@@ -267,7 +267,7 @@ class Context:
         out = (C.c_longlong * 6)()
         _lib.check(_lib.lib().glmmr_mcml_ctx_shard_stats(self._h, out))
         return dict(gathers=out[0], gather_doubles=out[1], theta_rounds=out[2], theta_evals_own=out[3],
-                    theta_evals_all=out[4])
+                    theta_evals_all=out[4], theta_factorised=out[5])
 
     def emulate_world(self, world, mode):
         """bench.py --as-rank-of N (include/glmmr_mcml_c.h glmmr_mcml_dbg_emulate_world): 1 record, 2 replay"""

@@ -422,7 +422,7 @@ extern "C" int glmmr_mcml_ctx_shard_stats(glmmr_mcml_ctx* h, long long* out6)
     MCML_REQUIRE(h && out6, "shard_stats: null argument");
     const Ctx& c = h->c;
     out6[0] = c.gather_calls; out6[1] = c.gather_doubles; out6[2] = c.theta_rounds; out6[3] = c.theta_evals_own;
-    out6[4] = c.theta_evals_all; out6[5] = 0;
+    out6[4] = c.theta_evals_all; out6[5] = c.theta_factorised;
     return MCML_OK;
 }
 
@@ -617,6 +617,7 @@ int drv_optim(Ctx& c, const double* start, int nstart, int trace, int mcnr, cons
 int drv_simlik(Ctx& c, const double* start, int nstart, int trace, const glmmr_mcml_ext* e, double* beta,
                double* theta, double* sigma);
 int drv_hess(Ctx& c, const double* start, int nstart, double tol, int trace, double* H);
+int drv_theta_round(Ctx& c, const double* thetas, int k, double* out);
 int drv_aic(Ctx& c, const double* beta_par, int nbeta, const double* cov_par, int ncov, double* out);
 int drv_full(Ctx& c, const double* start, int nstart, int mcnr, int m, int maxiter, int warmup, double tol,
              int verbose, double lambda, int trace, int refresh, int maxsteps, double target_accept,
@@ -703,6 +704,13 @@ extern "C" int glmmr_mcml_ctx_hess(glmmr_mcml_ctx* h, const double* start, int n
     MCML_REQUIRE(h->c.n > 0 && tol > 0, "hess: context has no model / bad tol");
     MCML_HIP(hipSetDevice(h->c.device));
     return drv_hess(h->c, start, nstart, tol, trace, H);
+}
+
+extern "C" int glmmr_mcml_dbg_theta_round(glmmr_mcml_ctx* h, const double* thetas, int k, double* out)
+{
+    MCML_REQUIRE(h, "theta_round: null context");
+    MCML_HIP(hipSetDevice(h->c.device));
+    return drv_theta_round(h->c, thetas, k, out);
 }
 
 extern "C" int glmmr_mcml_ctx_aic(glmmr_mcml_ctx* h, const double* beta_par, int nbeta, const double* cov_par,

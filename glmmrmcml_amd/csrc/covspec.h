@@ -41,6 +41,9 @@ struct CovSpec {
         static const int t[15] = {0, 1, 1, 1, 2, 2, 1, 2, 2, 2, 2, 2, 2, 2, 1};
         return (fn >= 1 && fn <= 14) ? t[fn] : -1;
     }
+    // exponent of the function's FIRST parameter where that parameter only scales the term (cov_term): gr t^2, sqexp /
+    // fexp t0; 0 = the function has no pure scale parameter (theta_scale.h)
+    static int fn_scale_exp(int fn) { return fn == 1 ? 2 : (fn == 4 || fn == 7) ? 1 : 0; }
     static bool fn_built(int fn) { return fn == 1 || fn == 2 || fn == 3 || fn == 4 || fn == 7 || fn == 14; }
     int c(int r, int col) const { return cov[r + (size_t)col * rows]; }
 

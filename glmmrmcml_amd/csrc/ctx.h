@@ -283,6 +283,8 @@ struct Ctx {
     bool theta_log_on = false;          // tests: every MVN objective evaluation as (theta..., log-likelihood)
     std::vector<double> theta_log;
     long long theta_rounds = 0, theta_evals_own = 0, theta_evals_all = 0;   // sharded theta-step: exchanges, evaluations here / everywhere
+    long long theta_factorised = 0;     // ... and the matrices this rank actually factorised for them (theta_scale.h)
+    std::vector<int> theta_scale_p;     // scale exponents of the covariance parameters (theta_scale.h), set by mvn_setup
     // rank emulation on one GPU (bench.py --as-rank-of N, include/glmmr_mcml_c.h glmmr_mcml_dbg_emulate_world): the
     // other ranks are copies of this one -- a sum is `emu_world` times the local value, a gather `emu_world` copies of
     // the local block; the candidate thetas of the other ranks are evaluated here too (mode 1, values recorded) or taken
@@ -332,6 +334,10 @@ int mvn_loglik_sum(Ctx& c, const double* theta, double* sum_out);
 int mvn_loglik_sum_on(Ctx& c, const double* theta, const double* U, int ldu, int m, double* sum_out);
 // k candidate thetas (npar x k, column-major) factorised side by side: sums[j], rcs[j] = MCML_OK | MCML_ENOTPD
 int mvn_loglik_batch(Ctx& c, const double* thetas, int k, const double* U, int ldu, int m, double* sums, int* rcs);
+// the k representatives of a round of `round` > 1 candidates, dense-block models only: as mvn_loglik_batch, and
+// parts[2 j], parts[2 j + 1] = candidate j's log-determinant and sum of squares (theta_scale.h)
+int mvn_loglik_batch_parts(Ctx& c, const double* thetas, int k, int round, const double* U, int ldu, int m, double* sums,
+                           int* rcs, double* parts);
 // L = genD(0, chol=true, upper=false) (mcml_full.cpp:68): block-diagonal lower factor
 int mvn_gen_L(Ctx& c, const double* theta, bool chol);
 int potrf_lower(Ctx& c, double* A, int n, int lda);                          // in place

@@ -329,6 +329,7 @@ extern "C" int glmmr_mcml_dbg_minstd(uint32_t seed, int n, double* out)
 // ---- host optimiser hooks (no GPU needed) ----
 #include "../../include/glmmr_mcml_c.h"
 #include "optim.h"
+#include "theta_scale.h"
 #include <cmath>
 extern "C" int glmmr_mcml_dbg_bobyqa(glmmr_mcml_objective f, void* user, int n, const double* x0,
                                      const double* lower, const double* upper, double rhobeg, double rhoend,
@@ -393,6 +394,49 @@ extern "C" int glmmr_mcml_dbg_bobyqa_rounds(glmmr_mcml_batch_objective fb, void*
     if (f_out) *f_out = r.fval;
     if (nfev_out) *nfev_out = r.nfev;
     if (rounds_out) *rounds_out = r.rounds;
+    return MCML_OK;
+}
+// bobyqa_batch over log(theta) on the grouped round evaluation of the theta-step (theta_scale.h), the factorisations left
+// to the caller: fb(X, n, k, logdet, sumsq, status, user) is asked for the representatives only (grouped != 0) or for
+// every candidate; the objective is -(MVN sum) / m from the two scalars, +inf where status != 0
+extern "C" int glmmr_mcml_dbg_theta_scale_rounds(glmmr_mcml_parts_objective fb, void* user, int n, const int* exps, int dim,
+                                                 int m, int grouped, const double* x0, const double* lower,
+                                                 const double* upper, double rhobeg, double rhoend, int maxfun, int width,
+                                                 double* x_out, double* f_out, int* nfev_out, int* rounds_out,
+                                                 long long* factorised_out)
+{
+    MCML_REQUIRE(fb && n > 0 && exps && x0 && x_out && width >= 1 && dim > 0 && m > 0, "dbg_theta_scale_rounds: bad argument");
+    ThetaScaleMemo ts;
+    ts.reset(grouped ? std::vector<int>(exps, exps + n) : std::vector<int>(n, 0), true);
+    batch_objective_fn obj = [&](const std::vector<std::vector<double>>& X, std::vector<double>* F) {
+        const int k = (int)X.size();
+        std::vector<double> flat((size_t)n * k);
+        for (int j = 0; j < k; ++j) for (int i = 0; i < n; ++i) flat[(size_t)j * n + i] = X[j][i];
+        const std::vector<int> reps = ts.plan(flat.data(), n, k);
+        const int nr = (int)reps.size();
+        std::vector<double> rx((size_t)n * nr + 1), parts((size_t)2 * nr + 2), ld(nr + 1), ss(nr + 1), rsums(nr + 1), sums(k);
+        std::vector<int> st(nr + 1, 0), rcs(k, 0);
+        for (int q = 0; q < nr; ++q) for (int i = 0; i < n; ++i) rx[(size_t)q * n + i] = flat[(size_t)reps[q] * n + i];
+        if (nr > 0) MCML_TRY(fb(rx.data(), n, nr, ld.data(), ss.data(), st.data(), user));
+        for (int q = 0; q < nr; ++q) {
+            parts[2 * q] = ld[q]; parts[2 * q + 1] = ss[q]; st[q] = st[q] ? MCML_ENOTPD : MCML_OK;
+            rsums[q] = theta_scale_value(dim, m, ld[q], ss[q]);
+        }
+        ts.finish(flat.data(), n, k, reps, rsums.data(), parts.data(), st.data(), dim, m, sums.data(), rcs.data());
+        F->resize(k);
+        for (int j = 0; j < k; ++j) (*F)[j] = rcs[j] == MCML_OK ? -1.0 * (sums[j] / m) : HUGE_VAL;
+        return (int)MCML_OK; };
+    std::vector<double> x(x0, x0 + n), lo(n, -HUGE_VAL), up(n, HUGE_VAL);
+    if (lower) lo.assign(lower, lower + n);
+    if (upper) up.assign(upper, upper + n);
+    BobyqaOpts o; o.rhobeg = rhobeg; o.rhoend = rhoend; if (maxfun > 0) o.maxfun = maxfun;
+    BobyqaResult r;
+    MCML_TRY(bobyqa_batch(obj, x, lo, up, o, width, &r));
+    for (int i = 0; i < n; ++i) x_out[i] = r.x[i];
+    if (f_out) *f_out = r.fval;
+    if (nfev_out) *nfev_out = r.nfev;
+    if (rounds_out) *rounds_out = r.rounds;
+    if (factorised_out) *factorised_out = ts.factorised;
     return MCML_OK;
 }
 extern "C" int glmmr_mcml_dbg_fd_hessian(glmmr_mcml_objective f, void* user, int n, const double* x, double ndeps,

@@ -16,6 +16,7 @@
 #include "../../include/glmmr_mcml_c.h"
 #include "ctx.h"
 #include "optim.h"
+#include "theta_scale.h"
 #include "trace.h"
 #include <algorithm>
 #include <cmath>
@@ -84,6 +85,36 @@ struct McmlOptim {
 
     BobyqaOpts bopts() const { BobyqaOpts o; o.iprint = trace; if (maxfun > 0) o.maxfun = maxfun; return o; }
 
+    // Candidates that differ in a pure scale parameter only share a factorisation (theta_scale.h): where rounds of
+    // candidates are the schedule -- D of large dense blocks only -- and the specification proves a scale.
+    // GLMMR_MCML_THETA_SCALE=0: one factorisation per candidate.
+    bool scale_active() const
+    {
+        return c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0 && theta_scale_any(c.theta_scale_p) && theta_scale_enabled();
+    }
+
+    // The MVN sums of one round: k candidates, X their coordinates as the optimiser holds them (candidate j at
+    // X[j * R ..], the memo says whether log theta or theta), ths the thetas themselves (R x k).  With a memo, only the
+    // first member of every group not seen in this theta-step is factorised (mvn_loglik_batch_parts); the others are
+    // rescaled on the host.  A round of ONE new candidate runs the single evaluation as before and leaves no entry.
+    int eval_round(ThetaScaleMemo* ts, const double* X, const double* ths, int k, const double* Us, int ldu, int m,
+                   double* sums, int* rcs)
+    {
+        if (!ts) { c.theta_factorised += k; return mvn_loglik_batch(c, ths, k, Us, ldu, m, sums, rcs); }
+        const std::vector<int> reps = ts->plan(X, R, k);
+        const int nr = (int)reps.size();
+        if (k == 1 && nr == 1) { c.theta_factorised += 1; return mvn_loglik_batch(c, ths, 1, Us, ldu, m, sums, rcs); }
+        std::vector<double> rth((size_t)R * nr), rsums(nr, 0.0), parts((size_t)2 * nr, 0.0);
+        std::vector<int> rrcs(nr, 0);
+        for (int q = 0; q < nr; ++q) memcpy(&rth[(size_t)q * R], ths + (size_t)reps[q] * R, sizeof(double) * R);
+        int brc = MCML_OK;
+        if (nr > 0) brc = mvn_loglik_batch_parts(c, rth.data(), nr, k, Us, ldu, m, rsums.data(), rrcs.data(), parts.data());
+        if (brc != MCML_OK) { for (int j = 0; j < k; ++j) rcs[j] = brc; return brc; }
+        c.theta_factorised += nr;
+        ts->finish(X, R, k, reps, rsums.data(), parts.data(), rrcs.data(), c.cov.N, m, sums, rcs);
+        return MCML_OK;
+    }
+
     // d_optim of a chain-sharded job (no reference counterpart: the reference is one process).  The
     // factorisation of D(theta) does not shard -- replicated, it was 43 % of a rank's step at 8 GPUs -- but the
     // optimiser's EVALUATIONS do: the sample columns are all-gathered once per iteration (every rank then holds all of
@@ -97,6 +128,10 @@ struct McmlOptim {
     {
         MCML_TRY(gather_samples(c));
         const int wr = comm_world(c), mall = c.mcols * wr;
+        // one memo per rank whose share is evaluated here, alive for this theta-step only (the samples are fixed in it):
+        // a rank groups inside its own share of a round, candidates are never re-dealt between ranks
+        std::vector<ThetaScaleMemo> memos(scale_active() ? wr : 0);
+        for (ThetaScaleMemo& ts : memos) ts.reset(c.theta_scale_p, true);
         batch_objective_fn fb = [&](const std::vector<std::vector<double>>& Zs, std::vector<double>* F) -> int {
             const int nc = (int)Zs.size();
             std::vector<double> vals(nc, 0.0);
@@ -110,11 +145,12 @@ struct McmlOptim {
                 std::vector<int> own;
                 for (int j = 0; j < nc; ++j) if ((j % wr) == rr) own.push_back(j);
                 if (own.empty()) continue;
-                std::vector<double> ths((size_t)R * own.size()), sums(own.size(), 0.0);
+                std::vector<double> ths((size_t)R * own.size()), zs((size_t)R * own.size()), sums(own.size(), 0.0);
                 std::vector<int> rcs(own.size(), 0);
                 for (size_t q = 0; q < own.size(); ++q)
-                    for (int i = 0; i < R; ++i) ths[q * R + i] = std::exp(Zs[own[q]][i]);
-                const int brc = mvn_loglik_batch(c, ths.data(), (int)own.size(), c.Uall.d(), c.Uall.ld, mall, sums.data(), rcs.data());
+                    for (int i = 0; i < R; ++i) { zs[q * R + i] = Zs[own[q]][i]; ths[q * R + i] = std::exp(Zs[own[q]][i]); }
+                const int brc = eval_round(memos.empty() ? nullptr : &memos[rr], zs.data(), ths.data(), (int)own.size(),
+                                           c.Uall.d(), c.Uall.ld, mall, sums.data(), rcs.data());
                 for (size_t q = 0; q < own.size(); ++q) {
                     const int j = own[q];
                     const int rc = (rcs[q] == MCML_OK && brc != MCML_OK) ? brc : rcs[q];
@@ -247,12 +283,15 @@ struct McmlOptim {
     int f_optim_batch(int width, double denomD)
     {
         const double fix_var_par = sigma;
+        ThetaScaleMemo memo;                                     // this call's: the samples are fixed in it
+        const bool scale = scale_active();
+        if (scale) memo.reset(c.theta_scale_p, true);
         batch_objective_fn fb = [&](const std::vector<std::vector<double>>& Zs, std::vector<double>* F) -> int {
             const int nc = (int)Zs.size();
-            std::vector<double> ths((size_t)R * nc), sums(nc, 0.0);
+            std::vector<double> ths((size_t)R * nc), zs((size_t)R * nc), sums(nc, 0.0);
             std::vector<int> rcs(nc, 0);
-            for (int j = 0; j < nc; ++j) for (int i = 0; i < R; ++i) ths[(size_t)j * R + i] = std::exp(Zs[j][P + i]);
-            MCML_TRY(mvn_loglik_batch(c, ths.data(), nc, c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
+            for (int j = 0; j < nc; ++j) for (int i = 0; i < R; ++i) { zs[(size_t)j * R + i] = Zs[j][P + i]; ths[(size_t)j * R + i] = std::exp(Zs[j][P + i]); }
+            MCML_TRY(eval_round(scale ? &memo : nullptr, zs.data(), ths.data(), nc, c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
             F->assign(nc, 0.0);
             for (int j = 0; j < nc; ++j) {
                 model_var_par = fix_var_par;
@@ -315,7 +354,11 @@ struct McmlOptim {
             std::vector<double> ths((size_t)R * want.size()), sums(want.size(), 0.0);
             std::vector<int> rcs(want.size(), 0);
             for (size_t q = 0; q < want.size(); ++q) for (int i = 0; i < R; ++i) ths[q * R + i] = want[q][i];
-            MCML_TRY(mvn_loglik_batch(c, ths.data(), (int)want.size(), c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
+            // the points move one or two coordinates at a time: those that differ in a scale parameter only share a matrix
+            ThetaScaleMemo ts;
+            const bool scale = scale_active();
+            if (scale) ts.reset(c.theta_scale_p, false);         // these coordinates are theta itself
+            MCML_TRY(eval_round(scale ? &ts : nullptr, ths.data(), ths.data(), (int)want.size(), c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
             for (size_t q = 0; q < want.size(); ++q)
                 (*memo)[want[q]] = rcs[q] == MCML_OK ? sums[q] / c.mcols : -HUGE_VAL;       // as eval_mvn
         }
@@ -375,6 +418,24 @@ int drv_hess(Ctx& c, const double* start, int nstart, double tol, int trace, dou
     MCML_REQUIRE(c.mcols > 0, "no samples u set");
     McmlOptim mc(c, start, trace, 0, 1.0);
     return mc.f_hess(tol, H);
+}
+
+// One round of k candidate thetas (R x k) exactly as a theta-step evaluates it, with a memo of its own: out[j] =
+// log-likelihood at candidate j, NaN where D is not positive definite (tests: glmmr_mcml_dbg_theta_round)
+int drv_theta_round(Ctx& c, const double* thetas, int k, double* out)
+{
+    MCML_REQUIRE(thetas && out && k >= 1 && k <= 64, "theta_round: bad argument");
+    MCML_REQUIRE(c.mcols > 0 && c.U.d(), "theta_round: no samples set");
+    const std::vector<double> start((size_t)c.P + c.cov.npar + 1, 0.0);
+    McmlOptim mc(c, start.data(), 0, 0, 1.0);
+    ThetaScaleMemo ts;
+    const bool scale = mc.scale_active();
+    if (scale) ts.reset(c.theta_scale_p, false);
+    std::vector<double> sums(k, 0.0);
+    std::vector<int> rcs(k, 0);
+    MCML_TRY(mc.eval_round(scale ? &ts : nullptr, thetas, thetas, k, c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
+    for (int j = 0; j < k; ++j) out[j] = rcs[j] == MCML_OK ? sums[j] / c.mcols : NAN;
+    return MCML_OK;
 }
 
 // aic_mcml (mcml_optim.cpp:356-392)

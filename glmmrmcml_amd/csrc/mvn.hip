@@ -21,6 +21,7 @@
 #include "dgemm_mfma.h"
 #include "dgemm_dl.h"
 #include "reduce.h"
+#include "theta_scale.h"
 
 namespace mcml {
 
@@ -576,6 +577,14 @@ __global__ void k_finish_large(double* scal, int dim, int mcols)
     scal[0] += (double)mcols * (-0.5 * dim * LOG_2PI - 0.5 * scal[1]) - 0.5 * scal[2];
 }
 
+// the two terms of the block at hand, added up per candidate for the host (mvn_loglik_batch_parts): thread j = candidate j
+__global__ void k_accum_parts(const double* scal, int sstride, double* parts)
+{
+    const double* sj = scal + (size_t)threadIdx.x * sstride;
+    parts[2 * threadIdx.x] += sj[1];
+    parts[2 * threadIdx.x + 1] += sj[2];
+}
+
 __global__ void k_zero_upper(double* A, int lda, int n)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -587,7 +596,8 @@ __global__ void k_zero_upper(double* A, int lda, int n)
 // launch of the schedule covers all of them (leaf: one workgroup per matrix; products: blockIdx.y), so the latency
 // chain of the late steps -- leaf, two single-block products, their gaps -- is paid once per round, not once per
 // candidate.  sA / sL: element strides from one matrix / one set of inverted diagonal blocks to the next.
-struct Bat { int n = 1; size_t sA = 0, sL = 0; int* err = nullptr; };   // err: one flag per matrix (null: the context's own)
+// round: candidates of the optimiser's round the n matrices stand for (0: n itself) -- what the schedule is chosen by
+struct Bat { int n = 1; size_t sA = 0, sL = 0; int* err = nullptr; int round = 0; };   // err: one flag per matrix (null: the context's own)
 
 // The K = 128 products of the blocked factorisation and of the blocked solve: deep-ring direct-to-LDS kernel
 // (dgemm_dl.h) when its contract holds, the register-staged kernel otherwise (one matrix, no shifted lower-only
@@ -686,7 +696,10 @@ static int potrf_blocked(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
     if (two) { MCML_TRY(lookahead_setup(c)); sL = c.aux; }
     const int nsteps = (n + CHOL_NB - 1) / CHOL_NB;
     constexpr int SPW = CHOL_NB * 8;                              // super-panel width: 8 panels
-    const bool twolevel = bt.n > 1 && n > SPW + CHOL_NB;
+    // decided by the ROUND the matrices come from, not by how many of its candidates are factorised: a round whose
+    // candidates share a factorisation (theta_scale.h) keeps the regrouped sums of the full round, so a candidate's
+    // value does not depend on which of its neighbours happened to need a matrix of their own
+    const bool twolevel = (bt.round ? bt.round : bt.n) > 1 && n > SPW + CHOL_NB;
     MCML_TRY(L.leaf(sM, 0, n < CHOL_NB ? n : CHOL_NB));
     bool forked = false;
     for (int t = 0; t < nsteps; ++t) {
@@ -694,7 +707,7 @@ static int potrf_blocked(Ctx& c, double* A, int lda, int n, int extra, Bat bt = 
         const int k = s.k, nb = s.nb, rem = s.rem, R = s.R, nb2 = s.nb2;
         if (R <= 0) break;
         if (forked) { MCML_HIP(hipStreamWaitEvent(sM, c.ev_leaf, 0)); forked = false; }   // leaf(t) done
-        // Two levels of blocking for a BATCH (bt.n > 1), whose rounds are bound by the trailing updates, not by the chain:
+        // Two levels of blocking for a BATCH (a round of more than one candidate), whose rounds are bound by the trailing updates, not by the chain:
         // inside a super-panel of 8 panels the K = 128 updates touch the super-panel's own columns only; the columns to
         // its right receive all eight panels in ONE pass with K = 1024 when the super-panel is done (the same LDS-DMA
         // kernel: 48 against 35 TF on the trailing update of a 4000 x 4000 block, scripts/dl_k_sweep.py) -- five
@@ -1008,6 +1021,7 @@ int trsm_left_lower_trans(Ctx& c, const double* R, int ldr, int n, double* T, in
 int mvn_setup(Ctx& c)
 {
     const CovSpec& cs = c.cov;
+    c.theta_scale_p = theta_scale_exponents(cs);
     MCML_TRY(c.d_cov.ensure(sizeof(int32_t) * cs.cov.size()));
     MCML_TRY(copy_h2d(c.d_cov.p, cs.cov.data(), sizeof(int32_t) * cs.cov.size(), c.stream));
     MCML_TRY(c.d_data.ensure(sizeof(double) * (cs.data.size() + 1)));
@@ -1093,14 +1107,18 @@ int mvn_loglik_sum(Ctx& c, const double* theta, double* sum_out)
 // one-chain graph (measured, then removed) -- a graph without a parallel branch cannot overlap the two, and one
 // with a branch is subject to the executable lottery described at CholGraph.  The host keeps ahead easily (~250
 // launches per round).  kb = 1 (a single evaluation, or the last round of k = 8 j + 1 candidates) takes the graph.
+// round > 1: the kb matrices are the representatives of a round of `round` candidates (mvn_loglik_batch_parts); they
+// take the batch's schedule whatever kb is.  parts (nullable): 2 doubles per candidate, += (log-determinant, sum of
+// squares) of every block.
 static int mvn_large_blocks(Ctx& c, DevMat& W, int kb, const ThetaArg* th, const double* Us, int ldu, int m,
-                            double* scal, int sstride, int* flags)
+                            double* scal, int sstride, int* flags, int round = 0, double* parts = nullptr)
 {
+    const bool batch = (round ? round : kb) > 1;
     const CovSpec& cs = c.cov;
     const int32_t* dcov = c.d_cov.as<int32_t>();
     const CovBlock* dblk = c.d_blocks.as<CovBlock>();
     const int ld = W.ld, dmax = round_up(c.maxdim_large, 16);
-    Bat bt; bt.n = kb; bt.sA = (size_t)ld * dmax; bt.sL = linv_size(dmax); bt.err = flags;
+    Bat bt; bt.n = kb; bt.sA = (size_t)ld * dmax; bt.sL = linv_size(dmax); bt.err = flags; bt.round = round;
     ThetaBatch tb;
     memset(&tb, 0, sizeof tb);
     for (int j = 0; j < kb; ++j) tb.t[j] = th[j];
@@ -1113,7 +1131,7 @@ static int mvn_large_blocks(Ctx& c, DevMat& W, int kb, const ThetaArg* th, const
         const int dp = round_up(d, 16);
         c.mvn_ws[&W == &c.Dbatch] = Ctx::MvnWs{d, dp, m, ld, kb};
         const dim3 gb((dp + 63) / 64, (dp + 15) / 16, kb);
-        if (kb == 1)
+        if (!batch)
             hipLaunchKernelGGL(k_build_dense, gb, dim3(256), 0, c.stream, W.d(), ld, b, dblk, dcov, cs.rows, c.d_data.d(),
                                th[0], 0, dp);
         else
@@ -1126,7 +1144,7 @@ static int mvn_large_blocks(Ctx& c, DevMat& W, int kb, const ThetaArg* th, const
             for (int j = 0; j < kb; ++j)
                 MCML_HIP(hipMemset2DAsync(W.d() + j * bt.sA + dp + (size_t)d * ld, sizeof(double) * ld, 0, sizeof(double) * m, dp - d, c.stream));
         MCML_TRY(leaf_prepare(c, dmax, kb));
-        MCML_TRY(kb > 1 ? potrf_blocked(c, W.d(), ld, dp, m, bt) : potrf_graphed(c, W.d(), ld, dp, m, bt));
+        MCML_TRY(batch ? potrf_blocked(c, W.d(), ld, dp, m, bt) : potrf_graphed(c, W.d(), ld, dp, m, bt));
         // the solved samples: m rows x d columns below each factor
         const int gx = (m + 255) / 256, gy = d < 64 ? d : 64;
         MCML_TRY(c.partials.ensure(sizeof(double) * (size_t)(gx * gy + 16)));
@@ -1138,6 +1156,7 @@ static int mvn_large_blocks(Ctx& c, DevMat& W, int kb, const ThetaArg* th, const
             hipLaunchKernelGGL(k_logdet, dim3(1), dim3(256), 0, c.stream, Aj, ld, d, sj + 1);
             hipLaunchKernelGGL(k_finish_large, dim3(1), dim3(1), 0, c.stream, sj, d, m);
         }
+        if (parts) hipLaunchKernelGGL(k_accum_parts, dim3(1), dim3(kb), 0, c.stream, scal, sstride, parts);
         MCML_HIP(hipGetLastError());
     }
     return MCML_OK;
@@ -1205,19 +1224,13 @@ int mvn_loglik_sum_on(Ctx& c, const double* theta, const double* Us, int ldu, in
 // is paid once per round.  (Measured dead end: the k evaluations as k independent streams / graphs -- "lanes" -- do
 // not overlap on this stack: 3.6 ms per evaluation alone, 4.1 / 4.8 / 5.0 ms each with 2 / 4 / 8 lanes, worse with
 // more hardware queues.)  Models whose D has diagonal or small blocks besides, and k = 1, take the single path.
-int mvn_loglik_batch(Ctx& c, const double* thetas, int k, const double* Us, int ldu, int m, double* sums, int* rcs)
+static bool mvn_batchable(const Ctx& c) { return c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0; }
+
+// the side-by-side pass in chunks of MVN_MAXBATCH.  round / parts: see mvn_large_blocks (parts here: host, 2 per candidate)
+static int mvn_batch_pass(Ctx& c, const double* thetas, int k, int round, const double* Us, int ldu, int m, double* sums,
+                          int* rcs, double* parts)
 {
-    MCML_REQUIRE(k >= 1 && thetas && sums && rcs && m > 0 && Us, "mvn_ll batch: bad arguments");
     const int R = c.cov.npar;
-    const bool batchable = k > 1 && c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0;
-    if (!batchable) {
-        int first_rc = MCML_OK;
-        for (int j = 0; j < k; ++j) {
-            rcs[j] = mvn_loglik_sum_on(c, thetas + (size_t)j * R, Us, ldu, m, sums + j);
-            if (rcs[j] != MCML_OK && rcs[j] != MCML_ENOTPD && first_rc == MCML_OK) first_rc = rcs[j];
-        }
-        return first_rc;
-    }
     for (int j0 = 0; j0 < k; j0 += MVN_MAXBATCH) {
         const int kb = (k - j0 < MVN_MAXBATCH) ? k - j0 : MVN_MAXBATCH;
         ThetaArg th[MVN_MAXBATCH];
@@ -1227,19 +1240,52 @@ int mvn_loglik_batch(Ctx& c, const double* thetas, int k, const double* Us, int 
             MCML_TRY(c.Dbatch.alloc(dmax + m, MVN_MAXBATCH * dmax));
             MCML_HIP(hipMemsetAsync(c.Dbatch.d(), 0, sizeof(double) * (size_t)c.Dbatch.ld * MVN_MAXBATCH * dmax, c.stream));
         }
-        // results: 4 doubles per candidate, then one "not positive definite" flag (int) per candidate -- a buffer of
-        // their own (c.scalars is shared with the sampler's diagnostics)
-        MCML_TRY(c.bscal.ensure(sizeof(double) * 5 * MVN_MAXBATCH));
-        MCML_HIP(hipMemsetAsync(c.bscal.p, 0, sizeof(double) * 5 * MVN_MAXBATCH, c.stream));
+        // results: 4 doubles per candidate, then one "not positive definite" flag (int) per candidate, then the two
+        // summed terms per candidate -- a buffer of their own (c.scalars is shared with the sampler's diagnostics)
+        MCML_TRY(c.bscal.ensure(sizeof(double) * 7 * MVN_MAXBATCH));
+        MCML_HIP(hipMemsetAsync(c.bscal.p, 0, sizeof(double) * 7 * MVN_MAXBATCH, c.stream));
         int* bflags = reinterpret_cast<int*>(c.bscal.d() + 4 * MVN_MAXBATCH);
-        MCML_TRY(mvn_large_blocks(c, c.Dbatch, kb, th, Us, ldu, m, c.bscal.d(), 4, bflags));
+        double* bparts = c.bscal.d() + 5 * MVN_MAXBATCH;
+        MCML_TRY(mvn_large_blocks(c, c.Dbatch, kb, th, Us, ldu, m, c.bscal.d(), 4, bflags, round, parts ? bparts : nullptr));
         double hs[4 * MVN_MAXBATCH]; int hf[MVN_MAXBATCH];
         MCML_TRY(copy_d2h(hs, c.bscal.p, sizeof(double) * 4 * kb, c.stream));
         MCML_TRY(copy_d2h(hf, bflags, sizeof(int) * kb, c.stream));
+        if (parts) MCML_TRY(copy_d2h(parts + 2 * (size_t)j0, bparts, sizeof(double) * 2 * kb, c.stream));
         MCML_HIP(hipStreamSynchronize(c.stream));
         for (int j = 0; j < kb; ++j) { sums[j0 + j] = hs[4 * j]; rcs[j0 + j] = hf[j] ? MCML_ENOTPD : MCML_OK; }
     }
     return MCML_OK;
+}
+
+int mvn_loglik_batch(Ctx& c, const double* thetas, int k, const double* Us, int ldu, int m, double* sums, int* rcs)
+{
+    MCML_REQUIRE(k >= 1 && thetas && sums && rcs && m > 0 && Us, "mvn_ll batch: bad arguments");
+    const int R = c.cov.npar;
+    const bool batchable = k > 1 && mvn_batchable(c);
+    if (!batchable) {
+        int first_rc = MCML_OK;
+        for (int j = 0; j < k; ++j) {
+            rcs[j] = mvn_loglik_sum_on(c, thetas + (size_t)j * R, Us, ldu, m, sums + j);
+            if (rcs[j] != MCML_OK && rcs[j] != MCML_ENOTPD && first_rc == MCML_OK) first_rc = rcs[j];
+        }
+        return first_rc;
+    }
+    return mvn_batch_pass(c, thetas, k, 0, Us, ldu, m, sums, rcs, nullptr);
+}
+
+// The k REPRESENTATIVES of a round of `round` > 1 candidates (theta_scale.h: the others share a representative's
+// factorisation up to a scale), dense-block models only.  As mvn_loglik_batch, and parts[2 j .. 2 j + 1] = candidate
+// j's log-determinant and sum of squares summed over the blocks -- the two terms k_finish_large combines.
+// What decides the two-level blocking: the size of the ROUND (potrf_blocked), so a round of 8 reduced to 5 matrices, or
+// to one, regroups its sums exactly as the full round did; with k == round the sums are mvn_loglik_batch's to the bit.
+// A chunk of one (k = 8 j + 1 representatives) therefore runs the eager two-level schedule here, not the single
+// evaluation's graph mvn_loglik_batch gives such a chunk: a 1e-13 difference in that candidate's value.
+int mvn_loglik_batch_parts(Ctx& c, const double* thetas, int k, int round, const double* Us, int ldu, int m, double* sums,
+                           int* rcs, double* parts)
+{
+    MCML_REQUIRE(k >= 1 && round >= k && round > 1 && thetas && sums && rcs && parts && m > 0 && Us, "mvn_ll batch parts: bad arguments");
+    MCML_REQUIRE(mvn_batchable(c), "mvn_ll batch parts: the model has blocks that are not factorised side by side");
+    return mvn_batch_pass(c, thetas, k, round, Us, ldu, m, sums, rcs, parts);
 }
 
 // ------------------------------------------------------------------ genD

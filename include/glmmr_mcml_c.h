@@ -89,7 +89,8 @@ int glmmr_mcml_ctx_comm_allreduce(glmmr_mcml_ctx* ctx, double* vals, int n);
 /* collectives issued so far, doubles summed, 1 if the native communicator is in use (all nullable) */
 int glmmr_mcml_ctx_comm_stats(glmmr_mcml_ctx* ctx, long long* calls, long long* doubles, int* native);
 /* out6 = [all-gathers issued, doubles received by them, theta-step rounds (one all-reduce each), candidate thetas
- * evaluated on this rank, candidate thetas evaluated over all ranks, 0] since the context was made */
+ * evaluated on this rank, candidate thetas evaluated over all ranks, matrices this rank factorised for them (fewer than
+ * its candidates where some differ in a scale parameter only, csrc/theta_scale.h)] since the context was made */
 int glmmr_mcml_ctx_shard_stats(glmmr_mcml_ctx* ctx, long long* out6);
 
 /* samples u (Q x ncols, this rank's columns).  niter = columns the beta-step
@@ -477,6 +478,19 @@ typedef int (*glmmr_mcml_batch_objective)(const double* X, int n, int k, double*
 int glmmr_mcml_dbg_bobyqa_rounds(glmmr_mcml_batch_objective fb, void* user, int n, const double* x0, const double* lower,
                                  const double* upper, double rhobeg, double rhoend, int maxfun, int width,
                                  double* x_out, double* f_out, int* nfev_out, int* rounds_out);
+/* the theta-step's grouped round evaluation (csrc/theta_scale.h) under that schedule, over log(theta): exps = the scale
+ * exponent of every coordinate, dim / m = dimension of D / sample columns.  fb is asked for the log-determinant, the sum
+ * of squares and a status (0 = has a value) of the candidates that need a factorisation of their own -- all of them with
+ * grouped = 0; factorised_out = how many that were (CPU only) */
+typedef int (*glmmr_mcml_parts_objective)(const double* X, int n, int k, double* logdet, double* sumsq, int* status,
+                                          void* user);
+int glmmr_mcml_dbg_theta_scale_rounds(glmmr_mcml_parts_objective fb, void* user, int n, const int* exps, int dim, int m,
+                                      int grouped, const double* x0, const double* lower, const double* upper,
+                                      double rhobeg, double rhoend, int maxfun, int width, double* x_out, double* f_out,
+                                      int* nfev_out, int* rounds_out, long long* factorised_out);
+/* one round of k candidate thetas (npar x k) as a theta-step evaluates it -- candidates that differ in a scale parameter
+ * only share a factorisation unless GLMMR_MCML_THETA_SCALE=0 -- with a memo of its own: out[j] as mvn_ll_batch */
+int glmmr_mcml_dbg_theta_round(glmmr_mcml_ctx* ctx, const double* thetas, int k, double* out);
 /* host -> device -> host through the library's staged copies (csrc/common.hip copy_h2d_2d / copy_d2h_2d): `cols` columns of
  * `rows` doubles, host pitches ld_in / ld_out (in doubles), a padded pitch on the device */
 int glmmr_mcml_dbg_copy_roundtrip(const double* in, long long ld_in, double* out, long long ld_out, long long rows, long long cols);
