@@ -6,53 +6,15 @@ Tolerance 1e-10 relative (f64, different summation order)."""
 import numpy as np
 import pytest
 
-from glmmrmcml_amd import api, synth
+from glmmrmcml_amd import api
+from family_designs import CASES, design
 
 pytestmark = pytest.mark.gpu
 
 
 def _design(family, link, seed=5):
-    """small cluster design whose linear predictor stays inside the link's domain"""
-    d = synth.cluster_rct(ncl=6, nt=3, nind=6, seed=seed, family="poisson")
-    rng = np.random.default_rng(seed + 100)
-    n, P = d["n"], d["P"]
-    X = d["X"]
-    beta = np.zeros(P)
-    theta = np.array([0.05, 0.03])                      # tiny random effects: eta stays near X beta
-    centre = {"log": 0.3, "identity": 0.5, "logit": 0.2, "probit": 0.1, "inverse": 1.5}[link]
-    if family == "binomial" and link == "log":
-        centre = -1.0                                   # exp(eta) must stay below 1
-    if family == "poisson" and link == "identity":
-        centre = 3.0
-    if family == "gamma" and link == "identity":
-        centre = 2.0
-    if family == "gaussian" and link == "log":
-        centre = 1.5        # the reference logs y twice (mcmlmodel.h:90 and moremaths.h:81): keep log(y) > 0
-    beta[1:] = centre                                   # the period columns partition the rows
-    beta[0] = 0.05
-    eta = X @ beta
-    if family == "poisson":
-        mu = np.exp(eta) if link == "log" else eta
-        y = rng.poisson(mu).astype(float)
-    elif family == "binomial":
-        p = {"logit": 1 / (1 + np.exp(-eta)), "log": np.exp(eta), "identity": eta,
-             "probit": 0.5 * (1 + np.vectorize(__import__("math").erf)(eta / np.sqrt(2)))}[link]
-        y = (rng.random(n) < p).astype(float)
-    elif family == "gaussian":
-        y = eta + 0.3 * rng.normal(size=n) if link == "identity" else np.exp(eta + 0.1 * rng.normal(size=n))
-    elif family == "gamma":
-        mu = {"log": np.exp(eta), "inverse": 1 / eta, "identity": eta}[link]
-        y = rng.gamma(shape=2.0, scale=mu / 2.0)
-    else:                                               # beta
-        mu = 1 / (1 + np.exp(-eta))
-        y = np.clip(rng.beta(mu * 5, (1 - mu) * 5), 1e-3, 1 - 1e-3)
-    return dict(d, family=family, link=link, y=y, beta=beta, theta=theta)
-
-
-CASES = [("poisson", "log", 1.0), ("poisson", "identity", 1.0), ("binomial", "logit", 1.0), ("binomial", "log", 1.0),
-         ("binomial", "identity", 1.0), ("binomial", "probit", 1.0), ("gaussian", "identity", 0.7),
-         ("gaussian", "log", 0.6), ("gamma", "log", 2.0), ("gamma", "inverse", 2.0), ("gamma", "identity", 2.0),
-         ("beta", "logit", 4.0)]
+    """small cluster design whose linear predictor stays inside the link's domain (tests/family_designs.py)"""
+    return design(family, link, ncl=6, nt=3, nind=6, seed=seed)
 
 
 @pytest.mark.parametrize("family,link,vp", CASES)
