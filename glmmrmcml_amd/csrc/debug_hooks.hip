@@ -348,6 +348,24 @@ extern "C" int glmmr_mcml_dbg_bobyqa(glmmr_mcml_objective f, void* user, int n, 
     if (nfev_out) *nfev_out = r.nfev;
     return MCML_OK;
 }
+// the same with the number of interpolation points given (0: the default, min(n + 2, 2n) as minqa)
+extern "C" int glmmr_mcml_dbg_bobyqa_npt(glmmr_mcml_objective f, void* user, int n, const double* x0,
+                                         const double* lower, const double* upper, double rhobeg, double rhoend,
+                                         int maxfun, int npt, double* x_out, double* f_out, int* nfev_out)
+{
+    MCML_REQUIRE(f && n > 0 && x0 && x_out && npt >= 0, "dbg_bobyqa_npt: bad argument");
+    objective_fn obj = [&](const std::vector<double>& x, double* v) { *v = f(x.data(), n, user); return 0; };
+    std::vector<double> x(x0, x0 + n), lo(n, -HUGE_VAL), up(n, HUGE_VAL);
+    if (lower) lo.assign(lower, lower + n);
+    if (upper) up.assign(upper, upper + n);
+    BobyqaOpts o; o.rhobeg = rhobeg; o.rhoend = rhoend; o.npt = npt; if (maxfun > 0) o.maxfun = maxfun;
+    BobyqaResult r;
+    MCML_TRY(bobyqa(obj, x, lo, up, o, &r));
+    for (int i = 0; i < n; ++i) x_out[i] = r.x[i];
+    if (f_out) *f_out = r.fval;
+    if (nfev_out) *nfev_out = r.nfev;
+    return MCML_OK;
+}
 extern "C" int glmmr_mcml_dbg_bobyqa_batch(glmmr_mcml_objective f, void* user, int n, const double* x0,
                                            const double* lower, const double* upper, double rhobeg, double rhoend,
                                            int maxfun, int width, double* x_out, double* f_out, int* nfev_out,

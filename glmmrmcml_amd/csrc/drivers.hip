@@ -292,6 +292,8 @@ struct McmlOptim {
             std::vector<int> rcs(nc, 0);
             for (int j = 0; j < nc; ++j) for (int i = 0; i < R; ++i) { zs[(size_t)j * R + i] = Zs[j][P + i]; ths[(size_t)j * R + i] = std::exp(Zs[j][P + i]); }
             MCML_TRY(eval_round(scale ? &memo : nullptr, zs.data(), ths.data(), nc, c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
+            if (c.theta_log_on)
+                for (int j = 0; j < nc; ++j) if (rcs[j] == MCML_OK) { c.theta_log.insert(c.theta_log.end(), ths.begin() + (size_t)j * R, ths.begin() + (size_t)(j + 1) * R); c.theta_log.push_back(sums[j] / c.mcols); }
             F->assign(nc, 0.0);
             for (int j = 0; j < nc; ++j) {
                 model_var_par = fix_var_par;
@@ -325,8 +327,14 @@ struct McmlOptim {
         for (int i = 0; i < R; ++i) { x.push_back(theta[i]); lo.push_back(1e-6); }
         if (g) { x.push_back(sigma); lo.push_back(0.0); }
         up.assign(x.size(), HUGE_VAL);
+        // 2n + 1 interpolation points, not the n + 2 the other steps take over from minqa: in the P + R dimensions of this
+        // objective, whose curvatures differ by a factor of a hundred and more, a model on n + 2 points is all but linear --
+        // the run crept along the weak directions in steps of its final radius and stopped 2e-6 to 4e-6 from the optimum
+        // after 350 to 490 evaluations, where 2n + 1 points end within 4e-7 after 110 to 190
+        BobyqaOpts o = bopts();
+        o.npt = 2 * (int)x.size() + 1;
         BobyqaResult r;
-        MCML_TRY(bobyqa(f, x, lo, up, bopts(), &r));
+        MCML_TRY(bobyqa(f, x, lo, up, o, &r));
         beta.assign(r.x.begin(), r.x.begin() + P);
         theta.assign(r.x.begin() + P, r.x.begin() + P + R);
         if (g) sigma = r.x[P + R];
@@ -359,6 +367,8 @@ struct McmlOptim {
             const bool scale = scale_active();
             if (scale) ts.reset(c.theta_scale_p, false);         // these coordinates are theta itself
             MCML_TRY(eval_round(scale ? &ts : nullptr, ths.data(), ths.data(), (int)want.size(), c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
+            if (c.theta_log_on)
+                for (size_t q = 0; q < want.size(); ++q) if (rcs[q] == MCML_OK) { c.theta_log.insert(c.theta_log.end(), ths.begin() + q * R, ths.begin() + (q + 1) * R); c.theta_log.push_back(sums[q] / c.mcols); }
             for (size_t q = 0; q < want.size(); ++q)
                 (*memo)[want[q]] = rcs[q] == MCML_OK ? sums[q] / c.mcols : -HUGE_VAL;       // as eval_mvn
         }

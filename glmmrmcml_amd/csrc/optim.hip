@@ -159,7 +159,11 @@ public:
             else { step = -rhobeg; if (x[i] - lo_[i] < rhobeg * 0.999) step = 2 * rhobeg; if (up_[i] - x[i] < rhobeg * 0.999) step = -2 * rhobeg; }
             Y_[k][i] = std::min(std::max(x[i] + step, lo_[i]), up_[i]);
         }
-        for (int k = 0; k < npt_; ++k) { F_[k] = eval(Y_[k]); if (rc_) return rc_; }
+        // the initial design is this schedule's first round: the finite values of all of it count before any of its
+        // points without a value is given one (as eval_batch does for a round)
+        std::vector<char> nov(npt_, 0);
+        for (int k = 0; k < npt_; ++k) { F_[k] = eval(Y_[k]); nov[k] = no_value_; if (rc_) return rc_; }
+        for (int k = 0; k < npt_; ++k) if (nov[k]) F_[k] = no_value();
         kopt_ = (int)(std::min_element(F_.begin(), F_.end()) - F_.begin());
         q_.init(n); q_.c = 0; xb_ = Y_[kopt_];
         if (!refit(true)) { set_error("bobyqa: initial interpolation set is degenerate"); return MCML_EINVAL; }
@@ -541,7 +545,16 @@ private:
     vec F_;
     Quad q_;
     std::vector<double> Winv_; double sc_ = 1.0;   // inverse KKT matrix in coordinates (x - xb)/sc
-    double fin_lo_ = HUGE_VAL, fin_hi_ = -HUGE_VAL; // range of the finite objective values seen (eval_batch)
+    double fin_lo_ = HUGE_VAL, fin_hi_ = -HUGE_VAL; // range of the finite objective values seen (no_value)
+    bool no_value_ = false;                         // whether the last eval() had to substitute
+
+    // A point with no value (NaN, +inf: e.g. a covariance matrix that is not positive definite there) must stay
+    // "worse than anything seen" without poisoning the interpolation models with infinities: it gets the largest
+    // finite value seen so far plus ten times the spread of the finite values (1e30 while nothing finite has been seen).
+    // On both schedules: an infinity kept as it is makes every model through it NaN, and the sequential run then stops
+    // after its initial design at whatever point it holds.
+    void note_finite(double v) { if (std::isfinite(v)) { fin_lo_ = std::min(fin_lo_, v); fin_hi_ = std::max(fin_hi_, v); } }
+    double no_value() const { return (fin_hi_ >= fin_lo_) ? fin_hi_ + 10.0 * std::max(1.0, fin_hi_ - fin_lo_) : 1e30; }
 
     double eval(const vec& x)
     {
@@ -554,8 +567,9 @@ private:
         } else rc = f_(x, &v);
         ++nf_;
         if (rc) { rc_ = rc; return 0; }
-        if (v != v) v = HUGE_VAL;       // NaN objective: treat as +inf
-        return v;
+        note_finite(v);
+        no_value_ = !std::isfinite(v);
+        return no_value_ ? no_value() : v;
     }
 
     // one exchange: every point of X evaluated (by whoever owns it), all values returned
@@ -567,14 +581,9 @@ private:
         nf_ += (int)X.size();
         if (rc) { rc_ = rc; return false; }
         if (F->size() != X.size()) { rc_ = MCML_EINVAL; set_error("bobyqa_batch: objective returned %zu values for %zu points", F->size(), X.size()); return false; }
-        // A point with no value (NaN, +inf: e.g. a covariance matrix that is not positive definite there) must stay
-        // "worse than anything seen" without poisoning the interpolation models with infinities: it gets the largest
-        // finite value seen so far plus ten times the spread of the finite values
-        for (double v : *F) if (std::isfinite(v)) { fin_lo_ = std::min(fin_lo_, v); fin_hi_ = std::max(fin_hi_, v); }
-        for (double& v : *F)
-            if (!std::isfinite(v)) {
-                v = (fin_hi_ >= fin_lo_) ? fin_hi_ + 10.0 * std::max(1.0, fin_hi_ - fin_lo_) : 1e30;
-            }
+        // the finite values of the whole round count before any of its points without a value is given one (no_value)
+        for (double v : *F) note_finite(v);
+        for (double& v : *F) if (!std::isfinite(v)) v = no_value();
         return true;
     }
 

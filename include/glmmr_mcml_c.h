@@ -469,6 +469,9 @@ int glmmr_mcml_dbg_bobyqa(glmmr_mcml_objective f, void* user, int n, const doubl
                           double* f_out, int* nfev_out);
 /* the batch schedule of the same optimiser (csrc/optim.h bobyqa_batch): `width` points per round; rounds_out = the
  * sequential depth.  The callback is still called once per point. */
+int glmmr_mcml_dbg_bobyqa_npt(glmmr_mcml_objective f, void* user, int n, const double* x0, const double* lower,
+                              const double* upper, double rhobeg, double rhoend, int maxfun, int npt, double* x_out,
+                              double* f_out, int* nfev_out);
 int glmmr_mcml_dbg_bobyqa_batch(glmmr_mcml_objective f, void* user, int n, const double* x0, const double* lower,
                                 const double* upper, double rhobeg, double rhoend, int maxfun, int width,
                                 double* x_out, double* f_out, int* nfev_out, int* rounds_out);

@@ -67,8 +67,9 @@ class Model:
         return f
 
 
-def mcml_optim(mod, u, start, mcnr=False, niter=None):
-    """src/mcml_optim.cpp:35-68"""
+def mcml_optim(mod, u, start, mcnr=False, niter=None, var_par=1.0):
+    """src/mcml_optim.cpp:35-68; var_par: what the model holds when mcnr runs (1 in the export, :51; the loop of
+    mcml_full.cpp carries the last iteration's)"""
     start = np.asarray(start, float)
     niter = u.shape[1] if niter is None else niter
     beta = start[:mod.P].copy(); theta = start[mod.P:mod.P + mod.R].copy()
@@ -81,17 +82,18 @@ def mcml_optim(mod, u, start, mcnr=False, niter=None):
         if _is_gaussian(mod.fl):
             sigma = x[mod.P]
     else:
-        r = orc.mcnr(mod.X, mod.Z, mod.y, u, beta, 1.0, mod.family, mod.link, ncols=niter)
+        r = orc.mcnr(mod.X, mod.Z, mod.y, u, beta, var_par, mod.family, mod.link, ncols=niter)
         beta, sigma = r["beta"], r["sigma"]
     theta, _ = _minimise(mod.D_obj(u), theta, np.full(mod.R, 1e-6))
     return dict(beta=beta, theta=theta, sigma=sigma)
 
 
-def mcml_simlik(mod, u, start):
-    """src/mcml_optim.cpp:90-117 with the importance ratio evaluated in logs (defect D4)"""
+def mcml_simlik(mod, u, start, niter=None):
+    """src/mcml_optim.cpp:90-117 with the importance ratio evaluated in logs (defect D4); niter: the columns the
+    log-likelihood term reads (all of them unless given -- the MVN term always reads all, defect D5)"""
     start = np.asarray(start, float)
     sigma = start[mod.P + mod.R] if _is_gaussian(mod.fl) else 0.0
-    f = mod.F_obj(u, u.shape[1], sigma)
+    f = mod.F_obj(u, u.shape[1] if niter is None else niter, sigma)
     x0 = start[:mod.P + mod.R]
     lo = np.r_[np.full(mod.P, -np.inf), np.full(mod.R, 1e-6)]
     x, _ = _minimise(f, x0, lo)

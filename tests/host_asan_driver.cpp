@@ -30,6 +30,18 @@ int main() {
         rc = bobyqa(quad, x2, lo3, up3, o, &r);
         printf("  from-bound rc=%d f=%.3e nfev=%d\n", rc, r.fval, r.nfev);
         if (rc || r.fval > 1e-8) ++fails;
+        // points without a value (+inf in the initial design and beyond, NaN further out): sequential and batch schedule
+        objective_fn cut = [n](const std::vector<double>& x, double* v) {
+            double s = 0; for (int i = 0; i < n; ++i) s += (x[i] - 0.3 * (i + 1)) * (x[i] - 0.3 * (i + 1));
+            *v = x[0] > 0.95 ? HUGE_VAL : x[0] > 0.85 ? NAN : s; return 0; };
+        std::vector<double> x3(n, 0.75);         // the design's step along x[0] lands at 0.9
+        rc = bobyqa(cut, x3, lo3, up3, o, &r);
+        printf("  no-value rc=%d f=%.3e nfev=%d\n", rc, r.fval, r.nfev);
+        if (rc || r.fval > 1e-8) ++fails;
+        batch_objective_fn cutb = [&](const std::vector<std::vector<double>>& X, std::vector<double>* F) {
+            F->resize(X.size()); for (size_t i = 0; i < X.size(); ++i) cut(X[i], &(*F)[i]); return 0; };
+        rc = bobyqa_batch(cutb, x3, lo3, up3, o, 4, &r);
+        if (rc || r.fval > 1e-8) ++fails;
         std::vector<double> H, nd(n, 1e-4), none;
         rc = fd_hessian(quad, std::vector<double>(n, 0.5), nd, false, none, none, &H);
         if (rc || fabs(H[0] - 2.0) > 1e-5) ++fails;

@@ -231,3 +231,71 @@ def test_batch_schedule_survives_points_without_a_value():
         z, fb, nf, rounds, _ = _bobyqa_batch(g, np.log([0.25, 0.1]), width, lower=[np.log(1e-6)] * 2, upper=[np.inf] * 2,
                                              rhobeg=0.25, rhoend=1e-7)
         assert abs(fb - ref[1]) < 1e-9 * abs(ref[1]) and np.abs(np.exp(z) - ref[0]).max() < 2e-6, (width, np.exp(z), ref[0])
+
+
+# ---------------------------------------------------------------- points without a value on the sequential schedule
+# eval_mvn (csrc/drivers.hip) answers +inf where D(theta) is not positive definite.  The sequential optimiser used to keep
+# that infinity: every model through it was NaN, the run stopped after about 20 evaluations at whatever point it held and
+# reported success.  The rule of the batch schedule (worse than anything seen, but finite) now holds on both.
+def _ar1_objective(ncl=10, nt=6, m=40, tau=0.25, rho=0.8, seed=5):
+    """-(1/m) sum_j log N(u_j; 0, D), D = ncl blocks tau^2 rho^|s - t| (gr x ar1, the stepped-wedge covariance), +inf for
+    rho >= 1 where D is not positive definite; samples drawn at (tau, rho)"""
+    import scipy.linalg as sla
+    dt = np.abs(np.arange(nt)[:, None] - np.arange(nt)[None, :]).astype(float)
+    rng = np.random.default_rng(seed)
+    U = np.linalg.cholesky(tau ** 2 * rho ** dt) @ rng.standard_normal((nt, ncl * m))
+
+    def f(th):
+        if not th[1] < 1.0:
+            return np.inf
+        Lc = np.linalg.cholesky(th[0] ** 2 * th[1] ** dt)
+        z = sla.solve_triangular(Lc, U, lower=True)
+        return -(-0.5 * ncl * nt * np.log(2 * np.pi) - ncl * np.log(np.diag(Lc)).sum() - 0.5 * (z * z).sum() / m)
+    return f
+
+
+def _runs_without_a_value(g, x0, **kw):
+    """the sequential run and the batch entry at width 1, which delegates to it"""
+    a = _bobyqa(g, x0, **kw)
+    b = _bobyqa_batch(g, x0, 1, **kw)
+    assert np.array_equal(a[0], b[0]) and a[1] == b[1] and a[2] == b[2] == b[3]
+    return a
+
+
+def test_sequential_schedule_survives_a_design_point_without_a_value():
+    """the cut of test_batch_schedule_survives_points_without_a_value: the first step along theta_2 of the initial design
+    has no value"""
+    f = _mvn_objective()
+
+    def g(z):
+        th = np.exp(z)
+        return np.inf if th[1] > 0.12 else f(th)
+    ref = _bobyqa(f, [0.25, 0.1], lower=[1e-6] * 2, upper=[np.inf] * 2)
+    assert ref[0][1] < 0.12
+    z, fs, nf, calls = _runs_without_a_value(g, np.log([0.25, 0.1]), lower=[np.log(1e-6)] * 2, upper=[np.inf] * 2,
+                                             rhobeg=0.25, rhoend=1e-7)
+    assert not np.isfinite(g(calls[2])) and sum(not np.isfinite(g(c)) for c in calls) >= 1
+    print("nf %d, objective gap %.2e, parameter gap %.2e" % (nf, abs(fs - ref[1]) / abs(ref[1]), np.abs(np.exp(z) - ref[0]).max()))
+    assert abs(fs - ref[1]) < 1e-9 * abs(ref[1]) and np.abs(np.exp(z) - ref[0]).max() < 2e-6, (np.exp(z), ref[0])
+    assert nf >= 40, nf                    # the early stop came after 19 to 22 evaluations, inside the first level of rho
+
+
+@pytest.mark.parametrize("rho,start", [(0.80, (0.3, 0.9)), (0.95, (0.3, 0.8)), (0.60, (0.3, 0.9))])
+def test_sequential_schedule_survives_rho_above_one(rho, start):
+    """the theta-step of a gr x ar1 model as d_optim runs it (over theta, default radius): from these starts a point with
+    rho > 1 is evaluated -- in the initial design, or (0.95) by a later trust-region step"""
+    f = _ar1_objective(rho=rho)
+    ref = optimize.minimize(f, [0.25, rho], method="Nelder-Mead", options=dict(xatol=1e-11, fatol=1e-14, maxfev=4000))
+    assert ref.success and 0.1 < ref.x[1] < 0.99
+    x, fs, nf, calls = _runs_without_a_value(f, start, lower=[1e-6] * 2, upper=[np.inf] * 2)
+    assert sum(not np.isfinite(f(c)) for c in calls) >= 1
+    print("nf %d, objective gap %.2e, parameter gap %.2e" % (nf, (fs - ref.fun) / abs(ref.fun), np.abs(x - ref.x).max()))
+    assert fs <= ref.fun + 1e-9 * abs(ref.fun) and np.abs(x - ref.x).max() < 2e-6, (x, ref.x)
+    assert nf >= 40, nf
+
+
+def test_nothing_finite_seen_yet():
+    """the start itself has no value: it stands at 1e30 until a finite value is seen, and the run moves off it"""
+    g = lambda x: np.inf if x[0] > 1.9 else (x[0] - 1) ** 2 + x[1] ** 2
+    x, f, nf, _ = _runs_without_a_value(g, [2.0, 1.0])
+    assert np.abs(x - [1, 0]).max() < 1e-5 and f < 1e-10
