@@ -76,12 +76,12 @@ def get_default_trajectory():
     return {v: k for k, v in _TRAJ.items()}[_lib.lib().glmmr_mcml_get_default_trajectory()]
 
 
-_DRAWS = {"hmc": 0, "exact": 1}
+_DRAWS = {"hmc": 0, "exact": 1, "exact_component": 2}
 _DRAWS_NAME = {v: k for k, v in _DRAWS.items()}
 
 
 def set_default_draws(mode):
-    """what hmc_sample draws on new contexts ("hmc" or "exact"), the contexts the one-shot exports create included
+    """what hmc_sample draws on new contexts ("hmc", "exact" or "exact_component"), the contexts the one-shot exports create included
     (include/glmmr_mcml_c.h glmmr_mcml_set_default_draws)"""
     _lib.check(_lib.lib().glmmr_mcml_set_default_draws(_DRAWS[mode]))
 
@@ -432,7 +432,8 @@ class Context:
 
     def last_kernels(self):
         """kernel family of the sampler's last (forward, backward) product"""
-        names = {-1: None, 0: "skinny", 1: "band", 2: "dlds", 3: "reg", 4: "sparse", 5: "component", 6: "exact"}
+        names = {-1: None, 0: "skinny", 1: "band", 2: "dlds", 3: "reg", 4: "sparse", 5: "component", 6: "exact",
+                 7: "exact_component"}
         f = C.c_int(); b = C.c_int()
         _lib.check(_lib.lib().glmmr_mcml_ctx_last_kernels(self._h, C.byref(f), C.byref(b)))
         return names[f.value], names[b.value]
@@ -479,7 +480,8 @@ class Context:
     def set_draws(self, mode):
         """what hmc_sample draws: "hmc" (trajectories) or "exact" (csrc/hmc_exact.h: the conditional distribution of the
         whitened effects directly, where it is Gaussian -- gaussian / identity on the dense ZL operator; elsewhere the
-        request changes nothing)"""
+        request changes nothing) or "exact_component" ("exact", and on the sparse operator of a block-structured design the
+        same draw one connected component at a time, csrc/hmc_exact_comp.h, where no component has more than 128 variables)"""
         _lib.check(_lib.lib().glmmr_mcml_ctx_set_draws(self._h, _DRAWS[mode]))
 
     def draws_plan(self):
@@ -489,9 +491,11 @@ class Context:
         _lib.check(_lib.lib().glmmr_mcml_dbg_draws_plan(self._h, out))
         return dict(requested=_DRAWS_NAME[int(out[0])], applicable=bool(out[1]), Q=int(out[2]), m_bytes=int(out[3]))
 
-    def exact_sample(self, beta, var_par, nsamp, seed, chains=1, chain_offset=0, iter_idx=0, inj_z=None):
+    def exact_sample(self, beta, var_par, nsamp, seed, chains=1, chain_offset=0, iter_idx=0, inj_z=None, operator="dense"):
         """exact conditional draws whatever set_draws says (McmlError where the path does not apply); the samples have
-        hmc_sample's shape.  inj_z (Q x columns) replaces the generated standard normals"""
+        hmc_sample's shape.  inj_z (Q x columns) replaces the generated standard normals.  operator: "dense"
+        (csrc/hmc_exact.h) or "component" (csrc/hmc_exact_comp.h, on the sparse operator)"""
+        entry = {"dense": "glmmr_mcml_ctx_exact_sample", "component": "glmmr_mcml_ctx_exact_component_sample"}[operator]
         beta = _f(beta).ravel()
         o = HmcOpts(0, nsamp, 0, 1.0, 1, 0.9, chains, chain_offset)
         d = HmcDiag()
@@ -500,12 +504,29 @@ class Context:
         if iz is not None and iz.shape != (self.Q, want):
             raise ValueError("inj_z must be Q x %d" % want)
         ncols = C.c_int()
-        _lib.check(_lib.lib().glmmr_mcml_ctx_exact_sample(
+        _lib.check(getattr(_lib.lib(), entry)(
             self._h, _p(beta), C.c_double(var_par), C.byref(o), C.c_uint64(seed), C.c_uint32(iter_idx), _p(iz),
             C.byref(d), C.byref(ncols)))
         self.mcols = ncols.value
         return dict(accept_rate=d.accept_rate, mean_e=d.mean_e, min_e=d.min_e, max_e=d.max_e,
                     max_steps_used=d.max_steps_used, leapfrog_total=d.leapfrog_total)
+
+    def exact_component_plan(self):
+        """the component-wise exact path as the next hmc_sample would (not) take it, valid after update_L (test hook,
+        include/glmmr_mcml_c.h glmmr_mcml_dbg_exact_component_plan)"""
+        out = (C.c_longlong * 8)()
+        _lib.check(_lib.lib().glmmr_mcml_dbg_exact_component_plan(self._h, out))
+        keys = ("requested", "applicable", "ncomp", "max_vars", "max_rows", "factor_waves", "draw_lds_bytes", "factor_bytes")
+        d = dict(zip(keys, (int(v) for v in out)))
+        d["requested"] = _DRAWS_NAME[d["requested"]]
+        d["applicable"] = bool(d["applicable"])
+        return d
+
+    def exact_component_phases(self, enable=True):
+        """HIP-event ms of the phases of the last component-wise exact call recorded; enable: record the following calls"""
+        out = np.zeros(4)
+        _lib.check(_lib.lib().glmmr_mcml_dbg_exact_component_phases(self._h, int(enable), _p(out)))
+        return dict(zip(("factor_mean", "draw", "transpose", "lv"), (float(v) for v in out)))
 
     def exact_phases(self, enable=True):
         """HIP-event ms of the phases of the last exact call recorded; enable: record the following calls"""

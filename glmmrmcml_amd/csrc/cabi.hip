@@ -19,6 +19,10 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
 bool hmc_exact_applicable(const Ctx& c);
 int hmc_exact_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed, uint32_t iter_idx,
                      const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out);
+bool hmc_exact_component_applicable(const Ctx& c);
+int hmc_exact_component_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed,
+                               uint32_t iter_idx, const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out);
+void hmc_exact_component_sizes(const Ctx& c, long long* out3);
 }
 
 // process-wide default of Ctx::traj_mode: -1 until first asked, then GLMMR_MCML_TRAJ=component|step (read once) or 0
@@ -35,7 +39,7 @@ static int default_trajectory()
     return v;
 }
 
-// the same for Ctx::draws_mode: GLMMR_MCML_DRAWS=exact|hmc (read once) or 0
+// the same for Ctx::draws_mode: GLMMR_MCML_DRAWS=exact|exact_component|hmc (read once) or 0
 static std::atomic<int> g_default_draws{-1};
 static int default_draws()
 {
@@ -43,7 +47,7 @@ static int default_draws()
     if (v < 0) {
         const char* e = getenv("GLMMR_MCML_DRAWS");
         int unset = -1;
-        g_default_draws.compare_exchange_strong(unset, (e && !strcmp(e, "exact")) ? 1 : 0);
+        g_default_draws.compare_exchange_strong(unset, (e && !strcmp(e, "exact")) ? 1 : (e && !strcmp(e, "exact_component")) ? 2 : 0);
         v = g_default_draws.load();
     }
     return v;
@@ -309,7 +313,7 @@ extern "C" int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* h, int chains, long
 
 extern "C" int glmmr_mcml_set_default_draws(int mode)
 {
-    MCML_REQUIRE(mode == 0 || mode == 1, "set_default_draws: mode must be 0 (hmc) or 1 (exact)");
+    MCML_REQUIRE(mode >= 0 && mode <= 2, "set_default_draws: mode must be 0 (hmc), 1 (exact) or 2 (exact_component)");
     g_default_draws.store(mode);
     return MCML_OK;
 }
@@ -318,7 +322,7 @@ extern "C" int glmmr_mcml_get_default_draws(void) { return default_draws(); }
 
 extern "C" int glmmr_mcml_ctx_set_draws(glmmr_mcml_ctx* h, int mode)
 {
-    MCML_REQUIRE(h && (mode == 0 || mode == 1), "set_draws: mode must be 0 (hmc) or 1 (exact)");
+    MCML_REQUIRE(h && mode >= 0 && mode <= 2, "set_draws: mode must be 0 (hmc), 1 (exact) or 2 (exact_component)");
     h->c.draws_mode = mode;
     return MCML_OK;
 }
@@ -341,6 +345,37 @@ extern "C" int glmmr_mcml_ctx_exact_sample(glmmr_mcml_ctx* h, const double* beta
     MCML_REQUIRE(h && beta && opts, "exact_sample: null argument");
     MCML_HIP(hipSetDevice(h->c.device));
     return hmc_exact_sample(h->c, beta, var_par, opts, seed, iter_idx, inj_z, diag, ncols_out);
+}
+
+extern "C" int glmmr_mcml_ctx_exact_component_sample(glmmr_mcml_ctx* h, const double* beta, double var_par,
+                                                     const glmmr_mcml_hmc_opts* opts, uint64_t seed, uint32_t iter_idx,
+                                                     const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out)
+{
+    MCML_REQUIRE(h && beta && opts, "exact_component_sample: null argument");
+    MCML_HIP(hipSetDevice(h->c.device));
+    return hmc_exact_component_sample(h->c, beta, var_par, opts, seed, iter_idx, inj_z, diag, ncols_out);
+}
+
+// read-only: the component path as the next hmc_sample call would (not) take it
+extern "C" int glmmr_mcml_dbg_exact_component_plan(glmmr_mcml_ctx* h, long long* out8)
+{
+    MCML_REQUIRE(h && out8, "dbg_exact_component_plan: null argument");
+    const Ctx& c = h->c;
+    for (int i = 0; i < 8; ++i) out8[i] = 0;
+    out8[0] = c.draws_mode;
+    if (!hmc_exact_component_applicable(c)) return MCML_OK;
+    const ComponentPlan& p = c.cp.plan;
+    out8[1] = 1; out8[2] = p.ncomp; out8[3] = p.max_vars; out8[4] = p.max_rows;
+    hmc_exact_component_sizes(c, out8 + 5);
+    return MCML_OK;
+}
+
+extern "C" int glmmr_mcml_dbg_exact_component_phases(glmmr_mcml_ctx* h, int enable, double* out4)
+{
+    MCML_REQUIRE(h, "dbg_exact_component_phases: null context");
+    if (out4) for (int i = 0; i < 4; ++i) out4[i] = h->c.exact_comp.ms[i];
+    h->c.exact_comp.prof = enable != 0;
+    return MCML_OK;
 }
 
 extern "C" int glmmr_mcml_dbg_exact_phases(glmmr_mcml_ctx* h, int enable, double* out5)

@@ -20,7 +20,8 @@ typedef int (*reduce_fn)(void* user, double* dev_buf, int n);
 
 // kernel family that served an HMC product (glmmr_mcml_ctx_last_kernels)
 enum { KERNEL_SKINNY = 0, KERNEL_BAND = 1, KERNEL_DLDS = 2, KERNEL_REG = 3, KERNEL_SPARSE = 4, KERNEL_COMPONENT = 5,
-       KERNEL_EXACT = 6 };   // 6: no product pair at all, the exact conditional draw (hmc_exact.h)
+       KERNEL_EXACT = 6,     // 6: no product pair at all, the exact conditional draw (hmc_exact.h)
+       KERNEL_EXACT_COMPONENT = 7 };   // 7: the same, component by component on the sparse operator (hmc_exact_comp.h)
 
 // the sampler's step-count read-back (hmc.hip hmc_sample): a ring of host memory mapped into the device, written by
 // k_max_steps with (proposal sequence number << 32 | count), read by the host with plain loads (StepAhead, step_ahead.h);
@@ -207,6 +208,17 @@ struct ExactState {
     double ms[5] = {0, 0, 0, 0, 0};   // M build | factorisation | right-hand side + fill | transposed solve | L V, of the last call
 };
 
+// component-wise exact draws (hmc_exact_comp.h): the factors of every M_c (sum_c nv_c^2 doubles, at most Q * 128) and where
+// each starts, W = 1 / sigma^2 for every observation, b -> mu*, the factor kernel's log-determinants (not read), the draws
+// chain-major and transposed; kept between calls
+struct ExactCompState {
+    DevBuf fac, fac_ptr, W, b, mu, logdet, CM;
+    DevMat T;
+    long long fac_doubles = 0;          // 0: fac_ptr not uploaded yet
+    bool prof = false;
+    double ms[5] = {0, 0, 0, 0, 0};     // factor + mean | draw kernel | transpose | L V | 0, of the last call
+};
+
 struct Ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -220,8 +232,10 @@ struct Ctx {
     SparseZL sp;
     ComponentDev cp;
     int traj_mode = 0;          // 0: a launch per leapfrog step; 1: component-local trajectories where feasible (hmc_traj.h)
-    int draws_mode = 0;         // hmc_sample: 0 HMC trajectories; 1 exact conditional draws where the target is Gaussian (hmc_exact.h)
+    int draws_mode = 0;         // hmc_sample: 0 HMC trajectories; 1 exact conditional draws where the target is Gaussian (hmc_exact.h);
+                                // 2 the same, and component by component where the sparse operator runs (hmc_exact_comp.h)
     ExactState exact;
+    ExactCompState exact_comp;
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT
     int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (la_comp.h); 2 the same up
                                 // to CP_WIDE_MAX_VARS variables per component, a wave or a workgroup each
@@ -353,6 +367,11 @@ int trsm_left_lower_trans(Ctx& c, const double* R, int ldr, int n, double* T, in
 // M (Q x Q) = ZL' diag(W) ZL + I from the current c.ZL / c.ZLT.  W null: W = w0 for every observation, ZLT is multiplied as it
 // is (ZLTW is not touched).  lower_only: the tiles strictly above the diagonal are left zero
 int build_M_dense(Ctx& c, const double* W, double w0, DevMat& M, DevMat& ZLTW, bool lower_only);
+// every M_c = I + ZL_c' diag(W) ZL_c of the component records built and factorised in one launch (la_comp.h): waves = 1 a wave,
+// 4 a workgroup per component.  logdet: ncomp.  g / x nullable: x = M^-1 g (Q).  fac / fac_ptr nullable: the factors' lower
+// triangles, component c column-major (leading dimension nv_c) at fac + fac_ptr[c].  A failed pivot raises c.errflag()
+int lac_factor_launch(Ctx& c, const double* W, const double* g, double* x, double* logdet, double* fac, const int* fac_ptr, int waves);
+int lac_waves_now(const ComponentPlan& p);                   // the form "component_wide" takes now (honours GLMMR_MCML_LA_WAVES)
 
 // ---- model.hip ----
 int model_setup(Ctx& c, const double* Z, const double* X, const double* y);

@@ -726,6 +726,7 @@ static int samples_to_U(Ctx& c, const DevMat& samp, int ncols)
 }  // namespace mcml
 
 #include "hmc_exact.h"      // exact conditional draws (gaussian / identity): ends in samples_to_U like the samplers here
+#include "hmc_exact_comp.h" // the same, component by component on the sparse operator
 
 namespace mcml {
 
@@ -735,6 +736,21 @@ int hmc_exact_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcm
                      const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out)
 {
     return exact_gaussian_sample(c, beta, var_par, o, seed, iter_idx, inj_z, nullptr, nullptr, diag, ncols_out);
+}
+
+bool hmc_exact_component_applicable(const Ctx& c) { return exact_component_applicable(c); }
+int hmc_exact_component_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed,
+                               uint32_t iter_idx, const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out)
+{
+    return exact_component_sample(c, beta, var_par, o, seed, iter_idx, inj_z, nullptr, nullptr, diag, ncols_out);
+}
+// glmmr_mcml_dbg_exact_component_plan: waves of the factor kernel, LDS bytes of the draw kernel, bytes of the factor scratch
+void hmc_exact_component_sizes(const Ctx& c, long long* out3)
+{
+    const ComponentPlan& p = c.cp.plan;
+    long long fac = 0;
+    for (int k = 0; k < p.ncomp; ++k) { const long long nv = p.var_ptr[k + 1] - p.var_ptr[k]; fac += nv * nv; }
+    out3[0] = lac_waves_now(p); out3[1] = exc_lds_bytes(p.max_vars); out3[2] = 8 * fac;
 }
 
 // ---- hmc_sample in parts ----
@@ -931,8 +947,10 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
     MCML_REQUIRE(beta, "hmc: beta is null");
     // exact conditional draws: asked for (Ctx::draws_mode) and the target is the Gaussian hmc_exact.h draws from; anywhere else the
     // request changes nothing
-    if (c.draws_mode == 1 && exact_applicable(c))
+    if ((c.draws_mode == 1 || c.draws_mode == 2) && exact_applicable(c))
         return exact_gaussian_sample(c, beta, var_par, o, seed, iter_idx, nullptr, flags_out, probs_out, diag, ncols_out);
+    if (c.draws_mode == 2 && exact_component_applicable(c))      // the same target where M is block diagonal (hmc_exact_comp.h)
+        return exact_component_sample(c, beta, var_par, o, seed, iter_idx, nullptr, flags_out, probs_out, diag, ncols_out);
     const int C = o->chains > 0 ? o->chains : 1;
     const int d = (C == 1) ? o->nsamp : (o->nsamp + C - 1) / C;   // draws per chain
     const int total = o->warmup + d;

@@ -30,6 +30,8 @@ struct LacArgs {
     double* x;
     double* logdet;                                  // ncomp: 2 sum log diag chol(M_c)
     int* errflag;                                    // raised on a non-positive pivot (Ctx::errflag)
+    double* fac = nullptr;                           // nullable: the lower triangle of chol(M_c), diagonal included, is stored
+    const int* fac_ptr = nullptr;                    // column-major (leading dimension nv) at fac + fac_ptr[comp] (hmc_exact_comp.h)
 };
 
 // the lanes of ONE wave exchange data through LDS: LDS operations of a wave complete in issue order, so only the
@@ -107,6 +109,14 @@ __global__ __launch_bounds__(64 * LAC_WAVES) void k_lac_factor(LacArgs a)
     if (lane == 0) {
         a.logdet[comp] = 2 * lg;                     // moremaths.h:105-116
         if (bad) *a.errflag = 1;
+    }
+    if (a.fac && !bad) {                             // a copy: nothing below reads it
+        double* F = a.fac + a.fac_ptr[comp];
+        for (int i = i0, j = j0; j < nv;) {
+            if (i >= j) F[i + j * nv] = M[i + j * LAC_LD];
+            i += r64; j += q64;
+            if (i >= nv) { i -= nv; ++j; }
+        }
     }
     if (!a.g || bad) return;
     // ---- x = L'^-1 L^-1 g: column sweeps forward, row sweeps backward (stride LAC_LD: conflict-free)
@@ -260,6 +270,14 @@ __global__ __launch_bounds__(LACW_THREADS) void k_lac_factor_wg(LacArgs a, int m
     if (tid == 0) {
         a.logdet[comp] = 2 * (((red[0] + red[1]) + red[2]) + red[3]);       // moremaths.h:105-116
         if (bad) *a.errflag = 1;
+    }
+    if (a.fac && !bad) {                             // a copy: nothing below reads it
+        double* F = a.fac + a.fac_ptr[comp];
+        for (int i = i0, j = j0; j < nv;) {
+            if (i >= j) F[i + j * nv] = M[i + j * ld];
+            i += r256; j += q256;
+            if (i >= nv) { i -= nv; ++j; }
+        }
     }
     if (!a.g || bad) return;
     // ---- x = L'^-1 L^-1 g.  Thread i keeps entry i in a register and publishes it once it is final: one barrier per column

@@ -36,6 +36,25 @@ namespace mcml {
 static std::atomic<long long> g_lac_launches{0};
 long long la_component_launch_count() { return g_lac_launches.load(); }
 
+// one launch of k_lac_factor (waves = 1) or k_lac_factor_wg (4) over the resident component records: the Laplace fits below
+// and the component-wise exact draws (hmc_exact_comp.h, which passes fac / fac_ptr)
+int lac_factor_launch(Ctx& c, const double* W, const double* g, double* x, double* logdet, double* fac, const int* fac_ptr, int waves)
+{
+    const ComponentDev& cp = c.cp;
+    LacArgs a{cp.var_ptr.as<int>(), cp.vars.as<int>(), cp.slot_ptr.as<int>(), cp.slot_i.as<int>(), cp.slot_d.d(), W,
+              cp.plan.ncomp, g, x, logdet, c.errflag(), fac, fac_ptr};
+    if (waves == 4) {
+        MCML_TRY(ensure_dynamic_lds((const void*)k_lac_factor_wg, lacw_lds_bytes(CP_WIDE_MAX_VARS)));
+        hipLaunchKernelGGL(k_lac_factor_wg, dim3(cp.plan.ncomp), dim3(LACW_THREADS), lacw_lds_bytes(cp.plan.max_vars), c.stream, a,
+                           cp.plan.max_vars);
+    } else {
+        hipLaunchKernelGGL(k_lac_factor, dim3((cp.plan.ncomp + LAC_WAVES - 1) / LAC_WAVES), dim3(64 * LAC_WAVES), 0, c.stream, a);
+    }
+    MCML_HIP(hipGetLastError());
+    return MCML_OK;
+}
+int lac_waves_now(const ComponentPlan& p) { return lac_waves(p, lac_forced_waves()); }
+
 static bool la_is_gaussian(int flink) { return flink == 7 || flink == 8; }
 static bool la_has_var_par(int flink) { return flink == 7 || flink == 8 || flink == 12; }
 
@@ -379,17 +398,7 @@ struct LaFit {
     // every M_c built and factorised from the current record values and W (la_comp.h); with g, x = M^-1 g as well
     int lac_factor(const double* g, double* x)
     {
-        const ComponentDev& cp = c.cp;
-        LacArgs a{cp.var_ptr.as<int>(), cp.vars.as<int>(), cp.slot_ptr.as<int>(), cp.slot_i.as<int>(), cp.slot_d.d(), W.d(),
-                  cp.plan.ncomp, g, x, lac_ld.d(), c.errflag()};
-        if (waves == 4) {
-            MCML_TRY(ensure_dynamic_lds((const void*)k_lac_factor_wg, lacw_lds_bytes(CP_WIDE_MAX_VARS)));
-            hipLaunchKernelGGL(k_lac_factor_wg, dim3(cp.plan.ncomp), dim3(LACW_THREADS), lacw_lds_bytes(cp.plan.max_vars), c.stream, a,
-                               cp.plan.max_vars);
-        } else {
-            hipLaunchKernelGGL(k_lac_factor, dim3((cp.plan.ncomp + LAC_WAVES - 1) / LAC_WAVES), dim3(64 * LAC_WAVES), 0, c.stream, a);
-        }
-        MCML_HIP(hipGetLastError());
+        MCML_TRY(lac_factor_launch(c, W.d(), g, x, lac_ld.d(), nullptr, nullptr, waves));
         ++c.la_launches; ++g_lac_launches;
         return MCML_OK;
     }

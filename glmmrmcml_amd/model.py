@@ -241,10 +241,11 @@ class ModelMCML:
     # ---- MCML ----------------------------------------------------------------------------------------------------
     def MCML(self, y, *args, trajectory=None, draws=None, **kwargs):
         """_mcml below (its arguments, unchanged); trajectory ("step" / "component", None = leave the backend's default
-        alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  draws ("hmc" / "exact",
-        None = leave the default alone): what the HMC sampler's call returns -- "exact" draws the conditional distribution of
-        the random effects directly where it is Gaussian (gaussian / identity on the dense operator, csrc/hmc_exact.h) and
-        changes nothing elsewhere; `sampler` below picks the route, not this.  Either becomes the backend's process-wide
+        alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  draws ("hmc" / "exact" /
+        "exact_component", None = leave the default alone): what the HMC sampler's call returns -- "exact" draws the conditional distribution of
+        the random effects directly where it is Gaussian (gaussian / identity on the dense operator, csrc/hmc_exact.h;
+        "exact_component" also on the sparse operator of a block-structured design, csrc/hmc_exact_comp.h) and changes
+        nothing elsewhere; `sampler` below picks the route, not this.  Either becomes the backend's process-wide
         default for the duration of the call -- the contexts the exports create inherit it -- and the previous default is
         restored; do not run two fits with different choices in one process at the same time."""
         prev_t = prev_d = None

@@ -227,7 +227,8 @@ int glmmr_mcml_ctx_profile_launches(glmmr_mcml_ctx* ctx, long long* fwd, long lo
 /* kernel family that served the sampler's last forward / backward product: 0 streamed few-column kernel
  * (dgemm_skinny.h), 1 banded FP64 MFMA kernel (dgemm_band.h), 2 dense direct-to-LDS MFMA kernel (dgemm_dlds.h),
  * 3 register-staged MFMA kernel (dgemm_mfma.h), 4 sparse chain-major operator (hmc_cm.h), 5 component-local trajectory
- * kernel (hmc_traj.h, both entries), 6 no product pair: exact conditional draws (hmc_exact.h, both entries); -1 none yet */
+ * kernel (hmc_traj.h, both entries), 6 no product pair: exact conditional draws (hmc_exact.h, both entries), 7 the same
+ * component by component on the sparse operator (hmc_exact_comp.h, both entries); -1 none yet */
 int glmmr_mcml_ctx_last_kernels(glmmr_mcml_ctx* ctx, int* fwd, int* bwd);
 /* The banded kernel's work decomposition (csrc/band_plan.h) for `chains` columns of the sampler's forward (which = 0) or
  * backward (which = 1) product, read-only: out10 = [banded kernel selected for this operand, bands of 80 rows, K tiles
@@ -263,7 +264,8 @@ int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* ctx, int chains, long long* ou
 /* k_cm_traj launches of this process so far, over all contexts: tells whether a context that a one-shot export created
  * internally took the component path. */
 long long glmmr_mcml_dbg_traj_launches(void);
-/* What glmmr_mcml_ctx_hmc_sample draws: 0 = HMC trajectories (the default), 1 = exact conditional draws (csrc/hmc_exact.h).
+/* What glmmr_mcml_ctx_hmc_sample draws: 0 = HMC trajectories (the default), 1 = exact conditional draws (csrc/hmc_exact.h),
+ * 2 = the same and, where the context runs the sparse ZL operator, component by component (csrc/hmc_exact_comp.h; below).
  * For gaussian / identity the density HMC targets in the whitened effects is v | y ~ N(mu*, M^-1) with
  * M = I + ZL' ZL / sigma^2 and M mu* = ZL' (y - X beta) / sigma^2; mode 1 draws from it directly -- one Q x Q product, one
  * Cholesky factorisation, one transposed triangular solve for all columns -- instead of simulating it.  The output has
@@ -272,10 +274,16 @@ long long glmmr_mcml_dbg_traj_launches(void);
  * The draws are independent and follow their own RNG addressing (csrc/rng.h tag 8): a different, exact estimator of the same
  * conditional distribution, not the HMC draws.  Honoured where the model is gaussian / identity AND the context runs the
  * dense ZL operator; for every other family / link (gaussian / log included), on the sparse operator and for the No-U-Turn
- * sampler the call changes nothing. */
+ * sampler the call changes nothing.
+ * Mode 2 is mode 1 on the dense operator.  On the sparse operator (block-structured designs) M is block diagonal over the
+ * connected components of ZL's coupling graph: every M_c is built and factorised in LDS by the Laplace fits' component
+ * kernels, and v_c = mu*_c + R_c^-T z_c is drawn for all columns by one kernel -- where no component has more than 128
+ * variables.  Same output shape, flags, probs, diag and RNG addressing as mode 1; the draw equals the dense formula up to
+ * rounding.  Elsewhere (other families, larger components, the No-U-Turn sampler) mode 2 changes nothing. */
 int glmmr_mcml_ctx_set_draws(glmmr_mcml_ctx* ctx, int mode);
-/* The mode new contexts start with, the ones the one-shot exports create included.  Initially GLMMR_MCML_DRAWS=exact|hmc from
- * the environment (read once), else 0.  One atomic per process, as the trajectory default. */
+/* The mode new contexts start with, the ones the one-shot exports create included.  Initially
+ * GLMMR_MCML_DRAWS=exact|exact_component|hmc from the environment (read once), else 0.  One atomic per process, as the
+ * trajectory default. */
 int glmmr_mcml_set_default_draws(int mode);
 int glmmr_mcml_get_default_draws(void);
 /* out4 = [mode requested, 1 if the exact path applies to the context as it is now (gaussian / identity, dense operator, L
@@ -287,6 +295,19 @@ int glmmr_mcml_dbg_draws_plan(glmmr_mcml_ctx* ctx, int* out4);
 int glmmr_mcml_ctx_exact_sample(glmmr_mcml_ctx* ctx, const double* beta, double var_par, const glmmr_mcml_hmc_opts* opts,
                                 uint64_t seed, uint32_t iter_idx, const double* inj_z, glmmr_mcml_hmc_diag* diag,
                                 int* ncols_out);
+/* The component-wise exact path whatever the mode, arguments as glmmr_mcml_ctx_exact_sample; MCML_EUNSUPPORTED (-2) where it
+ * does not apply (the samples are left alone). */
+int glmmr_mcml_ctx_exact_component_sample(glmmr_mcml_ctx* ctx, const double* beta, double var_par,
+                                          const glmmr_mcml_hmc_opts* opts, uint64_t seed, uint32_t iter_idx,
+                                          const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out);
+/* Read-only, valid after update_L: out8 = [mode requested, 1 if the component-wise exact path applies to the context as it
+ * is now (gaussian / identity, sparse operator active, L set, no component above 128 variables), components, most variables
+ * in one, most observations in one, waves per component of the factor kernel (1 or 4; honours GLMMR_MCML_LA_WAVES), LDS
+ * bytes per workgroup of the draw kernel, bytes of the factor scratch].  Entries 2-7 are 0 where it does not apply. */
+int glmmr_mcml_dbg_exact_component_plan(glmmr_mcml_ctx* ctx, long long* out8);
+/* HIP-event times of the phases of the component-wise exact path: enable != 0 records them on the following calls; out4
+ * (nullable) = ms of the last recorded call's [right-hand side + factors + mean, draw kernel, transpose, L V] */
+int glmmr_mcml_dbg_exact_component_phases(glmmr_mcml_ctx* ctx, int enable, double* out4);
 /* HIP-event times of the phases of the exact path: enable != 0 records them on the following calls; out5 (nullable) = ms of
  * the last recorded call's [M build, factorisation, right-hand side and fill, transposed solve, L V] */
 int glmmr_mcml_dbg_exact_phases(glmmr_mcml_ctx* ctx, int enable, double* out5);
