@@ -140,8 +140,26 @@ extern "C" int glmmr_mcml_dbg_dgemm_bench2(int M, int N, int K, int b_nmajor, in
 // C = A * B through the banded kernel (dgemm_band.h) exactly as the sampler uses it: A is copied into a
 // buffer whose columns are zero-padded to a multiple of 32, B's rows likewise, the K-tile ranges come from
 // k_band_ranges.  For tests/ only.
+static int dbg_dgemm_band(int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc,
+                          int* tiles_executed, int form, int* whole_band);
+
 extern "C" int glmmr_mcml_dbg_dgemm_band(int M, int N, int K, const double* A, int lda, const double* B, int ldb,
                                          double* C, int ldc, int* tiles_executed)
+{
+    return dbg_dgemm_band(M, N, K, A, lda, B, ldb, C, ldc, tiles_executed, BAND_FORM_AUTO, nullptr);
+}
+
+// The same through the form asked for -- 0: the 8-wave kernel, 1: the feeder form (dgemm_band.h), whatever production
+// would pick for the plan; whole_band (nullable) = 1 if the plan is the whole-band one, 0 if streamed.
+extern "C" int glmmr_mcml_dbg_dgemm_band_form(int M, int N, int K, const double* A, int lda, const double* B, int ldb,
+                                              double* C, int ldc, int* tiles_executed, int form, int* whole_band)
+{
+    MCML_REQUIRE(form == BAND_FORM_8WAVE || form == BAND_FORM_FEED, "dbg_dgemm_band_form: form is 0 or 1");
+    return dbg_dgemm_band(M, N, K, A, lda, B, ldb, C, ldc, tiles_executed, form, whole_band);
+}
+
+static int dbg_dgemm_band(int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc,
+                          int* tiles_executed, int form, int* whole_band)
 {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -171,7 +189,7 @@ extern "C" int glmmr_mcml_dbg_dgemm_band(int M, int N, int K, const double* A, i
     plan.reset(M, K, hk);
     if (tiles_executed) *tiles_executed = (int)plan.tiles;
     EpiAxpby epi{dC.d(), dC.ld, 1.0, 0.0};
-    MCML_TRY(launch_gemm_band(s, plan, N, dA.d(), dA.ld, dB.d(), dB.ld, epi));
+    MCML_TRY(launch_gemm_band(s, plan, N, dA.d(), dA.ld, dB.d(), dB.ld, epi, nullptr, 0, form, whole_band));
     MCML_TRY(download_matrix(C, ldc, dC.d(), dC.ld, M, N, s));
     return MCML_OK;
 }

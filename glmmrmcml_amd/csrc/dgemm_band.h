@@ -36,6 +36,10 @@
 // 5 x 1 v_mfma_f64_16x16x4 tiles), K step 32, 3-stage LDS ring (156 KB), counted vmcnt + raw
 // barriers.  The A image [k][80 doubles] has 640-byte rows = 32 banks mod 64, so the two
 // 16-lane halves of a ds_read_b64 (rows k, k+1) are conflict-free without a swizzle.
+//
+// Two forms of the kernel share all of that: dgemm_band_kernel, whose eight waves each load and multiply, and
+// dgemm_band_feed_kernel (further down; what the sampler runs where its instantiation needs no scratch), four MFMA
+// waves with an 80 x 32 strip each fed by four DMA waves.  Same bits from both.
 #pragma once
 #include "dgemm_dlds.h"
 #include "band_plan.h"
@@ -392,6 +396,252 @@ __global__ __launch_bounds__(512) void dgemm_band_kernel(BandP bp, Epi epi)
         }
 }
 
+// ---- the feeder form: four MFMA waves, four DMA waves -----------------------------------
+// In dgemm_band_kernel every wave issues its 7 LDS-DMA pieces back to back at the top of a K tile, and a wave inside
+// that block issues no MFMA (waves issue in order); the two waves of a SIMD are there together.  Here the roles are
+// split by wave number: waves 0-3 (one per SIMD) own an 80 x 32 strip each -- two of the 8-wave kernel's strips,
+// acc[2][5] -- and issue NO vector-memory instruction and no vmcnt wait inside a K loop; waves 4-7 (their SIMD
+// partners) issue the tile's 52 one-KiB pieces, 13 each, keep the counted vmcnt and meet the MFMA waves at the same
+// barriers.  Tile, ring, LDS images, item list and XCD map are dgemm_band_kernel's.  Every output element is still
+// accumulated by one wave, over K in the same order, by the same instruction with the same operand roles, and the
+// epilogue functor is called once per 16-column strip as before: the results are the 8-wave kernel's bit for bit.
+// The epilogue's stores drain under the next item's K loop (nothing there waits on vmcnt), and the feeders, which run
+// no epilogue, have the next item's first ring stages in flight while the MFMA waves are still in theirs.
+// Selected per epilogue type (BandFeed<Epi>::ok: instantiations that compile without scratch); GLMMR_MCML_BAND_FEED=0
+// keeps the 8-wave kernel everywhere.
+template <class Epi> struct BandFeed { static constexpr bool ok = false; };
+template <> struct BandFeed<EpiAxpby> { static constexpr bool ok = true; };
+
+constexpr int BF_NA = 5, BF_NB = 8, BF_PER_TILE = BF_NA + BF_NB;      // LDS-DMA pieces per feeder wave per tile
+static_assert(4 * BF_NA * 1024 == BD_A_BYTES && 4 * BF_NB * 1024 == BD_B_BYTES, "four feeders cover a stage");
+
+static inline bool band_feed_enabled()         // read per call: the parity tests run both forms in one process
+{
+    const char* e = getenv("GLMMR_MCML_BAND_FEED");
+    return !(e && !strcmp(e, "0"));
+}
+
+// operands of K substep KS of both 16-column sub-strips: the second strip's B is the first one's + 256 bytes
+template <int KS>
+__device__ __forceinline__ void bf_read(double (&a)[5], double (&b)[2], unsigned aaddr, unsigned baddr)
+{
+    BD_RD(a[0], aaddr, KS * 4 * BD_BM * 8);
+    BD_RD(a[1], aaddr, KS * 4 * BD_BM * 8 + 128);
+    BD_RD(a[2], aaddr, KS * 4 * BD_BM * 8 + 256);
+    BD_RD(a[3], aaddr, KS * 4 * BD_BM * 8 + 384);
+    BD_RD(a[4], aaddr, KS * 4 * BD_BM * 8 + 512);
+    BD_RD(b[0], baddr, KS * 2 * BD_BN * 16);
+    BD_RD(b[1], baddr, KS * 2 * BD_BN * 16 + 256);
+}
+template <int LEAVE>
+__device__ __forceinline__ void bf_wait(double (&a)[5], double (&b)[2])
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (LEAVE == 7)
+        asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]), "+v"(b[1]));
+    else
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]), "+v"(b[1]));
+#endif
+}
+__device__ __forceinline__ void bf_mfma(d4 (&acc)[2][5][1], const double (&a)[5], const double (&b)[2])
+{
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) acc[j][i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a[i], acc[j][i][0], 0, 0, 0);
+}
+// the scalar item load of dgemm_band_kernel (see there)
+__device__ __forceinline__ BandItem bf_item(const BandItem* ip)
+{
+    BandItem item{0, 0, 0, -1};
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef int i4s __attribute__((ext_vector_type(4)));
+    i4s raw;
+    asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(raw) : "s"(ip) : "memory");
+    item.band = raw.x; item.kt0 = raw.y; item.kt1 = raw.z; item.slot = raw.w;
+#else
+    item = *ip;
+#endif
+    return item;
+}
+
+template <class Epi>
+__global__ __launch_bounds__(512) void dgemm_band_feed_kernel(BandP bp, Epi epi)
+{
+    const GemmP& p = bp.g;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    char* lds = reinterpret_cast<char*>(smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)lds;
+
+    // the XCD-aware map of dgemm_band_kernel
+    const int nblk = bp.nwg * p.gn;
+    const int bid = blockIdx.x;
+    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
+    const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int pw = nid / p.gn, bj = nid - pw * p.gn;
+    const int n0 = bj * BD_BN;
+    const int it0 = bp.wg_ptr[pw], it1 = bp.wg_ptr[pw + 1];
+
+    // Both roles walk the same items and pass the same barriers: per item with K tiles one before the K loop and one
+    // per tile, and one behind an item whose successor's ring fill is not already in flight (`pre`).
+    if (wave >= 4) {
+        // ---- feeder: pieces f, f + 4, ... of the 20 A and the 32 B pieces of a stage
+        // (one static s_setprio 1 here measured no different: 839.4 / 844.9 against 842.9 / 842.9 ms per bench step)
+        const int f = wave - 4;
+        const size_t stepA = (size_t)BD_BK * p.lda * 8;      // bytes per K tile
+        unsigned vob[BF_NB];
+#pragma unroll
+        for (int s = 0; s < BF_NB; ++s) {
+            const int c = f + 4 * s;
+            const int kp = c >> 1, n = ((c & 1) << 6) + lane;
+            int gn = n0 + n;
+            if (gn >= p.N) gn = 0;
+            vob[s] = (unsigned)((2 * kp + (size_t)gn * p.ldb) * 8);
+        }
+        unsigned voa[BF_NA];
+        const char* sA = nullptr; const char* sB = nullptr;                 // uniform
+        BandItem item{0, 0, 0, -1};
+        auto load_item = [&](int it) {
+            item = bf_item(bp.items + it);
+            const int m0 = item.band * BD_BM;
+#pragma unroll
+            for (int s = 0; s < BF_NA; ++s) {
+                const int o = (f + 4 * s) * 1024 + lane * 16;
+                const int k = o / (BD_BM * 8), m = (o - k * BD_BM * 8) >> 3;
+                int gm = m0 + m;
+                if (gm >= p.M) gm = 0;
+                voa[s] = (unsigned)((gm + (size_t)k * p.lda) * 8);
+            }
+            sA = reinterpret_cast<const char*>(p.A) + (size_t)item.kt0 * stepA;
+            sB = reinterpret_cast<const char*>(p.B) + (size_t)item.kt0 * (BD_BK * 8);
+        };
+        auto issue = [&](int stage) {
+            const unsigned lbase = lds0 + stage * BD_STAGE_BYTES + f * 1024;
+#pragma unroll
+            for (int s = 0; s < BF_NA; ++s) lds_dma16(lbase + s * 4096, voa[s], sA);
+#pragma unroll
+            for (int s = 0; s < BF_NB; ++s) lds_dma16(lbase + BD_A_BYTES + s * 4096, vob[s], sB);
+            sA += stepA;
+            sB += BD_BK * 8;
+        };
+        auto wait_leave = [&](int tiles) {
+            static_assert(BF_PER_TILE == 13, "vmcnt immediates below");
+            if (tiles >= 2) asm volatile("s_waitcnt vmcnt(26)" ::: "memory");
+            else if (tiles == 1) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        };
+        bool pre = false;
+        int issued = 0;
+        if (it0 < it1) load_item(it0);
+        for (int it = it0; it < it1;) {
+            const int nk = item.kt1 - item.kt0;
+            if (nk > 0) {
+                if (!pre) { issued = 0; for (; issued < BD_STAGES - 1 && issued < nk; ++issued) issue(issued); }
+                wait_leave(issued - 1);
+                __builtin_amdgcn_s_barrier();
+                int st = 0;
+                for (int kt = 0; kt < nk; ++kt) {
+                    // the stage tile kt - 1 was read from: every MFMA wave finished its reads before that tile's barrier
+                    if (issued < nk) {
+                        int sn = st + BD_STAGES - 1; if (sn >= BD_STAGES) sn -= BD_STAGES;
+                        issue(sn);
+                        ++issued;
+                    }
+                    wait_leave(issued - kt - 2);            // this wave's pieces of tile kt + 1 have landed
+                    __builtin_amdgcn_s_barrier();
+                    ++st; if (st >= BD_STAGES) st = 0;
+                }
+            }
+            ++it;
+            pre = false;
+            if (it < it1) {
+                load_item(it);
+                const int nkn = item.kt1 - item.kt0;
+                // the ring is free once every wave has passed the last barrier of a K loop: the next item's first
+                // stages go out while the MFMA waves run their epilogue
+                if (nk > 0 && nkn > 0) {
+                    issued = 0;
+                    for (; issued < BD_STAGES - 1 && issued < nkn; ++issued) issue(issued);
+                    pre = true;
+                }
+            }
+            if (!pre) __builtin_amdgcn_s_barrier();
+        }
+        return;
+    }
+
+    // ---- MFMA wave: columns n0 + 32 wave .. + 31 as two 16-column sub-strips
+    const int l15 = lane & 15, lk = lane >> 4;
+    const unsigned aoff = lds0 + lk * (BD_BM * 8) + l15 * 8;
+    const unsigned boff = lds0 + BD_A_BYTES + (((lk >> 1) * BD_BN + wave * 32 + l15) << 4) + ((lk & 1) << 3);
+    BandItem item{0, 0, 0, -1};
+    if (it0 < it1) item = bf_item(bp.items + it0);
+    for (int it = it0; it < it1;) {
+        const int band = item.band, e_m0 = item.band * BD_BM, slot = item.slot;
+        const int nk = item.kt1 - item.kt0;
+
+        d4 acc[2][5][1];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 5; ++i) acc[j][i][0] = d4{0.0, 0.0, 0.0, 0.0};
+
+        if (nk > 0) {
+            __builtin_amdgcn_s_barrier();
+            int st = 0;
+            double ra[2][5], rb[2][2];
+            bf_read<0>(ra[0], rb[0], aoff, boff);
+            for (int kt = 0; kt < nk; ++kt) {
+                const unsigned aaddr = aoff + st * BD_STAGE_BYTES, baddr = boff + st * BD_STAGE_BYTES;
+                int stn = st + 1; if (stn >= BD_STAGES) stn = 0;
+#define BF_STEP(KS, CUR, NXT)                                   \
+                bf_read<KS + 1>(ra[NXT], rb[NXT], aaddr, baddr); \
+                bf_wait<7>(ra[CUR], rb[CUR]);                    \
+                bf_mfma(acc, ra[CUR], rb[CUR]);                  \
+                __builtin_amdgcn_sched_barrier(0);
+                BF_STEP(0, 0, 1) BF_STEP(1, 1, 0) BF_STEP(2, 0, 1) BF_STEP(3, 1, 0)
+                BF_STEP(4, 0, 1) BF_STEP(5, 1, 0) BF_STEP(6, 0, 1)
+#undef BF_STEP
+                // last substep: this wave's reads of tile kt complete, meet the feeders (tile kt + 1 has landed),
+                // start the next tile's first reads, then the MFMAs
+                bf_wait<0>(ra[1], rb[1]);
+                __builtin_amdgcn_s_barrier();
+                if (kt + 1 < nk) bf_read<0>(ra[0], rb[0], aoff + stn * BD_STAGE_BYTES, boff + stn * BD_STAGE_BYTES);
+                bf_mfma(acc, ra[1], rb[1]);
+                __builtin_amdgcn_sched_barrier(0);
+                st = stn;
+            }
+        }
+        ++it;
+        bool pre = false;
+        if (it < it1) {
+            item = bf_item(bp.items + it);
+            pre = nk > 0 && item.kt1 - item.kt0 > 0;
+        }
+        if (slot < 0) {
+            // Register budget (80 accumulator registers stay live into the first call): one call at a time, and the
+            // lane number made opaque per item, or the epilogue's per-lane addresses of BOTH strips are hoisted out
+            // of the item loop and held across the K loop -- EpiBackward then spills
+            int elane = lane;
+            asm volatile("" : "+v"(elane));
+            epi(acc[0], e_m0, n0 + wave * 32, elane, p.M, p.N, band);
+            __builtin_amdgcn_sched_barrier(0);
+            epi(acc[1], e_m0, n0 + wave * 32 + 16, elane, p.M, p.N, band);
+        } else {
+            // raw accumulator tiles of the 8-wave kernel's waves 2 wave and 2 wave + 1 (see there)
+            double* P = bp.part + ((size_t)slot * p.gn + bj) * BD_TILE_ELEMS + (size_t)(2 * wave) * (20 * 64) + lane;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int i = 0; i < 5; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) P[(j * 20 + i * 4 + r) * 64] = acc[j][i][0][r];
+        }
+        if (!pre) __builtin_amdgcn_s_barrier();
+    }
+}
+
 // second stage of the streamed decomposition: one workgroup of 2 waves per (split band, column tile,
 // wave pair) sums the band's pieces in K order and applies the epilogue with the GEMM kernel's own
 // register mapping
@@ -428,10 +678,14 @@ __global__ __launch_bounds__(128) void k_band_reduce(const BandRed* red, const d
     epi(acc, rd.band * BD_BM, bj * BD_BN + wave * 16, lane, M, N, rd.band);
 }
 
+// form: BAND_FORM_AUTO, or one of the two kernels whatever the plan (debug hooks: the parity tests compare them);
+// whole_band (nullable): whether the plan is the whole-band one
+enum { BAND_FORM_AUTO = -1, BAND_FORM_8WAVE = 0, BAND_FORM_FEED = 1 };
 template <class Epi, bool DBG = false>
 static inline int launch_gemm_band(hipStream_t s, BandPlan& plan, int N, const double* A, int lda,
                                    const double* B, int ldb, const Epi& epi,
-                                   unsigned long long* clocks = nullptr, int mode = 0)
+                                   unsigned long long* clocks = nullptr, int mode = 0, int form = BAND_FORM_AUTO,
+                                   int* whole_band = nullptr)
 {
     const int gn = (N + BD_BN - 1) / BD_BN;
     BandPlanDev* d = nullptr;
@@ -444,8 +698,21 @@ static inline int launch_gemm_band(hipStream_t s, BandPlan& plan, int N, const d
     bp.wg_ptr = d->wg_ptr.as<int>();
     bp.nwg = d->nwg;
     bp.part = d->part.d();
-    MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&dgemm_band_kernel<Epi, DBG>), (int)BD_LDS_BYTES));
-    hipLaunchKernelGGL((dgemm_band_kernel<Epi, DBG>), dim3(d->nwg * gn), dim3(512), BD_LDS_BYTES, s, bp, epi);
+    if (whole_band) *whole_band = d->paired;
+    bool feed = false;
+    if constexpr (BandFeed<Epi>::ok && !DBG) {
+        // whole-band and streamed plans alike: at 128 chains the feeder form measured 181.0 against 187.5 ms per step
+        feed = form == BAND_FORM_AUTO ? band_feed_enabled() : form == BAND_FORM_FEED;
+        if (feed) {
+            MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&dgemm_band_feed_kernel<Epi>), (int)BD_LDS_BYTES));
+            hipLaunchKernelGGL((dgemm_band_feed_kernel<Epi>), dim3(d->nwg * gn), dim3(512), BD_LDS_BYTES, s, bp, epi);
+        }
+    }
+    MCML_REQUIRE(feed || form != BAND_FORM_FEED, "launch_gemm_band: no feeder form of this instantiation");
+    if (!feed) {
+        MCML_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&dgemm_band_kernel<Epi, DBG>), (int)BD_LDS_BYTES));
+        hipLaunchKernelGGL((dgemm_band_kernel<Epi, DBG>), dim3(d->nwg * gn), dim3(512), BD_LDS_BYTES, s, bp, epi);
+    }
     if (d->nred > 0)
         hipLaunchKernelGGL((k_band_reduce<Epi>), dim3(d->nred, gn, 4), dim3(128), 0, s, d->red.as<BandRed>(),
                            d->part.d(), gn, plan.M, N, epi);

@@ -208,6 +208,13 @@ struct EpiBackward {
     }
 };
 
+// The banded products run the feeder form of the kernel (dgemm_band.h) with the epilogues whose instantiation of it
+// compiles without scratch
+template <> struct BandFeed<EpiBackward> { static constexpr bool ok = true; };
+template <> struct BandFeed<EpiForwardT<1>> { static constexpr bool ok = true; };
+template <> struct BandFeed<EpiForwardT<3>> { static constexpr bool ok = true; };
+template <> struct BandFeed<EpiForwardT<7>> { static constexpr bool ok = true; };
+
 // ------------------------------------------------------------------ sparse ZL products
 // The forward / backward products of the sparse operator and the per-chain kernels that go with them live in
 // hmc_cm.h: with a sparse ZL the whole sampler state is chain-major.

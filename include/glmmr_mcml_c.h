@@ -529,6 +529,11 @@ int glmmr_mcml_dbg_dgemm_bench2(int M, int N, int K, int b_nmajor, int iters, in
  * K tiles of 32 actually multiplied, summed over the 80-row bands */
 int glmmr_mcml_dbg_dgemm_band(int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C,
                               int ldc, int* tiles_executed);
+/* the same through one form of the kernel whatever the sampler would pick -- form 0: eight waves that each load and
+ * multiply, 1: four MFMA waves fed by four DMA waves; whole_band (nullable) = 1 if the plan gives a workgroup whole
+ * bands, 0 if it streams runs of K tiles through k_band_reduce */
+int glmmr_mcml_dbg_dgemm_band_form(int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C,
+                                   int ldc, int* tiles_executed, int form, int* whole_band);
 /* sustained shader clock under the banded FP64 MFMA kernel: out3 = [ms per launch, shader MHz, executed TFLOP/s] */
 int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, double* out3);
 /* mode: 0 the real kernel; timing experiments (results meaningless): 1 no LDS-DMA, 2 no barriers, 4 no ds_reads */
