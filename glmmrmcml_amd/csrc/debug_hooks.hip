@@ -197,8 +197,12 @@ static int dbg_dgemm_band(int M, int N, int K, const double* A, int lda, const d
 // Sustained shader clock under the banded FP64 MFMA kernel: a lower-triangular M x M operand
 // times an M x N matrix, `iters` launches; workgroup 0 accumulates s_memtime (shader clock) and
 // s_memrealtime (constant 100 MHz) over its lifetime.  out3 = [ms per launch, shader MHz, executed TFLOP/s]
+// mode 0: that; negative: the sampler's own instantiation, events only; 16: per-workgroup phase stamps, + 32: every workgroup's
 extern "C" int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, double* out3)
 {
+    MCML_REQUIRE(mode < 0 || !(mode & 15),
+                 "dbg_band_clocks: modes 1, 2, 4 and 8 (the K loop with parts switched off) were retired by the commit "
+                 "'Band HMC products: one K-loop pipeline under both kernel forms'; their findings are in DESIGN.md 5.1");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         set_error("no HIP device: libglmmr_mcml_hip has no CPU fallback");

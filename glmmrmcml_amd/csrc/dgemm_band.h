@@ -32,14 +32,25 @@
 //     over four workgroups and finds the pieces in L2.  With agent-scope release / acquire fences instead of
 //     write-through stores every wave issues a buffer_wbl2, a walk over the XCD's whole L2: 160 us per product.)
 //
-// Same direct-to-LDS machinery as dgemm_dlds.h: 80 x 128 tile, 8 waves (each a 80 x 16 strip =
-// 5 x 1 v_mfma_f64_16x16x4 tiles), K step 32, 3-stage LDS ring (156 KB), counted vmcnt + raw
-// barriers.  The A image [k][80 doubles] has 640-byte rows = 32 banks mod 64, so the two
-// 16-lane halves of a ds_read_b64 (rows k, k+1) are conflict-free without a swizzle.
-//
-// Two forms of the kernel share all of that: dgemm_band_kernel, whose eight waves each load and multiply, and
-// dgemm_band_feed_kernel (further down; what the sampler runs where its instantiation needs no scratch), four MFMA
-// waves with an 80 x 32 strip each fed by four DMA waves.  Same bits from both.
+// One pipeline (band_walk), the direct-to-LDS machinery of dgemm_dlds.h: 80 x 128 tile, 512 threads, K step 32,
+// 3-stage LDS ring (156 KB), counted vmcnt + raw barriers.  The A image [k][80 doubles] has 640-byte rows = 32 banks
+// mod 64, so the two 16-lane halves of a ds_read_b64 (rows k, k+1) are conflict-free without a swizzle.  A wave of
+// the pipeline has up to two jobs: it FILLS the ring -- a BandFill issues every STRIDE-th of the 52 one-KiB LDS-DMA
+// pieces of a stage and keeps the counted vmcnt -- and it MULTIPLIES, NS 80 x 16 strips of the tile (5 x NS
+// v_mfma_f64_16x16x4 tiles per K substep, operands read from LDS by hand-scheduled ds_reads).  All waves walk the
+// same item list and pass the same barriers.  Two kernels instantiate it:
+//   * dgemm_band_kernel, the 8-wave form: every wave does both, pieces wave, wave + 8, ... (7 per tile) and strip
+//     `wave` (NS = 1).  Its waves issue their pieces back to back at the top of a K tile, and a wave inside that
+//     block issues no MFMA (waves issue in order); the two waves of a SIMD are there together.
+//   * dgemm_band_feed_kernel, the feeder form (what the sampler runs where its instantiation needs no scratch):
+//     waves 4-7 only fill, 13 pieces each per tile, and run no epilogue, so the next item's first ring stages are in
+//     flight while the MFMA waves are still in theirs; waves 0-3 (their SIMD partners) only multiply, strips 2 wave
+//     and 2 wave + 1 (NS = 2), with NO vector-memory instruction and no vmcnt wait inside a K loop -- their
+//     epilogue's stores drain under the next item's K loop.
+// Every output element is accumulated by one wave, over K in the same order, by the same instruction with the same
+// operand roles, and the epilogue functor is called once per 16-column strip in both: same bits from both.
+// Selected per epilogue type (BandFeed<Epi>::ok: instantiations that compile without scratch);
+// GLMMR_MCML_BAND_FEED=0 keeps the 8-wave form everywhere.
 #pragma once
 #include "dgemm_dlds.h"
 #include "band_plan.h"
@@ -52,7 +63,7 @@ struct BandP {
     const int* wg_ptr;     // items of workgroup w (of any column tile): [wg_ptr[w], wg_ptr[w+1])
     int nwg;               // workgroups per column tile
     double* part;          // partial tiles: [(slot * gn + column tile) * BD_TILE_ELEMS]
-    int mode;              // DBG kernels only -- timing experiments: 1 no LDS-DMA, 2 no barriers, 4 no ds_reads, 8 compiler-scheduled reads
+    int mode;              // DBG kernels only -- bit 16: per-workgroup phase stamps into clocks[8 ..]
     unsigned long long* clocks;   // DBG kernels only (nullable): workgroup 0 adds its shader-clock and 100 MHz real-time ticks
 };
 
@@ -86,10 +97,10 @@ static __global__ __launch_bounds__(256) void k_band_ranges(const double* A, int
 
 // ---- hand-scheduled operand reads -------------------------------------------------------
 // The compiler's waitcnt insertion puts `s_waitcnt lgkmcnt(0)` in front of every MFMA group,
-// which also waits for the reads just issued for the NEXT group: measured (debug modes of
-// glmmr_mcml_dbg_band_clocks) the matrix pipe then idles ~14% of the K loop on LDS latency.
+// which also waits for the reads just issued for the NEXT group: measured (with a compiler-scheduled
+// copy of the K loop, since removed) the matrix pipe then idles ~14% of the K loop on LDS latency.
 // The reads are therefore issued through inline asm the compiler does not track, and the
-// counted waits are placed by hand (LDS returns in order: lgkmcnt(6) = "everything but the six
+// counted waits are placed by hand (LDS returns in order: lgkmcnt(5 + NS) = "everything but the
 // reads just issued").  The waits carry the operand registers as in/out operands so the MFMAs
 // that consume them cannot be scheduled above the wait.
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -97,361 +108,46 @@ static __global__ __launch_bounds__(256) void k_band_ranges(const double* A, int
 #else
 #define BD_RD(dst, addr, off) (dst = 0.0)
 #endif
-// operands of K substep KS (4 k's) of the stage whose per-lane byte addresses are aaddr / baddr
-template <int KS>
-__device__ __forceinline__ void bd_read(double (&a)[5], double& b, unsigned aaddr, unsigned baddr)
+// operands of K substep KS (4 k's) of the stage whose per-lane byte addresses are aaddr / baddr, for NS adjacent
+// 16-column strips: the second strip's B is the first one's + 256 bytes
+template <int KS, int NS>
+__device__ __forceinline__ void bd_read(double (&a)[5], double (&b)[NS], unsigned aaddr, unsigned baddr)
 {
-    BD_RD(a[0], aaddr, KS * 4 * BD_BM * 8);
-    BD_RD(a[1], aaddr, KS * 4 * BD_BM * 8 + 128);
-    BD_RD(a[2], aaddr, KS * 4 * BD_BM * 8 + 256);
-    BD_RD(a[3], aaddr, KS * 4 * BD_BM * 8 + 384);
-    BD_RD(a[4], aaddr, KS * 4 * BD_BM * 8 + 512);
-    BD_RD(b, baddr, KS * 2 * BD_BN * 16);
-}
-template <int LEAVE>
-__device__ __forceinline__ void bd_wait(double (&a)[5], double& b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (LEAVE == 6)
-        asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b));
-    else
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b));
-#endif
-}
-__device__ __forceinline__ void bd_mfma(d4 (&acc)[5][1], const double (&a)[5], double b)
-{
-#pragma unroll
-    for (int i = 0; i < 5; ++i) acc[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b, a[i], acc[i][0], 0, 0, 0);
-}
-
-// DBG = true only for the timing hooks of debug_hooks.hip (bp.mode / bp.clocks); the sampler's instantiation
-// carries neither the experiment branches nor the clock reads
-template <class Epi, bool DBG>
-__global__ __launch_bounds__(512) void dgemm_band_kernel(BandP bp, Epi epi)
-{
-    const GemmP& p = bp.g;
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    char* lds = reinterpret_cast<char*>(smem);
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15 = lane & 15, lk = lane >> 4;
-    unsigned long long t0c = 0, t0r = 0;
-    if constexpr (DBG)
-        if (bp.clocks && blockIdx.x == 0 && tid == 0) { t0c = __builtin_amdgcn_s_memtime(); t0r = __builtin_amdgcn_s_memrealtime(); }
-
-    // XCD-aware map over (workgroup of the plan, column tile): the column tiles of one run of K tiles
-    // share an XCD (they read the same pieces of A)
-    const int nblk = bp.nwg * p.gn;
-    const int bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-    const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int pw = nid / p.gn, bj = nid - pw * p.gn;
-    const int n0 = bj * BD_BN;
-
-    // Operand addressing: a UNIFORM base (SGPR pair, advanced per K tile by scalar adds) plus a per-lane 32-bit
-    // byte offset that never changes inside a K loop (`global_load_lds_dwordx4 voff, s[base]`).  With per-lane
-    // 64-bit pointers advanced by VALU adds the compiler may place an add right behind the LDS-DMA that reads
-    // the same address register; that write-after-read stalls the wave until the load has left the queue
-    // (measured: 458 vs 419 us per launch, the difference in SQ_WAIT_INST_ANY).
-    // B pieces do not depend on the band: 32 chunks, chunk c -> (kp = c >> 1, half = c & 1)
-    unsigned vob[BD_NB]; int lb[BD_NB];
-#pragma unroll
-    for (int s = 0; s < BD_NB; ++s) {
-        const int c = wave + 8 * s;
-        const int kp = c >> 1, n = ((c & 1) << 6) + lane;
-        int gn = n0 + n;
-        if (gn >= p.N) gn = 0;
-        vob[s] = (unsigned)((2 * kp + (size_t)gn * p.ldb) * 8);
-        lb[s] = BD_A_BYTES + c * 1024;
-    }
-    const size_t stepA = (size_t)BD_BK * p.lda * 8;      // bytes per K tile
-
-    // The item list is read with a SCALAR load (hand-written: the compiler will not scalarise a load it
-    // cannot prove unclobbered by the epilogue's stores).  A vector load here sits behind the previous item's
-    // epilogue stores -- vector memory completes in order, its `s_waitcnt vmcnt(0)` drains every store before
-    // the next item's first LDS-DMA can even be issued: measured 471 vs 428 us per launch at 1024 chains.
-    const int it0 = bp.wg_ptr[pw], it1 = bp.wg_ptr[pw + 1];
-    // the item being worked on and its operand addressing; load_item() replaces them (after a K loop they are dead)
-    BandItem item{0, 0, 0, -1};
-    int m0 = 0;
-    unsigned voa[BD_NA]; int la[BD_NA];
-#pragma unroll
-    for (int s = 0; s < BD_NA; ++s) {
-        int c = wave + 8 * s;
-        if (c >= 20) c = wave + 8;                          // waves 4-7 repeat a chunk: uniform vmcnt
-        la[s] = c * 1024;                                   // LDS offset of the piece: the same for every item
-    }
-    const char* sA = nullptr; const char* sB = nullptr;                 // uniform
-    auto load_item = [&](int it) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        {
-            typedef int i4s __attribute__((ext_vector_type(4)));
-            i4s raw;
-            const BandItem* ip = bp.items + it;
-            asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(raw) : "s"(ip) : "memory");
-            item.band = raw.x; item.kt0 = raw.y; item.kt1 = raw.z; item.slot = raw.w;
-        }
-#else
-        item = bp.items[it];
-#endif
-        m0 = item.band * BD_BM;
-#pragma unroll
-        for (int s = 0; s < BD_NA; ++s) {
-            int c = wave + 8 * s;
-            if (c >= 20) c = wave + 8;                      // waves 4-7 repeat a chunk: uniform vmcnt
-            const int o = c * 1024 + lane * 16;
-            const int k = o / (BD_BM * 8), m = (o - k * BD_BM * 8) >> 3;
-            int gm = m0 + m;
-            if (gm >= p.M) gm = 0;
-            voa[s] = (unsigned)((gm + (size_t)k * p.lda) * 8);
-        }
-        sA = reinterpret_cast<const char*>(p.A) + (size_t)item.kt0 * stepA;
-        sB = reinterpret_cast<const char*>(p.B) + (size_t)item.kt0 * (BD_BK * 8);
-    };
-    auto issue = [&](int stage) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        // hand-written so that the scalar-base form is what runs (hipcc materialises base + offset into one
-        // 64-bit temporary per load instead); M0 = LDS byte address of the piece, lane l lands at M0 + 16 l;
-        // the s_nop is the wait state an LDS-DMA needs behind a SALU write of M0 (hipcc pads nothing inside asm)
-        const unsigned lbase = (unsigned)(size_t)(lds_ptr_t)lds + stage * BD_STAGE_BYTES;
-#pragma unroll
-        for (int s = 0; s < BD_NA; ++s)
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                         :: "s"(lbase + la[s]), "v"(voa[s]), "s"(sA) : "memory", "m0");
-#pragma unroll
-        for (int s = 0; s < BD_NB; ++s)
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                         :: "s"(lbase + lb[s]), "v"(vob[s]), "s"(sB) : "memory", "m0");
-        sA += stepA;
-        sB += BD_BK * 8;
-#else
-        (void)stage; (void)stepA; (void)sA; (void)sB;
-#endif
-    };
-    auto wait_leave = [&](int tiles) {
-        static_assert(BD_PER_TILE == 7, "vmcnt immediates below");
-        if (tiles >= 2) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-        else if (tiles == 1) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    const int mode = DBG ? (bp.mode & 15) : 0;
-    // DBG, mode bit 16: every workgroup leaves 100 MHz real-time stamps of its phases at clocks[8 + 8 * bid ..]:
-    // [start, first ring stages landed, K loop of the first item done, its epilogue / partial store issued, end]
-    const bool stamps = DBG && (bp.mode & 16) && bp.clocks;
-    auto stamp = [&](int i) {
-        if constexpr (DBG)
-            if (stamps && tid == 0) bp.clocks[8 + 8 * (size_t)blockIdx.x + i] = __builtin_amdgcn_s_memrealtime();
-    };
-    stamp(0);
-    bool first_item = true;
-    // `pre`: the first ring stages of the item about to start are already in flight -- they were issued BEFORE the
-    // previous item's epilogue (the ring is free once every wave has passed the last barrier of a K loop), so the
-    // fill's memory latency runs under the epilogue's loads and stores instead of after them
-    bool pre = false;
-    int issued = 0;
-    if (it0 < it1) load_item(it0);
-    for (int it = it0; it < it1;) {
-        const int band = item.band, e_m0 = m0, slot = item.slot;
-        const int nk = item.kt1 - item.kt0;
-
-        d4 acc[5][1];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) acc[i][0] = d4{0.0, 0.0, 0.0, 0.0};
-
-        if (nk > 0 && mode == 0) {
-            // per-lane LDS byte addresses of the operand reads inside stage 0
-            const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)lds;
-            const unsigned aoff = lds0 + lk * (BD_BM * 8) + l15 * 8;
-            const unsigned boff = lds0 + BD_A_BYTES + (((lk >> 1) * BD_BN + wave * 16 + l15) << 4) + ((lk & 1) << 3);
-            if (!pre) { issued = 0; for (; issued < BD_STAGES - 1 && issued < nk; ++issued) issue(issued); }
-            wait_leave(issued - 1);
-            __builtin_amdgcn_s_barrier();
-            if (first_item) stamp(1);
-            int st = 0;
-            double ra[2][5], rb[2];
-            bd_read<0>(ra[0], rb[0], aoff, boff);
-            for (int kt = 0; kt < nk; ++kt) {
-                if (issued < nk) {
-                    int sn = st + BD_STAGES - 1; if (sn >= BD_STAGES) sn -= BD_STAGES;
-                    issue(sn);
-                    ++issued;
-                }
-                const unsigned aaddr = aoff + st * BD_STAGE_BYTES, baddr = boff + st * BD_STAGE_BYTES;
-                int stn = st + 1; if (stn >= BD_STAGES) stn = 0;
-#define BD_STEP(KS, CUR, NXT)                                   \
-                bd_read<KS + 1>(ra[NXT], rb[NXT], aaddr, baddr); \
-                bd_wait<6>(ra[CUR], rb[CUR]);                    \
-                bd_mfma(acc, ra[CUR], rb[CUR]);                  \
-                __builtin_amdgcn_sched_barrier(0);
-                BD_STEP(0, 0, 1) BD_STEP(1, 1, 0) BD_STEP(2, 0, 1) BD_STEP(3, 1, 0)
-                BD_STEP(4, 0, 1) BD_STEP(5, 1, 0) BD_STEP(6, 0, 1)
-#undef BD_STEP
-                // last substep: synchronise first (this wave's pieces of tile kt+1 landed, its own
-                // reads of tile kt complete), start the next tile's first reads, then the MFMAs
-                wait_leave(issued - kt - 2);
-                bd_wait<0>(ra[1], rb[1]);
-                __builtin_amdgcn_s_barrier();
-                if (kt + 1 < nk) bd_read<0>(ra[0], rb[0], aoff + stn * BD_STAGE_BYTES, boff + stn * BD_STAGE_BYTES);
-                bd_mfma(acc, ra[1], rb[1]);
-                __builtin_amdgcn_sched_barrier(0);
-                st = stn;
-            }
-        } else if (DBG && nk > 0 && mode == 8) {
-            // compiler-scheduled operand reads (the loop the hand-scheduled one replaced)
-            int issued = 0;
-            for (; issued < BD_STAGES - 1 && issued < nk; ++issued) issue(issued);
-            wait_leave(issued - 1);
-            __builtin_amdgcn_s_barrier();
-            int st = 0;
-            for (int kt = 0; kt < nk; ++kt) {
-                if (issued < nk) {
-                    int sn = st + BD_STAGES - 1; if (sn >= BD_STAGES) sn -= BD_STAGES;
-                    issue(sn);
-                    ++issued;
-                }
-                const double* as = reinterpret_cast<const double*>(lds + st * BD_STAGE_BYTES);
-                const double* bs = reinterpret_cast<const double*>(lds + st * BD_STAGE_BYTES + BD_A_BYTES);
-#pragma unroll
-                for (int ks = 0; ks < BD_BK / 4; ++ks) {
-                    const int kk = 4 * ks + lk;
-                    double a[5];
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) a[i] = as[kk * BD_BM + 16 * i + l15];
-                    const double b = bs[((kk >> 1) * BD_BN + wave * 16 + l15) * 2 + (kk & 1)];
-#pragma unroll
-                    for (int i = 0; i < 5; ++i)
-                        acc[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b, a[i], acc[i][0], 0, 0, 0);
-                }
-                wait_leave(issued - kt - 2);
-                __builtin_amdgcn_s_barrier();
-                st = st + 1; if (st >= BD_STAGES) st = 0;
-            }
-        } else if (DBG && nk > 0) {
-            // timing experiments: the same loop with parts switched off (results meaningless)
-            int issued = 0;
-            if (!(mode & 1)) {
-                for (; issued < BD_STAGES - 1 && issued < nk; ++issued) issue(issued);
-                wait_leave(issued - 1);
-            }
-            __builtin_amdgcn_s_barrier();
-            int st = 0;
-            double a[5] = {1.0 + lane, 2.0, 3.0, 4.0, 5.0}, b = 0.5 + lane;
-            for (int kt = 0; kt < nk; ++kt) {
-                if (!(mode & 1) && issued < nk) {
-                    int sn = st + BD_STAGES - 1; if (sn >= BD_STAGES) sn -= BD_STAGES;
-                    issue(sn);
-                    ++issued;
-                }
-                const double* as = reinterpret_cast<const double*>(lds + st * BD_STAGE_BYTES);
-                const double* bs = reinterpret_cast<const double*>(lds + st * BD_STAGE_BYTES + BD_A_BYTES);
-#pragma unroll
-                for (int ks = 0; ks < BD_BK / 4; ++ks) {
-                    const int kk = 4 * ks + lk;
-                    if (!(mode & 4)) {
-#pragma unroll
-                        for (int i = 0; i < 5; ++i) a[i] = as[kk * BD_BM + 16 * i + l15];
-                        b = bs[((kk >> 1) * BD_BN + wave * 16 + l15) * 2 + (kk & 1)];
-                    }
-#pragma unroll
-                    for (int i = 0; i < 5; ++i)
-                        acc[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b, a[i], acc[i][0], 0, 0, 0);
-                }
-                if (!(mode & 1)) wait_leave(issued - kt - 2);
-                if (!(mode & 2)) __builtin_amdgcn_s_barrier();
-                st = st + 1; if (st >= BD_STAGES) st = 0;
-            }
-        }
-        if (first_item) stamp(2);
-        ++it;
-        pre = false;
-        if (it < it1) {
-            load_item(it);
-            const int nkn = item.kt1 - item.kt0;
-            if (mode == 0 && nk > 0 && nkn > 0) {
-                issued = 0;
-                for (; issued < BD_STAGES - 1 && issued < nkn; ++issued) issue(issued);
-                pre = true;
-            }
-        }
-        if (slot < 0) {
-            epi(acc, e_m0, n0 + wave * 16, lane, p.M, p.N, band);
-        } else {
-            // raw accumulator tile in register order: element (wave, i, r, lane) -- each store instruction
-            // writes 512 contiguous bytes; k_band_reduce reads it back with the same thread mapping
-            double* P = bp.part + ((size_t)slot * p.gn + bj) * BD_TILE_ELEMS + (size_t)wave * (20 * 64) + lane;
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) P[(i * 4 + r) * 64] = acc[i][0][r];
-        }
-        if (first_item) { stamp(3); first_item = false; }
-        // without a prefetch the next item's first LDS-DMA may overwrite a stage another wave is still reading
-        if (!pre) __builtin_amdgcn_s_barrier();
-    }
-    if constexpr (DBG)
-        if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(4); }
-    if constexpr (DBG)
-        if (bp.clocks && blockIdx.x == 0 && tid == 0) {
-            atomicAdd(bp.clocks, __builtin_amdgcn_s_memtime() - t0c);
-            atomicAdd(bp.clocks + 1, __builtin_amdgcn_s_memrealtime() - t0r);
-        }
-}
-
-// ---- the feeder form: four MFMA waves, four DMA waves -----------------------------------
-// In dgemm_band_kernel every wave issues its 7 LDS-DMA pieces back to back at the top of a K tile, and a wave inside
-// that block issues no MFMA (waves issue in order); the two waves of a SIMD are there together.  Here the roles are
-// split by wave number: waves 0-3 (one per SIMD) own an 80 x 32 strip each -- two of the 8-wave kernel's strips,
-// acc[2][5] -- and issue NO vector-memory instruction and no vmcnt wait inside a K loop; waves 4-7 (their SIMD
-// partners) issue the tile's 52 one-KiB pieces, 13 each, keep the counted vmcnt and meet the MFMA waves at the same
-// barriers.  Tile, ring, LDS images, item list and XCD map are dgemm_band_kernel's.  Every output element is still
-// accumulated by one wave, over K in the same order, by the same instruction with the same operand roles, and the
-// epilogue functor is called once per 16-column strip as before: the results are the 8-wave kernel's bit for bit.
-// The epilogue's stores drain under the next item's K loop (nothing there waits on vmcnt), and the feeders, which run
-// no epilogue, have the next item's first ring stages in flight while the MFMA waves are still in theirs.
-// Selected per epilogue type (BandFeed<Epi>::ok: instantiations that compile without scratch); GLMMR_MCML_BAND_FEED=0
-// keeps the 8-wave kernel everywhere.
-template <class Epi> struct BandFeed { static constexpr bool ok = false; };
-template <> struct BandFeed<EpiAxpby> { static constexpr bool ok = true; };
-
-constexpr int BF_NA = 5, BF_NB = 8, BF_PER_TILE = BF_NA + BF_NB;      // LDS-DMA pieces per feeder wave per tile
-static_assert(4 * BF_NA * 1024 == BD_A_BYTES && 4 * BF_NB * 1024 == BD_B_BYTES, "four feeders cover a stage");
-
-static inline bool band_feed_enabled()         // read per call: the parity tests run both forms in one process
-{
-    const char* e = getenv("GLMMR_MCML_BAND_FEED");
-    return !(e && !strcmp(e, "0"));
-}
-
-// operands of K substep KS of both 16-column sub-strips: the second strip's B is the first one's + 256 bytes
-template <int KS>
-__device__ __forceinline__ void bf_read(double (&a)[5], double (&b)[2], unsigned aaddr, unsigned baddr)
-{
+    static_assert(NS == 1 || NS == 2, "one or two strips per wave");
     BD_RD(a[0], aaddr, KS * 4 * BD_BM * 8);
     BD_RD(a[1], aaddr, KS * 4 * BD_BM * 8 + 128);
     BD_RD(a[2], aaddr, KS * 4 * BD_BM * 8 + 256);
     BD_RD(a[3], aaddr, KS * 4 * BD_BM * 8 + 384);
     BD_RD(a[4], aaddr, KS * 4 * BD_BM * 8 + 512);
     BD_RD(b[0], baddr, KS * 2 * BD_BN * 16);
-    BD_RD(b[1], baddr, KS * 2 * BD_BN * 16 + 256);
+    if constexpr (NS == 2) BD_RD(b[1], baddr, KS * 2 * BD_BN * 16 + 256);
 }
-template <int LEAVE>
-__device__ __forceinline__ void bf_wait(double (&a)[5], double (&b)[2])
+// LEAVE: 5 + NS (the reads of the next substep stay in flight) or 0
+template <int LEAVE, int NS>
+__device__ __forceinline__ void bd_wait(double (&a)[5], double (&b)[NS])
 {
+    static_assert(LEAVE == 0 || LEAVE == 5 + NS, "one substep's reads");
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (LEAVE == 7)
-        asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]), "+v"(b[1]));
+    if constexpr (NS == 1)
+        asm volatile("s_waitcnt lgkmcnt(%[n])" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]) : [n] "n"(LEAVE));
     else
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]), "+v"(b[1]));
+        asm volatile("s_waitcnt lgkmcnt(%[n])" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]), "+v"(b[1]) : [n] "n"(LEAVE));
 #endif
 }
-__device__ __forceinline__ void bf_mfma(d4 (&acc)[2][5][1], const double (&a)[5], const double (&b)[2])
+template <int NS>
+__device__ __forceinline__ void bd_mfma(d4 (&acc)[NS][5][1], const double (&a)[5], const double (&b)[NS])
 {
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NS; ++j)
 #pragma unroll
         for (int i = 0; i < 5; ++i) acc[j][i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a[i], acc[j][i][0], 0, 0, 0);
 }
-// the scalar item load of dgemm_band_kernel (see there)
-__device__ __forceinline__ BandItem bf_item(const BandItem* ip)
+
+// The item list is read with a SCALAR load (hand-written: the compiler will not scalarise a load it
+// cannot prove unclobbered by the epilogue's stores).  A vector load here sits behind the previous item's
+// epilogue stores -- vector memory completes in order, its `s_waitcnt vmcnt(0)` drains every store before
+// the next item's first LDS-DMA can even be issued: measured 471 vs 428 us per launch at 1024 chains.
+__device__ __forceinline__ BandItem band_item(const BandItem* ip)
 {
     BandItem item{0, 0, 0, -1};
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -465,181 +161,274 @@ __device__ __forceinline__ BandItem bf_item(const BandItem* ip)
     return item;
 }
 
-template <class Epi>
-__global__ __launch_bounds__(512) void dgemm_band_feed_kernel(BandP bp, Epi epi)
-{
-    const GemmP& p = bp.g;
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    char* lds = reinterpret_cast<char*>(smem);
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)lds;
+// ---- the fill role ------------------------------------------------------------------------
+// One wave's share of the ring fill: pieces f, f + STRIDE, ... of the 20 A and the 32 B one-KiB pieces of a stage,
+// NA + NB LDS-DMAs per K tile (lane l's 16 bytes of a piece land at its LDS address + 16 l).
+// Operand addressing: a UNIFORM base (SGPR pair, advanced per K tile by scalar adds) plus a per-lane 32-bit
+// byte offset that never changes inside a K loop (lds_dma16, dgemm_dlds.h, says why).
+template <int STRIDE, int NA, int NB>
+struct BandFill {
+    static constexpr int PER_TILE = NA + NB, A_CHUNKS = BD_A_BYTES / 1024;
+    static_assert(STRIDE * NA >= A_CHUNKS && STRIDE * NB * 1024 == BD_B_BYTES, "the role's waves cover a stage");
+    const GemmP& p;
+    const BandItem* items;
+    const int f, lane;
+    const unsigned lds0;
+    const size_t stepA;                                      // bytes per K tile
+    unsigned voa[NA], vob[NB];
+    const char* sA = nullptr; const char* sB = nullptr;      // uniform
+    BandItem item{0, 0, 0, -1};                              // the item being worked on; load_item() replaces it
 
-    // the XCD-aware map of dgemm_band_kernel
-    const int nblk = bp.nwg * p.gn;
-    const int bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-    const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int pw = nid / p.gn, bj = nid - pw * p.gn;
-    const int n0 = bj * BD_BN;
-    const int it0 = bp.wg_ptr[pw], it1 = bp.wg_ptr[pw + 1];
-
-    // Both roles walk the same items and pass the same barriers: per item with K tiles one before the K loop and one
-    // per tile, and one behind an item whose successor's ring fill is not already in flight (`pre`).
-    if (wave >= 4) {
-        // ---- feeder: pieces f, f + 4, ... of the 20 A and the 32 B pieces of a stage
-        // (one static s_setprio 1 here measured no different: 839.4 / 844.9 against 842.9 / 842.9 ms per bench step)
-        const int f = wave - 4;
-        const size_t stepA = (size_t)BD_BK * p.lda * 8;      // bytes per K tile
-        unsigned vob[BF_NB];
+    // A piece s of this wave is chunk f + a_rel(s).  Where STRIDE waves x NA pieces exceed the 20 chunks (8-wave
+    // form: waves 4-7), the wave repeats its second chunk, so that every wave issues PER_TILE loads: uniform vmcnt
+    __device__ __forceinline__ int a_rel(int s) const
+    {
+        return (STRIDE * NA > A_CHUNKS && f + STRIDE * s >= A_CHUNKS) ? STRIDE : STRIDE * s;
+    }
+    __device__ __forceinline__ BandFill(const BandP& bp, int f_, int lane_, int n0, unsigned lds0_)
+        : p(bp.g), items(bp.items), f(f_), lane(lane_), lds0(lds0_), stepA((size_t)BD_BK * bp.g.lda * 8)
+    {
+        // B pieces do not depend on the band: chunk c -> (kp = c >> 1, half = c & 1)
 #pragma unroll
-        for (int s = 0; s < BF_NB; ++s) {
-            const int c = f + 4 * s;
+        for (int s = 0; s < NB; ++s) {
+            const int c = f + STRIDE * s;
             const int kp = c >> 1, n = ((c & 1) << 6) + lane;
             int gn = n0 + n;
             if (gn >= p.N) gn = 0;
             vob[s] = (unsigned)((2 * kp + (size_t)gn * p.ldb) * 8);
         }
-        unsigned voa[BF_NA];
-        const char* sA = nullptr; const char* sB = nullptr;                 // uniform
-        BandItem item{0, 0, 0, -1};
-        auto load_item = [&](int it) {
-            item = bf_item(bp.items + it);
-            const int m0 = item.band * BD_BM;
-#pragma unroll
-            for (int s = 0; s < BF_NA; ++s) {
-                const int o = (f + 4 * s) * 1024 + lane * 16;
-                const int k = o / (BD_BM * 8), m = (o - k * BD_BM * 8) >> 3;
-                int gm = m0 + m;
-                if (gm >= p.M) gm = 0;
-                voa[s] = (unsigned)((gm + (size_t)k * p.lda) * 8);
-            }
-            sA = reinterpret_cast<const char*>(p.A) + (size_t)item.kt0 * stepA;
-            sB = reinterpret_cast<const char*>(p.B) + (size_t)item.kt0 * (BD_BK * 8);
-        };
-        auto issue = [&](int stage) {
-            const unsigned lbase = lds0 + stage * BD_STAGE_BYTES + f * 1024;
-#pragma unroll
-            for (int s = 0; s < BF_NA; ++s) lds_dma16(lbase + s * 4096, voa[s], sA);
-#pragma unroll
-            for (int s = 0; s < BF_NB; ++s) lds_dma16(lbase + BD_A_BYTES + s * 4096, vob[s], sB);
-            sA += stepA;
-            sB += BD_BK * 8;
-        };
-        auto wait_leave = [&](int tiles) {
-            static_assert(BF_PER_TILE == 13, "vmcnt immediates below");
-            if (tiles >= 2) asm volatile("s_waitcnt vmcnt(26)" ::: "memory");
-            else if (tiles == 1) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        };
-        bool pre = false;
-        int issued = 0;
-        if (it0 < it1) load_item(it0);
-        for (int it = it0; it < it1;) {
-            const int nk = item.kt1 - item.kt0;
-            if (nk > 0) {
-                if (!pre) { issued = 0; for (; issued < BD_STAGES - 1 && issued < nk; ++issued) issue(issued); }
-                wait_leave(issued - 1);
-                __builtin_amdgcn_s_barrier();
-                int st = 0;
-                for (int kt = 0; kt < nk; ++kt) {
-                    // the stage tile kt - 1 was read from: every MFMA wave finished its reads before that tile's barrier
-                    if (issued < nk) {
-                        int sn = st + BD_STAGES - 1; if (sn >= BD_STAGES) sn -= BD_STAGES;
-                        issue(sn);
-                        ++issued;
-                    }
-                    wait_leave(issued - kt - 2);            // this wave's pieces of tile kt + 1 have landed
-                    __builtin_amdgcn_s_barrier();
-                    ++st; if (st >= BD_STAGES) st = 0;
-                }
-            }
-            ++it;
-            pre = false;
-            if (it < it1) {
-                load_item(it);
-                const int nkn = item.kt1 - item.kt0;
-                // the ring is free once every wave has passed the last barrier of a K loop: the next item's first
-                // stages go out while the MFMA waves run their epilogue
-                if (nk > 0 && nkn > 0) {
-                    issued = 0;
-                    for (; issued < BD_STAGES - 1 && issued < nkn; ++issued) issue(issued);
-                    pre = true;
-                }
-            }
-            if (!pre) __builtin_amdgcn_s_barrier();
-        }
-        return;
     }
-
-    // ---- MFMA wave: columns n0 + 32 wave .. + 31 as two 16-column sub-strips
-    const int l15 = lane & 15, lk = lane >> 4;
-    const unsigned aoff = lds0 + lk * (BD_BM * 8) + l15 * 8;
-    const unsigned boff = lds0 + BD_A_BYTES + (((lk >> 1) * BD_BN + wave * 32 + l15) << 4) + ((lk & 1) << 3);
-    BandItem item{0, 0, 0, -1};
-    if (it0 < it1) item = bf_item(bp.items + it0);
-    for (int it = it0; it < it1;) {
-        const int band = item.band, e_m0 = item.band * BD_BM, slot = item.slot;
-        const int nk = item.kt1 - item.kt0;
-
-        d4 acc[2][5][1];
+    __device__ __forceinline__ void load_item(int it)
+    {
+        item = band_item(items + it);
+        const int m0 = item.band * BD_BM;
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int s = 0; s < NA; ++s) {
+            const int o = (f + a_rel(s)) * 1024 + lane * 16;
+            const int k = o / (BD_BM * 8), m = (o - k * BD_BM * 8) >> 3;
+            int gm = m0 + m;
+            if (gm >= p.M) gm = 0;
+            voa[s] = (unsigned)((gm + (size_t)k * p.lda) * 8);
+        }
+        sA = reinterpret_cast<const char*>(p.A) + (size_t)item.kt0 * stepA;
+        sB = reinterpret_cast<const char*>(p.B) + (size_t)item.kt0 * (BD_BK * 8);
+    }
+    // the item's next K tile into ring stage `stage`
+    __device__ __forceinline__ void issue(int stage)
+    {
+        const unsigned lbase = lds0 + stage * BD_STAGE_BYTES + f * 1024;
+#pragma unroll
+        for (int s = 0; s < NA; ++s) lds_dma16(lbase + a_rel(s) * 1024, voa[s], sA);
+#pragma unroll
+        for (int s = 0; s < NB; ++s) lds_dma16(lbase + BD_A_BYTES + STRIDE * s * 1024, vob[s], sB);
+        sA += stepA;
+        sB += BD_BK * 8;
+    }
+    // wait until at most `tiles` of this wave's tiles are in flight
+    __device__ __forceinline__ void wait_leave(int tiles) const
+    {
+        if (tiles >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * PER_TILE) : "memory");
+        else if (tiles == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_TILE) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+};
+// a wave that leaves the fill to others (the feeder form's MFMA waves): the item alone, nothing to issue or wait for
+struct BandNoFill {
+    const BandItem* items;
+    BandItem item{0, 0, 0, -1};
+    __device__ __forceinline__ BandNoFill(const BandP& bp, int, int, int, unsigned) : items(bp.items) {}
+    __device__ __forceinline__ void load_item(int it) { item = band_item(items + it); }
+    __device__ __forceinline__ void issue(int) {}
+    __device__ __forceinline__ void wait_leave(int) const {}
+};
+constexpr int BF_NA = 5, BF_NB = 8;      // LDS-DMA pieces per feeder wave per tile (BD_NA, BD_NB: per wave of the 8-wave form)
+
+// raw accumulator tile of one 16-column strip (0..7) in register order: element (strip, i, r, lane) -- each store
+// instruction writes 512 contiguous bytes; k_band_reduce reads it back with the same thread mapping
+__device__ __forceinline__ void band_store_partial(double* tile, int strip, int lane, const d4 (&acc)[5][1])
+{
+    double* P = tile + (size_t)strip * (20 * 64) + lane;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) P[(i * 4 + r) * 64] = acc[i][0][r];
+}
+
+// what the waves of a workgroup start from: the wave's number, the thread's lane, the column tile, the items
+struct BandWg {
+    int wave, lane, bj, it0, it1;
+    __device__ __forceinline__ explicit BandWg(const BandP& bp)
+    {
+        const int tid = threadIdx.x;
+        lane = tid & 63;
+        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        // XCD-aware map over (workgroup of the plan, column tile): the column tiles of one run of K tiles
+        // share an XCD (they read the same pieces of A)
+        const int nid = xcd_block_map(blockIdx.x, bp.nwg * bp.g.gn);
+        const int pw = nid / bp.g.gn;
+        bj = nid - pw * bp.g.gn;
+        it0 = bp.wg_ptr[pw]; it1 = bp.wg_ptr[pw + 1];
+    }
+};
+
+// ---- the item walk ------------------------------------------------------------------------
+// What one wave does with its workgroup's items.  Fill: its share of the ring fill (BandFill), or BandNoFill.
+// NS: the number of 16-column strips it multiplies, strip0, strip0 + 1, ...; 0 for a wave that only fills.
+// Whatever its jobs, a wave passes the barriers of this one function: per item with K tiles one before the K loop
+// and one per tile, and one behind an item whose successor's ring fill is not already in flight (`pre`).
+// DBG = true only for the timing hooks of debug_hooks.hip (bp.mode / bp.clocks); the other instantiations carry no
+// stamp and read no clock.
+template <int NS, class Fill, bool DBG, class Epi>
+__device__ __forceinline__ void band_walk(const BandP& bp, const Epi& epi, const BandWg& wg, int piece0, int strip0)
+{
+    constexpr int NJ = NS > 0 ? NS : 1;     // a wave that only fills declares the operand registers and never touches them
+    const GemmP& p = bp.g;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t) reinterpret_cast<char*>(smem);
+    const int lane = wg.lane, l15 = lane & 15, lk = lane >> 4;
+    const int bj = wg.bj, n0 = bj * BD_BN, it0 = wg.it0, it1 = wg.it1;
+
+    // DBG, mode bit 16: every workgroup leaves 100 MHz real-time stamps of its phases at clocks[8 + 8 * bid ..]:
+    // [start, first ring stages landed, K loop of the first item done, its epilogue / partial store issued, end]
+    auto stamp = [&](int i) {
+        if constexpr (DBG)
+            if ((bp.mode & 16) && bp.clocks && threadIdx.x == 0)
+                bp.clocks[8 + 8 * (size_t)blockIdx.x + i] = __builtin_amdgcn_s_memrealtime();
+    };
+    stamp(0);
+    bool first_item = true;
+    Fill fill(bp, piece0, lane, n0, lds0);
+    // `pre`: the first ring stages of the item about to start are already in flight -- they were issued BEFORE the
+    // previous item's epilogue (the ring is free once every wave has passed the last barrier of a K loop), so the
+    // fill's memory latency runs under the epilogue's loads and stores instead of after them
+    bool pre = false;
+    int issued = 0;
+    if (it0 < it1) fill.load_item(it0);
+    for (int it = it0; it < it1;) {
+        const int band = fill.item.band, slot = fill.item.slot;
+        const int nk = fill.item.kt1 - fill.item.kt0;
+
+        d4 acc[NJ][5][1];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int i = 0; i < 5; ++i) acc[j][i][0] = d4{0.0, 0.0, 0.0, 0.0};
 
         if (nk > 0) {
+            // per-lane LDS byte addresses of the operand reads inside stage 0
+            const unsigned aoff = lds0 + lk * (BD_BM * 8) + l15 * 8;
+            const unsigned boff = lds0 + BD_A_BYTES + (((lk >> 1) * BD_BN + strip0 * 16 + l15) << 4) + ((lk & 1) << 3);
+            if (!pre) { issued = 0; for (; issued < BD_STAGES - 1 && issued < nk; ++issued) fill.issue(issued); }
+            fill.wait_leave(issued - 1);
             __builtin_amdgcn_s_barrier();
+            if (first_item) stamp(1);
             int st = 0;
-            double ra[2][5], rb[2][2];
-            bf_read<0>(ra[0], rb[0], aoff, boff);
+            double ra[2][5], rb[2][NJ];
+            if constexpr (NS > 0) bd_read<0>(ra[0], rb[0], aoff, boff);
             for (int kt = 0; kt < nk; ++kt) {
+                // the stage tile kt - 1 was read from: every wave finished its reads before that tile's barrier
+                if (issued < nk) {
+                    int sn = st + BD_STAGES - 1; if (sn >= BD_STAGES) sn -= BD_STAGES;
+                    fill.issue(sn);
+                    ++issued;
+                }
                 const unsigned aaddr = aoff + st * BD_STAGE_BYTES, baddr = boff + st * BD_STAGE_BYTES;
                 int stn = st + 1; if (stn >= BD_STAGES) stn = 0;
-#define BF_STEP(KS, CUR, NXT)                                   \
-                bf_read<KS + 1>(ra[NXT], rb[NXT], aaddr, baddr); \
-                bf_wait<7>(ra[CUR], rb[CUR]);                    \
-                bf_mfma(acc, ra[CUR], rb[CUR]);                  \
-                __builtin_amdgcn_sched_barrier(0);
-                BF_STEP(0, 0, 1) BF_STEP(1, 1, 0) BF_STEP(2, 0, 1) BF_STEP(3, 1, 0)
-                BF_STEP(4, 0, 1) BF_STEP(5, 1, 0) BF_STEP(6, 0, 1)
-#undef BF_STEP
-                // last substep: this wave's reads of tile kt complete, meet the feeders (tile kt + 1 has landed),
-                // start the next tile's first reads, then the MFMAs
-                bf_wait<0>(ra[1], rb[1]);
+                if constexpr (NS > 0) {
+#define BD_STEP(KS, CUR, NXT)                                   \
+                    bd_read<KS + 1>(ra[NXT], rb[NXT], aaddr, baddr); \
+                    bd_wait<5 + NS>(ra[CUR], rb[CUR]);               \
+                    bd_mfma(acc, ra[CUR], rb[CUR]);                  \
+                    __builtin_amdgcn_sched_barrier(0);
+                    BD_STEP(0, 0, 1) BD_STEP(1, 1, 0) BD_STEP(2, 0, 1) BD_STEP(3, 1, 0)
+                    BD_STEP(4, 0, 1) BD_STEP(5, 1, 0) BD_STEP(6, 0, 1)
+#undef BD_STEP
+                }
+                // last substep: synchronise first (this wave's pieces of tile kt + 1 landed, its own
+                // reads of tile kt complete), start the next tile's first reads, then the MFMAs
+                fill.wait_leave(issued - kt - 2);
+                if constexpr (NS > 0) bd_wait<0>(ra[1], rb[1]);
                 __builtin_amdgcn_s_barrier();
-                if (kt + 1 < nk) bf_read<0>(ra[0], rb[0], aoff + stn * BD_STAGE_BYTES, boff + stn * BD_STAGE_BYTES);
-                bf_mfma(acc, ra[1], rb[1]);
-                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (NS > 0) {
+                    if (kt + 1 < nk) bd_read<0>(ra[0], rb[0], aoff + stn * BD_STAGE_BYTES, boff + stn * BD_STAGE_BYTES);
+                    bd_mfma(acc, ra[1], rb[1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 st = stn;
             }
         }
+        if (first_item) stamp(2);
         ++it;
-        bool pre = false;
+        pre = false;
         if (it < it1) {
-            item = bf_item(bp.items + it);
-            pre = nk > 0 && item.kt1 - item.kt0 > 0;
+            fill.load_item(it);
+            const int nkn = fill.item.kt1 - fill.item.kt0;
+            if (nk > 0 && nkn > 0) {
+                issued = 0;
+                for (; issued < BD_STAGES - 1 && issued < nkn; ++issued) fill.issue(issued);
+                pre = true;
+            }
         }
-        if (slot < 0) {
-            // Register budget (80 accumulator registers stay live into the first call): one call at a time, and the
-            // lane number made opaque per item, or the epilogue's per-lane addresses of BOTH strips are hoisted out
-            // of the item loop and held across the K loop -- EpiBackward then spills
-            int elane = lane;
-            asm volatile("" : "+v"(elane));
-            epi(acc[0], e_m0, n0 + wave * 32, elane, p.M, p.N, band);
-            __builtin_amdgcn_sched_barrier(0);
-            epi(acc[1], e_m0, n0 + wave * 32 + 16, elane, p.M, p.N, band);
-        } else {
-            // raw accumulator tiles of the 8-wave kernel's waves 2 wave and 2 wave + 1 (see there)
-            double* P = bp.part + ((size_t)slot * p.gn + bj) * BD_TILE_ELEMS + (size_t)(2 * wave) * (20 * 64) + lane;
+        if constexpr (NS > 0) {
+            if (slot < 0) {
+                // Register budget with two strips (80 accumulator registers stay live into the first call): one call
+                // at a time, and the lane number made opaque per item, or the epilogue's per-lane addresses of BOTH
+                // strips are hoisted out of the item loop and held across the K loop -- EpiBackward then spills
+                int elane = lane;
+                if constexpr (NS > 1) asm volatile("" : "+v"(elane));
+                epi(acc[0], band * BD_BM, n0 + strip0 * 16, elane, p.M, p.N, band);
+                if constexpr (NS > 1) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    epi(acc[1], band * BD_BM, n0 + strip0 * 16 + 16, elane, p.M, p.N, band);
+                }
+            } else {
+                double* tile = bp.part + ((size_t)slot * p.gn + bj) * BD_TILE_ELEMS;
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) P[(j * 20 + i * 4 + r) * 64] = acc[j][i][0][r];
+                for (int j = 0; j < NS; ++j) band_store_partial(tile, strip0 + j, lane, acc[j]);
+            }
         }
+        if (first_item) { stamp(3); first_item = false; }
+        // without a prefetch the next item's first LDS-DMA may overwrite a stage another wave is still reading
         if (!pre) __builtin_amdgcn_s_barrier();
     }
+    if constexpr (DBG)
+        if ((bp.mode & 16) && bp.clocks) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(4); }
+}
+
+// the 8-wave form: every wave fills (pieces wave, wave + 8, ...) and multiplies strip `wave`
+template <class Epi, bool DBG>
+__global__ __launch_bounds__(512) void dgemm_band_kernel(BandP bp, Epi epi)
+{
+    const BandWg wg(bp);
+    unsigned long long t0c = 0, t0r = 0;
+    if constexpr (DBG)
+        if (bp.clocks && blockIdx.x == 0 && threadIdx.x == 0) { t0c = __builtin_amdgcn_s_memtime(); t0r = __builtin_amdgcn_s_memrealtime(); }
+    band_walk<1, BandFill<8, BD_NA, BD_NB>, DBG>(bp, epi, wg, wg.wave, wg.wave);
+    if constexpr (DBG)
+        if (bp.clocks && blockIdx.x == 0 && threadIdx.x == 0) {
+            atomicAdd(bp.clocks, __builtin_amdgcn_s_memtime() - t0c);
+            atomicAdd(bp.clocks + 1, __builtin_amdgcn_s_memrealtime() - t0r);
+        }
+}
+
+// which epilogues run the feeder form (specialised where the epilogue is defined)
+template <class Epi> struct BandFeed { static constexpr bool ok = false; };
+template <> struct BandFeed<EpiAxpby> { static constexpr bool ok = true; };
+
+static inline bool band_feed_enabled()         // read per call: the parity tests run both forms in one process
+{
+    const char* e = getenv("GLMMR_MCML_BAND_FEED");
+    return !(e && !strcmp(e, "0"));
+}
+
+// the feeder form: waves 4-7 fill (pieces wave - 4, wave, ...), waves 0-3 multiply strips 2 wave and 2 wave + 1
+// (one static s_setprio 1 in the feeders measured no different: 839.4 / 844.9 against 842.9 / 842.9 ms per bench step)
+template <class Epi>
+__global__ __launch_bounds__(512) void dgemm_band_feed_kernel(BandP bp, Epi epi)
+{
+    const BandWg wg(bp);
+    if (wg.wave >= 4) band_walk<0, BandFill<4, BF_NA, BF_NB>, false>(bp, epi, wg, wg.wave - 4, 0);
+    else band_walk<2, BandNoFill, false>(bp, epi, wg, 0, 2 * wg.wave);
 }
 
 // second stage of the streamed decomposition: one workgroup of 2 waves per (split band, column tile,

@@ -79,10 +79,7 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_dl_kernel(GemmP p, Epi epi
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WN, wc = wave - wr * WN;
 
-    const int nblk = gridDim.x;
-    const int bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-    const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int nid = xcd_block_map(blockIdx.x, gridDim.x);
     int bi, bj;
     if (p.lower_only) {
         // only the tiles that touch the lower triangle were launched (dl_lower_tiles): row band bi holds

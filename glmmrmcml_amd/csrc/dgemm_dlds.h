@@ -115,10 +115,7 @@ __global__ __launch_bounds__(512) void dgemm_dlds_asm_kernel(GemmP p, Epi epi)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
 
-    const int nblk = p.gm * p.gn;
-    const int bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-    const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int nid = xcd_block_map(blockIdx.x, p.gm * p.gn);
     const int bi = nid / p.gn, bj = nid - bi * p.gn;
     const int m0 = bi * DL_BM, n0 = bj * DL_BN;
 

@@ -48,6 +48,15 @@ struct GemmP {
     size_t bsA = 0, bsB = 0;    // dgemm_dl batches (blockIdx.y): element strides of A and B from one problem to the next
 };
 
+// XCD-aware, bijective map blockIdx -> work index: workgroups are dealt round-robin to the 8 XCDs, so XCD
+// (bid % 8) takes a contiguous run of the nblk indices (the first nblk % 8 runs one longer) and what
+// neighbouring indices share -- a band of A, the B panels -- stays in that XCD's L2
+__device__ __forceinline__ int xcd_block_map(int bid, int nblk)
+{
+    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
 // WTM x WTN: 16x16 MFMA tiles per wave; WM x WN: waves per workgroup.
 template <int WTM, int WTN, int WM, int WN, bool BNMAJOR, int BK = 16, bool ATRANS = false>
 struct GemmCfg {
@@ -117,11 +126,7 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_mfma_kernel(GemmP p, Epi e
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave / WN, wc = wave - wr * WN;
 
-    // XCD-aware, bijective blockIdx -> tile map
-    const int nblk = p.gm * p.gn;
-    const int bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-    const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int nid = xcd_block_map(blockIdx.x, p.gm * p.gn);
     const int bi = nid / p.gn, bj = nid - bi * p.gn;
     if (p.lower_only && (bi + 1) * BM <= bj * BN) return;
     const int m0 = bi * BM, n0 = bj * BN;

@@ -536,7 +536,9 @@ int glmmr_mcml_dbg_dgemm_band_form(int M, int N, int K, const double* A, int lda
                                    int ldc, int* tiles_executed, int form, int* whole_band);
 /* sustained shader clock under the banded FP64 MFMA kernel: out3 = [ms per launch, shader MHz, executed TFLOP/s] */
 int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, double* out3);
-/* mode: 0 the real kernel; timing experiments (results meaningless): 1 no LDS-DMA, 2 no barriers, 4 no ds_reads */
+/* mode: 0 the clock-reading instantiation; negative: the sampler's own (events only); 16 prints per-workgroup phase
+ * stamps of one launch, + 32 every workgroup's.  Bits 1, 2, 4 and 8 (the K loop with parts switched off) are retired
+ * and rejected. */
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,7 @@
 """standalone timing of the banded FP64 MFMA kernel (plain store epilogue): ms per launch, shader MHz, executed TFLOP/s
-usage: python scripts/band_clocks.py [M=5000] [N=1024] [iters=50] [mode=0]"""
+usage: python scripts/band_clocks.py [M=5000] [N=1024] [iters=50] [mode=0]
+mode 0: the 8-wave form with clock reads; negative: the sampler's own instantiation (what a profiler should look at);
+16: per-workgroup phase stamps of one launch (mean / max), 48: the same and every workgroup's line"""
 import ctypes as C, sys
 sys.path.insert(0, '.')
 import numpy as np
