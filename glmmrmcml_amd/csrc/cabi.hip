@@ -1,6 +1,7 @@
 // cabi.hip -- the extern "C" boundary (include/glmmr_mcml_c.h).
 #include "../../include/glmmr_mcml_c.h"
 #include "ctx.h"
+#include "hmc_chain.h"
 #include <algorithm>
 #include <atomic>
 #include <random>
@@ -667,9 +668,7 @@ int drv_la_probe(Ctx& c, const double* start, int nstart, int kind, const double
 
 extern "C" int glmmr_mcml_sample_cols(int m, int chains)
 {
-    if (m <= 0) return 0;
-    if (chains <= 1) return m + 1;                 // mhmcmc.h:126
-    return chains * ((m + chains - 1) / chains);
+    return m <= 0 ? 0 : sample_shape(m, 0, chains).ncols;
 }
 
 // kernel timing (HIP events on the context's stream).

@@ -44,7 +44,7 @@ struct HmcState {
                                 // sampler packs the chains whose trees still grow into the first Cw columns)
     DevMat V, R, UP, GRAD, GRADP;   // Q x C
     DevMat MU, S;               // n x C
-    DevBuf chain;               // per-chain scalars, see hmc.hip
+    DevBuf chain;               // per-chain scalars, see hmc_chain.h
     DevBuf partial;             // per-(row slot, chain) partial sums
     int partial_slots = 0;
     bool cm = false;            // chain-major state (sparse ZL operator, hmc_cm.h): element (c, r) at c + r * ld
@@ -89,6 +89,8 @@ struct ComponentDev {
     ComponentPlan plan;
     bool ready = false;                        // the device copies below are there
     DevBuf item_ptr, var_ptr, vars, slot_ptr, slot_quarter, slot_i, slot_src, slot_d;
+    // slot_i, 8 ints per record: local columns [4], entries, last record of its observation, observation, 0
+    // slot_d, 8 doubles per record: values [4], xb_i, y_i (k_cp_fill_xy, hmc_traj.h), 0, 0
 };
 
 // HIP-event timing of the dominant kernels, on the stream they are launched on
@@ -357,6 +359,9 @@ int mvn_gen_L(Ctx& c, const double* theta, bool chol);
 int potrf_lower(Ctx& c, double* A, int n, int lda);                          // in place
 int potrf_leaf_profile(Ctx& c, unsigned long long* host10);                 // debug: phase clocks of one leaf
 int potrf_lower_checked(Ctx& c, double* A, int n, int lda);                  // + MCML_ENOTPD if a pivot failed
+// a kernel raised c.errflag() (a non-positive pivot): the flag is cleared, `message` becomes the error, MCML_ENOTPD.
+// Synchronises the stream
+int check_errflag(Ctx& c, const char* message);
 // x <- (L L')^-1 x for one vector, L from the LAST potrf_lower (its diagonal-block inverses are in c.linv)
 int potrs_lower_vec(Ctx& c, const double* L, int ldl, int n, double* x, double* tmp);
 int trsm_left_lower(Ctx& c, const double* L, int ldl, int n, double* U, int ldu, int m);

@@ -15,6 +15,7 @@
 //       reference does (mhmcmc.h:127), with seeds derived from (seed, iteration).
 #include "../../include/glmmr_mcml_c.h"
 #include "ctx.h"
+#include "glm.h"
 #include "optim.h"
 #include "theta_scale.h"
 #include "trace.h"
@@ -30,11 +31,6 @@ namespace mcml {
 int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed,
                uint32_t iter_idx, const double* inj_init, const double* inj_mom, uint8_t* flags_out,
                double* probs_out, glmmr_mcml_hmc_diag* diag, int* ncols_out);
-
-static bool is_gaussian(int flink) { return flink == 7 || flink == 8; }
-// family_=="gaussian"||"Gamma"||"beta" (likelihood.h:61,95): the map keys are
-// lower-case "gamma" (mcmlmodel.h:83-85), so "Gamma" never reaches this point
-static bool has_var_par(int flink) { return flink == 7 || flink == 8 || flink == 12; }
 
 // ---- device-backed scalar evaluations (all-reduced over ranks) ----
 static int eval_loglik(Ctx& c, const double* beta, double var_par, double* ll)
@@ -80,7 +76,7 @@ struct McmlOptim {
         beta.assign(start, start + P);
         theta.assign(start + P, start + P + R);
         cov_par_fix = theta;
-        sigma = is_gaussian(c.flink) ? start[P + R] : 0;         // mcmloptim.h:30
+        sigma = glm_is_gaussian(c.flink) ? start[P + R] : 0;         // mcmloptim.h:30
     }
 
     BobyqaOpts bopts() const { BobyqaOpts o; o.iprint = trace; if (maxfun > 0) o.maxfun = maxfun; return o; }
@@ -216,9 +212,9 @@ struct McmlOptim {
     int l_optim()
     {
         if (c.flink == 12) { set_error("l_optim: beta family is not built (reference reads par[P] out of range, defect D8)"); return MCML_EUNSUPPORTED; }
-        const bool g = is_gaussian(c.flink);
+        const bool g = glm_is_gaussian(c.flink);
         objective_fn f = [&](const std::vector<double>& par, double* v) {
-            model_var_par = has_var_par(c.flink) ? par[P] : 0.0;   // fix_var_ = false, fix_var_par_ = 0
+            model_var_par = glm_has_var_par(c.flink) ? par[P] : 0.0;   // fix_var_ = false, fix_var_par_ = 0
             double ll; MCML_TRY(eval_loglik(c, par.data(), model_var_par, &ll)); *v = -1 * ll; return (int)MCML_OK; };
         std::vector<double> x = beta, lo(P, -HUGE_VAL), up(P, HUGE_VAL);
         if (g) { x.push_back(sigma); lo.push_back(0.0); up.push_back(HUGE_VAL); }
@@ -318,7 +314,7 @@ struct McmlOptim {
     // f_optim (mcmloptim.h:91-113)
     int f_optim()
     {
-        const bool g = is_gaussian(c.flink);
+        const bool g = glm_is_gaussian(c.flink);
         double denomD = 0;
         MCML_TRY(eval_mvn(c, cov_par_fix.data(), &denomD));      // constant in the parameters
         if (comm_world(c) == 1 && batch_width() > 1) return f_optim_batch(batch_width(), denomD);
@@ -390,7 +386,7 @@ int drv_optim(Ctx& c, const double* start, int nstart, int trace, int mcnr, cons
               double* beta, double* theta, double* sigma)
 {
     const int P = c.P, R = c.cov.npar;
-    MCML_REQUIRE(start && nstart >= P + R + (is_gaussian(c.flink) ? 1 : 0), "start has %d values, need %d", nstart, P + R + (is_gaussian(c.flink) ? 1 : 0));
+    MCML_REQUIRE(start && nstart >= P + R + (glm_is_gaussian(c.flink) ? 1 : 0), "start has %d values, need %d", nstart, P + R + (glm_is_gaussian(c.flink) ? 1 : 0));
     MCML_REQUIRE(c.mcols > 0, "no samples u set");
     McmlOptim mc(c, start, trace, e ? e->maxfun : 0, 1.0);      // model built with var_par = 1 (mcml_optim.cpp:51)
     mc.theta_batch = e ? e->theta_batch : 0;
@@ -410,7 +406,7 @@ int drv_simlik(Ctx& c, const double* start, int nstart, int trace, const glmmr_m
                double* theta, double* sigma)
 {
     const int P = c.P, R = c.cov.npar;
-    MCML_REQUIRE(start && nstart >= P + R + (is_gaussian(c.flink) ? 1 : 0), "start too short");
+    MCML_REQUIRE(start && nstart >= P + R + (glm_is_gaussian(c.flink) ? 1 : 0), "start too short");
     MCML_REQUIRE(c.mcols > 0, "no samples u set");
     McmlOptim mc(c, start, trace, e ? e->maxfun : 0, 1.0);
     mc.theta_batch = e ? e->theta_batch : 0;
@@ -424,7 +420,7 @@ int drv_simlik(Ctx& c, const double* start, int nstart, int trace, const glmmr_m
 int drv_hess(Ctx& c, const double* start, int nstart, double tol, int trace, double* H)
 {
     const int P = c.P, R = c.cov.npar;
-    MCML_REQUIRE(start && nstart >= P + R + (is_gaussian(c.flink) ? 1 : 0), "start too short");
+    MCML_REQUIRE(start && nstart >= P + R + (glm_is_gaussian(c.flink) ? 1 : 0), "start too short");
     MCML_REQUIRE(c.mcols > 0, "no samples u set");
     McmlOptim mc(c, start, trace, 0, 1.0);
     return mc.f_hess(tol, H);
@@ -452,7 +448,7 @@ int drv_theta_round(Ctx& c, const double* thetas, int k, double* out)
 int drv_aic(Ctx& c, const double* beta_par, int nbeta, const double* cov_par, int ncov, double* out)
 {
     const int P = c.P;
-    const bool var = (c.flink == 7 || c.flink == 8 || c.flink == 12);
+    const bool var = glm_has_var_par(c.flink);
     MCML_REQUIRE(nbeta >= P + (var ? 1 : 0) && ncov >= c.cov.npar, "aic_mcml: parameter vectors too short");
     MCML_REQUIRE(c.mcols > 0, "no samples u set");
     const double var_par = var ? beta_par[P] : 0;
@@ -475,7 +471,7 @@ int drv_full(Ctx& c, const double* start, int nstart, int mcnr, int m, int maxit
     MCML_REQUIRE(start && nstart >= P + R + 1, "mcml_full: start needs c(beta, theta, sigma|1) = %d values", P + R + 1);
     MCML_REQUIRE(m > 0 && maxiter >= 1, "mcml_full: bad m / maxiter");
     std::vector<double> theta(start + P, start + P + R), beta(start, start + P);
-    double var_par = is_gaussian(c.flink) ? start[nstart - 1] : 1;          // :65
+    double var_par = glm_is_gaussian(c.flink) ? start[nstart - 1] : 1;          // :65
     const uint64_t seed = default_seed(e);
     const int chains = (e && e->chains > 0) ? e->chains : 1;
     MCML_TRY(mvn_gen_L(c, theta.data(), true));                               // :66-68
@@ -508,7 +504,7 @@ int drv_full(Ctx& c, const double* start, int nstart, int mcnr, int m, int maxit
         }
         const std::vector<double>& nb = mc.beta; const std::vector<double>& nt = mc.theta;
         double new_var_par = 1;
-        if (is_gaussian(c.flink)) new_var_par = mc.sigma;                      // :105
+        if (glm_is_gaussian(c.flink)) new_var_par = mc.sigma;                      // :105
         else new_var_par = var_par;
         maxdiff = 0;
         for (int i = 0; i < P; ++i) maxdiff = std::max(maxdiff, std::fabs(beta[i] - nb[i]));
@@ -527,7 +523,7 @@ int drv_full(Ctx& c, const double* start, int nstart, int mcnr, int m, int maxit
             for (double b : beta) printf(" %.6g", b);
             printf("  theta:");
             for (double t : theta) printf(" %.6g", t);
-            if (is_gaussian(c.flink)) printf("  sigma: %.6g", var_par);
+            if (glm_is_gaussian(c.flink)) printf("  sigma: %.6g", var_par);
             printf("  max diff %.4g  accept %.3f%s\n", maxdiff, dg.accept_rate, converged ? "  CONVERGED" : "");
             fflush(stdout);
         }

@@ -72,10 +72,16 @@ __device__ __forceinline__ double glm_logpdf(double y, double mu, double var_par
     return logl;
 }
 
+// gaussian / identity and gaussian / log: var_par is the residual standard deviation
+__host__ __device__ __forceinline__ bool glm_is_gaussian(int flink) { return flink == 7 || flink == 8; }
+// family_=="gaussian"||"Gamma"||"beta" (likelihood.h:61,95): the map keys are lower-case "gamma" (mcmlmodel.h:83-85), so
+// "Gamma" never reaches this point
+__host__ __device__ __forceinline__ bool glm_has_var_par(int flink) { return glm_is_gaussian(flink) || flink == 12; }
+
 // scalar applied after ZL' s (mcmlmodel.h:235,241,251,257,263)
 __host__ __device__ __forceinline__ double glm_score_post(double var_par, int flink)
 {
-    if (flink == 7 || flink == 8) return 1.0 / (var_par * var_par);
+    if (glm_is_gaussian(flink)) return 1.0 / (var_par * var_par);
     if (flink >= 9 && flink <= 11) return var_par;
     return 1.0;
 }

@@ -26,30 +26,11 @@
 #include "glm.h"
 #include "reduce.h"
 #include "rng.h"
+#include "hmc_chain.h"
 #include "hmc_cm.h"
 #include "hmc_traj.h"
 
 namespace mcml {
-
-struct ChainArrays {
-    double *e, *ebar, *H, *lpcur, *K0;
-    int *steps, *acc;
-    uint32_t* gen;
-    long long* leap;
-};
-
-static ChainArrays chain_arrays(const HmcState& h)
-{
-    ChainArrays a;
-    const size_t C = (size_t)round_up(h.C, 16);
-    double* d = h.chain.d();
-    a.e = d; a.ebar = d + C; a.H = d + 2 * C; a.lpcur = d + 3 * C; a.K0 = d + 4 * C;
-    a.leap = reinterpret_cast<long long*>(d + 5 * C);
-    a.steps = reinterpret_cast<int*>(d + 6 * C);
-    a.acc = a.steps + C;
-    a.gen = reinterpret_cast<uint32_t*>(a.acc + C);
-    return a;
-}
 
 // ------------------------------------------------------------------ GEMM epilogues
 // forward: MU = xb + acc ; S = score(y, MU)          (mcmlmodel.h:160-162,169-276)
@@ -244,11 +225,7 @@ __global__ __launch_bounds__(256) void k_hmc_init(double* V, int ld, int Q, Chai
     for (int q = threadIdx.x; q < Q; q += 256)
         V[q + (size_t)c * ld] = inj_init ? inj_init[q + (size_t)c * Q]
                                          : rng_normal(seed, (uint32_t)q, gid, 0u, 16u * iter_idx + 0u);
-    if (threadIdx.x == 0) {                                   // initialise_u, mhmcmc.h:47-59
-        ca.e[c] = 0.001; ca.ebar[c] = 1.0; ca.H[c] = 0.0; ca.acc[c] = 0; ca.leap[c] = 0;
-        ca.gen[c] = chain_minstd_seed(seed, gid, iter_idx);
-        ca.steps[c] = 1;
-    }
+    if (threadIdx.x == 0) chain_reset(ca, c, seed, gid, iter_idx);
 }
 
 // log_prob of column c: sum_i logf(y_i | MU_ic) + sum_k logN(x_k; 0, 1)   (mcmlmodel.h:138-153)
@@ -319,14 +296,7 @@ __global__ __launch_bounds__(256) void k_hmc_propose(const double* V, const doub
         UP[off] = v + e * r;
     }
     double tot = block_sum(ss, sh);
-    if (threadIdx.x == 0) {
-        ca.K0[c] = 0.5 * tot;
-        double st = round(lambda / e);                       // mhmcmc.h:69-70
-        if (!(st >= 1.0)) st = 1.0;
-        if (st > (double)max_steps) st = (double)max_steps;
-        ca.steps[c] = (int)st;
-        ca.leap[c] += (long long)st;
-    }
+    if (threadIdx.x == 0) chain_begin_proposal(ca, c, tot, lambda, max_steps);
 }
 
 // slot (nullable): host memory mapped into the device -- the count goes there too, tagged with the proposal's sequence number,
@@ -367,31 +337,7 @@ __global__ __launch_bounds__(256) void k_hmc_accept(double* V, double* GRAD, con
             if (k0 + 256 * u < Q) kin += r4[u] * r4[u];
     }
     kin = block_sum(kin, sh);
-    if (threadIdx.x == 0) {
-        const double lprt = 0.5 * kin, lpr = ca.K0[c], l1 = ca.lpcur[c];
-        const double prob = fmin(1.0, exp(-l1 + lpr + l2 - lprt));
-        uint32_t g = ca.gen[c];
-        const double runif = minstd_canonical(g);
-        ca.gen[c] = g;
-        const int acc = runif < prob;
-        acc_s = acc;
-        if (acc) { ca.lpcur[c] = l2; ca.acc[c] += 1; }
-        if (flags) flags[c + (size_t)it * C] = (uint8_t)acc;
-        if (probs) probs[c + (size_t)it * C] = prob;
-        if (adapt) {                                         // mhmcmc.h:107-114
-            const int iter = it + 1;
-            const double f1 = 1.0 / (iter + 10);
-            const double H = (1 - f1) * ca.H[c] + f1 * (target_accept - prob);
-            ca.H[c] = H;
-            const double loge = -4.60517 - (sqrt((double)iter / 0.05)) * H;
-            const double powm = pow((double)iter, -0.75);
-            const double logbare = powm * loge + (1 - powm) * log(ca.ebar[c]);
-            ca.e[c] = exp(loge);
-            ca.ebar[c] = exp(logbare);
-        } else {
-            ca.e[c] = ca.ebar[c];                            // :116
-        }
-    }
+    if (threadIdx.x == 0) acc_s = chain_decide(ca, c, l2, kin, target_accept, adapt, it, C, flags, probs);
     __syncthreads();
     const int acc = acc_s;
     if (acc)
@@ -624,10 +570,6 @@ static int hmc_backward(Ctx& c, const double* Xs, double* G, int s, double var_p
 }
 
 // ---- chain-major helpers (sparse ZL operator, hmc_cm.h) ----
-static CmChain cm_chain(const ChainArrays& a)
-{
-    return CmChain{a.e, a.ebar, a.H, a.lpcur, a.K0, a.steps, a.acc, a.gen, a.leap};
-}
 static int cm_fwd_chunks(const Ctx& c) { return (c.n + 4 * CM_FR - 1) / (4 * CM_FR); }     // workgroups of k_cm_forward = its ll partials
 struct CmParts { double *ll, *lp, *kin, *ss; int nchn, nchq, ldp; };
 static CmParts cm_parts(const Ctx& c)
@@ -691,7 +633,7 @@ static int sampler_init_state(Ctx& c, uint64_t seed, uint32_t chain_offset, uint
     const ChainArrays ca = chain_arrays(h);
     if (h.cm)
         hipLaunchKernelGGL(k_cm_init, dim3((h.C + 63) / 64, cm_parts(c).nchq), dim3(256), 0, c.stream, h.V.d(), h.V.ld, c.Q, h.C,
-                           cm_chain(ca), seed, chain_offset, iter_idx, init);
+                           ca, seed, chain_offset, iter_idx, init);
     else
         hipLaunchKernelGGL(k_hmc_init, dim3(h.C), dim3(256), 0, c.stream, h.V.d(), h.V.ld, c.Q, ca, seed, chain_offset, iter_idx,
                            init);
@@ -795,7 +737,7 @@ struct HmcTiming {
 // what the proposals of one hmc_sample call share; constant over the call but for pending_commit
 struct HmcCall {
     const glmmr_mcml_hmc_opts* o; double var_par; uint64_t seed; uint32_t iter_idx;
-    int C, d, total;                      // chains, draws per chain, proposals
+    SampleShape sh;                       // chains, draws per chain, proposals, columns
     ChainArrays ca;
     const double* mom; uint8_t* flags; double* probs;   // device, or null: injected momenta; accept flags / probabilities out
     const DevMat* samp;                   // the draws
@@ -811,20 +753,17 @@ struct HmcCall {
 static void commit_cm(Ctx& c, HmcCall& k, int it)
 {
     HmcState& h = c.hmc;
-    const bool stores_now = (k.C == 1) ? (it >= k.o->warmup - 1) : (it >= k.o->warmup);
-    if (it + 1 < k.total && !stores_now) k.pending_commit = true;
-    else hipLaunchKernelGGL(k_cm_commit, dim3((k.C + 63) / 64, cm_parts(c).nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(),
-                            h.UP.d(), h.GRADP.d(), h.V.ld, c.Q, k.C, h.cm_acc.as<int>());
+    int stride;
+    const bool stores_now = k.sh.column_of(it, &stride) >= 0;
+    if (it + 1 < k.sh.total && !stores_now) k.pending_commit = true;
+    else hipLaunchKernelGGL(k_cm_commit, dim3((k.sh.C + 63) / 64, cm_parts(c).nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(),
+                            h.UP.d(), h.GRADP.d(), h.V.ld, c.Q, k.sh.C, h.cm_acc.as<int>());
 }
 
 static void store_draw(Ctx& c, const HmcCall& k, int it)
 {
-    const int warmup = k.o->warmup;
-    int col = -1, stride = 0;
-    if (k.C == 1) {
-        if (it == warmup - 1) col = 0;                      // samples.col(0) = u_, :142
-        else if (it >= warmup) col = it - warmup + 1;       // samples.col(i+1) = u_, :147
-    } else if (it >= warmup) { col = it - warmup; stride = k.d; }
+    int stride;
+    const int col = k.sh.column_of(it, &stride);
     if (col >= 0) store_columns(c, *k.samp, stride, col);
 }
 
@@ -837,7 +776,7 @@ static int leapfrog_steps(Ctx& c, const HmcCall& k, StepAhead& ahead, HmcTiming&
     StepRing& ring = *k.ring;
     const unsigned seq = ++ring.seq;
     const int slot = (int)(seq % StepRing::SLOTS);
-    hipLaunchKernelGGL(k_max_steps, dim3(1), dim3(256), 0, c.stream, k.ca.steps, k.C, k.d_maxs, ring.d + slot, seq);
+    hipLaunchKernelGGL(k_max_steps, dim3(1), dim3(256), 0, c.stream, k.ca.steps, k.sh.C, k.d_maxs, ring.d + slot, seq);
     MCML_HIP(hipGetLastError());
     t.mark(HmcTiming::PROPOSE);
     int maxs = ahead.launched(seq, HmcTiming::now_ms);
@@ -874,14 +813,14 @@ static int propose_dense(Ctx& c, HmcCall& k, StepAhead& ahead, HmcTiming& t, int
 {
     HmcState& h = c.hmc;
     const glmmr_mcml_hmc_opts* o = k.o;
-    hipLaunchKernelGGL(k_hmc_propose, dim3(k.C), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(), h.UP.d(),
+    hipLaunchKernelGGL(k_hmc_propose, dim3(k.sh.C), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(), h.UP.d(),
                        h.V.ld, c.Q, k.ca, o->lambda, o->max_steps, k.seed, (uint32_t)o->chain_offset, k.iter_idx, it,
-                       k.mom, k.C);
+                       k.mom, k.sh.C);
     MCML_TRY(leapfrog_steps(c, k, ahead, t, it));
     dispatch_flink<1, 3, 7>(c.flink, [&](auto FL) {
-        hipLaunchKernelGGL((k_hmc_accept<FL()>), dim3(k.C), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(), h.UP.d(),
+        hipLaunchKernelGGL((k_hmc_accept<FL()>), dim3(k.sh.C), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(), h.UP.d(),
                            h.GRADP.d(), h.V.ld, c.Q, h.MU.d(), h.MU.ld, c.n, c.y.d(), k.var_par, c.flink, k.ca,
-                           o->target_accept, k.adapt(it), it, k.C, k.flags, k.probs);
+                           o->target_accept, k.adapt(it), it, k.sh.C, k.flags, k.probs);
     });
     store_draw(c, k, it);
     MCML_HIP(hipGetLastError());
@@ -895,17 +834,16 @@ static int propose_cm(Ctx& c, HmcCall& k, StepAhead& ahead, HmcTiming& t, int it
     HmcState& h = c.hmc;
     const glmmr_mcml_hmc_opts* o = k.o;
     const CmParts p = cm_parts(c);
-    const CmChain cc = cm_chain(k.ca);
-    const dim3 chains((k.C + 63) / 64);
+    const dim3 chains((k.sh.C + 63) / 64);
     hipLaunchKernelGGL(k_cm_propose, dim3(chains.x, p.nchq), dim3(256), 0, c.stream, h.V.d(), h.GRAD.d(), h.R.d(),
-                       h.UP.d(), h.V.ld, c.Q, k.C, cc, k.seed, (uint32_t)o->chain_offset, k.iter_idx, it, k.mom,
+                       h.UP.d(), h.V.ld, c.Q, k.sh.C, k.ca, k.seed, (uint32_t)o->chain_offset, k.iter_idx, it, k.mom,
                        p.ss, p.ldp, k.pending_commit ? h.cm_acc.as<int>() : nullptr, h.GRADP.d());
     k.pending_commit = false;
-    hipLaunchKernelGGL(k_cm_propose_fin, chains, dim3(256), 0, c.stream, p.ss, p.nchq, p.ldp, k.C, cc, o->lambda, o->max_steps);
+    hipLaunchKernelGGL(k_cm_propose_fin, chains, dim3(256), 0, c.stream, p.ss, p.nchq, p.ldp, k.sh.C, k.ca, o->lambda, o->max_steps);
     MCML_TRY(leapfrog_steps(c, k, ahead, t, it));
     MCML_TRY(cm_logprob_partials(c, h.UP.d(), h.R.d(), k.var_par, true));
     hipLaunchKernelGGL((k_cm_accept_fin<false>), chains, dim3(256), 0, c.stream, h.cm_part_fwd.d(), p.lp, p.kin,
-                       cm_fwd_chunks(c), p.nchq, p.ldp, k.C, cc, o->target_accept, k.adapt(it), it, k.flags, k.probs,
+                       cm_fwd_chunks(c), p.nchq, p.ldp, k.sh.C, k.ca, o->target_accept, k.adapt(it), it, k.flags, k.probs,
                        h.cm_acc.as<int>(), (const double*)nullptr, 0, 0.0, 0);
     commit_cm(c, k, it);
     store_draw(c, k, it);
@@ -919,9 +857,8 @@ static int propose_component(Ctx& c, HmcCall& k, int it)
 {
     HmcState& h = c.hmc;
     const glmmr_mcml_hmc_opts* o = k.o;
-    const CmChain cc = cm_chain(k.ca);
     double* const tpart = k.tpart; const size_t tstride = k.tstride;
-    TrajArgs a{h.V.d(), h.GRAD.d(), h.UP.d(), h.GRADP.d(), h.V.ld, k.C, c.Q, cc, k.seed, (uint32_t)o->chain_offset,
+    TrajArgs a{h.V.d(), h.GRAD.d(), h.UP.d(), h.GRADP.d(), h.V.ld, k.sh.C, c.Q, k.ca, k.seed, (uint32_t)o->chain_offset,
                k.iter_idx, it, k.mom, k.pending_commit ? h.cm_acc.as<int>() : nullptr, o->lambda, o->max_steps, c.flink,
                k.var_par, glm_score_post(k.var_par, c.flink), tpart, tpart + tstride, tpart + 2 * tstride,
                tpart + 3 * tstride, h.V.ld, c.cp.plan.max_vars};
@@ -934,8 +871,8 @@ static int propose_component(Ctx& c, HmcCall& k, int it)
     c.prof.unchain();
     MCML_TRY(rc);
     const int ni = c.cp.plan.nitems();
-    hipLaunchKernelGGL((k_cm_accept_fin<true>), dim3((k.C + 63) / 64), dim3(256), 0, c.stream, tpart + tstride, tpart + 2 * tstride,
-                       tpart + 3 * tstride, ni, ni, h.V.ld, k.C, cc, o->target_accept, k.adapt(it), it, k.flags, k.probs,
+    hipLaunchKernelGGL((k_cm_accept_fin<true>), dim3((k.sh.C + 63) / 64), dim3(256), 0, c.stream, tpart + tstride, tpart + 2 * tstride,
+                       tpart + 3 * tstride, ni, ni, h.V.ld, k.sh.C, k.ca, o->target_accept, k.adapt(it), it, k.flags, k.probs,
                        h.cm_acc.as<int>(), tpart, ni, o->lambda, o->max_steps);
     commit_cm(c, k, it);
     store_draw(c, k, it);
@@ -958,10 +895,8 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
         return exact_gaussian_sample(c, beta, var_par, o, seed, iter_idx, nullptr, flags_out, probs_out, diag, ncols_out);
     if (c.draws_mode == 2 && exact_component_applicable(c))      // the same target where M is block diagonal (hmc_exact_comp.h)
         return exact_component_sample(c, beta, var_par, o, seed, iter_idx, nullptr, flags_out, probs_out, diag, ncols_out);
-    const int C = o->chains > 0 ? o->chains : 1;
-    const int d = (C == 1) ? o->nsamp : (o->nsamp + C - 1) / C;   // draws per chain
-    const int total = o->warmup + d;
-    const int ncols = (C == 1) ? d + 1 : C * d;                   // mhmcmc.h:126: Q x (nsamp+1)
+    const SampleShape sh = sample_shape(o->nsamp, o->warmup, o->chains);
+    const int C = sh.C, total = sh.total, ncols = sh.ncols;
     const int Q = c.Q;
     HmcState& h = c.hmc;
     HmcTiming t;
@@ -995,13 +930,13 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
 
     // component-local trajectories: one launch per proposal instead of the loop over the steps
     const bool traj = h.cm && cm_traj_used(c);
-    HmcCall k{o, var_par, seed, iter_idx, C, d, total, chain_arrays(h), d_mom.d(), d_flags.as<uint8_t>(), d_probs.d(), &samp,
+    HmcCall k{o, var_par, seed, iter_idx, sh, chain_arrays(h), d_mom.d(), d_flags.as<uint8_t>(), d_probs.d(), &samp,
               h.cm ? cm_fuse_width(c) : 0, traj ? h.cp_part.d() : nullptr, traj ? (size_t)c.cp.plan.nitems() * h.V.ld : 0,
               &ring, c.scalars.as<int>() + 34, false};
 
     MCML_TRY(sampler_init_state(c, seed, (uint32_t)o->chain_offset, iter_idx, d_init.d()));
     MCML_TRY(hmc_eval_state(c, var_par));
-    if (C == 1 && o->warmup == 0) store_columns(c, samp, 0, 0);
+    if (sh.single_chain_layout && o->warmup == 0) store_columns(c, samp, 0, 0);   // no warm-up: column 0 is the start value
     if (traj) {                                 // xb follows beta: the records' copy of it
         const int ns = c.cp.plan.nslots;
         hipLaunchKernelGGL(k_cp_fill_xy, dim3((ns + 255) / 256), dim3(256), 0, c.stream, ns, c.cp.slot_i.as<int>(), c.xb.d(),
@@ -1017,7 +952,7 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
     }
     t.loop = t.phase_end();
     MCML_TRY(samples_to_U(c, samp, ncols));     // return (L * samples)  (mhmcmc.h:155)
-    c.niter = (C == 1) ? d : ncols;             // mcmlmodel.h:73 vs mhmcmc.h:126 (D5)
+    c.niter = sh.niter;
     if (flags_out) MCML_TRY(copy_d2h(flags_out, d_flags.p, (size_t)C * total, c.stream));
     if (probs_out) MCML_TRY(copy_d2h(probs_out, d_probs.p, sizeof(double) * (size_t)C * total, c.stream));
     double dg[6] = {0, 0, 0, 0, 0, 0};

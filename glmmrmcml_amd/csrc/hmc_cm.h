@@ -16,46 +16,12 @@
 #pragma once
 #include "ctx.h"
 #include "glm.h"
+#include "hmc_chain.h"   // ChainArrays and the per-chain rules
 #include "rng.h"
+#include "sload.h"       // the scalar loads of wave-uniform metadata
 #include "sparse_plan.h"      // CM_ROWS, cm_qrows and the launch decisions hmc.hip shares with the test hook
 
 namespace mcml {
-
-struct CmChain {                  // the per-chain scalars of hmc.hip::ChainArrays
-    double *e, *ebar, *H, *lpcur, *K0;
-    int *steps, *acc;
-    uint32_t* gen;
-    long long* leap;
-};
-
-// ---- scalar loads of wave-uniform, read-only metadata --------------------------------------------------------------
-// hipcc keeps such loads on the vector pipe (64 lanes fetching one address) because it cannot prove that the kernel's
-// stores do not alias them; these issue them on the scalar pipe, a batch at a time with one wait.  The pointers must be
-// wave-uniform (SGPR operands); dword / dwordx2 loads need 4-byte alignment only.
-__device__ __forceinline__ void sload8(const int* ip, const double* dp, int (&iv)[8], double (&dv)[8])
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_load_dword %0, %16, 0x0\n\ts_load_dword %1, %16, 0x4\n\ts_load_dword %2, %16, 0x8\n\ts_load_dword %3, %16, 0xc\n\t"
-                 "s_load_dword %4, %16, 0x10\n\ts_load_dword %5, %16, 0x14\n\ts_load_dword %6, %16, 0x18\n\ts_load_dword %7, %16, 0x1c\n\t"
-                 "s_load_dwordx2 %8, %17, 0x0\n\ts_load_dwordx2 %9, %17, 0x8\n\ts_load_dwordx2 %10, %17, 0x10\n\ts_load_dwordx2 %11, %17, 0x18\n\t"
-                 "s_load_dwordx2 %12, %17, 0x20\n\ts_load_dwordx2 %13, %17, 0x28\n\ts_load_dwordx2 %14, %17, 0x30\n\ts_load_dwordx2 %15, %17, 0x38\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&s"(iv[0]), "=&s"(iv[1]), "=&s"(iv[2]), "=&s"(iv[3]), "=&s"(iv[4]), "=&s"(iv[5]), "=&s"(iv[6]), "=&s"(iv[7]),
-                   "=&s"(dv[0]), "=&s"(dv[1]), "=&s"(dv[2]), "=&s"(dv[3]), "=&s"(dv[4]), "=&s"(dv[5]), "=&s"(dv[6]), "=&s"(dv[7])
-                 : "s"(ip), "s"(dp) : "memory");
-#else
-    for (int u = 0; u < 8; ++u) { iv[u] = ip[u]; dv[u] = dp[u]; }
-#endif
-}
-__device__ __forceinline__ void sload_f64x2(const double* a, const double* b, double& x, double& y)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(x), "=&s"(y) : "s"(a), "s"(b) : "memory");      // early clobber: an output must not reuse a pointer's registers
-#else
-    x = *a; y = *b;
-#endif
-}
 
 // ---- products -------------------------------------------------------------------------------------------------
 // forward: MU[c, i] = xb_i + sum_k val_k X[c, col_k] ; S = score(y_i, MU)      (ELL row of observation i)
@@ -244,17 +210,6 @@ __global__ __launch_bounds__(256) void k_cm_backward_long(int Q, int C, int ldc,
 //   forward   LX = L X        (k_cm_Lrow, Q x C, tiny)      MU = xb + Z LX    (k_cm_forward on the rows of Z)
 //   backward  T  = Z' S       (k_cm_backward*, mode 2)      g  = -x + post * L' T, leapfrog update (k_cm_Lcol)
 // so that X / S are gathered nnz(Z) times instead of nnz(ZL) times.
-__device__ __forceinline__ double sload_f64(const double* a)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    double x;
-    asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(x) : "s"(a) : "memory");
-    return x;
-#else
-    return *a;
-#endif
-}
-
 // LX[c, q] = sum_{j = start(q)}^{q} L[q, j] X[c, j]  (row q of the block-diagonal lower-triangular L, ascending j)
 __global__ __launch_bounds__(256) void k_cm_Lrow(int Q, int C, int ldc, const int* start, const double* L, int ldl,
                                                  const double* X, double* LX)
@@ -413,7 +368,7 @@ __device__ __forceinline__ double cm_sum_chunks(const double* part, int nchunk, 
     return ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
 }
 
-__global__ __launch_bounds__(256) void k_cm_init(double* V, int ldc, int Q, int C, CmChain ca, uint64_t seed,
+__global__ __launch_bounds__(256) void k_cm_init(double* V, int ldc, int Q, int C, ChainArrays ca, uint64_t seed,
                                                  uint32_t chain_offset, uint32_t iter_idx, const double* inj_init)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -424,11 +379,7 @@ __global__ __launch_bounds__(256) void k_cm_init(double* V, int ldc, int Q, int 
     for (int q = q0 + w; q < q0 + QR && q < Q; q += 4)
         V[c + (size_t)q * ldc] = inj_init ? inj_init[q + (size_t)c * Q]
                                           : rng_normal(seed, (uint32_t)q, gid, 0u, 16u * iter_idx + 0u);
-    if (blockIdx.y == 0 && w == 0) {                              // initialise_u, mhmcmc.h:47-59
-        ca.e[c] = 0.001; ca.ebar[c] = 1.0; ca.H[c] = 0.0; ca.acc[c] = 0; ca.leap[c] = 0;
-        ca.gen[c] = chain_minstd_seed(seed, gid, iter_idx);
-        ca.steps[c] = 1;
-    }
+    if (blockIdx.y == 0 && w == 0) chain_reset(ca, c, seed, gid, iter_idx);
 }
 
 // partial sums of log f(y_i | MU[c,i]) over observation chunks [0, nchunk_n) and of log N(X[c,q]; 0, 1) (+ R[c,q]^2
@@ -490,7 +441,7 @@ __global__ __launch_bounds__(256) void k_cm_lp0_fin(const double* part_ll, const
 // from UP / GRADP and written through to V / GRAD here, so the separate commit pass (k_cm_commit: one more read and write of
 // the Q x C state, 131 us per proposal at config 5) is folded into this one.
 __global__ __launch_bounds__(256) void k_cm_propose(double* V, double* GRAD, double* R, double* UP, int ldc,
-                                                    int Q, int C, CmChain ca, uint64_t seed, uint32_t chain_offset,
+                                                    int Q, int C, ChainArrays ca, uint64_t seed, uint32_t chain_offset,
                                                     uint32_t iter_idx, int it, const double* inj_mom, double* part_ss,
                                                     int ldp, const int* accflag, const double* GRADP)
 {
@@ -518,18 +469,13 @@ __global__ __launch_bounds__(256) void k_cm_propose(double* V, double* GRAD, dou
     cm_block_partial(ss, part_ss, blockIdx.y, ldp, c, cin);
 }
 
-__global__ __launch_bounds__(256) void k_cm_propose_fin(const double* part_ss, int nchunk_q, int ldp, int C, CmChain ca,
+__global__ __launch_bounds__(256) void k_cm_propose_fin(const double* part_ss, int nchunk_q, int ldp, int C, ChainArrays ca,
                                                         double lambda, int max_steps)
 {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
     const double tot = cm_sum_chunks(part_ss, nchunk_q, ldp, c < C ? c : 0);
     if (threadIdx.x >= 64 || c >= C) return;
-    ca.K0[c] = 0.5 * tot;
-    double st = round(lambda / ca.e[c]);                          // mhmcmc.h:69-70
-    if (!(st >= 1.0)) st = 1.0;
-    if (st > (double)max_steps) st = (double)max_steps;
-    ca.steps[c] = (int)st;
-    ca.leap[c] += (long long)st;
+    chain_begin_proposal(ca, c, tot, lambda, max_steps);
 }
 
 // new_proposal, second part (mhmcmc.h:80-117): the decision of every chain
@@ -538,7 +484,7 @@ __global__ __launch_bounds__(256) void k_cm_propose_fin(const double* part_ss, i
 // trajectory ran with (part_k0, nchunk_k0, lambda, max_steps are read in this form only)
 template <bool TRAJ>
 __global__ __launch_bounds__(256) void k_cm_accept_fin(const double* part_ll, const double* part_lp, const double* part_kin,
-                                                       int nchunk_n, int nchunk_q, int ldp, int C, CmChain ca,
+                                                       int nchunk_n, int nchunk_q, int ldp, int C, ChainArrays ca,
                                                        double target_accept, int adapt, int it, uint8_t* flags,
                                                        double* probs, int* accflag, const double* part_k0, int nchunk_k0,
                                                        double lambda, int max_steps)
@@ -551,38 +497,8 @@ __global__ __launch_bounds__(256) void k_cm_accept_fin(const double* part_ll, co
     double k0 = 0.0;
     if constexpr (TRAJ) k0 = cm_sum_chunks(part_k0, nchunk_k0, ldp, cc);
     if (threadIdx.x >= 64 || c >= C) return;
-    if constexpr (TRAJ) {                                         // k_cm_propose_fin
-        ca.K0[c] = 0.5 * k0;
-        double st = round(lambda / ca.e[c]);
-        if (!(st >= 1.0)) st = 1.0;
-        if (st > (double)max_steps) st = (double)max_steps;
-        ca.steps[c] = (int)st;
-        ca.leap[c] += (long long)st;
-    }
-    const double l2 = a + b;
-    const double lprt = 0.5 * kin, lpr = ca.K0[c], l1 = ca.lpcur[c];
-    const double prob = fmin(1.0, exp(-l1 + lpr + l2 - lprt));
-    uint32_t g = ca.gen[c];
-    const double runif = minstd_canonical(g);
-    ca.gen[c] = g;
-    const int acc = runif < prob;
-    accflag[c] = acc;
-    if (acc) { ca.lpcur[c] = l2; ca.acc[c] += 1; }
-    if (flags) flags[c + (size_t)it * C] = (uint8_t)acc;
-    if (probs) probs[c + (size_t)it * C] = prob;
-    if (adapt) {                                                  // mhmcmc.h:107-114
-        const int iter = it + 1;
-        const double f1 = 1.0 / (iter + 10);
-        const double H = (1 - f1) * ca.H[c] + f1 * (target_accept - prob);
-        ca.H[c] = H;
-        const double loge = -4.60517 - (sqrt((double)iter / 0.05)) * H;
-        const double powm = pow((double)iter, -0.75);
-        const double logbare = powm * loge + (1 - powm) * log(ca.ebar[c]);
-        ca.e[c] = exp(loge);
-        ca.ebar[c] = exp(logbare);
-    } else {
-        ca.e[c] = ca.ebar[c];                                     // :116
-    }
+    if constexpr (TRAJ) chain_begin_proposal(ca, c, k0, lambda, max_steps);
+    accflag[c] = chain_decide(ca, c, a + b, kin, target_accept, adapt, it, C, flags, probs);
 }
 
 // accepted chains: V <- UP, GRAD <- GRADP

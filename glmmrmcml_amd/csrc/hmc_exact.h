@@ -34,8 +34,8 @@ __global__ __launch_bounds__(256) void k_exact_rhs(const double* ZL, int ld, int
     if (lane == 0) b[j] = post * s;
 }
 
-// T[q, j] = z(q, j) + w[q]: column j is draw j % d of chain j / d (C > 1) or draw j of chain 0 (C = 1), the layout
-// store_draw gives the HMC draws; z is injected (Q x ncols, no padding) or the standard normal of rng.h, tag 8
+// T[q, j] = z(q, j) + w[q]: column j is a draw of a chain as in the HMC draws' layout (draw_of_column, hmc_chain.h); z is
+// injected (Q x ncols, no padding) or the standard normal of rng.h, tag 8
 __global__ __launch_bounds__(256) void k_exact_fill(double* T, int ldt, int Q, int ncols, const double* w, const double* inj_z,
                                                     uint64_t seed, uint32_t chain_offset, uint32_t iter_idx, int C, int d)
 {
@@ -43,7 +43,8 @@ __global__ __launch_bounds__(256) void k_exact_fill(double* T, int ldt, int Q, i
     if (q >= Q) return;
     const double wq = w[q];
     for (int j = blockIdx.y; j < ncols; j += gridDim.y) {
-        const uint32_t chain = C > 1 ? (uint32_t)(j / d) : 0u, draw = C > 1 ? (uint32_t)(j % d) : (uint32_t)j;
+        uint32_t chain, draw;
+        draw_of_column(j, C, d, &chain, &draw);
         const double z = inj_z ? inj_z[q + (size_t)j * Q]
                                : rng_normal(seed, (uint32_t)q, chain_offset + chain, draw, 16u * iter_idx + 8u);
         T[q + (size_t)j * ldt] = z + wq;
@@ -77,10 +78,8 @@ static int exact_gaussian_sample(Ctx& c, const double* beta, double var_par, con
         set_error("exact draws need a gaussian / identity model on the dense ZL operator with L set");
         return MCML_EUNSUPPORTED;
     }
-    const int C = o->chains > 0 ? o->chains : 1;
-    const int d = (C == 1) ? o->nsamp : (o->nsamp + C - 1) / C;   // draws per chain
-    const int total = o->warmup + d;
-    const int ncols = (C == 1) ? d + 1 : C * d;                   // hmc_sample's shape; column 0 of one chain is just another draw
+    const SampleShape sh = sample_shape(o->nsamp, o->warmup, o->chains);   // column 0 of one chain is just another draw
+    const int ncols = sh.ncols;
     const int Q = c.Q, n = c.n;
     const double post = glm_score_post(var_par, c.flink);
     ExactState& x = c.exact;
@@ -108,25 +107,18 @@ static int exact_gaussian_sample(Ctx& c, const double* beta, double var_par, con
         MCML_TRY(copy_h2d(d_z.p, inj_z, sizeof(double) * (size_t)Q * ncols, c.stream));
     }
     hipLaunchKernelGGL(k_exact_fill, dim3((Q + 255) / 256, ncols < 1024 ? ncols : 1024), dim3(256), 0, c.stream, x.T.d(), x.T.ld,
-                       Q, ncols, x.b.d(), d_z.d(), seed, (uint32_t)o->chain_offset, iter_idx, C, d);
+                       Q, ncols, x.b.d(), d_z.d(), seed, (uint32_t)o->chain_offset, iter_idx, sh.C, sh.d);
     MCML_HIP(hipGetLastError());
     prof.mark();
     MCML_TRY(trsm_left_lower_trans(c, x.M.d(), x.M.ld, Q, x.T.d(), x.T.ld, ncols));
     prof.mark();
     MCML_TRY(samples_to_U(c, x.T, ncols));                        // return (L * samples)  (mhmcmc.h:155)
     prof.mark();
-    c.niter = (C == 1) ? d : ncols;
+    c.niter = sh.niter;
     c.last_kernel[0] = c.last_kernel[1] = KERNEL_EXACT;
     MCML_HIP(hipStreamSynchronize(c.stream));
     prof.collect(x.ms);
-    if (flags_out) memset(flags_out, 1, (size_t)C * total);
-    if (probs_out) for (size_t i = 0; i < (size_t)C * total; ++i) probs_out[i] = 1.0;
-    if (diag) {
-        diag->accept_rate = 1.0;
-        diag->mean_e = 0.0; diag->min_e = 0.0; diag->max_e = 0.0;
-        diag->max_steps_used = 0; diag->leapfrog_total = 0;
-    }
-    if (ncols_out) *ncols_out = ncols;
+    exact_finish(sh, flags_out, probs_out, diag, ncols_out);
     return MCML_OK;
 }
 

@@ -47,14 +47,6 @@ __global__ __launch_bounds__(256) void k_exc_fill(double* W, int n, double v)
 // vector block), a uniform load from the factor scratch above (one wave per workgroup, the vector block alone: 64 KB at
 // CP_WIDE_MAX_VARS).
 constexpr int EXC_WAVES = 4;
-// the lanes of one wave exchange R_c through LDS, whose operations complete in issue order: only the compiler has to be kept
-// from moving them across (la_comp.h's lac_wave_sync; that header's kernels belong to laplace.hip)
-__device__ __forceinline__ void exc_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 inline int exc_ldr(int max_vars) { return max_vars | 1; }
 inline int exc_wave_doubles(int max_vars) { return max_vars <= CP_MAX_VARS ? max_vars * 64 + max_vars * exc_ldr(max_vars) : max_vars * 64; }
 inline int exc_waves(int max_vars) { return max_vars <= CP_MAX_VARS ? EXC_WAVES : 1; }
@@ -70,7 +62,7 @@ struct ExcArgs {
     double* out;                         // chain-major: element (column j, variable q) at j + q * ld
     size_t ld;
     int nitems, Q, ncols, mv;            // mv: the plan's max_vars (sizes the LDS)
-    int C, d;                            // column j is draw j % d of chain j / d (C > 1) or draw j of chain 0: k_exact_fill's layout
+    int C, d;                            // draw_of_column
     uint64_t seed; uint32_t chain_offset, tag;
 };
 
@@ -88,19 +80,20 @@ __global__ __launch_bounds__(64 * EXC_WAVES) void k_exc_draw(ExcArgs a)
     double* R = x + a.mv * 64;                                                   // column-major, ldr (STAGE)
     const int col = blockIdx.y * 64 + lane;
     const bool live = col < a.ncols;
-    const uint32_t chain = a.chain_offset + (a.C > 1 ? (uint32_t)(col / a.d) : 0u);
-    const uint32_t draw = a.C > 1 ? (uint32_t)(col % a.d) : (uint32_t)col;
+    uint32_t chain, draw;
+    draw_of_column(col, a.C, a.d, &chain, &draw);
+    chain += a.chain_offset;
     const int c0 = a.item_ptr ? a.item_ptr[item] : item, c1 = a.item_ptr ? a.item_ptr[item + 1] : item + 1;
     for (int comp = c0; comp < c1; ++comp) {
         const int v0 = a.var_ptr[comp], nv = a.var_ptr[comp + 1] - v0;           // 1 <= nv <= mv
         const double* F = a.fac + a.fac_ptr[comp];                               // lower triangle, leading dimension nv
         if (STAGE) {
-            exc_wave_sync();                         // the previous component's reads of R
+            wave_lds_sync();                         // the previous component's reads of R
             for (int e = lane; e < nv * nv; e += 64) {
                 const int i = e % nv, j = e / nv;
                 if (i >= j) R[i + j * ldr] = F[e];
             }
-            exc_wave_sync();
+            wave_lds_sync();
         }
         for (int i = 0; i < nv; ++i) {
             const int q = a.vars[v0 + i];
@@ -139,10 +132,8 @@ static int exact_component_sample(Ctx& c, const double* beta, double var_par, co
                   "component above %d variables", CP_WIDE_MAX_VARS);
         return MCML_EUNSUPPORTED;
     }
-    const int C = o->chains > 0 ? o->chains : 1;
-    const int d = (C == 1) ? o->nsamp : (o->nsamp + C - 1) / C;   // draws per chain
-    const int total = o->warmup + d;
-    const int ncols = (C == 1) ? d + 1 : C * d;                   // hmc_sample's shape
+    const SampleShape sh = sample_shape(o->nsamp, o->warmup, o->chains);
+    const int ncols = sh.ncols;
     const int Q = c.Q, n = c.n;
     const double post = glm_score_post(var_par, c.flink);
     const ComponentDev& cp = c.cp;
@@ -183,7 +174,7 @@ static int exact_component_sample(Ctx& c, const double* beta, double var_par, co
     // ---- the draws, chain-major
     const bool stage = p.max_vars <= CP_MAX_VARS;                 // then the plan is feasible: its work items are built
     ExcArgs a{stage ? cp.item_ptr.as<int>() : nullptr, cp.var_ptr.as<int>(), cp.vars.as<int>(), x.fac_ptr.as<int>(), x.fac.d(),
-              x.mu.d(), d_z.d(), x.CM.d(), ldc, stage ? p.nitems() : p.ncomp, Q, ncols, p.max_vars, C, d, seed,
+              x.mu.d(), d_z.d(), x.CM.d(), ldc, stage ? p.nitems() : p.ncomp, Q, ncols, p.max_vars, sh.C, sh.d, seed,
               (uint32_t)o->chain_offset, 16u * iter_idx + 8u};
     const int lds = exc_lds_bytes(p.max_vars);
     const dim3 grid((a.nitems + exc_waves(p.max_vars) - 1) / exc_waves(p.max_vars), (ncols + 63) / 64);
@@ -204,25 +195,12 @@ static int exact_component_sample(Ctx& c, const double* beta, double var_par, co
     prof.mark();
     MCML_TRY(samples_to_U(c, x.T, ncols));                        // return (L * samples)  (mhmcmc.h:155)
     prof.mark();
-    c.niter = (C == 1) ? d : ncols;
+    c.niter = sh.niter;
     c.last_kernel[0] = c.last_kernel[1] = KERNEL_EXACT_COMPONENT;
-    int flag = 0;                                                 // a non-positive pivot of some M_c
-    MCML_TRY(copy_d2h(&flag, c.errflag(), sizeof(int), c.stream));
-    MCML_HIP(hipStreamSynchronize(c.stream));
+    const int rc = check_errflag(c, "exact draws: I + ZL' ZL / sigma^2 is not positive definite");   // a pivot of some M_c
     prof.collect(x.ms);
-    if (flag) {
-        MCML_HIP(hipMemsetAsync(c.errflag(), 0, sizeof(int), c.stream));
-        set_error("exact draws: I + ZL' ZL / sigma^2 is not positive definite");
-        return MCML_ENOTPD;
-    }
-    if (flags_out) memset(flags_out, 1, (size_t)C * total);
-    if (probs_out) for (size_t i = 0; i < (size_t)C * total; ++i) probs_out[i] = 1.0;
-    if (diag) {
-        diag->accept_rate = 1.0;
-        diag->mean_e = 0.0; diag->min_e = 0.0; diag->max_e = 0.0;
-        diag->max_steps_used = 0; diag->leapfrog_total = 0;
-    }
-    if (ncols_out) *ncols_out = ncols;
+    MCML_TRY(rc);
+    exact_finish(sh, flags_out, probs_out, diag, ncols_out);
     return MCML_OK;
 }
 

@@ -23,14 +23,14 @@ namespace mcml {
 
 struct CpDev {                       // ComponentPlan on the device (ctx.h ComponentDev)
     const int *item_ptr, *var_ptr, *vars, *slot_ptr, *slot_quarter;
-    const int* slot_i;               // 8 per record: local columns [4], entries, last record of its observation, observation, 0
-    const double* slot_d;            // 8 per record: values [4], xb_i, y_i, 0, 0
+    const int* slot_i;               // the records, 8 ints and 8 doubles each (ComponentDev)
+    const double* slot_d;
 };
 
 struct TrajArgs {
     double *V, *GRAD, *UP, *GRADP;
     int ld, C, Q;
-    CmChain ca;
+    ChainArrays ca;
     uint64_t seed; uint32_t chain_offset, iter_idx; int it;
     const double* inj_mom;
     const int* accflag;              // nullable: the previous proposal's decisions, not yet applied to V / GRAD (k_cm_propose)
@@ -47,38 +47,6 @@ __global__ __launch_bounds__(256) void k_cp_fill_xy(int nslots, const int* slot_
     if (s >= nslots) return;
     const int i = slot_i[8 * (size_t)s + 6];
     slot_d[8 * (size_t)s + 4] = xb[i]; slot_d[8 * (size_t)s + 5] = y[i];
-}
-
-// ---- wave-uniform metadata on the scalar pipe (see hmc_cm.h) ----
-typedef int cp_i8 __attribute__((ext_vector_type(8)));
-typedef double cp_d8 __attribute__((ext_vector_type(8)));
-// one record: 32 + 64 bytes, naturally aligned (hipMalloc'ed arrays, strides of 32 and 64 bytes), one wait
-__device__ __forceinline__ void sload_slot(const int* ip, const double* dp, cp_i8& iv, cp_d8& dv)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dwordx16 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(iv), "=&s"(dv) : "s"(ip), "s"(dp) : "memory");
-#else
-    for (int u = 0; u < 8; ++u) { iv[u] = ip[u]; dv[u] = dp[u]; }
-#endif
-}
-__device__ __forceinline__ void sload_i32x2(const int* p, int& a, int& b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %2, 0x4\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a), "=&s"(b) : "s"(p) : "memory");
-#else
-    a = p[0]; b = p[1];
-#endif
-}
-__device__ __forceinline__ int sload_i32(const int* p)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    int a;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a) : "s"(p) : "memory");
-    return a;
-#else
-    return *p;
-#endif
 }
 
 // the observations of records [s0, s1) (whole observations): eta, score, accumulate.  xs / gs: this lane's column of the
@@ -137,10 +105,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_cm_traj(CpDev m, TrajArgs a)
     const int cc = cin ? c : 0;
     const uint32_t gid = a.chain_offset + (uint32_t)cc;
     const double e = a.ca.e[cc];
-    double stf = round(a.lambda / e);                        // mhmcmc.h:69-70, as k_cm_propose_fin
-    if (!(stf >= 1.0)) stf = 1.0;
-    if (stf > (double)a.max_steps) stf = (double)a.max_steps;
-    const int st = (int)stf;
+    const int st = chain_step_count(a.lambda, e, a.max_steps);
     const bool accp = a.accflag && a.accflag[cc];
     const double* Vin = accp ? a.UP : a.V;
     const double* Gin = accp ? a.GRADP : a.GRAD;

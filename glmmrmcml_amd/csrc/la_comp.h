@@ -22,8 +22,8 @@ static_assert(LAC_WAVES * LAC_WAVE_DOUBLES * 8 <= 64 * 1024, "k_lac_factor keeps
 
 struct LacArgs {
     const int *var_ptr, *vars, *slot_ptr;            // ComponentDev
-    const int* slot_i;                               // 8 per record: local columns [4], entries, last record of its observation, observation, 0
-    const double* slot_d;                            // 8 per record: values [4], (xb, y, 0, 0: not read here)
+    const int* slot_i;                               // the records, 8 ints and 8 doubles each (ComponentDev); xb and y are not
+    const double* slot_d;                            // read here
     const double* W;                                 // n
     int ncomp;
     const double* g;                                 // nullable: right-hand side (Q); x = M^-1 g is written to x
@@ -33,15 +33,6 @@ struct LacArgs {
     double* fac = nullptr;                           // nullable: the lower triangle of chol(M_c), diagonal included, is stored
     const int* fac_ptr = nullptr;                    // column-major (leading dimension nv) at fac + fac_ptr[comp] (hmc_exact_comp.h)
 };
-
-// the lanes of ONE wave exchange data through LDS: LDS operations of a wave complete in issue order, so only the
-// compiler has to be kept from moving them across
-__device__ __forceinline__ void lac_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // grid ceil(ncomp / LAC_WAVES), 64 * LAC_WAVES threads.  No workgroup barrier: the waves are independent
 __global__ __launch_bounds__(64 * LAC_WAVES) void k_lac_factor(LacArgs a)
@@ -79,16 +70,16 @@ __global__ __launch_bounds__(64 * LAC_WAVES) void k_lac_factor(LacArgs a)
             if (last || s >= s1) break;
         }
         const double wi = a.W[obs];
-        lac_wave_sync();                             // the previous observation's reads of r
+        wave_lds_sync();                             // the previous observation's reads of r
         if (lane < nv) r[lane] = rj;
-        lac_wave_sync();
+        wave_lds_sync();
         for (int i = i0, j = j0; j < nv;) {
             M[i + j * LAC_LD] += wi * r[i] * r[j];
             i += r64; j += q64;
             if (i >= nv) { i -= nv; ++j; }
         }
     }
-    lac_wave_sync();
+    wave_lds_sync();
     // ---- right-looking Cholesky of the lower triangle; lane & 31 = row, two columns of the trailing update at a time
     bool bad = false;
     const int ti = lane & 31, tj = lane >> 5;
@@ -96,13 +87,13 @@ __global__ __launch_bounds__(64 * LAC_WAVES) void k_lac_factor(LacArgs a)
         const double d = M[k + k * LAC_LD];
         if (!(d > 0.0)) { bad = true; break; }       // the same value in every lane
         const double sd = sqrt(d);
-        lac_wave_sync();
+        wave_lds_sync();
         if (lane == k) M[k + k * LAC_LD] = sd;
         else if (lane > k && lane < nv) M[lane + k * LAC_LD] = M[lane + k * LAC_LD] / sd;
-        lac_wave_sync();
+        wave_lds_sync();
         for (int j = k + 1 + tj; j < nv; j += 2)
             if (ti >= j && ti < nv) M[ti + j * LAC_LD] -= M[ti + k * LAC_LD] * M[j + k * LAC_LD];
-        lac_wave_sync();
+        wave_lds_sync();
     }
     double lg = (!bad && lane < nv) ? log(M[lane + lane * LAC_LD]) : 0.0;
     lg = wave_sum(lg);
@@ -121,20 +112,20 @@ __global__ __launch_bounds__(64 * LAC_WAVES) void k_lac_factor(LacArgs a)
     if (!a.g || bad) return;
     // ---- x = L'^-1 L^-1 g: column sweeps forward, row sweeps backward (stride LAC_LD: conflict-free)
     if (lane < nv) xs[lane] = a.g[a.vars[v0 + lane]];
-    lac_wave_sync();
+    wave_lds_sync();
     for (int k = 0; k < nv; ++k) {
         const double yk = xs[k] / M[k + k * LAC_LD];
-        lac_wave_sync();
+        wave_lds_sync();
         if (lane == k) xs[k] = yk;
         else if (lane > k && lane < nv) xs[lane] -= M[lane + k * LAC_LD] * yk;
-        lac_wave_sync();
+        wave_lds_sync();
     }
     for (int k = nv - 1; k >= 0; --k) {
         const double xk = xs[k] / M[k + k * LAC_LD];
-        lac_wave_sync();
+        wave_lds_sync();
         if (lane == k) xs[k] = xk;
         else if (lane < k) xs[lane] -= M[k + lane * LAC_LD] * xk;
-        lac_wave_sync();
+        wave_lds_sync();
     }
     if (lane < nv) a.x[a.vars[v0 + lane]] = xs[lane];
 }
@@ -168,12 +159,6 @@ inline int lac_waves(const ComponentPlan& p, int forced = -1)
     if (p.max_vars > CP_MAX_VARS) return 4;
     if (forced == 1 || forced == 4) return forced;
     return p.max_rows >= CP_WAVES4_ROWS ? 4 : 1;
-}
-
-// workgroup barrier for LDS traffic only, as mvn.hip's leaf_sync: __syncthreads() would also wait for the global stores
-__device__ __forceinline__ void lacw_sync()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 // grid ncomp, LACW_THREADS threads, lacw_lds_bytes(mv) of dynamic LDS; mv = the plan's max_vars.  Every entry of M_c and of
@@ -233,7 +218,7 @@ __global__ __launch_bounds__(LACW_THREADS) void k_lac_factor_wg(LacArgs a, int m
             if (lane < nv) st[b * nv + lane] = rj;
             if (lane + 64 < nv) st[b * nv + lane + 64] = rj2;
         }
-        lacw_sync();
+        lds_barrier();
         for (int i = i0, j = j0; j < nv;) {
             if (i >= j) {
                 double m = M[i + j * ld];
@@ -243,10 +228,10 @@ __global__ __launch_bounds__(LACW_THREADS) void k_lac_factor_wg(LacArgs a, int m
             i += r256; j += q256;
             if (i >= nv) { i -= nv; ++j; }
         }
-        lacw_sync();                                 // the batch is read: the staging area is free again
+        lds_barrier();                                 // the batch is read: the staging area is free again
         s += __popcll(__ballot(ob < nb && t < s1));
     }
-    lacw_sync();
+    lds_barrier();
     // ---- right-looking Cholesky of the lower triangle: the column is scaled by its rows' threads, the trailing columns
     // are dealt over the waves, their rows over the lanes.  Two barriers per column: d is read by everyone before the
     // first, and overwritten by sqrt(d) after it
@@ -255,18 +240,18 @@ __global__ __launch_bounds__(LACW_THREADS) void k_lac_factor_wg(LacArgs a, int m
         if (!(d > 0.0)) { bad = true; break; }       // the same value in every thread
         const double sd = sqrt(d);
         if (tid > k && tid < nv) M[tid + k * ld] = M[tid + k * ld] / sd;
-        lacw_sync();
+        lds_barrier();
         if (tid == 0) M[k + k * ld] = sd;
         for (int j = k + 1 + w; j < nv; j += 4) {
             const double mjk = M[j + k * ld];
             for (int i = j + lane; i < nv; i += 64) M[i + j * ld] -= M[i + k * ld] * mjk;
         }
-        lacw_sync();
+        lds_barrier();
     }
     double lg = (!bad && tid < nv) ? log(M[tid + tid * ld]) : 0.0;
     lg = wave_sum(lg);
     if (lane == 0) red[w] = lg;
-    lacw_sync();
+    lds_barrier();
     if (tid == 0) {
         a.logdet[comp] = 2 * (((red[0] + red[1]) + red[2]) + red[3]);       // moremaths.h:105-116
         if (bad) *a.errflag = 1;
@@ -285,12 +270,12 @@ __global__ __launch_bounds__(LACW_THREADS) void k_lac_factor_wg(LacArgs a, int m
     double xv = tid < nv ? a.g[a.vars[v0 + tid]] : 0.0;
     for (int k = 0; k < nv; ++k) {
         if (tid == k) { xv = xv / M[k + k * ld]; xs[k] = xv; }
-        lacw_sync();
+        lds_barrier();
         if (tid > k && tid < nv) xv -= M[tid + k * ld] * xs[k];
     }
     for (int k = nv - 1; k >= 0; --k) {
         if (tid == k) { xv = xv / M[k + k * ld]; xs[k] = xv; }
-        lacw_sync();
+        lds_barrier();
         if (tid < k) xv -= M[k + tid * ld] * xs[k];
     }
     if (tid < nv) a.x[a.vars[v0 + tid]] = xv;

@@ -55,9 +55,6 @@ int lac_factor_launch(Ctx& c, const double* W, const double* g, double* x, doubl
 }
 int lac_waves_now(const ComponentPlan& p) { return lac_waves(p, lac_forced_waves()); }
 
-static bool la_is_gaussian(int flink) { return flink == 7 || flink == 8; }
-static bool la_has_var_par(int flink) { return flink == 7 || flink == 8 || flink == 12; }
-
 // ------------------------------------------------------------------ kernels
 // y = A x  (A rows x cols, column-major): one thread per row
 __global__ __launch_bounds__(256) void k_la_gemv_n(const double* A, int lda, int rows, int cols, const double* x,
@@ -263,7 +260,7 @@ struct LaFit {
         beta.assign(start, start + P);
         theta.assign(start + P, start + P + R);
         theta_model = theta;
-        sigma = la_is_gaussian(flink) ? start[P + R] : 0;         // mcmloptim.h:30
+        sigma = glm_is_gaussian(flink) ? start[P + R] : 0;         // mcmloptim.h:30
         var_par = 1.0;
         hv.assign(Q, 0.0);
         MCML_TRY(v.ensure(sizeof(double) * (size_t)(Q + 64)));
@@ -368,7 +365,7 @@ struct LaFit {
         if (useL) { MCML_TRY(ensure_model_L()); MCML_TRY(zl_times_v(zv.d())); }
         else MCML_TRY(z_times_v(zv.d()));
         double nvar = 1.0;
-        if (la_is_gaussian(flink)) nvar = var_par * var_par;
+        if (glm_is_gaussian(flink)) nvar = var_par * var_par;
         else if (flink == 12) nvar = 1 + var_par;
         hipLaunchKernelGGL(k_la_W, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.xb.d(), zv.d(), n, flink, nvar, W.d());
         MCML_HIP(hipGetLastError());
@@ -403,18 +400,7 @@ struct LaFit {
         return MCML_OK;
     }
     // a non-positive pivot of some M_c, as potrf_lower_checked reports one of M; synchronises the stream
-    int lac_check()
-    {
-        int flag = 0;
-        MCML_TRY(copy_d2h(&flag, c.errflag(), sizeof(int), c.stream));
-        MCML_HIP(hipStreamSynchronize(c.stream));
-        if (flag) {
-            MCML_HIP(hipMemsetAsync(c.errflag(), 0, sizeof(int), c.stream));
-            set_error("mcml_la: ZL' W ZL + I is not positive definite");
-            return MCML_ENOTPD;
-        }
-        return MCML_OK;
-    }
+    int lac_check() { return check_errflag(c, "mcml_la: ZL' W ZL + I is not positive definite"); }
     int logdet_M(double* out)
     {
         if (comp) {
@@ -460,14 +446,14 @@ struct LaFit {
     // LA_likelihood_cov (likelihood.h:142-183): par = (theta[, var_par])
     int obj_cov(const std::vector<double>& par, double* val)
     {
-        const int Rp = la_has_var_par(flink) ? (int)par.size() - 1 : (int)par.size();
-        if (la_has_var_par(flink)) var_par = par[Rp];
+        const int Rp = glm_has_var_par(flink) ? (int)par.size() - 1 : (int)par.size();
+        if (glm_has_var_par(flink)) var_par = par[Rp];
         return obj_theta_tail(par.data(), val);
     }
     // LA_likelihood_btheta (likelihood.h:185-230): par = (beta, theta[, var_par if gaussian])
     int obj_btheta(const std::vector<double>& par, double* val)
     {
-        if (la_is_gaussian(flink)) var_par = par.back();
+        if (glm_is_gaussian(flink)) var_par = par.back();
         MCML_TRY(model_update_beta(c, par.data()));
         MCML_TRY(update_W(false));
         return obj_theta_tail(par.data() + P, val);
@@ -492,13 +478,13 @@ struct LaFit {
     int la_optim_cov()
     {
         std::vector<double> x(theta), lo(R, 1e-6), up;
-        if (la_has_var_par(flink)) { x.push_back(sigma); lo.push_back(0.0); }
+        if (glm_has_var_par(flink)) { x.push_back(sigma); lo.push_back(0.0); }
         up.assign(x.size(), HUGE_VAL);
         objective_fn f = [&](const std::vector<double>& par, double* val) { return obj_cov(par, val); };
         BobyqaResult r;
         MCML_TRY(bobyqa(f, x, lo, up, bopts(), &r));
         theta.assign(r.x.begin(), r.x.begin() + R);
-        if (la_has_var_par(flink)) { sigma = r.x[R]; var_par = sigma; }   // model left at the optimum
+        if (glm_has_var_par(flink)) { sigma = r.x[R]; var_par = sigma; }   // model left at the optimum
         return MCML_OK;
     }
     // mcmloptim.h:153-178
@@ -506,14 +492,14 @@ struct LaFit {
     {
         std::vector<double> x(beta), lo(P, -HUGE_VAL), up;
         for (int i = 0; i < R; ++i) { x.push_back(theta[i]); lo.push_back(1e-6); }
-        if (la_is_gaussian(flink)) { x.push_back(sigma); lo.push_back(0.0); }
+        if (glm_is_gaussian(flink)) { x.push_back(sigma); lo.push_back(0.0); }
         up.assign(x.size(), HUGE_VAL);
         objective_fn f = [&](const std::vector<double>& par, double* val) { return obj_btheta(par, val); };
         BobyqaResult r;
         MCML_TRY(bobyqa(f, x, lo, up, bopts(), &r));
         beta.assign(r.x.begin(), r.x.begin() + P);
         theta.assign(r.x.begin() + P, r.x.begin() + P + R);
-        if (la_is_gaussian(flink)) { sigma = r.x[P + R]; var_par = sigma; }
+        if (glm_is_gaussian(flink)) { sigma = r.x[P + R]; var_par = sigma; }
         return MCML_OK;
     }
     // mcmloptim.h:180-195
@@ -522,7 +508,7 @@ struct LaFit {
         if (flink == 12) { set_error("hess_la: the beta family is not built (the reference functor mis-sizes theta)"); return MCML_EUNSUPPORTED; }
         std::vector<double> x(beta);
         x.insert(x.end(), theta.begin(), theta.end());
-        if (la_has_var_par(flink)) x.push_back(sigma);
+        if (glm_has_var_par(flink)) x.push_back(sigma);
         std::vector<double> nd(x.size(), tol), none;
         objective_fn f = [&](const std::vector<double>& par, double* val) { return obj_btheta(par, val); };
         return fd_hessian(f, x, nd, false, none, none, H);
@@ -609,7 +595,7 @@ struct LaFit {
             MCML_TRY(update_W(nr));
             MCML_TRY(la_optim_cov());
             std::vector<double> nt = theta;
-            if (la_is_gaussian(flink) || (nr && flink == 12)) new_vp = sigma;     // :84 vs :222
+            if (glm_is_gaussian(flink) || (nr && flink == 12)) new_vp = sigma;     // :84 vs :222
             maxdiff = fabs(vp - new_vp);
             for (int i = 0; i < P; ++i) maxdiff = fmax(maxdiff, fabs(b0[i] - nb[i]));
             for (int i = 0; i < R; ++i) maxdiff = fmax(maxdiff, fabs(t0[i] - nt[i]));
@@ -641,7 +627,7 @@ struct LaFit {
             ++it;
         }
         MCML_TRY(la_optim_bcov());
-        if (la_is_gaussian(flink)) vp = sigma;
+        if (glm_is_gaussian(flink)) vp = sigma;
         for (int i = 0; i < P; ++i) beta_out[i] = beta[i];
         for (int i = 0; i < R; ++i) theta_out[i] = theta[i];
         *sigma_out = vp;
@@ -650,7 +636,7 @@ struct LaFit {
             if (usehess) {
                 std::vector<double> H;
                 MCML_TRY(hess_la(1e-4, &H));
-                const int nv = P + R + (la_has_var_par(flink) ? 1 : 0);
+                const int nv = P + R + (glm_has_var_par(flink) ? 1 : 0);
                 std::vector<double> Hi;
                 MCML_TRY(spd_inverse_host(H, nv, &Hi));
                 for (int i = 0; i < nv && i < nstart; ++i) se_out[i] = sqrt(Hi[i + (size_t)i * nv]);
@@ -719,7 +705,7 @@ int drv_la(Ctx& c, const double* start, int nstart, int nr, int usehess, double 
            int* converged, int* iters)
 {
     MCML_REQUIRE(c.n > 0 && c.cov.npar > 0, "mcml_la: the context has no model / covariance");
-    MCML_REQUIRE(start && nstart >= c.P + c.cov.npar + (la_is_gaussian(c.flink) ? 1 : 0), "mcml_la: start too short");
+    MCML_REQUIRE(start && nstart >= c.P + c.cov.npar + (glm_is_gaussian(c.flink) ? 1 : 0), "mcml_la: start too short");
     MCML_REQUIRE(beta && theta && sigma, "mcml_la: null output");
     LaScope scope(c);
     LaFit f(c);

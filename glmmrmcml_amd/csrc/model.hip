@@ -507,7 +507,7 @@ int model_mcnr_stats(Ctx& c, double var_par, double* stats)
     MCML_TRY(model_update_zu(c));
     const int n = c.n, P = c.P, m = c.niter;
     double nvar_par = 1.0;                       // mcmlmodel.h:123-130
-    if (c.flink == 7 || c.flink == 8) nvar_par *= var_par * var_par;
+    if (glm_is_gaussian(c.flink)) nvar_par *= var_par * var_par;
     else if (c.flink >= 9 && c.flink <= 11) nvar_par *= var_par;
     else if (c.flink == 12) nvar_par *= (1 + var_par);
     const int ns = P * P + P + 2;

@@ -292,12 +292,6 @@ template <> struct LeafProf<true> {
     }
     __device__ void stamp(int i) const { if (threadIdx.x == 0) out[i] = now(); }
 };
-// workgroup barrier for LDS traffic only.  __syncthreads() also waits for vmcnt(0): with Linv stored to global
-// memory as the leaf goes, every barrier would wait for those stores to be acknowledged (~1-2 us each).
-__device__ __forceinline__ void leaf_sync()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 template <bool PROF>
 __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int n, double* Linv, int* errflag,
                                                     size_t bsA, size_t bsL, LeafProf<PROF> prof)
@@ -469,7 +463,7 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
             rest_update(kt - 1);
             inverse_row(kt - 1);
         }
-        leaf_sync();
+        lds_barrier();
         if constexpr (PROF) {
             prof.q3 += prof.now() - prof.u;      // wave 0's wait at the barrier
             prof.ta += prof.now() - prof.t; prof.t = prof.now();
@@ -491,7 +485,7 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
 #pragma unroll
             for (int r = 0; r < 4; ++r) S[(r0 + lk + 4 * r) * LS + kb + l15] = acc[r];
         }
-        leaf_sync();
+        lds_barrier();
         if constexpr (PROF) { prof.tb += prof.now() - prof.t; prof.t = prof.now(); }
         // P3: wave 0 updates what its next P1 reads and goes on without a barrier; the other waves pick up the
         // rest of this step's trailing update at the top of the next iteration
@@ -503,7 +497,7 @@ __global__ __launch_bounds__(LEAF_NT) void k_potrf_leaf(double* A, int lda, int 
         }
         if constexpr (PROF) prof.tc += prof.now() - prof.t;
     }
-    leaf_sync();
+    lds_barrier();
     if constexpr (PROF) prof.stamp(5);
     {   // write L
         const int i = tid & 127, j0 = tid >> 7;
@@ -1070,14 +1064,14 @@ static int theta_arg(const Ctx& c, const double* theta, ThetaArg& th)
     return MCML_OK;
 }
 
-static int check_errflag(Ctx& c, const char* what)
+int check_errflag(Ctx& c, const char* message)
 {
     int flag = 0;
     MCML_TRY(copy_d2h(&flag, c.errflag(), sizeof(int), c.stream));
     MCML_HIP(hipStreamSynchronize(c.stream));
     if (flag) {
         MCML_HIP(hipMemsetAsync(c.errflag(), 0, sizeof(int), c.stream));
-        set_error("%s: covariance block is not positive definite", what);
+        set_error("%s", message);
         return MCML_ENOTPD;
     }
     return MCML_OK;
@@ -1086,7 +1080,7 @@ static int check_errflag(Ctx& c, const char* what)
 int potrf_lower_checked(Ctx& c, double* A, int n, int lda)
 {
     MCML_TRY(potrf_lower(c, A, n, lda));
-    return check_errflag(c, "potrf");
+    return check_errflag(c, "potrf: covariance block is not positive definite");
 }
 
 // ------------------------------------------------------------------ loglik
@@ -1214,7 +1208,7 @@ int mvn_loglik_sum_on(Ctx& c, const double* theta, const double* Us, int ldu, in
 {
     MCML_TRY(mvn_loglik_enqueue(c, theta, Us, ldu, m));
     MCML_TRY(copy_d2h(sum_out, c.scalars.d(), sizeof(double), c.stream));
-    MCML_TRY(check_errflag(c, "mvn_ll"));
+    MCML_TRY(check_errflag(c, "mvn_ll: covariance block is not positive definite"));
     return MCML_OK;
 }
 
@@ -1343,7 +1337,7 @@ int mvn_gen_L(Ctx& c, const double* theta, bool chol)
         }
     }
     MCML_HIP(hipGetLastError());
-    MCML_TRY(check_errflag(c, "genD"));
+    MCML_TRY(check_errflag(c, "genD: covariance block is not positive definite"));
     if (chol) c.l_foreign = false;
     c.have_L = chol;
     return MCML_OK;

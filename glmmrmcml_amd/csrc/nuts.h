@@ -713,8 +713,8 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
     const double delta = o->adapt_delta > 0 ? o->adapt_delta : 0.8;
     MCML_REQUIRE(delta < 1, "nuts: adapt_delta must be in (0, 1)");
     const double eps0 = o->stepsize > 0 ? o->stepsize : 1.0;
-    const int C = o->chains, Q = c.Q;
-    const int d = (o->nsamp + C - 1) / C, total = o->warmup + d, ncols = C * d;
+    const SampleShape sh = sample_shape(o->nsamp, o->warmup, o->chains, true);
+    const int C = sh.C, Q = c.Q, total = sh.total, ncols = sh.ncols;
     HmcState& h = c.hmc;
     MCML_TRY(model_update_beta(c, beta));
     MCML_TRY(hmc_alloc(c, C));
@@ -807,11 +807,13 @@ int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nut
                 heur_leaps += r.leapfrogs - before;
             }
         }
-        if (it >= o->warmup) store_columns(c, samp, d, it - o->warmup);
+        int stride;
+        const int col = sh.column_of(it, &stride);
+        if (col >= 0) store_columns(c, samp, stride, col);
         MCML_HIP(hipGetLastError());
     }
     MCML_TRY(samples_to_U(c, samp, ncols));                              // u = L * gamma (gen_u_samples.R:66)
-    c.niter = ncols;
+    c.niter = sh.niter;
     if (depth_out) MCML_TRY(copy_d2h(depth_out, d_depth.p, sizeof(int) * (size_t)C * total, c.stream));
     if (nleap_out) MCML_TRY(copy_d2h(nleap_out, d_nleap.p, sizeof(int) * (size_t)C * total, c.stream));
     if (eps_out) MCML_TRY(copy_d2h(eps_out, d_eps.p, sizeof(double) * (size_t)C * total, c.stream));

@@ -1,0 +1,40 @@
+"""Generates tests/golden/sampler_bits.json: SHA-256 of what the samplers return on the cases of
+tests/test_gpu_sampler_bits.py, and of the cases' seeded designs.
+
+The fixture pins the bits of a REFERENCE build, so run it on the GPU with GLMMR_MCML_LIB pointing at the library built
+from the commit to pin to -- the parent of a change to the samplers' per-chain rules or sample layout, never the code
+under test:
+
+    GLMMR_MCML_LIB=/path/to/parent/libglmmr_mcml_hip.so python tests/golden/make_sampler_bits.py "<commit it was built from>"
+"""
+import json
+import os
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(0, os.path.dirname(HERE))
+import test_gpu_sampler_bits as sb       # noqa: E402
+
+
+def main():
+    assert os.environ.get("GLMMR_MCML_LIB"), "point GLMMR_MCML_LIB at the reference build (see the docstring)"
+    cases = {}
+    for name in sb.CASES:
+        with pytest.MonkeyPatch.context() as mp:
+            cases[name] = sb.digests(name, mp)
+    out = {"recorded_from": sys.argv[1],
+           "hash": "SHA-256 of the values in column-major order: accept flags as bytes, everything else as float64; inputs: "
+                   "Z, X, y, cov, data, eff_range, beta, theta; diag: " + ", ".join(sb.DIAG_KEYS) + " (nuts: "
+                   + ", ".join(sb.NUTS_DIAG_KEYS) + ")",
+           "cases": cases}
+    with open(os.path.join(HERE, "sampler_bits.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out, indent=1))
+
+
+if __name__ == "__main__":
+    main()
