@@ -514,36 +514,6 @@ extern "C" int glmmr_mcml_ctx_gen_D(glmmr_mcml_ctx* h, const double* theta, int 
     return download_matrix(out, ldo, c.L.d(), c.L.ld, c.Q, c.Q, c.stream);
 }
 
-// beta += (1/m sum X'W_iX)^-1 X' (1/m sum W_i detadmu resid_i); sigma = mean sigma_i
-// (mcmloptim.h:227-235); Gauss-Jordan with partial pivoting stands in for Eigen's .inverse()
-int mcml::mcnr_finish(int P, const double* stats, const double* beta, double* beta_out, double* sigma_out)
-{
-    const double m = stats[P * P + P + 1];
-    MCML_REQUIRE(m > 0, "mcnr: no samples");
-    std::vector<double> A(stats, stats + P * P), B((size_t)P * P, 0.0);
-    for (auto& v : A) v *= (double)1 / m;
-    for (int i = 0; i < P; i++) B[i + (size_t)i * P] = 1.0;
-    for (int c = 0; c < P; c++) {
-        int p = c; double best = fabs(A[c + (size_t)c * P]);
-        for (int i = c + 1; i < P; i++) if (fabs(A[i + (size_t)c * P]) > best) { best = fabs(A[i + (size_t)c * P]); p = i; }
-        if (best == 0.0 || best != best) { set_error("mcnr: X'WX is singular"); return MCML_ESINGULAR; }
-        if (p != c) for (int j = 0; j < P; j++) { std::swap(A[c + (size_t)j * P], A[p + (size_t)j * P]); std::swap(B[c + (size_t)j * P], B[p + (size_t)j * P]); }
-        double d = A[c + (size_t)c * P];
-        for (int j = 0; j < P; j++) { A[c + (size_t)j * P] /= d; B[c + (size_t)j * P] /= d; }
-        for (int i = 0; i < P; i++) if (i != c) {
-            double f = A[i + (size_t)c * P];
-            if (f != 0.0) for (int j = 0; j < P; j++) { A[i + (size_t)j * P] -= f * A[c + (size_t)j * P]; B[i + (size_t)j * P] -= f * B[c + (size_t)j * P]; }
-        }
-    }
-    for (int a = 0; a < P; a++) {
-        double inc = 0;
-        for (int b = 0; b < P; b++) inc += B[a + (size_t)b * P] * (stats[P * P + b] / m);
-        beta_out[a] = beta[a] + inc;
-    }
-    *sigma_out = stats[P * P + P] / m;
-    return MCML_OK;
-}
-
 extern "C" int glmmr_mcml_ctx_loglik(glmmr_mcml_ctx* h, const double* beta, double var_par, double* out)
 {
     MCML_REQUIRE(h && beta && out, "loglik: null argument");
@@ -1028,7 +998,7 @@ extern "C" int glmmr_mcml_gen_u_samples(const double* Z, const double* L, const 
 // The n x n host array A goes to the device AS GIVEN (upper triangle included), potrf_lower_checked factorises it, then every
 // solve runs on a fresh copy of B (n x m) against that factor: trsm_left_lower -> Xfwd, trsm_left_lower_trans -> Ytrans,
 // potrs_lower_vec column by column -> Zpotrs (each n x m with leading dimension ldb; null: skipped).  A receives the whole
-// array as the device left it, Linv (nullable) the ceil(n / 128) inverted 128 x 128 diagonal blocks of c.linv.
+// array as the device left it, Linv (nullable) the ceil(n / 128) inverted 128 x 128 diagonal blocks of c.chol.linv.
 extern "C" int glmmr_mcml_dbg_chol(glmmr_mcml_ctx* h, int n, double* A, int lda, int m, const double* B, int ldb,
                                    double* Xfwd, double* Ytrans, double* Zpotrs, double* Linv)
 {
@@ -1043,7 +1013,7 @@ extern "C" int glmmr_mcml_dbg_chol(glmmr_mcml_ctx* h, int n, double* A, int lda,
     MCML_TRY(potrf_lower_checked(c, dA.d(), n, dA.ld));
     MCML_TRY(download_matrix(A, lda, dA.d(), dA.ld, n, n, c.stream));
     if (Linv) {
-        MCML_TRY(copy_d2h(Linv, c.linv.d(), sizeof(double) * (size_t)((n + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB, c.stream));
+        MCML_TRY(copy_d2h(Linv, c.chol.linv.d(), sizeof(double) * (size_t)((n + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB, c.stream));
         MCML_HIP(hipStreamSynchronize(c.stream));
     }
     if (m == 0) return MCML_OK;

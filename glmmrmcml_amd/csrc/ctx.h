@@ -3,15 +3,13 @@
 // parameter vectors go down and scalars / small statistics come back.
 #pragma once
 #include "common.h"
+#include "chol.h"
 #include "covspec.h"
 #include "band_plan.h"
 #include "component_plan.h"
 #include "step_ahead.h"
 
 namespace mcml {
-
-constexpr int CHOL_NB = 128;     // panel / leaf size of the blocked Cholesky / TRSM
-constexpr int SMALL_BLOCK = 32;  // blocks up to this size are factorised one wave each
 
 // cross-rank reduction hook (sum, f64, in place on a device buffer).  Single
 // process: null.  bench.py / the distributed front end install a callback that
@@ -142,65 +140,6 @@ struct KernelProf {
     ~KernelProf() { for (auto e : ev) (void)hipEventDestroy(e); }
 };
 
-// the factorisation's launch sequence as a hipGraph (mvn.hip potrf_graphed): the theta-step evaluates the same
-// (matrix, shape) dozens of times per MCML iteration; key = what the captured kernels' arguments depend on
-struct CholGraph {
-    hipGraphExec_t exec = nullptr;
-    const double* A = nullptr; const double* linv = nullptr; int lda = 0, n = 0, extra = 0, seen = 0;
-    long long used = 0;                 // launch counter value at the last use (the least recently used entry is replaced)
-    // Calibration (mvn.hip potrf_graphed).  On this stack every other hipGraphInstantiate in a process yields an
-    // executable whose two chains run 1.5-2x slower than the same graph instantiated before or after it (measured: the
-    // 3rd and 5th instantiation; the parallel branch lands on a hardware queue that does not overlap with the launch
-    // stream's).  The first replays are therefore timed against the eager launch sequence and a slow executable is
-    // instantiated again from the kept template.
-    hipGraph_t tmpl = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    float eager_ms = 0.f, best_ms = 0.f;
-    hipGraphExec_t best = nullptr;      // fastest executable seen so far while `exec` is the one on trial
-    int tries = 0, trial_launches = 0;  // an executable's first launch carries its upload: the second one is timed
-    bool timed = false, settled = false;
-    void release() {
-        if (best && best != exec) (void)hipGraphExecDestroy(best);
-        best = nullptr;
-        if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
-        if (tmpl) { (void)hipGraphDestroy(tmpl); tmpl = nullptr; }
-        if (t0) { (void)hipEventDestroy(t0); t0 = nullptr; }
-        if (t1) { (void)hipEventDestroy(t1); t1 = nullptr; }
-    }
-};
-// a few graphs side by side: a model with two or more large covariance blocks of different size evaluates them in turn,
-// and a one-entry cache would re-capture (i.e. run eagerly) every time.  Every graph is a two-chain one (a single
-// evaluation): at most two of those are kept alive (of three or more alive in a process every new instantiation measured
-// slow, whatever the number of tries)
-struct CholGraphCache {
-    static constexpr int CAP = 2;
-    std::vector<CholGraph> g;
-    long long tick = 0;
-    void clear() { for (CholGraph& e : g) e.release(); g.clear(); }
-    ~CholGraphCache() { clear(); }
-    CholGraphCache() = default;
-    CholGraphCache(const CholGraphCache&) = delete;
-    CholGraphCache& operator=(const CholGraphCache&) = delete;
-    CholGraphCache(CholGraphCache&& o) noexcept : g(std::move(o.g)), tick(o.tick) { o.g.clear(); }
-    CholGraphCache& operator=(CholGraphCache&& o) noexcept { if (this != &o) { clear(); g = std::move(o.g); tick = o.tick; o.g.clear(); } return *this; }
-    CholGraph& find(const double* A, const double* linv, int lda, int n, int extra) {
-        ++tick;
-        for (CholGraph& e : g)
-            if (e.A == A && e.linv == linv && e.lda == lda && e.n == n && e.extra == extra) { e.used = tick; return e; }
-        size_t old = 0;
-        for (size_t i = 1; i < g.size(); ++i)
-            if (g[i].used < g[old].used) old = i;
-        if ((int)g.size() >= CAP) {
-            g[old].release();
-            g[old] = CholGraph();
-            std::swap(g[old], g.back());
-        } else g.push_back(CholGraph());
-        CholGraph& e = g.back();
-        e.A = A; e.linv = linv; e.lda = lda; e.n = n; e.extra = extra; e.seen = 0; e.used = tick;
-        return e;
-    }
-};
-
 // exact conditional draws (hmc_exact.h): M = I + ZL' ZL / sigma^2 and its factor, the Q x ncols right-hand sides / draws, the
 // Q-vector b -> w; kept between calls (Q x Q: 200 MB at Q = 5000).  prof: HIP events around the phases of the next calls
 struct ExactState {
@@ -270,7 +209,6 @@ struct Ctx {
 
     // MVN workspaces
     DevMat Dwork;               // maxdim x maxdim
-    DevBuf linv;                // (maxdim/128 + 1) x 128 x 128
     DevBuf partials;            // reduction partials
     DevBuf scalars;             // 64 small device scalars (doubles): [0..3] mvn_ll, [4] model log-likelihood, [8..15] sampler
                                 // diagnostics, [16] the "not positive definite" flag (int), [17..] sampler step counts (ints)
@@ -310,25 +248,15 @@ struct Ctx {
     DevBuf reduce_buf;          // doubles handed to the collective
     DevBuf scratch;             // short-lived per-call scratch
 
-    // side stream + events for the Cholesky look-ahead (mvn.hip potrf_blocked)
-    hipStream_t aux = nullptr;      // high priority: the leaf of the eager fork-join
-    hipStream_t aux_lo = nullptr;   // lowest priority: the bulk chain of the captured schedule
-    hipEvent_t ev_col = nullptr, ev_leaf = nullptr;
-    CholGraphCache chol_graphs;
-    std::vector<hipEvent_t> ev_ring;                 // one event per dependency edge of the captured schedule (mvn.hip)
     DevMat Dbatch;                                   // mvn_loglik_batch: the candidates' matrices side by side
     DevBuf bscal;                                    // ... and their result scalars (4 per candidate)
     // tests (glmmr_mcml_dbg_mvn_workspace): what mvn_large_blocks last left in Dwork [0] / Dbatch [1] -- the block's
     // dimension d, round_up(d, 16), the sample rows m, the leading dimension, the number of matrices (0: no call yet)
     struct MvnWs { int d = 0, dp = 0, m = 0, ld = 0, kb = 0; } mvn_ws[2];
-    ~Ctx() {
-        for (hipEvent_t e : ev_ring) if (e) (void)hipEventDestroy(e);
-        comm_release_hook();
-        if (ev_col) (void)hipEventDestroy(ev_col);
-        if (ev_leaf) (void)hipEventDestroy(ev_leaf);
-        if (aux) (void)hipStreamDestroy(aux);
-        if (aux_lo) (void)hipStreamDestroy(aux_lo);
-    }
+    // the dense Cholesky stack (chol.h): inverted diagonal blocks, side streams + events, graph cache.  Last member: it is
+    // torn down first, right after the communicator
+    CholState chol;
+    ~Ctx() { comm_release_hook(); }
 
     int sync() { MCML_HIP(hipStreamSynchronize(stream)); return MCML_OK; }
     void comm_release_hook();
@@ -356,17 +284,8 @@ int mvn_loglik_batch_parts(Ctx& c, const double* thetas, int k, int round, const
                            int* rcs, double* parts);
 // L = genD(0, chol=true, upper=false) (mcml_full.cpp:68): block-diagonal lower factor
 int mvn_gen_L(Ctx& c, const double* theta, bool chol);
-int potrf_lower(Ctx& c, double* A, int n, int lda);                          // in place
-int potrf_leaf_profile(Ctx& c, unsigned long long* host10);                 // debug: phase clocks of one leaf
-int potrf_lower_checked(Ctx& c, double* A, int n, int lda);                  // + MCML_ENOTPD if a pivot failed
-// a kernel raised c.errflag() (a non-positive pivot): the flag is cleared, `message` becomes the error, MCML_ENOTPD.
-// Synchronises the stream
-int check_errflag(Ctx& c, const char* message);
-// x <- (L L')^-1 x for one vector, L from the LAST potrf_lower (its diagonal-block inverses are in c.linv)
-int potrs_lower_vec(Ctx& c, const double* L, int ldl, int n, double* x, double* tmp);
-int trsm_left_lower(Ctx& c, const double* L, int ldl, int n, double* U, int ldu, int m);
-// T <- R^-T T (the transposed solve of the same factor, all m columns at once)
-int trsm_left_lower_trans(Ctx& c, const double* R, int ldr, int n, double* T, int ldt, int m);
+
+// ---- chol.hip: see chol.h; vecops.hip (the vector-sized kernels): see vecops.h ----
 
 // ---- laplace.hip ----
 // M (Q x Q) = ZL' diag(W) ZL + I from the current c.ZL / c.ZLT.  W null: W = w0 for every observation, ZLT is multiplied as it
@@ -393,9 +312,6 @@ int mcnr_finish(int P, const double* stats, const double* beta, double* beta_out
 struct glmmr_mcml_hmc_opts_fwd;
 int hmc_dbg_log_prob_grad(Ctx& c, const double* beta, double var_par, const double* V, int ncols, double* lp,
                           double* G);
-
-// ---- reductions shared by several modules ----
-int device_sum(Ctx& c, const double* partials, int n, double* dev_out);
 
 }  // namespace mcml
 

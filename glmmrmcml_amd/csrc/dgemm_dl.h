@@ -1,6 +1,6 @@
 // dgemm_dl.h -- short-K GEMM for the Cholesky / triangular-solve updates.
 //
-// The panel updates of potrf_blocked / trsm_left_lower (mvn.hip) are GEMMs with K = 128:
+// The panel updates of potrf_blocked / trsm_left_lower (chol.hip) are GEMMs with K = 128:
 // eight K steps of 16.  With register staging (dgemm_mfma.h) every step waits for a global
 // load issued only one step earlier, so a launch costs ~8 memory latencies (20-40 us) for a
 // few microseconds of MFMA work.  This kernel stages global -> LDS with LDS-DMA
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(64 * WM * WN) void dgemm_dl_kernel(GemmP p, Epi epi
     }
     const size_t stepA = (size_t)BK * p.lda * 8, stepB = BNMAJOR ? (size_t)BK * p.ldb * 8 : (size_t)BK * 8;
     // blockIdx.y: one of several independent problems of the same shape (the candidate thetas of a theta-step round
-    // factorised side by side, mvn.hip)
+    // factorised side by side, chol.hip)
     const int by = blockIdx.y;
     const char* sA = reinterpret_cast<const char*>(p.A + (size_t)by * p.bsA);
     const char* sB = reinterpret_cast<const char*>(p.B + (size_t)by * p.bsB);

@@ -5,7 +5,7 @@
 //   C(M x N) = epilogue( A(M x K) * B(K x N) )
 //
 // A is column-major (M contiguous), or -- ATRANS -- read transposed in place: A(i, k) = A[k + i*lda], K
-// contiguous, as the R21' panels of the transposed triangular solve are (mvn.hip trsm_left_lower_trans).
+// contiguous, as the R21' panels of the transposed triangular solve are (chol.hip trsm_left_lower_trans).
 // B is either K-major (column-major K x N, as the Q x m sample matrices are) or N-major (B^T stored
 // column-major, as the L21 panels of the Cholesky update are).  All operands f64.
 //

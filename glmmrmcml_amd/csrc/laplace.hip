@@ -26,7 +26,10 @@
 #include "glm.h"
 #include "la_comp.h"
 #include "optim.h"
+#include "host_linalg.h"
 #include "reduce.h"
+#include "vecops.h"
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 
@@ -56,29 +59,6 @@ int lac_factor_launch(Ctx& c, const double* W, const double* g, double* x, doubl
 int lac_waves_now(const ComponentPlan& p) { return lac_waves(p, lac_forced_waves()); }
 
 // ------------------------------------------------------------------ kernels
-// y = A x  (A rows x cols, column-major): one thread per row
-__global__ __launch_bounds__(256) void k_la_gemv_n(const double* A, int lda, int rows, int cols, const double* x,
-                                                   double* y)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows) return;
-    double s = 0;
-    for (int j = 0; j < cols; ++j) s += A[i + (size_t)j * lda] * x[j];
-    y[i] = s;
-}
-
-// y[j] = beta y[j] + alpha sum_i A[i + j lda] x[i]  (A' x): one wave per column
-__global__ __launch_bounds__(256) void k_la_gemv_t(const double* A, int lda, int rows, int cols, const double* x,
-                                                   double* y, double alpha, double beta)
-{
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (j >= cols) return;
-    double s = 0;
-    for (int i = lane; i < rows; i += 64) s += A[i + (size_t)j * lda] * x[i];
-    s = wave_sum(s);
-    if (lane == 0) y[j] = (beta != 0.0 ? beta * y[j] : 0.0) + alpha * s;
-}
-
 // partial sums of log f(y_i | xb_i + zv_i)
 __global__ __launch_bounds__(256) void k_la_ll(const double* y, const double* xb, const double* zv, int n,
                                                double var_par, int flink, double* partials)
@@ -89,24 +69,6 @@ __global__ __launch_bounds__(256) void k_la_ll(const double* y, const double* xb
         acc += glm_logpdf(y[i], xb[i] + zv[i], var_par, flink);
     const double r = block_sum(acc, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = r;
-}
-
-__global__ __launch_bounds__(256) void k_la_sumsq(const double* v, int n, double* partials)
-{
-    __shared__ double sh[4];
-    double acc = 0;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) acc += v[i] * v[i];
-    const double r = block_sum(acc, sh);
-    if (threadIdx.x == 0) partials[blockIdx.x] = r;
-}
-
-__global__ __launch_bounds__(256) void k_la_sum(const double* partials, int n, double* out)
-{
-    __shared__ double sh[4];
-    double acc = 0;
-    for (int i = threadIdx.x; i < n; i += 256) acc += partials[i];
-    const double r = block_sum(acc, sh);
-    if (threadIdx.x == 0) out[0] = r;
 }
 
 // W_i = 1 / (dhdmu(xb_i + zv_i) nvar)   (mcmlmodel.h:122-133)
@@ -130,15 +92,6 @@ __global__ void k_la_add_identity(double* M, int ld, int n)
     if (i < n) M[i + (size_t)i * ld] += 1.0;
 }
 
-__global__ __launch_bounds__(256) void k_la_logdet(const double* A, int lda, int n, double* out)
-{
-    __shared__ double sh[4];
-    double acc = 0;
-    for (int i = threadIdx.x; i < n; i += 256) acc += log(A[i + (size_t)i * lda]);
-    const double r = block_sum(acc, sh);
-    if (threadIdx.x == 0) out[0] = 2 * r;                     // moremaths.h:105-116
-}
-
 // mcnr_b's per-observation pieces (mcmloptim.h:248-266): resid, Wu = W detadmu resid, score(xb + Zv)
 __global__ void k_la_nr_obs(const double* y, const double* xb, const double* zlv, const double* zv, const double* W,
                             int n, int flink, int link_code, double var_par, double* resid, double* Wu, double* score)
@@ -150,12 +103,6 @@ __global__ void k_la_nr_obs(const double* y, const double* xb, const double* zlv
     resid[i] = r;
     Wu[i] = W[i] * glm_detadmu(eta, link_code) * r;
     score[i] = flink == 12 ? glm_score_beta(y[i], xb[i] + zv[i], var_par) : glm_score(y[i], xb[i] + zv[i], flink);
-}
-
-__global__ void k_la_axpy(double* y, const double* x, double a, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) y[i] += a * x[i];
 }
 
 // X' diag(W) X (P x P) and X' Wu (P): tiny P, one block per (a, b) pair / per a
@@ -174,30 +121,6 @@ __global__ __launch_bounds__(256) void k_la_xtwx(const double* X, int ldx, int n
     }
     const double r = block_sum(acc, sh);
     if (threadIdx.x == 0) out[idx] = r;
-}
-
-__global__ void k_la_copy(double* dst, const double* src, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-
-// x <- L'^-1 (L^-1 x): forward solve through the blocked TRSM (one right-hand side), backward
-// solve block by block with the inverted diagonal blocks potrf_lower left in c.linv
-int potrs_lower_vec(Ctx& c, const double* L, int ldl, int n, double* x, double* tmp)
-{
-    MCML_TRY(trsm_left_lower(c, L, ldl, n, x, pad_ld(n), 1));
-    const int nblk = (n + CHOL_NB - 1) / CHOL_NB;
-    for (int kb = nblk - 1; kb >= 0; --kb) {
-        const int k0 = kb * CHOL_NB, nb = (n - k0 < CHOL_NB) ? n - k0 : CHOL_NB;
-        const double* Linv = c.linv.d() + (size_t)kb * CHOL_NB * CHOL_NB;
-        hipLaunchKernelGGL(k_la_gemv_t, dim3((nb + 3) / 4), dim3(256), 0, c.stream, Linv, CHOL_NB, nb, nb, x + k0, tmp, 1.0, 0.0);
-        hipLaunchKernelGGL(k_la_copy, dim3(1), dim3(128), 0, c.stream, x + k0, tmp, nb);
-        if (k0 > 0)
-            hipLaunchKernelGGL(k_la_gemv_t, dim3((k0 + 3) / 4), dim3(256), 0, c.stream, L + k0, ldl, nb, k0, x + k0, x, -1.0, 1.0);
-        MCML_HIP(hipGetLastError());
-    }
-    return MCML_OK;
 }
 
 // M = ZL' diag(W) ZL + I from the current c.ZL / c.ZLT (ctx.h): the Laplace fits' M with their per-observation weights, the
@@ -271,7 +194,7 @@ struct LaFit {
         MCML_TRY(tmpn3.ensure(sizeof(double) * (size_t)n));
         MCML_TRY(tmpq.ensure(sizeof(double) * (size_t)(Q + 64)));
         MCML_TRY(tmpq2.ensure(sizeof(double) * (size_t)(Q + 64)));
-        MCML_TRY(part.ensure(sizeof(double) * 1100));
+        MCML_TRY(part.ensure(sizeof(double) * (size_t)std::max(1100, (Q + 255) / 256)));   // ll_and_vv: nblk() <= 1024 | Q / 256 partials
         MCML_TRY(small.ensure(sizeof(double) * (size_t)(P * P + P + 16)));
         MCML_HIP(hipMemsetAsync(v.p, 0, sizeof(double) * (size_t)(Q + 64), c.stream));
         // the component operator: asked for, and the model has the sparse ZL with a component plan its kernel takes (L
@@ -335,10 +258,7 @@ struct LaFit {
             MCML_HIP(hipGetLastError());
             return MCML_OK;
         }
-        hipLaunchKernelGGL(k_la_gemv_t, dim3((n + 3) / 4), dim3(256), 0, c.stream, c.ZLT.d(), c.ZLT.ld, Q, n, v.d(), out,
-                           1.0, 0.0);
-        MCML_HIP(hipGetLastError());
-        return MCML_OK;
+        return dev_gemv_t(c, c.ZLT.d(), c.ZLT.ld, Q, n, v.d(), out, 1.0, 0.0);
     }
     int z_times_v(double* out)
     {
@@ -348,9 +268,7 @@ struct LaFit {
             MCML_HIP(hipGetLastError());
             return MCML_OK;
         }
-        hipLaunchKernelGGL(k_la_gemv_n, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.Z.d(), c.Z.ld, n, Q, v.d(), out);
-        MCML_HIP(hipGetLastError());
-        return MCML_OK;
+        return dev_gemv_n(c, c.Z.d(), c.Z.ld, n, Q, v.d(), out);
     }
     int scalar_from(const double* dev, double* host)
     {
@@ -378,11 +296,11 @@ struct LaFit {
         MCML_TRY(zl_times_v(tmpn.d()));
         const int nb = nblk();
         hipLaunchKernelGGL(k_la_ll, dim3(nb), dim3(256), 0, c.stream, c.y.d(), c.xb.d(), tmpn.d(), n, var_par, flink, part.d());
-        hipLaunchKernelGGL(k_la_sum, dim3(1), dim3(256), 0, c.stream, part.d(), nb, small.d());
-        int qb = (Q + 255) / 256; if (qb > 1024) qb = 1024;
-        hipLaunchKernelGGL(k_la_sumsq, dim3(qb), dim3(256), 0, c.stream, v.d(), Q, part.d());
-        hipLaunchKernelGGL(k_la_sum, dim3(1), dim3(256), 0, c.stream, part.d(), qb, small.d() + 1);
         MCML_HIP(hipGetLastError());
+        MCML_TRY(dev_sum(c, part.d(), nb, small.d()));
+        const int qb = (Q + 255) / 256;                          // v as one column: a partial per 256 entries (part: init)
+        MCML_TRY(dev_sumsq_partials(c, v.d(), Q, Q, 1, qb, 1, part.d()));
+        MCML_TRY(dev_sum(c, part.d(), qb, small.d() + 1));
         double h[2];
         MCML_TRY(copy_d2h(h, small.p, sizeof(double) * 2, c.stream));
         MCML_HIP(hipStreamSynchronize(c.stream));
@@ -405,16 +323,14 @@ struct LaFit {
     {
         if (comp) {
             MCML_TRY(lac_factor(nullptr, nullptr));
-            hipLaunchKernelGGL(k_la_sum, dim3(1), dim3(256), 0, c.stream, lac_ld.d(), c.cp.plan.ncomp, small.d() + 2);
-            MCML_HIP(hipGetLastError());
+            MCML_TRY(dev_sum(c, lac_ld.d(), c.cp.plan.ncomp, small.d() + 2));
             MCML_TRY(copy_d2h(out, small.d() + 2, sizeof(double), c.stream));
             return lac_check();
         }
         MCML_TRY(build_M());
         int rc = potrf_lower_checked(c, M.d(), Q, M.ld);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_la_logdet, dim3(1), dim3(256), 0, c.stream, M.d(), M.ld, Q, small.d() + 2);
-        MCML_HIP(hipGetLastError());
+        MCML_TRY(dev_logdet_chol(c, M.d(), M.ld, Q, small.d() + 2));       // moremaths.h:105-116
         return scalar_from(small.d() + 2, out);
     }
 
@@ -539,42 +455,23 @@ struct LaFit {
             MCML_TRY(lac_check());
         } else {
             // vgrad = -D0 v + post * ZL' score
-            hipLaunchKernelGGL(k_la_gemv_t, dim3((Q + 3) / 4), dim3(256), 0, c.stream, c.ZL.d(), c.ZL.ld, n, Q, tmpn.d(),
-                               tmpq.d(), glm_score_post(var_par, flink), 0.0);
-            hipLaunchKernelGGL(k_la_gemv_t, dim3((Q + 3) / 4), dim3(256), 0, c.stream, D0.d(), D0.ld, Q, Q, v.d(), tmpq.d(),
-                               -1.0, 1.0);
-            MCML_HIP(hipGetLastError());
+            MCML_TRY(dev_gemv_t(c, c.ZL.d(), c.ZL.ld, n, Q, tmpn.d(), tmpq.d(), glm_score_post(var_par, flink), 0.0));
+            MCML_TRY(dev_gemv_t(c, D0.d(), D0.ld, Q, Q, v.d(), tmpq.d(), -1.0, 1.0));
             // vincr = (ZL' W ZL + I)^-1 vgrad
             MCML_TRY(build_M());
             MCML_TRY(potrf_lower_checked(c, M.d(), Q, M.ld));
             MCML_TRY(potrs_lower_vec(c, M.d(), M.ld, Q, tmpq.d(), tmpq2.d()));
         }
-        hipLaunchKernelGGL(k_la_axpy, dim3((Q + 255) / 256), dim3(256), 0, c.stream, v.d(), tmpq.d(), 1.0, Q);
-        MCML_HIP(hipGetLastError());
+        MCML_TRY(dev_axpy(c, v.d(), tmpq.d(), 1.0, Q));
         MCML_TRY(get_v());                                        // also synchronises st / resid
         double mean = 0;
         for (int i = 0; i < n; ++i) mean += resid[i];
         mean /= n;
         double ss = 0;
         for (int i = 0; i < n; ++i) ss += (resid[i] - mean) * (resid[i] - mean);
-        // beta += (X'WX)^-1 X' Wu: Gaussian elimination with partial pivoting on the P x P system
+        // beta += (X'WX)^-1 X' Wu
         std::vector<double> A(st.begin(), st.begin() + (size_t)P * P), b(st.begin() + (size_t)P * P, st.end());
-        for (int k = 0; k < P; ++k) {
-            int piv = k;
-            for (int i = k + 1; i < P; ++i) if (fabs(A[i + (size_t)k * P]) > fabs(A[piv + (size_t)k * P])) piv = i;
-            if (A[piv + (size_t)k * P] == 0.0) { set_error("mcnr_b: X'WX is singular"); return MCML_ESINGULAR; }
-            if (piv != k) { for (int j = 0; j < P; ++j) std::swap(A[k + (size_t)j * P], A[piv + (size_t)j * P]); std::swap(b[k], b[piv]); }
-            for (int i = k + 1; i < P; ++i) {
-                const double f = A[i + (size_t)k * P] / A[k + (size_t)k * P];
-                for (int j = k; j < P; ++j) A[i + (size_t)j * P] -= f * A[k + (size_t)j * P];
-                b[i] -= f * b[k];
-            }
-        }
-        for (int k = P - 1; k >= 0; --k) {
-            double s = b[k];
-            for (int j = k + 1; j < P; ++j) s -= A[k + (size_t)j * P] * b[j];
-            b[k] = s / A[k + (size_t)k * P];
-        }
+        if (!ge_solve(A, b, P)) { set_error("mcnr_b: X'WX is singular"); return MCML_ESINGULAR; }
         for (int k = 0; k < P; ++k) beta[k] += b[k];
         sigma = sqrt(ss / (n - 1));
         return MCML_OK;
@@ -638,55 +535,20 @@ struct LaFit {
                 MCML_TRY(hess_la(1e-4, &H));
                 const int nv = P + R + (glm_has_var_par(flink) ? 1 : 0);
                 std::vector<double> Hi;
-                MCML_TRY(spd_inverse_host(H, nv, &Hi));
+                // hess.llt().solve(I) (src/mcml_la.cpp:120-124)
+                if (!spd_inverse(H, nv, &Hi)) { set_error("hess_la: Hessian is not positive definite"); return MCML_ENOTPD; }
                 for (int i = 0; i < nv && i < nstart; ++i) se_out[i] = sqrt(Hi[i + (size_t)i * nv]);
             }
         }
         if (u_out) {                                              // u = L v with the driver's L
             model_L_valid = false;
             MCML_TRY(ensure_model_L());
-            hipLaunchKernelGGL(k_la_gemv_n, dim3((Q + 255) / 256), dim3(256), 0, c.stream, c.L.d(), c.L.ld, Q, Q, v.d(), tmpq.d());
-            MCML_HIP(hipGetLastError());
+            MCML_TRY(dev_gemv_n(c, c.L.d(), c.L.ld, Q, Q, v.d(), tmpq.d()));
             MCML_TRY(copy_d2h(u_out, tmpq.p, sizeof(double) * (size_t)Q, c.stream));
             MCML_HIP(hipStreamSynchronize(c.stream));
         }
         if (converged_out) *converged_out = converged ? 1 : 0;
         if (iters_out) *iters_out = it - 1;
-        return MCML_OK;
-    }
-
-    // hess.llt().solve(I) (src/mcml_la.cpp:120-124): Cholesky inverse of the small Hessian on the host
-    static int spd_inverse_host(const std::vector<double>& H, int nv, std::vector<double>* out)
-    {
-        std::vector<double> L(H);
-        for (int j = 0; j < nv; ++j) {
-            double d = L[j + (size_t)j * nv];
-            for (int k = 0; k < j; ++k) d -= L[j + (size_t)k * nv] * L[j + (size_t)k * nv];
-            if (!(d > 0.0)) { set_error("hess_la: Hessian is not positive definite"); return MCML_ENOTPD; }
-            d = sqrt(d);
-            L[j + (size_t)j * nv] = d;
-            for (int i = j + 1; i < nv; ++i) {
-                double s = L[i + (size_t)j * nv];
-                for (int k = 0; k < j; ++k) s -= L[i + (size_t)k * nv] * L[j + (size_t)k * nv];
-                L[i + (size_t)j * nv] = s / d;
-            }
-        }
-        out->assign((size_t)nv * nv, 0.0);
-        for (int col = 0; col < nv; ++col) {
-            std::vector<double> x(nv, 0.0);
-            x[col] = 1.0;
-            for (int i = 0; i < nv; ++i) {
-                double s = x[i];
-                for (int k = 0; k < i; ++k) s -= L[i + (size_t)k * nv] * x[k];
-                x[i] = s / L[i + (size_t)i * nv];
-            }
-            for (int i = nv - 1; i >= 0; --i) {
-                double s = x[i];
-                for (int k = i + 1; k < nv; ++k) s -= L[k + (size_t)i * nv] * x[k];
-                x[i] = s / L[i + (size_t)i * nv];
-            }
-            for (int i = 0; i < nv; ++i) (*out)[i + (size_t)col * nv] = x[i];
-        }
         return MCML_OK;
     }
 };

@@ -13,7 +13,9 @@
 #include "dgemm_mfma.h"
 #include "dgemm_band.h"
 #include "glm.h"
+#include "host_linalg.h"
 #include "reduce.h"
+#include "vecops.h"
 
 namespace mcml {
 
@@ -119,22 +121,6 @@ int model_update_zu(Ctx& c)
     MCML_TRY(z_times(c, c.U.d(), c.U.ld, c.mcols, c.ZU.d(), c.ZU.ld));
     c.zu_valid = true;
     return MCML_OK;
-}
-
-__global__ void k_transpose(const double* A, int lda, int rows, int cols, double* AT, int ldt)
-{
-    __shared__ double tile[32][33];
-    int bx = blockIdx.x * 32, by = blockIdx.y * 32;
-    int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    for (int r = ty; r < 32; r += 8) {
-        int i = bx + tx, j = by + r;
-        tile[r][tx] = (i < rows && j < cols) ? A[i + (size_t)j * lda] : 0.0;
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        int j = by + tx, i = bx + r;
-        if (i < rows && j < cols) AT[j + (size_t)i * ldt] = tile[tx][r];
-    }
 }
 
 // ---- sparse ZL (configs whose D has only diagonal / small blocks and whose Z is indicator-like)
@@ -330,9 +316,7 @@ int model_update_L(Ctx& c)
         EpiAxpby epi{c.ZL.d(), c.ZL.ld, 1.0, 0.0};
         MCML_TRY(launch_gemm<false>(c.stream, c.n, c.Q, c.Q, c.Z.d(), c.Z.ld, c.L.d(), c.L.ld, epi));
     }
-    hipLaunchKernelGGL(k_transpose, dim3((c.n + 31) / 32, (c.Q + 31) / 32), dim3(256), 0, c.stream, c.ZL.d(),
-                       c.ZL.ld, c.n, c.Q, c.ZLT.d(), c.ZLT.ld);
-    MCML_HIP(hipGetLastError());
+    MCML_TRY(dev_transpose(c, c.ZL.d(), c.ZL.ld, c.n, c.Q, c.ZLT.d(), c.ZLT.ld));
     // structural zeros of ZL / ZL' (triangular when Z = I): record each 80-row band's range of
     // nonzero K tiles; the banded kernel is used when it skips at least a fifth of the tiles
     c.band_fwd = c.band_bwd = false;
@@ -391,7 +375,7 @@ int model_loglik_sum(Ctx& c, double var_par, double* sum_out)
                            c.y.d(), var_par, c.flink, c.partials.d());
     });
     MCML_HIP(hipGetLastError());
-    MCML_TRY(device_sum(c, c.partials.d(), gx * gy, c.scalars.d() + 4));
+    MCML_TRY(dev_sum(c, c.partials.d(), gx * gy, c.scalars.d() + 4));
     MCML_TRY(copy_d2h(sum_out, c.scalars.d() + 4, sizeof(double), c.stream));
     MCML_HIP(hipStreamSynchronize(c.stream));
     return MCML_OK;
@@ -532,6 +516,24 @@ int model_mcnr_stats(Ctx& c, double var_par, double* stats)
     MCML_TRY(allreduce_dev(c, c.reduce_buf.d(), ns));              // RCCL all-reduce of the statistics (comm.hip)
     MCML_TRY(copy_d2h(stats, c.reduce_buf.p, sizeof(double) * ns, c.stream));
     MCML_HIP(hipStreamSynchronize(c.stream));
+    return MCML_OK;
+}
+
+// beta += (1/m sum X'W_iX)^-1 X' (1/m sum W_i detadmu resid_i); sigma = mean sigma_i
+// (mcmloptim.h:227-235); Gauss-Jordan with partial pivoting stands in for Eigen's .inverse()
+int mcnr_finish(int P, const double* stats, const double* beta, double* beta_out, double* sigma_out)
+{
+    const double m = stats[P * P + P + 1];
+    MCML_REQUIRE(m > 0, "mcnr: no samples");
+    std::vector<double> B(stats, stats + P * P);
+    for (auto& v : B) v *= (double)1 / m;
+    if (!gj_inverse(B, P, 0.0)) { set_error("mcnr: X'WX is singular"); return MCML_ESINGULAR; }
+    for (int a = 0; a < P; a++) {
+        double inc = 0;
+        for (int b = 0; b < P; b++) inc += B[a + (size_t)b * P] * (stats[P * P + b] / m);
+        beta_out[a] = beta[a] + inc;
+    }
+    *sigma_out = stats[P * P + P] / m;
     return MCML_OK;
 }
 

@@ -2,6 +2,7 @@
 // finite-difference gradient / Hessian.
 #include "optim.h"
 #include "common.h"
+#include "host_linalg.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -13,29 +14,6 @@ typedef std::vector<double> vec;
 
 static double dot(const vec& a, const vec& b) { double s = 0; for (size_t i = 0; i < a.size(); ++i) s += a[i] * b[i]; return s; }
 static double norm2(const vec& a) { return std::sqrt(dot(a, a)); }
-
-// in-place inverse by Gauss-Jordan with partial pivoting; false if singular
-static bool invert(std::vector<double>& A, int N)
-{
-    std::vector<double> B((size_t)N * N, 0.0);
-    for (int i = 0; i < N; ++i) B[i + (size_t)i * N] = 1.0;
-    double amax = 0;
-    for (double v : A) amax = std::max(amax, std::fabs(v));
-    for (int c = 0; c < N; ++c) {
-        int p = c; double best = std::fabs(A[c + (size_t)c * N]);
-        for (int i = c + 1; i < N; ++i) if (std::fabs(A[i + (size_t)c * N]) > best) { best = std::fabs(A[i + (size_t)c * N]); p = i; }
-        if (!(best > 1e-14 * amax)) return false;
-        if (p != c) for (int j = 0; j < N; ++j) { std::swap(A[c + (size_t)j * N], A[p + (size_t)j * N]); std::swap(B[c + (size_t)j * N], B[p + (size_t)j * N]); }
-        double d = A[c + (size_t)c * N];
-        for (int j = 0; j < N; ++j) { A[c + (size_t)j * N] /= d; B[c + (size_t)j * N] /= d; }
-        for (int i = 0; i < N; ++i) if (i != c) {
-            double f = A[i + (size_t)c * N];
-            if (f != 0.0) for (int j = 0; j < N; ++j) { A[i + (size_t)j * N] -= f * A[c + (size_t)j * N]; B[i + (size_t)j * N] -= f * B[c + (size_t)j * N]; }
-        }
-    }
-    A.swap(B);
-    return true;
-}
 
 struct Quad {          // q(x) = c + g'(x - xb) + 1/2 (x - xb)' H (x - xb)
     double c = 0; vec g, H; int n = 0;
@@ -614,7 +592,7 @@ private:
             W[a + (size_t)m * N] = 1.0; W[m + (size_t)a * N] = 1.0;
             for (int i = 0; i < n; ++i) { W[a + (size_t)(m + 1 + i) * N] = S[i + (size_t)a * n]; W[(m + 1 + i) + (size_t)a * N] = S[i + (size_t)a * n]; }
         }
-        if (!invert(W, N)) return false;
+        if (!gj_inverse(W, N, 1e-14)) return false;
         Winv_.swap(W);
         return true;
     }

@@ -1,4 +1,4 @@
-"""mvn_ll at k candidate thetas side by side (evaluation lanes, mvn.hip mvn_loglik_batch): ms per round and per evaluation.
+"""mvn_ll at k candidate thetas side by side (mvn.hip mvn_loglik_batch over chol.hip potrf_blocked): ms per round and per evaluation.
 usage: python scripts/time_mvn_batch.py [Q=5000] [m=1024] [k ...]"""
 import sys, time
 sys.path.insert(0, ".")

@@ -1,5 +1,5 @@
-"""Element-by-element reference for the blocked Cholesky factorisation and its triangular solves (csrc/mvn.hip
-potrf_blocked / potrf_graphed, trsm_left_lower, trsm_left_lower_trans; csrc/laplace.hip potrs_lower_vec).
+"""Element-by-element reference for the blocked Cholesky factorisation and its triangular solves (csrc/chol.hip
+potrf_blocked / potrf_graphed, trsm_left_lower, trsm_left_lower_trans, potrs_lower_vec).
 
 Nothing here calls the library.  A computed factor or solution is judged by its COMPONENTWISE BACKWARD ERROR, evaluated in
 long double (u = 2^-53 is the unit roundoff of the float64 under test):

@@ -20,13 +20,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # constant -> (value, the statement of csrc/model.hip it restates, its line when this was written)
 CONSTANTS = {
-    "ROW_BLOCK": (256, "int i = blockIdx.x * 256 + threadIdx.x;", 91),            # k_zgather; k_loglik :372, k_mcnr_row :443
-    "COL_LOOP": (256, "for (int j = threadIdx.x; j < n; j += 256)", 417),        # k_mcnr_col; k_mcnr_fin :491
-    "MCNR_CHUNK": (16, "constexpr int MCNR_CHUNK = 16;", 435),
-    "ROWSUM_UNROLL": (8, "for (; k + 8 <= nchunks; k += 8)", 470),               # k_mcnr_rowsum
-    "LOGLIK_GRID_Y": (64, "gy = c.niter < 64 ? c.niter : 64;", 387),              # model_loglik_sum
-    "ZGATHER_GRID_Y": (1024, "int gy = ncols < 1024 ? ncols : 1024;", 103),       # z_times
-    "Z_WIDTH_MAX": (8, "if (maxrow > 0 && maxrow <= 8 &&", 42),                   # model_setup
+    "ROW_BLOCK": (256, "int i = blockIdx.x * 256 + threadIdx.x;", 93),            # k_zgather; k_loglik :356, k_mcnr_row :427
+    "COL_LOOP": (256, "for (int j = threadIdx.x; j < n; j += 256)", 401),        # k_mcnr_col; k_mcnr_fin :475
+    "MCNR_CHUNK": (16, "constexpr int MCNR_CHUNK = 16;", 419),
+    "ROWSUM_UNROLL": (8, "for (; k + 8 <= nchunks; k += 8)", 454),               # k_mcnr_rowsum
+    "LOGLIK_GRID_Y": (64, "gy = c.niter < 64 ? c.niter : 64;", 371),              # model_loglik_sum
+    "ZGATHER_GRID_Y": (1024, "int gy = ncols < 1024 ? ncols : 1024;", 105),       # z_times
+    "Z_WIDTH_MAX": (8, "if (maxrow > 0 && maxrow <= 8 &&", 44),                   # model_setup
 }
 
 

@@ -1,5 +1,5 @@
 """Candidates of a theta-step round that differ in a pure scale parameter share one factorisation (csrc/theta_scale.h,
-mvn.hip mvn_loglik_batch_parts): the grouped round against single evaluations of every candidate, against the ungrouped
+mvn.hip mvn_loglik_batch_parts over chol.hip potrf_blocked): the grouped round against single evaluations of every candidate, against the ungrouped
 round (GLMMR_MCML_THETA_SCALE=0), the number of matrices factorised, "no value" propagation, models without a scale,
 and whole mcml_full / mcml_hess calls with the switch on and off.
 
