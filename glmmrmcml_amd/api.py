@@ -244,9 +244,9 @@ class Context:
         u = _f(u)
         if u.ndim == 1:
             u = u.reshape(-1, 1, order="F")
-        self.mcols = u.shape[1]
         _lib.check(_lib.lib().glmmr_mcml_set_u(self._h, _p(u), u.shape[0], u.shape[1],
                                                u.shape[1] if niter is None else niter))
+        self.mcols = u.shape[1]                 # after the check: a refused call leaves get_u() as it was
 
     def get_u(self):
         u = np.zeros((self.Q, self.mcols), order="F")

@@ -241,6 +241,11 @@ extern "C" int glmmr_mcml_dbg_band_plan(glmmr_mcml_ctx* h, int which, int chains
     const Ctx& c = h->c;
     const BandPlan& bp = which ? c.plan_bwd : c.plan_fwd;
     const int gn = (chains + BD_BN - 1) / BD_BN;
+    if (c.sp.active) {         // the operator is the sparse one: the plans of an earlier dense L (set_L) are kept but not in use
+        for (int i = 0; i < 10; ++i) out10[i] = 0;
+        out10[3] = gn;
+        return MCML_OK;
+    }
     int nempty = 0;
     for (int b = 0; b < bp.nbands; ++b) nempty += bp.kr[2 * b] == bp.kr[2 * b + 1];
     int nwg = 0, nred = 0, nslots = 0, paired = 0, built = 0;
@@ -510,8 +515,10 @@ extern "C" int glmmr_mcml_ctx_gen_D(glmmr_mcml_ctx* h, const double* theta, int 
     Ctx& c = h->c;
     MCML_REQUIRE(ldo >= c.Q, "gen_D: ldo too small");
     MCML_HIP(hipSetDevice(c.device));
-    MCML_TRY(mvn_gen_L(c, theta, chol != 0));
-    return download_matrix(out, ldo, c.L.d(), c.L.ld, c.Q, c.Q, c.stream);
+    // a query: built in a matrix of its own (off the hot path), the context's L and what was made from it stay in force
+    DevMat D;
+    MCML_TRY(mvn_gen_D(c, theta, chol != 0, D));
+    return download_matrix(out, ldo, D.d(), D.ld, c.Q, c.Q, c.stream);
 }
 
 extern "C" int glmmr_mcml_ctx_loglik(glmmr_mcml_ctx* h, const double* beta, double var_par, double* out)
@@ -541,14 +548,23 @@ extern "C" int glmmr_mcml_ctx_mcnr(glmmr_mcml_ctx* h, const double* beta, double
     return mcnr_finish(c.P, st.data(), beta, beta_out, sigma_out);
 }
 
+// c.L is new: the operator made from it (ZL, ZL' or the sparse pair).  If that fails the context holds a new L beside the
+// old operator, so it holds no L: the consumers refuse until the next successful update_L / set_L
+static int install_L(Ctx& c)
+{
+    int rc = model_update_L(c);
+    if (rc == MCML_OK) rc = c.sync();
+    if (rc != MCML_OK) c.have_L = false;
+    return rc;
+}
+
 extern "C" int glmmr_mcml_ctx_update_L(glmmr_mcml_ctx* h, const double* theta)
 {
     MCML_REQUIRE(h && theta, "update_L: null argument");
     Ctx& c = h->c;
     MCML_HIP(hipSetDevice(c.device));
     MCML_TRY(mvn_gen_L(c, theta, true));
-    MCML_TRY(model_update_L(c));
-    return c.sync();
+    return install_L(c);
 }
 
 extern "C" int glmmr_mcml_ctx_set_L(glmmr_mcml_ctx* h, const double* L, int ldl)
@@ -557,13 +573,13 @@ extern "C" int glmmr_mcml_ctx_set_L(glmmr_mcml_ctx* h, const double* L, int ldl)
     Ctx& c = h->c;
     MCML_REQUIRE(ldl >= c.Q, "set_L: ldl too small");
     MCML_HIP(hipSetDevice(c.device));
+    c.have_L = false;
     MCML_TRY(upload_matrix(c.L, L, c.Q, c.Q, ldl, c.stream));
     c.have_L = true;
     // a caller-supplied L need not have the block pattern the sparse ZL operator assumes (entries outside the
     // covariance blocks would be dropped): the dense products take whatever L holds
     c.l_foreign = true;
-    MCML_TRY(model_update_L(c));
-    return c.sync();
+    return install_L(c);
 }
 
 extern "C" int glmmr_mcml_ctx_hmc_sample(glmmr_mcml_ctx* h, const double* beta, double var_par,

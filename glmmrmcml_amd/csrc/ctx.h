@@ -282,8 +282,11 @@ int mvn_loglik_batch(Ctx& c, const double* thetas, int k, const double* U, int l
 // parts[2 j], parts[2 j + 1] = candidate j's log-determinant and sum of squares (theta_scale.h)
 int mvn_loglik_batch_parts(Ctx& c, const double* thetas, int k, int round, const double* U, int ldu, int m, double* sums,
                            int* rcs, double* parts);
-// L = genD(0, chol=true, upper=false) (mcml_full.cpp:68): block-diagonal lower factor
+// c.L = genD(0, chol=true, upper=false) (mcml_full.cpp:68): block-diagonal lower factor; have_L = chol.  A build that
+// fails (a block that is not positive definite) leaves have_L false: c.L is overwritten in place
 int mvn_gen_L(Ctx& c, const double* theta, bool chol);
+// the same matrix as a query: built into `out` (allocated here), no state of the context changes
+int mvn_gen_D(Ctx& c, const double* theta, bool chol, DevMat& out);
 
 // ---- chol.hip: see chol.h; vecops.hip (the vector-sized kernels): see vecops.h ----
 

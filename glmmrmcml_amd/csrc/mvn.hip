@@ -470,50 +470,67 @@ __global__ void k_diag_fill(double* L, int ldl, int Q, const int* rowblock, cons
     L[k + (size_t)k * ldl] = chol ? sqrt(val) : val;
 }
 
-int mvn_gen_L(Ctx& c, const double* theta, bool chol)
+// D(theta) or its block-diagonal lower factor built into L, which may be any Q x Q matrix: the context's state is not touched
+static int gen_D_into(Ctx& c, DevMat& L, const ThetaArg& th, bool chol)
 {
-    ThetaArg th;
-    MCML_TRY(theta_arg(c, theta, th));
     const CovSpec& cs = c.cov;
     const int Q = cs.N;
-    MCML_TRY(c.L.alloc(Q, Q));
-    MCML_HIP(hipMemsetAsync(c.L.d(), 0, sizeof(double) * (size_t)c.L.ld * Q, c.stream));
+    MCML_TRY(L.alloc(Q, Q));
+    MCML_HIP(hipMemsetAsync(L.d(), 0, sizeof(double) * (size_t)L.ld * Q, c.stream));
     const int32_t* dcov = c.d_cov.as<int32_t>();
     const CovBlock* dblk = c.d_blocks.as<CovBlock>();
     if (c.n_diag_rows > 0)
-        hipLaunchKernelGGL(k_diag_fill, dim3((Q + 255) / 256), dim3(256), 0, c.stream, c.L.d(), c.L.ld, Q,
+        hipLaunchKernelGGL(k_diag_fill, dim3((Q + 255) / 256), dim3(256), 0, c.stream, L.d(), L.ld, Q,
                            c.d_rowblock.as<int>(), dblk, dcov, cs.rows, th, chol ? 1 : 0);
     for (int b = 0; b < cs.B; ++b) {
         const CovBlock& blk = cs.blocks[b];
         if (blk.all_gr) continue;
         const int d = blk.dim;
-        double* A = c.L.at(blk.matstart, blk.matstart);
+        double* A = L.at(blk.matstart, blk.matstart);
         dim3 g((d + 63) / 64, (d + 15) / 16);
-        hipLaunchKernelGGL(k_build_dense, g, dim3(256), 0, c.stream, A, c.L.ld, b, dblk, dcov, cs.rows,
+        hipLaunchKernelGGL(k_build_dense, g, dim3(256), 0, c.stream, A, L.ld, b, dblk, dcov, cs.rows,
                            c.d_data.d(), th, chol ? 0 : 1, d);
         MCML_HIP(hipGetLastError());
         if (chol) {
             // blocks start at arbitrary (possibly odd) offsets: factorise in the
             // aligned workspace when the view is not 16-byte aligned
             if (d <= CHOL_NB || (blk.matstart & 1) == 0) {
-                MCML_TRY(potrf_lower(c, A, d, c.L.ld));
+                MCML_TRY(potrf_lower(c, A, d, L.ld));
             } else {
                 DevMat tmp;
                 MCML_TRY(tmp.alloc(d, d));
                 hipLaunchKernelGGL(k_copy_block, dim3((d + 255) / 256, d < 256 ? d : 256), dim3(256), 0, c.stream,
-                                   tmp.d(), tmp.ld, A, c.L.ld, d, d);
+                                   tmp.d(), tmp.ld, A, L.ld, d, d);
                 MCML_TRY(potrf_lower(c, tmp.d(), d, tmp.ld));
                 hipLaunchKernelGGL(k_copy_block, dim3((d + 255) / 256, d < 256 ? d : 256), dim3(256), 0, c.stream,
-                                   A, c.L.ld, tmp.d(), tmp.ld, d, d);
+                                   A, L.ld, tmp.d(), tmp.ld, d, d);
                 MCML_HIP(hipStreamSynchronize(c.stream));
             }
             // the SYRK updates of diagonal tiles also touch their upper halves
             if (d > CHOL_NB)
-                hipLaunchKernelGGL(k_zero_upper, dim3((d + 255) / 256, d), dim3(256), 0, c.stream, A, c.L.ld, d);
+                hipLaunchKernelGGL(k_zero_upper, dim3((d + 255) / 256, d), dim3(256), 0, c.stream, A, L.ld, d);
         }
     }
     MCML_HIP(hipGetLastError());
-    MCML_TRY(check_errflag(c, "genD: covariance block is not positive definite"));
+    return check_errflag(c, "genD: covariance block is not positive definite");
+}
+
+// A query (glmmr_mcml_ctx_gen_D): into the caller's matrix, so c.L, have_L and l_foreign stay as they are
+int mvn_gen_D(Ctx& c, const double* theta, bool chol, DevMat& out)
+{
+    ThetaArg th;
+    MCML_TRY(theta_arg(c, theta, th));
+    return gen_D_into(c, out, th, chol);
+}
+
+// c.L is overwritten in place (its address keys captured graphs), so a build that fails half way -- a block that is not
+// positive definite -- leaves no L at all: every consumer requires have_L and refuses until the next successful call
+int mvn_gen_L(Ctx& c, const double* theta, bool chol)
+{
+    ThetaArg th;
+    MCML_TRY(theta_arg(c, theta, th));
+    c.have_L = false;
+    MCML_TRY(gen_D_into(c, c.L, th, chol));
     if (chol) c.l_foreign = false;
     c.have_L = chol;
     return MCML_OK;

@@ -111,7 +111,9 @@ int glmmr_mcml_ctx_mvn_ll(glmmr_mcml_ctx* ctx, const double* theta, double* out)
  * after the other.  out[j] = log-likelihood at candidate j (equal to the single evaluation to rounding), NaN where
  * D(theta_j) is not positive definite.  k <= 64. */
 int glmmr_mcml_ctx_mvn_ll_batch(glmmr_mcml_ctx* ctx, const double* thetas, int k, double* out);
-/* DMatrix::genD(0, chol, false) (mcml_full.cpp:68) -> out (Q x Q) */
+/* DMatrix::genD(0, chol, false) (mcml_full.cpp:68) -> out (Q x Q).  A QUERY, like mvn_ll, mvn_ll_batch, loglik and mcnr:
+ * it is built in storage of its own and changes nothing the context holds -- the L of the last update_L / set_L and the
+ * operator made from it stay in force.  GLMMR_MCML_ENOTPD where D(theta) is not positive definite (chol != 0). */
 int glmmr_mcml_ctx_gen_D(glmmr_mcml_ctx* ctx, const double* theta, int chol, double* out, int ldo);
 
 /* mcmlModel::log_likelihood() at beta / var_par (mcmlmodel.h:284-304; L_likelihood,
@@ -122,7 +124,10 @@ int glmmr_mcml_ctx_loglik(glmmr_mcml_ctx* ctx, const double* beta, double var_pa
 int glmmr_mcml_ctx_mcnr(glmmr_mcml_ctx* ctx, const double* beta, double var_par, double* beta_out,
                         double* sigma_out, double* stats_out);
 /* dmat.update_parameters(theta); L = genD(0,true,false); model.update_L()
- * (mcml_full.cpp:120-125) */
+ * (mcml_full.cpp:120-125).  What later calls return depends on this L, the samples and the mode setters, never on the
+ * calls made before.  L is overwritten in place: if the call FAILS (GLMMR_MCML_ENOTPD: D(theta) is not positive definite)
+ * the context holds NO L afterwards, and the samplers, log_prob_grad and the exact draws fail with "L not set" until
+ * update_L or set_L succeeds.  The same holds for a failed set_L.  Any other failed call changes nothing. */
 int glmmr_mcml_ctx_update_L(glmmr_mcml_ctx* ctx, const double* theta);
 /* take L as given (export mcmc_sample receives it, mcml_full.cpp:315) */
 int glmmr_mcml_ctx_set_L(glmmr_mcml_ctx* ctx, const double* L, int ldl);

@@ -119,8 +119,8 @@ def tile_columns(C):
     return sorted(c for c in cols if c < C)
 
 
-def check_log_prob_grad(orc, d, lp, G, V, cols=None):
-    Lo = oracle_L(orc, d)
+def check_log_prob_grad(orc, d, lp, G, V, cols=None, L=None):
+    Lo = oracle_L(orc, d) if L is None else L
     ZL, xb, yo, fl = _oracle_model(orc, d, Lo)
     vp = next(c[2] for c in CASES if c[:2] == (d["family"], d["link"]))
     for c in (range(V.shape[1]) if cols is None else cols):
