@@ -169,6 +169,17 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(c_dp)
 
 
+def _weights(weights, m):
+    """the sample weights of mvn_ll_grad as the C ABI takes them (None stays None); a wrong count is refused here, the
+    library does not know the caller's"""
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+    if m > 0 and w.size != m:
+        raise _lib.McmlError(-1, "mvn_ll_grad: %d weights for %d sample columns" % (w.size, m))
+    return w
+
+
 class Context:
     """A device-resident MCML problem (glmmr_mcml_ctx).  Inputs are uploaded once;
     afterwards only parameter vectors go down and scalars come back."""
@@ -287,6 +298,18 @@ class Context:
         out = np.zeros(th.shape[0])
         _lib.check(_lib.lib().glmmr_mcml_ctx_mvn_ll_batch(self._h, _p(th), th.shape[0], _p(out)))
         return out
+
+    def mvn_ll_grad(self, theta, weights=None):
+        """(value, grad): value = sum_j w_j sum_b log N(u_bj; 0, D_b(theta)) over the context's own sample columns and its
+        gradient in theta, analytically (csrc/mvn_grad.h).  weights = None: 1 / mcols each, value is mvn_ll(theta) to the
+        bit.  A query: the context is left as mvn_ll(theta) leaves it.  McmlError -1 for weights of the wrong length,
+        negative or not finite; -3 where D(theta) is not positive definite"""
+        theta = _f(theta).ravel()
+        w = _weights(weights, self.mcols)
+        out = C.c_double()
+        grad = np.zeros(theta.size)
+        _lib.check(_lib.lib().glmmr_mcml_ctx_mvn_ll_grad(self._h, _p(theta), _p(w), C.byref(out), _p(grad)))
+        return out.value, grad
 
     def mvn_workspace(self, cand=-1):
         """(L, X, dims): what the last mvn_ll call (cand = -1) or candidate `cand` of the last mvn_ll_batch call left in its
@@ -845,3 +868,19 @@ def mvn_ll(cov, data, eff_range, gamma, u):
                                             _p(eff), eff.size, _p(gamma), gamma.size, _p(u), u.shape[0],
                                             u.shape[1], C.byref(out)))
     return out.value
+
+
+def mvn_ll_grad(cov, data, eff_range, gamma, u, weights=None):
+    """(value, grad) of Context.mvn_ll_grad on a context made for the call (glmmr_mcml_mvn_ll_grad): the analytic score of
+    mvn_ll in gamma; beyond the reference's exports"""
+    cov = _i(cov); data = _f(data).ravel(); eff = _f(eff_range).ravel(); gamma = _f(gamma).ravel()
+    u = _f(u)
+    if u.ndim == 1:
+        u = u.reshape(-1, 1, order="F")
+    w = _weights(weights, u.shape[1])
+    out = C.c_double()
+    grad = np.zeros(gamma.size)
+    _lib.check(_lib.lib().glmmr_mcml_mvn_ll_grad(cov.ctypes.data_as(c_ip), cov.shape[0], _p(data), data.size,
+                                                 _p(eff), eff.size, _p(gamma), gamma.size, _p(u), u.shape[0],
+                                                 u.shape[1], _p(w), C.byref(out), _p(grad)))
+    return out.value, grad

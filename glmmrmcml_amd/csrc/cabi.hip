@@ -493,6 +493,15 @@ extern "C" int glmmr_mcml_ctx_mvn_ll(glmmr_mcml_ctx* h, const double* theta, dou
     return MCML_OK;
 }
 
+extern "C" int glmmr_mcml_ctx_mvn_ll_grad(glmmr_mcml_ctx* h, const double* theta, const double* weights, double* value,
+                                          double* grad)
+{
+    MCML_REQUIRE(h && theta && value && grad, "mvn_ll_grad: null argument");
+    Ctx& c = h->c;
+    MCML_HIP(hipSetDevice(c.device));
+    return mvn_loglik_grad(c, theta, weights, value, grad);
+}
+
 extern "C" int glmmr_mcml_ctx_mvn_ll_batch(glmmr_mcml_ctx* h, const double* thetas, int k, double* out)
 {
     MCML_REQUIRE(h && thetas && out && k >= 1 && k <= 64, "mvn_ll_batch: bad argument");
@@ -628,6 +637,27 @@ extern "C" int glmmr_mcml_mvn_ll(const int32_t* cov, int cov_rows, const double*
     }
     if (!rc) rc = glmmr_mcml_set_u(h, u, Q, m, m);
     if (!rc) rc = glmmr_mcml_ctx_mvn_ll(h, gamma, out);
+    glmmr_mcml_ctx_destroy(h);
+    return rc;
+}
+
+extern "C" int glmmr_mcml_mvn_ll_grad(const int32_t* cov, int cov_rows, const double* data, int data_len,
+                                      const double* eff_range, int eff_len, const double* gamma, int ngamma,
+                                      const double* u, int Q, int m, const double* weights, double* value, double* grad)
+{
+    glmmr_mcml_problem p{};
+    p.cov = cov; p.cov_rows = cov_rows; p.data = data; p.data_len = data_len;
+    p.eff_range = eff_range; p.eff_len = eff_len; p.Q = Q;
+    glmmr_mcml_ctx* h = nullptr;
+    MCML_TRY(glmmr_mcml_ctx_create(&p, nullptr, &h));
+    int rc = MCML_OK;
+    if (ngamma < h->c.cov.npar) {
+        set_error("mvn_ll_grad: %d covariance parameters given, the functions need %d", ngamma, h->c.cov.npar);
+        rc = MCML_EINVAL;
+    }
+    if (!rc) rc = glmmr_mcml_set_u(h, u, Q, m, m);
+    if (!rc) rc = glmmr_mcml_ctx_mvn_ll_grad(h, gamma, weights, value, grad);
+    if (!rc) for (int k = h->c.cov.npar; k < ngamma; ++k) grad[k] = 0.0;
     glmmr_mcml_ctx_destroy(h);
     return rc;
 }

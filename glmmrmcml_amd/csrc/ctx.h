@@ -253,6 +253,17 @@ struct Ctx {
     // tests (glmmr_mcml_dbg_mvn_workspace): what mvn_large_blocks last left in Dwork [0] / Dbatch [1] -- the block's
     // dimension d, round_up(d, 16), the sample rows m, the leading dimension, the number of matrices (0: no call yet)
     struct MvnWs { int d = 0, dp = 0, m = 0, ld = 0, kb = 0; } mvn_ws[2];
+    // the analytic score of mvn_ll (mvn_grad.h): everything is allocated by the first gradient call, so a context that never
+    // asks pays nothing; Dwork and chol.linv are only read.  S / T: X' diag(w) X - (sum w) I and H of the large block at hand,
+    // Xw: the weighted copy of its solved sample rows; a dense block's parameters are slots [slot_base, + slot_count) of
+    // slot_par (the parameter index each adds to), small blocks first
+    struct MvnGrad {
+        bool ready = false;
+        DevMat S, T, Xw;
+        DevBuf w, diag, part, part_small, small_tab, res;
+        std::vector<int> slot_base, slot_count, slot_par;
+        int n_small_slots = 0, res_len = 0;
+    } grad;
     // the dense Cholesky stack (chol.h): inverted diagonal blocks, side streams + events, graph cache.  Last member: it is
     // torn down first, right after the communicator
     CholState chol;
@@ -285,6 +296,9 @@ int mvn_loglik_batch_parts(Ctx& c, const double* thetas, int k, int round, const
 // c.L = genD(0, chol=true, upper=false) (mcml_full.cpp:68): block-diagonal lower factor; have_L = chol.  A build that
 // fails (a block that is not positive definite) leaves have_L false: c.L is overwritten in place
 int mvn_gen_L(Ctx& c, const double* theta, bool chol);
+// value = sum_j w_j sum_b log N(u_bj; 0, D_b(theta)) over the locally held columns and grad[k] = d value / d theta_k, k < npar
+// (mvn_grad.h).  weights: mcols host values, or null for 1 each -- value is then mvn_loglik_sum's to the bit.  A query
+int mvn_loglik_grad(Ctx& c, const double* theta, const double* weights, double* value, double* grad);
 // the same matrix as a query: built into `out` (allocated here), no state of the context changes
 int mvn_gen_D(Ctx& c, const double* theta, bool chol, DevMat& out);
 

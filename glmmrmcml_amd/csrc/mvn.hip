@@ -16,7 +16,9 @@
 //     as extra rows, so the same GEMMs forward-substitute them -> Frobenius norm
 //     + log-det.
 // Reductions are two-stage with a fixed order, so the result is run-to-run
-// bit-reproducible.
+// bit-reproducible.  The analytic score of the same objective (beyond the reference's
+// exports) lives in mvn_grad.h, one gradient path per block kind.
+#include <cmath>
 #include "ctx.h"
 #include "reduce.h"
 #include "theta_scale.h"
@@ -207,6 +209,10 @@ __global__ void k_zero_upper(double* A, int lda, int n)
     if (i < n && j < n && i < j) A[i + (size_t)j * lda] = 0.0;
 }
 
+}  // namespace mcml
+#include "mvn_grad.h"      // the score's kernels and per-kind steps: they use cov_entry, k_diag_prep and LOG_2PI above
+namespace mcml {
+
 // ------------------------------------------------------------------ setup
 int mvn_setup(Ctx& c)
 {
@@ -248,6 +254,7 @@ int mvn_setup(Ctx& c)
         // the pointer the single evaluation's captured graph is keyed on
         MCML_TRY(c.chol.linv.ensure(sizeof(double) * linv_size(round_up(c.maxdim_large, 16)) * MVN_MAXBATCH));
     }
+    c.grad.ready = false;
     MCML_HIP(hipStreamSynchronize(c.stream));
     return MCML_OK;
 }
@@ -280,9 +287,11 @@ int mvn_loglik_sum(Ctx& c, const double* theta, double* sum_out)
 // launches per round).  kb = 1 (a single evaluation, or the last round of k = 8 j + 1 candidates) takes the graph.
 // round > 1: the kb matrices are the representatives of a round of `round` candidates (mvn_loglik_batch_parts); they
 // take the batch's schedule whatever kb is.  parts (nullable): 2 doubles per candidate, += (log-determinant, sum of
-// squares) of every block.
+// squares) of every block.  grad (nullable, kb = 1): the block's gradient terms follow its value terms (mvn_grad_large), while
+// c.chol.linv still holds this block's inverted diagonal blocks.
 static int mvn_large_blocks(Ctx& c, DevMat& W, int kb, const ThetaArg* th, const double* Us, int ldu, int m,
-                            double* scal, int sstride, int* flags, int round = 0, double* parts = nullptr)
+                            double* scal, int sstride, int* flags, int round = 0, double* parts = nullptr,
+                            const GradJob* grad = nullptr)
 {
     const bool batch = (round ? round : kb) > 1;
     const CovSpec& cs = c.cov;
@@ -328,11 +337,12 @@ static int mvn_large_blocks(Ctx& c, DevMat& W, int kb, const ThetaArg* th, const
         }
         if (parts) hipLaunchKernelGGL(k_accum_parts, dim3(1), dim3(kb), 0, c.stream, scal, sstride, parts);
         MCML_HIP(hipGetLastError());
+        if (grad) MCML_TRY(mvn_grad_large(c, *grad, b, W, dp, m, scal + 1));
     }
     return MCML_OK;
 }
 
-static int mvn_loglik_enqueue(Ctx& c, const double* theta, const double* Us, int ldu, int m)
+static int mvn_loglik_enqueue(Ctx& c, const double* theta, const double* Us, int ldu, int m, const GradJob* grad = nullptr)
 {
     MCML_REQUIRE(m > 0 && Us, "mvn_ll: no samples set");
     ThetaArg th;
@@ -375,7 +385,7 @@ static int mvn_loglik_enqueue(Ctx& c, const double* theta, const double* Us, int
             MCML_TRY(c.Dwork.alloc(c.maxdim_large + 16 + m, c.maxdim_large + 16));
             MCML_HIP(hipMemsetAsync(c.Dwork.d(), 0, sizeof(double) * (size_t)c.Dwork.ld * (c.maxdim_large + 16), c.stream));
         }
-        MCML_TRY(mvn_large_blocks(c, c.Dwork, 1, &th, Us, ldu, m, scal, 4, c.errflag()));
+        MCML_TRY(mvn_large_blocks(c, c.Dwork, 1, &th, Us, ldu, m, scal, 4, c.errflag(), 0, nullptr, grad));
     }
     return MCML_OK;
 }
@@ -385,6 +395,54 @@ int mvn_loglik_sum_on(Ctx& c, const double* theta, const double* Us, int ldu, in
     MCML_TRY(mvn_loglik_enqueue(c, theta, Us, ldu, m));
     MCML_TRY(copy_d2h(sum_out, c.scalars.d(), sizeof(double), c.stream));
     MCML_TRY(check_errflag(c, "mvn_ll: covariance block is not positive definite"));
+    return MCML_OK;
+}
+
+// The score (mvn_grad.h).  The value path runs exactly as mvn_loglik_sum_on enqueues it -- the same kernels in the same order,
+// so the workspace, the graph cache and, with unit weights, the value are what that call leaves -- with each large block's
+// gradient step after its value terms; the diagonal rows and the small blocks follow in buffers of their own.  One
+// read-back at the end; the slots are added to their parameters on the host, block by block.
+int mvn_loglik_grad(Ctx& c, const double* theta, const double* weights, double* value, double* grad)
+{
+    MCML_REQUIRE(c.mcols > 0 && c.U.d(), "mvn_ll: no samples set");
+    MCML_REQUIRE(theta && value && grad, "mvn_ll_grad: null argument");
+    const int m = c.mcols, R = c.cov.npar;
+    GradJob gj;
+    MCML_TRY(theta_arg(c, theta, gj.th));
+    gj.sw = (double)m;
+    if (weights) {
+        gj.sw = 0;
+        for (int j = 0; j < m; ++j) {
+            MCML_REQUIRE(weights[j] >= 0.0 && std::isfinite(weights[j]), "mvn_ll_grad: weight %d is negative or not finite", j);
+            gj.sw += weights[j];
+        }
+    }
+    MCML_TRY(mvn_grad_setup(c));
+    Ctx::MvnGrad& g = c.grad;
+    if (weights) {
+        MCML_TRY(g.w.ensure(sizeof(double) * (size_t)m));
+        MCML_TRY(copy_h2d(g.w.p, weights, sizeof(double) * (size_t)m, c.stream));
+        gj.w = g.w.d();
+    }
+    MCML_HIP(hipMemsetAsync(g.res.p, 0, sizeof(double) * g.res_len, c.stream));
+    int rc = mvn_loglik_enqueue(c, theta, c.U.d(), c.U.ld, m, &gj);
+    if (rc == MCML_OK) rc = mvn_grad_diag_small(c, gj, c.U.d(), c.U.ld, m);
+    std::vector<double> res(g.res_len);
+    double sum = 0;
+    if (rc == MCML_OK) rc = copy_d2h(res.data(), g.res.p, sizeof(double) * g.res_len, c.stream);
+    if (rc == MCML_OK) rc = copy_d2h(&sum, c.scalars.d(), sizeof(double), c.stream);
+    const int rc_flag = check_errflag(c, "mvn_ll_grad: covariance block is not positive definite");   // clears a raised flag
+    if (rc != MCML_OK) return rc;
+    MCML_TRY(rc_flag);
+    const CovSpec& cs = c.cov;
+    // unit weights stand for 1 / m each: the sums are divided as glmmr_mcml_ctx_mvn_ll divides its own
+    const double div = (double)m;
+    *value = weights ? res[0] + res[1] + res[2 + R] : sum / div;
+    for (int k = 0; k < R; ++k) grad[k] = res[2 + k];
+    for (int b = 0; b < cs.B; ++b)
+        for (int s = 0; s < g.slot_count[b]; ++s)
+            grad[g.slot_par[g.slot_base[b] + s]] += 0.5 * res[3 + R + g.slot_base[b] + s];
+    if (!weights) for (int k = 0; k < R; ++k) grad[k] /= div;
     return MCML_OK;
 }
 

@@ -78,6 +78,11 @@ class McmlFit(dict):
 
     __getattr__ = dict.__getitem__
 
+    @property
+    def theta_score(self):
+        """MCML(..., theta_score=True): the gradient of mvn_ll at the final covariance parameters; None otherwise"""
+        return self.get("theta_score")
+
     def table(self):
         """rows of print.mcml (R/printfunctions.R:41-58): (name, est, se, z, p, lower, upper) without the d's"""
         co = self["coefficients"]
@@ -113,6 +118,8 @@ class McmlFit(dict):
             out.append("%-14s %10.2f %10.2f %8.2f %8.2f %10.2f %10.2f" % r)
         out.append("cAIC: %.2f" % self["aic"])
         out.append("Approximate R-squared: Conditional: %.2f  Marginal: %.2f" % (self["Rsq"]["cond"], self["Rsq"]["marg"]))
+        if self.get("theta_score") is not None:
+            out.append("Max. |score| of the covariance parameters: %.3g" % np.max(np.abs(self["theta_score"])))
         if not self["converged"]:
             out.append("Warning: algorithm did not converge")
         return "\n".join(out)
@@ -239,7 +246,7 @@ class ModelMCML:
         return dict(par=list(names), est=est, SE=SE, lower=est - _Z975 * SE, upper=est + _Z975 * SE)
 
     # ---- MCML ----------------------------------------------------------------------------------------------------
-    def MCML(self, y, *args, trajectory=None, draws=None, **kwargs):
+    def MCML(self, y, *args, trajectory=None, draws=None, theta_score=False, **kwargs):
         """_mcml below (its arguments, unchanged); trajectory ("step" / "component", None = leave the backend's default
         alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  draws ("hmc" / "exact" /
         "exact_component", None = leave the default alone): what the HMC sampler's call returns -- "exact" draws the conditional distribution of
@@ -247,7 +254,10 @@ class ModelMCML:
         "exact_component" also on the sparse operator of a block-structured design, csrc/hmc_exact_comp.h) and changes
         nothing elsewhere; `sampler` below picks the route, not this.  Either becomes the backend's process-wide
         default for the duration of the call -- the contexts the exports create inherit it -- and the previous default is
-        restored; do not run two fits with different choices in one process at the same time."""
+        restored; do not run two fits with different choices in one process at the same time.
+        theta_score = True: the fit also carries `theta_score`, the analytic gradient of mvn_ll in the covariance parameters at
+        the final estimate on re_samps (the backend's mvn_ll_grad) -- how far the theta-step stopped from a stationary point;
+        False: nothing more is called."""
         prev_t = prev_d = None
         if trajectory is not None:
             prev_t = self._be.get_default_trajectory()
@@ -256,7 +266,12 @@ class ModelMCML:
             if draws is not None:
                 prev_d = self._be.get_default_draws()
                 self._be.set_default_draws(draws)
-            return self._mcml(y, *args, **kwargs)
+            fit = self._mcml(y, *args, **kwargs)
+            if theta_score:
+                P = self.X.shape[1]
+                cov_par = fit["theta"][P:P + self.cov_parameters.size]
+                fit["theta_score"] = np.asarray(self._be.mvn_ll_grad(*self._ddata(), cov_par, fit["re_samps"])[1])
+            return fit
         finally:
             if prev_d is not None:
                 self._be.set_default_draws(prev_d)

@@ -111,6 +111,14 @@ int glmmr_mcml_ctx_mvn_ll(glmmr_mcml_ctx* ctx, const double* theta, double* out)
  * after the other.  out[j] = log-likelihood at candidate j (equal to the single evaluation to rounding), NaN where
  * D(theta_j) is not positive definite.  k <= 64. */
 int glmmr_mcml_ctx_mvn_ll_batch(glmmr_mcml_ctx* ctx, const double* thetas, int k, double* out);
+/* The analytic score of the same objective (beyond the reference's exports, which only evaluate it): one factorisation
+ * and O(d^3 + d^2 m) of matrix-core work whatever the number of parameters.
+ * value = sum_j w_j sum_b log N(u_bj; 0, D_b(theta)) and grad[k] = d value / d theta_k, k < npar.
+ * weights: mcols values >= 0, or NULL for 1/mcols each (value is then glmmr_mcml_ctx_mvn_ll's, to the bit).
+ * A QUERY: changes nothing the context holds.  GLMMR_MCML_ENOTPD where D(theta) is not positive definite.
+ * A context that holds a shard of the columns differentiates its own columns: nothing is exchanged. */
+int glmmr_mcml_ctx_mvn_ll_grad(glmmr_mcml_ctx* ctx, const double* theta, const double* weights,
+                               double* value, double* grad);
 /* DMatrix::genD(0, chol, false) (mcml_full.cpp:68) -> out (Q x Q).  A QUERY, like mvn_ll, mvn_ll_batch, loglik and mcnr:
  * it is built in storage of its own and changes nothing the context holds -- the L of the last update_L / set_L and the
  * operator made from it stay in force.  GLMMR_MCML_ENOTPD where D(theta) is not positive definite (chol != 0). */
@@ -434,6 +442,10 @@ int glmmr_mcml_ctx_la(glmmr_mcml_ctx* ctx, const double* start, int nstart, int 
 int glmmr_mcml_mvn_ll(const int32_t* cov, int cov_rows, const double* data, int data_len,
                       const double* eff_range, int eff_len, const double* gamma, int ngamma,
                       const double* u, int Q, int m, double* out);
+/* the score of the same, stateless: glmmr_mcml_ctx_mvn_ll_grad on a context made for the call; grad holds ngamma values */
+int glmmr_mcml_mvn_ll_grad(const int32_t* cov, int cov_rows, const double* data, int data_len,
+                           const double* eff_range, int eff_len, const double* gamma, int ngamma,
+                           const double* u, int Q, int m, const double* weights, double* value, double* grad);
 
 /* ---- test hooks (building blocks exposed for tests/ and bench.py only) ---- */
 /* every evaluation of the theta-step's objective on this context as a row (theta_1 .. theta_R, MVN log-likelihood):
