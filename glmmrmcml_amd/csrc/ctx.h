@@ -262,6 +262,7 @@ struct Ctx {
         DevMat S, T, Xw;
         DevBuf w, diag, part, part_small, small_tab, res;
         std::vector<int> slot_base, slot_count, slot_par;
+        std::vector<int> slot_scale;     // per slot: c where dlog is the constant c / theta over the whole block (0: it is not)
         int n_small_slots = 0, res_len = 0;
     } grad;
     // the dense Cholesky stack (chol.h): inverted diagonal blocks, side streams + events, graph cache.  Last member: it is

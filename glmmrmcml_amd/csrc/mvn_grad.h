@@ -14,6 +14,7 @@
 //   * large blocks: after the factorisation the workspace holds L and the m solved rows X = (inv(L) U)'.  S = X' diag(w) X -
 //     (sum w) I (transposed-A GEMM, K = m, the weights on a copy of the rows), H = inv(L)' S inv(L) by two transposed solves
 //     with a transposition between them, and a reduction over the lower 64 x 16 tiles of H that rebuilds every entry's terms.
+//     A slot whose dlog is constant over the block (a pure scale) is coef trace(S) in closed form (k_grad_scale_slot).
 // All reductions are two-stage with a fixed order and there is no floating-point atomic: the result is run-to-run
 // bit-reproducible and does not depend on what the context did before.
 #pragma once
@@ -254,8 +255,10 @@ __global__ __launch_bounds__(256) void k_grad_weigh_rows(const double* X, int ld
         Xw[j + (size_t)i * ldw] = j < m ? wj * X[j + (size_t)i * ldx] : 0.0;
 }
 
-// S_ii -= sum w, i < n, and v[0] += sum w (-0.5 d log 2 pi - 0.5 logdet) - 0.5 trace(X' diag(w) X): the block's weighted value
-__global__ __launch_bounds__(256) void k_grad_sdiag(double* S, int lds, int d, int n, double sw, const double* logdet, double* v)
+// S_ii -= sum w, i < n, and v[0] += sum w (-0.5 d log 2 pi - 0.5 logdet) - 0.5 trace(X' diag(w) X): the block's weighted value;
+// trs[0] = trace(X' diag(w) X) - d sum w, the trace of the block's S (k_grad_scale_slot)
+__global__ __launch_bounds__(256) void k_grad_sdiag(double* S, int lds, int d, int n, double sw, const double* logdet, double* v,
+                                                    double* trs)
 {
     __shared__ double sh[4];
     double tr = 0;
@@ -265,8 +268,18 @@ __global__ __launch_bounds__(256) void k_grad_sdiag(double* S, int lds, int d, i
         S[i + (size_t)i * lds] = s - sw;
     }
     const double t = block_sum(tr, sh);
-    if (threadIdx.x == 0) v[0] += sw * (-0.5 * d * LOG_2PI - 0.5 * logdet[0]) - 0.5 * t;
+    if (threadIdx.x == 0) {
+        v[0] += sw * (-0.5 * d * LOG_2PI - 0.5 * logdet[0]) - 0.5 * t;
+        trs[0] = t - sw * d;
+    }
 }
+
+// A slot whose dlog is the constant coef over the whole block -- the scale of sqexp / fexp, a gr term of a dense block -- has
+// sum_ij D_ij H_ij dlog = coef trace(D H) = coef trace(S), D = L L' and H = inv(L)' S inv(L): the trace taken BEFORE the two
+// solves.  The contraction of H with D arrives at the same number through the solves against the inverted diagonal blocks and
+// loses kappa_2(L_kk) on the way (two to four digits of the scale's gradient at kappa_2(D) = 1e9 .. 1e12,
+// tests/illcond_cases.py); the slot is overwritten with the closed form.
+__global__ void k_grad_scale_slot(const double* trs, double coef, double* out) { out[0] = coef * trs[0]; }
 
 // partials[workgroup * GRAD_SLOTS + s] = the workgroup's sum of mult H_ij D_ij dlog_{slot0 + s} over its 64 x 16 tile of the
 // lower triangle (mult 1 on the diagonal, 2 below; the identity border i >= dim is skipped); tiles as build_dense_body
@@ -314,6 +327,7 @@ static int mvn_grad_setup(Ctx& c)
     g.slot_base.assign(cs.B, -1);
     g.slot_count.assign(cs.B, 0);
     g.slot_par.clear();
+    g.slot_scale.clear();
     std::vector<int> sbase, scount;
     for (int pass = 0; pass < 2; ++pass)
         for (int b = 0; b < cs.B; ++b) {
@@ -321,7 +335,12 @@ static int mvn_grad_setup(Ctx& c)
             if (blk.all_gr || (blk.dim <= SMALL_BLOCK) != (pass == 0)) continue;
             g.slot_base[b] = (int)g.slot_par.size();
             for (int r = blk.r0; r < blk.r1; ++r)
-                for (int q = 0; q < CovSpec::fn_npar(cs.c(r, 2)); ++q) g.slot_par.push_back(cs.c(r, 4) + q);
+                for (int q = 0; q < CovSpec::fn_npar(cs.c(r, 2)); ++q) {
+                    const int fn = cs.c(r, 2);
+                    g.slot_par.push_back(cs.c(r, 4) + q);
+                    // cov_term_dlog: gr 2 / t everywhere the product is not 0; sqexp and fexp 1 / t0
+                    g.slot_scale.push_back(fn == 1 ? 2 : ((fn == 4 || fn == 7) && q == 0) ? 1 : 0);
+                }
             g.slot_count[b] = (int)g.slot_par.size() - g.slot_base[b];
             if (pass == 0) { sbase.push_back(g.slot_base[b]); scount.push_back(g.slot_count[b]); }
         }
@@ -333,8 +352,8 @@ static int mvn_grad_setup(Ctx& c)
         MCML_TRY(copy_h2d(g.small_tab.as<int>() + sbase.size(), scount.data(), sizeof(int) * scount.size(), c.stream));
     }
     // results: [0] weighted value of the large blocks, [1] of the small ones, [2 .. 2 + npar] the diagonal rows' sums per
-    // parameter and their value, then one double per slot
-    g.res_len = 3 + cs.npar + (int)g.slot_par.size();
+    // parameter and their value, then one double per slot, then the trace of the large block at hand (k_grad_sdiag)
+    g.res_len = 4 + cs.npar + (int)g.slot_par.size();
     MCML_TRY(g.res.ensure(sizeof(double) * g.res_len));
     MCML_HIP(hipStreamSynchronize(c.stream));
     g.ready = true;
@@ -365,7 +384,8 @@ static int mvn_grad_large(Ctx& c, const GradJob& gj, int b, const DevMat& W, int
         EpiAxpby epi{g.S.d(), g.S.ld, 1.0, 0.0};
         MCML_TRY(launch_gemm_at(c.stream, dp, dp, m, X, ld, g.Xw.d(), g.Xw.ld, epi));
     }
-    hipLaunchKernelGGL(k_grad_sdiag, dim3(1), dim3(256), 0, c.stream, g.S.d(), g.S.ld, d, dp, gj.sw, logdet, g.res.d());
+    hipLaunchKernelGGL(k_grad_sdiag, dim3(1), dim3(256), 0, c.stream, g.S.d(), g.S.ld, d, dp, gj.sw, logdet, g.res.d(),
+                       g.res.d() + g.res_len - 1);
     MCML_HIP(hipGetLastError());
     // H = inv(L)' S inv(L): T1 = inv(L)' S in place, H = inv(L)' T1' (S is symmetric)
     MCML_TRY(trsm_left_lower_trans(c, W.d(), ld, dp, g.S.d(), g.S.ld, dp));
@@ -380,6 +400,13 @@ static int mvn_grad_large(Ctx& c, const GradJob& gj, int b, const DevMat& W, int
                            c.d_cov.as<int32_t>(), cs.rows, c.d_data.d(), gj.th, slot0, g.part.d());
         hipLaunchKernelGGL(k_grad_sum, dim3(ns), dim3(256), 0, c.stream, g.part.d(), nwg, (size_t)1, (size_t)GRAD_SLOTS,
                            grad_slot_out(c, g.slot_base[b] + slot0));
+        MCML_HIP(hipGetLastError());
+    }
+    for (int s = 0; s < g.slot_count[b]; ++s) {
+        const int slot = g.slot_base[b] + s;
+        if (!g.slot_scale[slot]) continue;
+        hipLaunchKernelGGL(k_grad_scale_slot, dim3(1), dim3(1), 0, c.stream, g.res.d() + g.res_len - 1,
+                           g.slot_scale[slot] / gj.th.v[g.slot_par[slot]], grad_slot_out(c, slot));
         MCML_HIP(hipGetLastError());
     }
     return MCML_OK;

@@ -10,8 +10,11 @@ long double (u = 2^-53 is the unit roundoff of the float64 under test):
     potrs              |L L' Z - B|    <= C n u (2 + C n u) |L| |L'| |Z|               (two-sided, derived at potrs_ratio)
 
 C = 1 is the textbook constant of the substitution algorithms for any order of summation.  The library multiplies panels by
-explicitly inverted 128-wide diagonal blocks, which adds a term proportional to kappa_2(L_kk) <= sqrt(kappa_2(A)): families W
-and S (kappa_2(A) <= 9, kappa_2(L_kk) <= 3) are held to C = 2; `twin_potrf` and the twin solves below restate the library's
+explicitly inverted 128-wide diagonal blocks, which adds a term proportional to kappa_2(L_kk) <= sqrt(kappa_2(A)) -- measured
+on sqexp blocks (tests/illcond_cases.py, the twin with the kernel's own leaf, twin_leaf16): the factor's ratio to the C = 1 bound
+is 0.42 at kappa_2(A) = 3e6, 2.0 at 2e9 and 15 at 1e12 (device: 0.33, 1.2, 17.6), a transposed solve's 1.2, 19 and 120
+(device: 0.7, 13.6, 55); the bounds up there carry a constant per rung of kappa --;
+families W and S (kappa_2(A) <= 9, kappa_2(L_kk) <= 3) are held to C = 2; `twin_potrf` and the twin solves below restate the library's
 algorithm in float64 numpy, and tests/test_chol_reference_cpu.py asserts that the twin stays at or below a quarter of every
 bound on every matrix the GPU tests use.  Every ratio function returns (worst ratio to the C = 1 bound, where), so a failure
 names the element.
@@ -235,11 +238,60 @@ def _leaf(Akk):
     return Lkk, np.tril(cl.forward_sub(Lkk, np.eye(len(Lkk))))
 
 
-def twin_potrf(A, extra=None, drop=None):
+def twin_leaf16(Akk, drop_term=None, wrong_tile=None):
+    """(L_kk, inv(L_kk)) in float64 as k_potrf_leaf (csrc/chol.hip) computes them: right-looking steps 16 columns wide.
+    Step t: the 16 x 16 diagonal tile is eliminated column by column, every row scaled by the RECIPROCAL pivot
+    y = 1 / sqrt(pivot); the 16 rows of the identity ride along (their solution is X_tt, the diagonal tile of the
+    inverse, whose diagonal is the reciprocal pivots) and so do the first 32 rows of the panel below -- these by
+    substitution; the remaining panel rows are PRODUCTS with X_tt'; the trailing matrix is updated with K = 16.  Block
+    row I of the inverse: X_IJ = -X_II (sum_{K = J}^{I - 1} L_IK X_KJ), J < I.  A ragged last tile is the kernel's
+    identity-padded one (the padding meets zeros only).  Raises LinAlgError at a pivot that is not > 0, as the kernel
+    flags it.
+
+    Mutations for the power checks: drop_term = (I, J, K) leaves the term K out of that sum; wrong_tile = t multiplies
+    the panel rows of step t (t >= 1) by the inverse tile of step t - 1."""
+    n = len(Akk)
+    S = np.tril(np.asarray(Akk, dtype=np.float64))
+    X = np.zeros((n, n))
+    nt = (n + 15) // 16
+    for t in range(nt):
+        kb, ke = 16 * t, min(16 * t + 16, n)
+        w, pe = ke - kb, min(kb + 48, n)
+        R = np.vstack([S[kb:pe, kb:ke], np.eye(w)])          # tile rows, ride-along panel rows, identity rows
+        for c in range(w):
+            if not R[c, c] > 0:
+                raise np.linalg.LinAlgError("leaf: pivot %d is not positive" % (kb + c))
+            l = R[:, c] * (1.0 / np.sqrt(R[c, c]))
+            R[:, c] = l
+            if c + 1 < w:
+                R[:, c + 1:] -= l[:, None] * l[None, c + 1:w]
+        S[kb:ke, kb:ke] = np.tril(R[:w])
+        S[ke:pe, kb:ke] = R[w:pe - kb]
+        Xtt = np.tril(R[pe - kb:].T)
+        X[kb:ke, kb:ke] = Xtt
+        if pe < n:
+            Xp = X[kb - 16:kb, kb - 16:kb] if wrong_tile == t else Xtt
+            S[pe:, kb:ke] = S[pe:, kb:ke] @ Xp.T
+        if ke < n:
+            P = S[ke:, kb:ke]
+            S[ke:, ke:] -= P @ P.T
+            S[ke:, ke:] = np.tril(S[ke:, ke:])
+        for J in range(t):                                   # block row t of the inverse
+            T = np.zeros((w, 16))
+            for K in range(J, t):
+                if drop_term != (t, J, K):
+                    T += S[kb:ke, 16 * K:16 * K + 16] @ X[16 * K:16 * K + 16, 16 * J:16 * J + 16]
+            X[kb:ke, 16 * J:16 * J + 16] = -(Xtt @ T)
+    return S, X
+
+
+def twin_potrf(A, extra=None, drop=None, leaf=None):
     """(L, X, invs): the library's algorithm in float64 numpy -- 128-wide panels; each diagonal block factorised and its
     factor inverted; the panel below (and the `extra` rows carried under the matrix, m x n) as a PRODUCT with that
     inverse; a SYRK update of the trailing matrix.  drop = (t, s): the trailing update of step t leaves out the
-    16-wide slice s of its K = 128 (the mutation of the power check)."""
+    16-wide slice s of its K = 128 (the mutation of the power check).  leaf: what factorises and inverts a diagonal
+    block (default _leaf, textbook substitution; twin_leaf16 restates the kernel's own leaf)."""
+    leaf = _leaf if leaf is None else leaf
     n = A.shape[0]
     m = 0 if extra is None else extra.shape[0]
     W = np.zeros((n + m, n))
@@ -249,7 +301,7 @@ def twin_potrf(A, extra=None, drop=None):
     invs = []
     for t, k in enumerate(range(0, n, NB)):
         nb = min(NB, n - k)
-        Lkk, inv = _leaf(W[k:k + nb, k:k + nb])
+        Lkk, inv = leaf(W[k:k + nb, k:k + nb])
         W[k:k + nb, k:k + nb] = Lkk
         invs.append(inv)
         if k + nb < n + m:

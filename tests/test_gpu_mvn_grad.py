@@ -6,7 +6,11 @@ must not serve the other block's solves) and EDGE32 (the 32 / 33 boundary).
 
 Tolerance of the gradient: bound_k = 2^-52 kappa mag_k (the helper's docstring), of which the float64 numpy twin of the
 same algorithm uses at most 0.0101 (test_mvn_grad_reference_cpu.py) and the device, measured, at most 0.016 (TWO_LARGE_B,
-m = 1); the value: the 1e-10 relative mvn_ll is pinned to."""
+m = 1); the value: the 1e-10 relative mvn_ll is pinned to.
+
+mag_k carries |inv(D)|, so bound_k is loose by about kappa once kappa is large (the device sits at 1e-9 to 1e-11 of it at
+kappa >= 1e9): tests/test_gpu_illcond.py holds the gradient to C 2^-52 kappa |ref grad_k| as well, on blocks up to
+kappa = 2e12."""
 import functools
 
 import numpy as np
