@@ -6,6 +6,7 @@ column-major float64 / int32 and handed over as plain pointers; no torch types
 cross the boundary.
 """
 import ctypes as C
+from contextlib import contextmanager as _contextmanager
 
 import numpy as np
 
@@ -63,75 +64,80 @@ def phase_ms(enable=True, reset=False):
     return {k: float(out[i]) for i, k in enumerate(("sample", "beta_step", "theta_step", "refresh"))}
 
 
-_TRAJ = {"step": 0, "component": 1}
+class _Mode:
+    """One of the three opt-in modes of a context (include/glmmr_mcml_c.h): its names in the order of their codes, the
+    process default new contexts start with and the setter of one context.  An unknown name is a KeyError."""
+
+    def __init__(self, entry, *names):
+        self.entry = entry                                  # glmmr_mcml_{set_default_, get_default_, ctx_set_}<entry>
+        self.code = {k: i for i, k in enumerate(names)}
+        self.name = dict(enumerate(names))
+
+    def set_default(self, mode):
+        _lib.check(getattr(_lib.lib(), "glmmr_mcml_set_default_" + self.entry)(self.code[mode]))
+
+    def get_default(self):
+        return self.name[getattr(_lib.lib(), "glmmr_mcml_get_default_" + self.entry)()]
+
+    def set(self, ctx, mode):
+        _lib.check(getattr(_lib.lib(), "glmmr_mcml_ctx_set_" + self.entry)(ctx._h, self.code[mode]))
+
+    @_contextmanager
+    def default(self, mode):
+        """mode=None leaves the process default alone; otherwise it is set for the duration of a call and restored"""
+        prev = None if mode is None else self.get_default()
+        if mode is not None:
+            self.set_default(mode)
+        try:
+            yield
+        finally:
+            if mode is not None:
+                self.set_default(prev)
+
+
+_TRAJ = _Mode("trajectory", "step", "component")
+_DRAWS = _Mode("draws", "hmc", "exact", "exact_component")
+_LA_OP = _Mode("la_operator", "dense", "component", "component_wide")
 
 
 def set_default_trajectory(mode):
     """the trajectory mode new contexts start with ("step" or "component"), the contexts the one-shot exports create
     included (include/glmmr_mcml_c.h glmmr_mcml_set_default_trajectory)"""
-    _lib.check(_lib.lib().glmmr_mcml_set_default_trajectory(_TRAJ[mode]))
+    _TRAJ.set_default(mode)
 
 
 def get_default_trajectory():
-    return {v: k for k, v in _TRAJ.items()}[_lib.lib().glmmr_mcml_get_default_trajectory()]
-
-
-_DRAWS = {"hmc": 0, "exact": 1, "exact_component": 2}
-_DRAWS_NAME = {v: k for k, v in _DRAWS.items()}
+    return _TRAJ.get_default()
 
 
 def set_default_draws(mode):
     """what hmc_sample draws on new contexts ("hmc", "exact" or "exact_component"), the contexts the one-shot exports create included
     (include/glmmr_mcml_c.h glmmr_mcml_set_default_draws)"""
-    _lib.check(_lib.lib().glmmr_mcml_set_default_draws(_DRAWS[mode]))
+    _DRAWS.set_default(mode)
 
 
 def get_default_draws():
-    return _DRAWS_NAME[_lib.lib().glmmr_mcml_get_default_draws()]
-
-
-_LA_OP = {"dense": 0, "component": 1, "component_wide": 2}
-_LA_OP_NAME = {v: k for k, v in _LA_OP.items()}
+    return _DRAWS.get_default()
 
 
 def set_default_la_operator(mode):
     """the operator of the Laplace fits new contexts start with ("dense", "component" or "component_wide"), the contexts mcml_la /
     mcml_la_nr create included (include/glmmr_mcml_c.h glmmr_mcml_set_default_la_operator)"""
-    _lib.check(_lib.lib().glmmr_mcml_set_default_la_operator(_LA_OP[mode]))
+    _LA_OP.set_default(mode)
 
 
 def get_default_la_operator():
-    return _LA_OP_NAME[_lib.lib().glmmr_mcml_get_default_la_operator()]
+    return _LA_OP.get_default()
 
 
 def la_component_launches():
     """k_lac_factor launches of this process so far, over all contexts (test hook, glmmr_mcml_dbg_la_component_launches)"""
-    f = _lib.lib().glmmr_mcml_dbg_la_component_launches
-    f.restype = C.c_longlong
-    return int(f())
-
-
-class _default_la_operator:
-    """operator=None leaves the process default alone; otherwise it is set for the duration of a call and restored"""
-
-    def __init__(self, operator):
-        self.operator = operator
-
-    def __enter__(self):
-        if self.operator is not None:
-            self.prev = get_default_la_operator()
-            set_default_la_operator(self.operator)
-
-    def __exit__(self, *a):
-        if self.operator is not None:
-            set_default_la_operator(self.prev)
+    return int(_lib.lib().glmmr_mcml_dbg_la_component_launches())
 
 
 def traj_launches():
     """k_cm_traj launches of this process so far, over all contexts (test hook, glmmr_mcml_dbg_traj_launches)"""
-    f = _lib.lib().glmmr_mcml_dbg_traj_launches
-    f.restype = C.c_longlong
-    return int(f())
+    return int(_lib.lib().glmmr_mcml_dbg_traj_launches())
 
 
 def dbg_dgemm_at(A, B, C0, K, alpha=1.0, beta=0.0, tile=-1):
@@ -145,7 +151,7 @@ def dbg_dgemm_at(A, B, C0, K, alpha=1.0, beta=0.0, tile=-1):
     M, N = A.shape[1], B.shape[1]
     out = B if C0 is None else np.array(C0, dtype=np.float64, order="F")
     assert C0 is None or out.shape == (M, N)
-    _lib.check(_lib.lib().glmmr_mcml_dbg_dgemm_at(M, N, int(K), _p(A), K2, _p(B), K2, C.c_double(alpha), C.c_double(beta),
+    _lib.check(_lib.lib().glmmr_mcml_dbg_dgemm_at(M, N, int(K), _p(A), K2, _p(B), K2, alpha, beta,
                                                   _p(out), out.shape[0], int(tile)))
     return out[:M]
 
@@ -166,6 +172,7 @@ def _i(a):
 
 
 def _p(a):
+    """the address of an array's data, whatever its dtype: the prototypes (_lib.py) take every pointer as void*"""
     return None if a is None else a.ctypes.data_as(c_dp)
 
 
@@ -180,6 +187,28 @@ def _weights(weights, m):
     return w
 
 
+def _cols(u):
+    """samples as a column-major matrix; a vector is one column"""
+    u = _f(u)
+    return u.reshape(-1, 1, order="F") if u.ndim == 1 else u
+
+
+def _diag(d):
+    """a diagnostics struct (HmcDiag, NutsDiag) as the dict of its fields"""
+    return {k: getattr(d, k) for k, _ in d._fields_}
+
+
+def _plan(fn, ctype, keys, *args, bools=(), named=()):
+    """a plan hook's integers as a dict: fn(*args, out) fills len(keys) values of `ctype`; the keys in `bools` become bool,
+    named = (a _Mode, its keys) become that mode's names"""
+    out = (ctype * len(keys))()
+    _lib.check(fn(*args, out))
+    d = dict(zip(keys, (int(v) for v in out)))
+    d.update((k, bool(d[k])) for k in bools)
+    d.update((k, named[0].name[d[k]]) for k in named[1:])
+    return d
+
+
 class Context:
     """A device-resident MCML problem (glmmr_mcml_ctx).  Inputs are uploaded once;
     afterwards only parameter vectors go down and scalars come back."""
@@ -187,23 +216,13 @@ class Context:
     def __init__(self, cov, data, eff_range, Z=None, X=None, y=None, family=None, link=None,
                  device=0, stream=None, rank=0, world=1, reduce=None):
         L = _lib.lib()
-        self._cov = _i(cov)
-        assert self._cov.ndim == 2 and self._cov.shape[1] == 5, "cov must be rows x 5"
-        self._data = _f(data).ravel()
-        self._eff = _f(eff_range).ravel()
-        p = Problem()
-        p.cov = self._cov.ctypes.data_as(c_ip); p.cov_rows = self._cov.shape[0]
-        p.data = _p(self._data); p.data_len = self._data.size
-        p.eff_range = _p(self._eff); p.eff_len = self._eff.size
-        self.n = self.P = 0
+        p, self._keep = _problem(cov, data, eff_range, Z, X, y, family, link)
+        cv = self._keep["cov"]
+        assert cv.ndim == 2 and cv.shape[1] == 5, "cov must be rows x 5"
+        self.n, self.P = p.n, p.P
         if Z is not None:
-            self._Z = _f(Z); self._X = _f(X); self._y = _f(y).ravel()
-            self.n, self.Q = self._Z.shape
-            self.P = self._X.shape[1]
-            assert self._X.shape[0] == self.n and self._y.size == self.n
-            p.Z = _p(self._Z); p.X = _p(self._X); p.y = _p(self._y)
-            p.n = self.n; p.Q = self.Q; p.P = self.P
-            p.family = family.encode(); p.link = link.encode()
+            self.Q = p.Q
+            assert self._keep["X"].shape[0] == self.n and self._keep["y"].size == self.n
         o = DevOpts()
         o.device = device; o.stream = stream; o.rank = rank; o.world = world
         self._reduce_cb = REDUCE_FN(reduce) if reduce is not None else REDUCE_FN()
@@ -213,7 +232,7 @@ class Context:
         _lib.check(L.glmmr_mcml_ctx_create(C.byref(p), C.byref(o), C.byref(self._h)))
         self.family, self.link = family, link
         if Z is None:
-            self.Q = int(sum(self._cov[np.r_[True, self._cov[1:, 0] != self._cov[:-1, 0]], 1]))
+            self.Q = int(sum(cv[np.r_[True, cv[1:, 0] != cv[:-1, 0]], 1]))
         self.mcols = 0
 
     def close(self):
@@ -252,9 +271,7 @@ class Context:
 
     # -- samples
     def set_u(self, u, niter=None):
-        u = _f(u)
-        if u.ndim == 1:
-            u = u.reshape(-1, 1, order="F")
+        u = _cols(u)
         _lib.check(_lib.lib().glmmr_mcml_set_u(self._h, _p(u), u.shape[0], u.shape[1],
                                                u.shape[1] if niter is None else niter))
         self.mcols = u.shape[1]                 # after the check: a refused call leaves get_u() as it was
@@ -357,14 +374,14 @@ class Context:
     def loglik(self, beta, var_par):
         beta = _f(beta).ravel()
         out = C.c_double()
-        _lib.check(_lib.lib().glmmr_mcml_ctx_loglik(self._h, _p(beta), C.c_double(var_par), C.byref(out)))
+        _lib.check(_lib.lib().glmmr_mcml_ctx_loglik(self._h, _p(beta), var_par, C.byref(out)))
         return out.value
 
     def mcnr(self, beta, var_par):
         beta = _f(beta).ravel()
         bout = np.zeros(self.P); sig = C.c_double()
         stats = np.zeros(self.P * self.P + self.P + 1)
-        _lib.check(_lib.lib().glmmr_mcml_ctx_mcnr(self._h, _p(beta), C.c_double(var_par), _p(bout),
+        _lib.check(_lib.lib().glmmr_mcml_ctx_mcnr(self._h, _p(beta), var_par, _p(bout),
                                                   C.byref(sig), _p(stats)))
         P = self.P
         return dict(beta=bout, sigma=sig.value, XtWX=stats[:P * P].reshape(P, P, order="F"),
@@ -383,7 +400,7 @@ class Context:
         """log_prob / log_grad of every column of V (test hook for A4/A5)"""
         beta = _f(beta).ravel(); V = _f(V)
         lp = np.zeros(V.shape[1]); G = np.zeros_like(V, order="F")
-        _lib.check(_lib.lib().glmmr_mcml_dbg_log_prob_grad(self._h, _p(beta), C.c_double(var_par), _p(V),
+        _lib.check(_lib.lib().glmmr_mcml_dbg_log_prob_grad(self._h, _p(beta), var_par, _p(V),
                                                            V.shape[1], _p(lp), _p(G)))
         return lp, G
 
@@ -400,15 +417,10 @@ class Context:
         probs = np.zeros((chains, total), order="F") if want_trace else None
         ncols = C.c_int()
         _lib.check(_lib.lib().glmmr_mcml_ctx_hmc_sample(
-            self._h, _p(beta), C.c_double(var_par), C.byref(o), C.c_uint64(seed), C.c_uint32(iter_idx),
-            _p(ii), _p(im), None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_uint8)),
-            _p(probs), C.byref(d), C.byref(ncols)))
+            self._h, _p(beta), var_par, C.byref(o), seed, iter_idx, _p(ii), _p(im), _p(flags), _p(probs), C.byref(d),
+            C.byref(ncols)))
         self.mcols = ncols.value
-        diag = dict(accept_rate=d.accept_rate, mean_e=d.mean_e, min_e=d.min_e, max_e=d.max_e,
-                    max_steps_used=d.max_steps_used, leapfrog_total=d.leapfrog_total)
-        if want_trace:
-            return diag, flags, probs
-        return diag
+        return (_diag(d), flags, probs) if want_trace else _diag(d)
 
     def nuts_sample(self, beta, var_par, warmup, nsamp, seed, chains=1, chain_offset=0, iter_idx=0, max_treedepth=10,
                     adapt_delta=0.8, stepsize=1.0, want_trace=False, metric="diag_e"):
@@ -418,7 +430,6 @@ class Context:
                      {"diag_e": 0, "unit_e": 1}[metric])
         d = NutsDiag()
         total = warmup + -(-nsamp // chains)
-        c_ip_ = C.POINTER(C.c_int)
         tr = None
         if want_trace:
             tr = dict(depth=np.zeros((chains, total), dtype=np.int32, order="F"),
@@ -426,14 +437,10 @@ class Context:
                       eps=np.zeros((chains, total), order="F"), accept=np.zeros((chains, total), order="F"))
         ncols = C.c_int()
         _lib.check(_lib.lib().glmmr_mcml_ctx_nuts_sample(
-            self._h, _p(beta), C.c_double(var_par), C.byref(o), C.c_uint64(seed), C.c_uint32(iter_idx),
-            None if tr is None else tr["depth"].ctypes.data_as(c_ip_), None if tr is None else tr["nleap"].ctypes.data_as(c_ip_),
-            None if tr is None else _p(tr["eps"]), None if tr is None else _p(tr["accept"]), C.byref(d), C.byref(ncols)))
+            self._h, _p(beta), var_par, C.byref(o), seed, iter_idx,
+            *(_p(tr[k]) if tr else None for k in ("depth", "nleap", "eps", "accept")), C.byref(d), C.byref(ncols)))
         self.mcols = ncols.value
-        diag = dict(mean_e=d.mean_e, min_e=d.min_e, max_e=d.max_e, divergent=d.divergent, treedepth_hits=d.treedepth_hits,
-                    batched_leapfrogs=d.batched_leapfrogs, stepsize_search_leapfrogs=d.stepsize_search_leapfrogs,
-                    packs=d.packs)
-        return (diag, tr) if want_trace else diag
+        return (_diag(d), tr) if want_trace else _diag(d)
 
     # -- drivers on the resident context
     def _ext(self, seed, chains, maxfun, theta_batch=0):
@@ -464,55 +471,42 @@ class Context:
     def band_plan(self, chains, which="fwd"):
         """the banded kernel's decomposition of the forward / backward product for `chains` columns (test hook,
         include/glmmr_mcml_c.h glmmr_mcml_dbg_band_plan)"""
-        out = (C.c_int * 10)()
-        _lib.check(_lib.lib().glmmr_mcml_dbg_band_plan(self._h, {"fwd": 0, "bwd": 1}[which], int(chains), out))
         keys = ("used", "nbands", "tiles", "gn", "nwg", "nred", "nslots", "paired", "nempty", "built")
-        d = dict(zip(keys, list(out)))
-        for k in ("used", "paired", "built"):
-            d[k] = bool(d[k])
-        return d
+        return _plan(_lib.lib().glmmr_mcml_dbg_band_plan, C.c_int, keys, self._h, {"fwd": 0, "bwd": 1}[which], int(chains),
+                     bools=("used", "paired", "built"))
 
     def sparse_plan(self, chains):
         """the sparse chain-major operator as hmc_sample / log_prob_grad would run it with `chains` chains, valid after update_L (test hook,
         include/glmmr_mcml_c.h glmmr_mcml_dbg_sparse_plan)"""
-        out = (C.c_longlong * 12)()
-        _lib.check(_lib.lib().glmmr_mcml_dbg_sparse_plan(self._h, int(chains), out))
         keys = ("active", "factored", "W", "nnz", "nnz_z", "nnz_l", "nblk", "max_blk", "long_rows", "fused", "qrows", "ncb")
-        d = dict(zip(keys, (int(v) for v in out)))
-        for k in ("active", "factored", "long_rows"):
-            d[k] = bool(d[k])
-        return d
+        return _plan(_lib.lib().glmmr_mcml_dbg_sparse_plan, C.c_longlong, keys, self._h, int(chains),
+                     bools=("active", "factored", "long_rows"))
 
     def set_trajectory(self, mode):
         """how hmc_sample runs a trajectory on the sparse operator: "step" (a forward and a backward launch per leapfrog
         step) or "component" (csrc/hmc_traj.h: one launch per proposal, where the component plan is feasible)"""
-        _lib.check(_lib.lib().glmmr_mcml_ctx_set_trajectory(self._h, _TRAJ[mode]))
+        _TRAJ.set(self, mode)
 
     def component_plan(self, chains):
         """the component-local trajectory path as the next hmc_sample with `chains` chains would take it, valid after
         update_L (test hook, include/glmmr_mcml_c.h glmmr_mcml_dbg_component_plan)"""
-        out = (C.c_longlong * 11)()
-        _lib.check(_lib.lib().glmmr_mcml_dbg_component_plan(self._h, int(chains), out))
         keys = ("requested", "feasible", "used", "ncomp", "max_vars", "max_rows", "empty_comps", "nitems", "waves_per_item",
                 "cap_vars", "lds_bytes_per_workgroup")
-        d = dict(zip(keys, (int(v) for v in out)))
-        for k in ("requested", "feasible", "used"):
-            d[k] = bool(d[k])
-        return d
+        return _plan(_lib.lib().glmmr_mcml_dbg_component_plan, C.c_longlong, keys, self._h, int(chains),
+                     bools=("requested", "feasible", "used"))
 
     def set_draws(self, mode):
         """what hmc_sample draws: "hmc" (trajectories) or "exact" (csrc/hmc_exact.h: the conditional distribution of the
         whitened effects directly, where it is Gaussian -- gaussian / identity on the dense ZL operator; elsewhere the
         request changes nothing) or "exact_component" ("exact", and on the sparse operator of a block-structured design the
         same draw one connected component at a time, csrc/hmc_exact_comp.h, where no component has more than 128 variables)"""
-        _lib.check(_lib.lib().glmmr_mcml_ctx_set_draws(self._h, _DRAWS[mode]))
+        _DRAWS.set(self, mode)
 
     def draws_plan(self):
         """the exact path as the next hmc_sample would (not) take it (test hook, include/glmmr_mcml_c.h
         glmmr_mcml_dbg_draws_plan)"""
-        out = (C.c_int * 4)()
-        _lib.check(_lib.lib().glmmr_mcml_dbg_draws_plan(self._h, out))
-        return dict(requested=_DRAWS_NAME[int(out[0])], applicable=bool(out[1]), Q=int(out[2]), m_bytes=int(out[3]))
+        return _plan(_lib.lib().glmmr_mcml_dbg_draws_plan, C.c_int, ("requested", "applicable", "Q", "m_bytes"), self._h,
+                     bools=("applicable",), named=(_DRAWS, "requested"))
 
     def exact_sample(self, beta, var_par, nsamp, seed, chains=1, chain_offset=0, iter_idx=0, inj_z=None, operator="dense"):
         """exact conditional draws whatever set_draws says (McmlError where the path does not apply); the samples have
@@ -528,22 +522,16 @@ class Context:
             raise ValueError("inj_z must be Q x %d" % want)
         ncols = C.c_int()
         _lib.check(getattr(_lib.lib(), entry)(
-            self._h, _p(beta), C.c_double(var_par), C.byref(o), C.c_uint64(seed), C.c_uint32(iter_idx), _p(iz),
-            C.byref(d), C.byref(ncols)))
+            self._h, _p(beta), var_par, C.byref(o), seed, iter_idx, _p(iz), C.byref(d), C.byref(ncols)))
         self.mcols = ncols.value
-        return dict(accept_rate=d.accept_rate, mean_e=d.mean_e, min_e=d.min_e, max_e=d.max_e,
-                    max_steps_used=d.max_steps_used, leapfrog_total=d.leapfrog_total)
+        return _diag(d)
 
     def exact_component_plan(self):
         """the component-wise exact path as the next hmc_sample would (not) take it, valid after update_L (test hook,
         include/glmmr_mcml_c.h glmmr_mcml_dbg_exact_component_plan)"""
-        out = (C.c_longlong * 8)()
-        _lib.check(_lib.lib().glmmr_mcml_dbg_exact_component_plan(self._h, out))
         keys = ("requested", "applicable", "ncomp", "max_vars", "max_rows", "factor_waves", "draw_lds_bytes", "factor_bytes")
-        d = dict(zip(keys, (int(v) for v in out)))
-        d["requested"] = _DRAWS_NAME[d["requested"]]
-        d["applicable"] = bool(d["applicable"])
-        return d
+        return _plan(_lib.lib().glmmr_mcml_dbg_exact_component_plan, C.c_longlong, keys, self._h, bools=("applicable",),
+                     named=(_DRAWS, "requested"))
 
     def exact_component_phases(self, enable=True):
         """HIP-event ms of the phases of the last component-wise exact call recorded; enable: record the following calls"""
@@ -563,15 +551,13 @@ class Context:
         more than 32 variables) or "component_wide" (the same up to 128 variables per component: a wave each, or a workgroup
         each where a component has more than 32 variables or 128 observations and more; GLMMR_MCML_LA_WAVES=1|4 forces a
         form).  Where the asked-for operator cannot run, the dense one does"""
-        _lib.check(_lib.lib().glmmr_mcml_ctx_set_la_operator(self._h, _LA_OP[mode]))
+        _LA_OP.set(self, mode)
 
     def la_plan(self):
         """what was asked for and what the last Laplace call on this context ran (test hook, include/glmmr_mcml_c.h
         glmmr_mcml_dbg_la_plan); waves: per component in that call, 0 (dense), 1 or 4"""
-        out = (C.c_longlong * 8)()
-        _lib.check(_lib.lib().glmmr_mcml_dbg_la_plan(self._h, out))
-        return dict(requested=_LA_OP_NAME[int(out[0])], operator=_LA_OP_NAME[int(out[1])], ncomp=int(out[2]),
-                    max_vars=int(out[3]), max_rows=int(out[4]), launches=int(out[5]), dense_bytes=int(out[6]), waves=int(out[7]))
+        keys = ("requested", "operator", "ncomp", "max_vars", "max_rows", "launches", "dense_bytes", "waves")
+        return _plan(_lib.lib().glmmr_mcml_dbg_la_plan, C.c_longlong, keys, self._h, named=(_LA_OP, "requested", "operator"))
 
     def mcml_optim(self, start, trace=0, mcnr=False, maxfun=0, theta_batch=0):
         start = _f(start).ravel(); R = self.npar()
@@ -592,7 +578,7 @@ class Context:
     def mcml_hess(self, start, tol=1e-5, trace=0):
         start = _f(start).ravel(); nv = self.P + self.npar()
         H = np.zeros((nv, nv), order="F")
-        _lib.check(_lib.lib().glmmr_mcml_ctx_hess(self._h, _p(start), start.size, C.c_double(tol), int(trace), _p(H)))
+        _lib.check(_lib.lib().glmmr_mcml_ctx_hess(self._h, _p(start), start.size, tol, int(trace), _p(H)))
         return H
 
     def aic_mcml(self, beta_par, cov_par):
@@ -609,8 +595,8 @@ class Context:
         d = HmcDiag()
         e = self._ext(seed, chains, maxfun, theta_batch)
         _lib.check(_lib.lib().glmmr_mcml_ctx_full(
-            self._h, _p(start), start.size, int(mcnr), int(m), int(maxiter), int(warmup), C.c_double(tol),
-            int(verbose), C.c_double(lambda_), int(trace), int(refresh), int(maxsteps), C.c_double(target_accept),
+            self._h, _p(start), start.size, int(mcnr), int(m), int(maxiter), int(warmup), tol,
+            int(verbose), lambda_, int(trace), int(refresh), int(maxsteps), target_accept,
             C.byref(e), _p(b), _p(t), C.byref(sg), C.byref(conv), C.byref(it), C.byref(d)))
         self.mcols = _lib.lib().glmmr_mcml_ctx_ncols(self._h)
         return dict(beta=b, theta=t, sigma=sg.value, converged=bool(conv.value), iters=it.value,
@@ -632,7 +618,7 @@ class Context:
         se = np.zeros(start.size); u = np.zeros(self.Q)
         e = self._ext(0, 1, maxfun)
         _lib.check(_lib.lib().glmmr_mcml_ctx_la(
-            self._h, _p(start), start.size, int(nr), int(usehess), C.c_double(tol), int(verbose), int(trace),
+            self._h, _p(start), start.size, int(nr), int(usehess), tol, int(verbose), int(trace),
             int(maxiter), C.byref(e), _p(b), _p(t), C.byref(sg), _p(se), _p(u), C.byref(conv), C.byref(it)))
         return dict(beta=b, theta=t, sigma=sg.value, se=se, u=u, converged=bool(conv.value), iters=it.value)
 
@@ -643,12 +629,12 @@ class Context:
         if kind == 3:
             vo = np.zeros(self.Q); bo = np.zeros(self.P); so = C.c_double()
             _lib.check(_lib.lib().glmmr_mcml_dbg_la_probe(self._h, _p(start), start.size, 3, _p(vv),
-                                                          C.c_double(var_par), None, 0, None, _p(vo), _p(bo),
+                                                          var_par, None, 0, None, _p(vo), _p(bo),
                                                           C.byref(so)))
             return dict(v=vo, beta=bo, sigma=so.value)
         pr = _f(par).ravel(); out = C.c_double()
         _lib.check(_lib.lib().glmmr_mcml_dbg_la_probe(self._h, _p(start), start.size, int(kind), _p(vv),
-                                                      C.c_double(var_par), _p(pr), pr.size, C.byref(out), None, None,
+                                                      var_par, _p(pr), pr.size, C.byref(out), None, None,
                                                       None))
         return out.value
 
@@ -663,15 +649,18 @@ class Context:
                     fwd_n_all=fa.value, bwd_n_all=ba.value)
 
 
-def _problem(cov, data, eff_range, Z, X, y, family, link):
-    keep = dict(cov=_i(cov), data=_f(data).ravel(), eff=_f(eff_range).ravel(), Z=_f(Z), X=_f(X), y=_f(y).ravel())
+def _problem(cov, data, eff_range, Z=None, X=None, y=None, family=None, link=None):
+    """(Problem, the arrays it points into: to be kept as long as it is in use).  Z = None: the covariance alone, no model"""
+    keep = dict(cov=_i(cov), data=_f(data).ravel(), eff=_f(eff_range).ravel())
     p = Problem()
     p.cov = keep["cov"].ctypes.data_as(c_ip); p.cov_rows = keep["cov"].shape[0]
     p.data = _p(keep["data"]); p.data_len = keep["data"].size
     p.eff_range = _p(keep["eff"]); p.eff_len = keep["eff"].size
-    p.Z = _p(keep["Z"]); p.X = _p(keep["X"]); p.y = _p(keep["y"])
-    p.n, p.Q = keep["Z"].shape; p.P = keep["X"].shape[1]
-    p.family = family.encode(); p.link = link.encode()
+    if Z is not None:
+        keep.update(Z=_f(Z), X=_f(X), y=_f(y).ravel())
+        p.Z = _p(keep["Z"]); p.X = _p(keep["X"]); p.y = _p(keep["y"])
+        p.n, p.Q = keep["Z"].shape; p.P = keep["X"].shape[1]
+        p.family = family.encode(); p.link = link.encode()
     return p, keep
 
 
@@ -692,8 +681,8 @@ def mcml_full(cov, data, eff_range, Z, X, y, family, link, start, mcnr=False, m=
     u = np.zeros((p.Q, ncol), order="F")
     e = Ext(int(seed), int(chains), int(maxfun), 0, 0)
     _lib.check(L.glmmr_mcml_full(C.byref(p), _p(start), start.size, int(mcnr), int(m), int(maxiter), int(warmup),
-                                 C.c_double(tol), int(verbose), C.c_double(lambda_), int(trace), int(refresh),
-                                 int(maxsteps), C.c_double(target_accept), C.byref(e), _p(b), _p(t), C.byref(sg),
+                                 tol, int(verbose), lambda_, int(trace), int(refresh),
+                                 int(maxsteps), target_accept, C.byref(e), _p(b), _p(t), C.byref(sg),
                                  C.byref(conv), _p(u), p.Q, C.byref(uc)))
     return dict(beta=b, theta=t, sigma=sg.value, converged=bool(conv.value), u=u[:, :uc.value])
 
@@ -704,7 +693,7 @@ def _la_call(fn, cov, data, eff_range, Z, X, y, family, link, start, usehess, to
     R = int(start.size - p.P - 1)
     b = np.zeros(p.P); t = np.zeros(R); sg = C.c_double(); se = np.zeros(start.size); u = np.zeros(p.Q)
     e = Ext(0, 1, int(maxfun), 0, 0)
-    _lib.check(fn(C.byref(p), _p(start), start.size, int(usehess), C.c_double(tol), int(verbose), int(trace),
+    _lib.check(fn(C.byref(p), _p(start), start.size, int(usehess), tol, int(verbose), int(trace),
                   int(maxiter), C.byref(e), _p(b), _p(t), C.byref(sg), _p(se), _p(u)))
     return dict(beta=b, theta=t, sigma=sg.value, se=se, u=u.reshape(-1, 1))
 
@@ -713,7 +702,7 @@ def mcml_la(cov, data, eff_range, Z, X, y, family, link, start, usehess=False, t
             maxiter=10, maxfun=0, operator=None):
     """mcml_la(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:28-155).  operator ("dense" / "component" /
     "component_wide", None = the process default): the default operator of the Laplace fits for the duration of the call"""
-    with _default_la_operator(operator):
+    with _LA_OP.default(operator):
         return _la_call(_lib.lib().glmmr_mcml_la, cov, data, eff_range, Z, X, y, family, link, start, usehess, tol,
                         verbose, trace, maxiter, maxfun)
 
@@ -722,25 +711,28 @@ def mcml_la_nr(cov, data, eff_range, Z, X, y, family, link, start, usehess=False
                maxiter=10, maxfun=0, operator=None):
     """mcml_la_nr(...) -> dict(beta, theta, sigma, se, u)   (src/mcml_la.cpp:174-290); operator ("dense" / "component" /
     "component_wide") as mcml_la"""
-    with _default_la_operator(operator):
+    with _LA_OP.default(operator):
         return _la_call(_lib.lib().glmmr_mcml_la_nr, cov, data, eff_range, Z, X, y, family, link, start, usehess, tol,
                         verbose, trace, maxiter, maxfun)
+
+
+def _sampler_args(Z, L, X, y, beta, family, link):
+    """the model with the caller's L as mcmc_sample / gen_u_samples pass it: (leading arguments, Q, the arrays to keep)"""
+    Z = _f(Z); L = _f(L); X = _f(X); y = _f(y).ravel(); beta = _f(beta).ravel()
+    n, Q = Z.shape
+    return (_p(Z), _p(L), _p(X), _p(y), n, Q, X.shape[1], _p(beta), family.encode(), link.encode()), Q, (Z, L, X, y, beta)
 
 
 def mcmc_sample(Z, L, X, y, beta, family, link, warmup, nsamp, lambda_, var_par=1, trace=0, refresh=500,
                 maxsteps=100, target_accept=0.9, seed=0, chains=1):
     """mcmc_sample(...) -> Q x (nsamp+1) matrix of u = L v   (src/mcml_full.cpp:314-338)"""
-    Z = _f(Z); Lm = _f(L); X = _f(X); y = _f(y).ravel(); beta = _f(beta).ravel()
-    n, Q = Z.shape
+    model, Q, keep = _sampler_args(Z, L, X, y, beta, family, link)
     lib = _lib.lib()
     ncol = lib.glmmr_mcml_sample_cols(int(nsamp), int(chains))
     out = np.zeros((Q, ncol), order="F"); nc = C.c_int()
     e = Ext(int(seed), int(chains), 0, 0, 0)
-    _lib.check(lib.glmmr_mcml_mcmc_sample(_p(Z), _p(Lm), _p(X), _p(y), n, Q, X.shape[1], _p(beta),
-                                          family.encode(), link.encode(), int(warmup), int(nsamp),
-                                          C.c_double(lambda_), C.c_double(var_par), int(trace), int(refresh),
-                                          int(maxsteps), C.c_double(target_accept), C.byref(e), _p(out), Q,
-                                          C.byref(nc)))
+    _lib.check(lib.glmmr_mcml_mcmc_sample(*model, int(warmup), int(nsamp), lambda_, var_par, int(trace), int(refresh),
+                                          int(maxsteps), target_accept, C.byref(e), _p(out), Q, C.byref(nc)))
     return out[:, :nc.value]
 
 
@@ -748,30 +740,33 @@ def gen_u_samples(y, X, Z, L, beta, family, link, sigma=1.0, warmup_iter=100, m=
                   max_treedepth=10, adapt_delta=0.8):
     """gen_u_samples(y, X, Z, L, beta, family, sigma, warmup_iter, m) -> Q x m matrix of u = L gamma
     (R/gen_u_samples.R:38-69; the NUTS sampler of csrc/nuts.h stands where cmdstanr is called)"""
-    Z = _f(Z); Lm = _f(L); X = _f(X); y = _f(y).ravel(); beta = _f(beta).ravel()
-    n, Q = Z.shape
+    model, Q, keep = _sampler_args(Z, L, X, y, beta, family, link)
     ncol = chains * -(-int(m) // chains)
     out = np.zeros((Q, ncol), order="F"); nc = C.c_int()
     e = Ext(int(seed), int(chains), 0, 0, 0)
     o = NutsOpts(int(warmup_iter), int(m), int(max_treedepth), float(adapt_delta), 0.0, int(chains), 0, 0)
-    _lib.check(_lib.lib().glmmr_mcml_gen_u_samples(_p(Z), _p(Lm), _p(X), _p(y), n, Q, X.shape[1], _p(beta), family.encode(),
-                                                   link.encode(), C.c_double(sigma), int(warmup_iter), int(m), C.byref(o),
-                                                   C.byref(e), _p(out), Q, C.byref(nc)))
+    _lib.check(_lib.lib().glmmr_mcml_gen_u_samples(*model, sigma, int(warmup_iter), int(m), C.byref(o), C.byref(e), _p(out), Q,
+                                                   C.byref(nc)))
     return out[:, :nc.value]
+
+
+def _call(fn, p, u, head, tail, sparse=None, maxfun=0):
+    """the calling sequence the mirrors that take samples share: fn(problem[, Ap, Ai, nnz], u, ucols, *head, ext, *tail)"""
+    u = _f(u)
+    e = Ext(0, 1, int(maxfun), 0, 0)
+    pattern = []
+    if sparse is not None:
+        Ap, Ai = _i(sparse[0]).ravel(), _i(sparse[1]).ravel()
+        pattern = [_p(Ap), _p(Ai), Ai.size]
+    _lib.check(fn(C.byref(p), *pattern, _p(u), u.shape[1], *head, C.byref(e), *tail))
 
 
 def _fit_call(fn, prob_args, u, start, extra, sparse=None, maxfun=0):
     p, keep = _problem(*prob_args)
-    u = _f(u); start = _f(start).ravel()
+    start = _f(start).ravel()
     R = int(start.size - p.P - 1) if start.size > p.P + 1 else 0
     b = np.zeros(p.P); t = np.zeros(max(R, 64)); sg = C.c_double()
-    e = Ext(0, 1, int(maxfun), 0, 0)
-    args = [C.byref(p)]
-    if sparse is not None:
-        Ap, Ai = _i(sparse[0]).ravel(), _i(sparse[1]).ravel()
-        args += [Ap.ctypes.data_as(c_ip), Ai.ctypes.data_as(c_ip), Ai.size]
-    args += [_p(u), u.shape[1], _p(start), start.size] + extra + [C.byref(e), _p(b), _p(t), C.byref(sg)]
-    _lib.check(fn(*args))
+    _call(fn, p, u, [_p(start), start.size] + extra, [_p(b), _p(t), C.byref(sg)], sparse, maxfun)
     return b, t, sg.value
 
 
@@ -800,20 +795,14 @@ def mcml_optim_sparse(cov, data, eff_range, Ap, Ai, Z, X, y, u, family, link, st
     """mcml_optim_sparse(...) -> dict(beta, theta, sigma, Ap, Ai, Ax, D)   (src/mcml_optim.cpp:147-184):
     Ap/Ai/Ax = the unit lower LDL' factor of D(theta) without its diagonal, D its pivots."""
     p, keep = _problem(cov, data, eff_range, Z, X, y, family, link)
-    u = _f(u); start = _f(start).ravel()
-    cv = keep["cov"]
+    start = _f(start).ravel()
     lib = _lib.lib()
-    cap = lib.glmmr_mcml_sparse_factor_nnz(cv.ctypes.data_as(c_ip), cv.shape[0], _p(keep["data"]), keep["data"].size)
-    R = _npar_of(cov)
-    b = np.zeros(p.P); t = np.zeros(R); sg = C.c_double()
+    cap = lib.glmmr_mcml_sparse_factor_nnz(p.cov, p.cov_rows, p.data, p.data_len)
+    b = np.zeros(p.P); t = np.zeros(_npar_of(cov)); sg = C.c_double()
     Lp = np.zeros(p.Q + 1, dtype=np.int32); Li = np.zeros(max(cap, 1), dtype=np.int32)
     Lx = np.zeros(max(cap, 1)); D = np.zeros(p.Q)
-    Ap_, Ai_ = _i(Ap).ravel(), _i(Ai).ravel()
-    e = Ext(0, 1, int(maxfun), 0, 0)
-    _lib.check(lib.glmmr_mcml_optim_sparse(C.byref(p), Ap_.ctypes.data_as(c_ip), Ai_.ctypes.data_as(c_ip), Ai_.size,
-                                           _p(u), u.shape[1], _p(start), start.size, int(trace), int(mcnr),
-                                           C.byref(e), _p(b), _p(t), C.byref(sg), Lp.ctypes.data_as(c_ip),
-                                           Li.ctypes.data_as(c_ip), _p(Lx), _p(D), cap))
+    _call(lib.glmmr_mcml_optim_sparse, p, u, [_p(start), start.size, int(trace), int(mcnr)],
+          [_p(b), _p(t), C.byref(sg), _p(Lp), _p(Li), _p(Lx), _p(D), cap], (Ap, Ai), maxfun)
     return dict(beta=b, theta=t, sigma=sg.value, Ap=Lp, Ai=Li[:cap], Ax=Lx[:cap], D=D)
 
 
@@ -827,18 +816,12 @@ def mcml_simlik_sparse(cov, data, eff_range, Ap, Ai, Z, X, y, u, family, link, s
 def mcml_hess(cov, data, eff_range, Z, X, y, u, family, link, start, tol=1e-5, trace=0, sparse=None):
     """mcml_hess(...) -> (P+R) x (P+R)   (src/mcml_optim.cpp:263-285; _sparse :313-337)"""
     p, keep = _problem(cov, data, eff_range, Z, X, y, family, link)
-    u = _f(u); start = _f(start).ravel()
+    start = _f(start).ravel()
     nv = p.P + _npar_of(cov)
     H = np.zeros((nv, nv), order="F")
-    e = Ext(0, 1, 0, 0, 0)
-    if sparse is None:
-        _lib.check(_lib.lib().glmmr_mcml_hess(C.byref(p), _p(u), u.shape[1], _p(start), start.size,
-                                              C.c_double(tol), int(trace), C.byref(e), _p(H)))
-    else:
-        Ap, Ai = _i(sparse[0]).ravel(), _i(sparse[1]).ravel()
-        _lib.check(_lib.lib().glmmr_mcml_hess_sparse(C.byref(p), Ap.ctypes.data_as(c_ip), Ai.ctypes.data_as(c_ip),
-                                                     Ai.size, _p(u), u.shape[1], _p(start), start.size,
-                                                     C.c_double(tol), int(trace), C.byref(e), _p(H)))
+    lib = _lib.lib()
+    _call(lib.glmmr_mcml_hess if sparse is None else lib.glmmr_mcml_hess_sparse, p, u,
+          [_p(start), start.size, tol, int(trace)], [_p(H)], sparse)
     return H
 
 
@@ -849,38 +832,34 @@ def mcml_hess_sparse(cov, data, eff_range, Ap, Ai, Z, X, y, u, family, link, sta
 def aic_mcml(cov, data, eff_range, Z, X, y, u, family, link, beta_par, cov_par):
     """aic_mcml(...) -> double   (src/mcml_optim.cpp:356-392)"""
     p, keep = _problem(cov, data, eff_range, Z, X, y, family, link)
-    u = _f(u); bp = _f(beta_par).ravel(); cp = _f(cov_par).ravel()
-    out = C.c_double(); e = Ext(0, 1, 0, 0, 0)
-    _lib.check(_lib.lib().glmmr_mcml_aic(C.byref(p), _p(u), u.shape[1], _p(bp), bp.size, _p(cp), cp.size,
-                                         C.byref(e), C.byref(out)))
+    bp = _f(beta_par).ravel(); cp = _f(cov_par).ravel()
+    out = C.c_double()
+    _call(_lib.lib().glmmr_mcml_aic, p, u, [_p(bp), bp.size, _p(cp), cp.size], [C.byref(out)])
     return out.value
 
+
+def _mvn_args(cov, data, eff_range, gamma, u):
+    """what mvn_ll / mvn_ll_grad pass ahead of their outputs: (arguments, gamma, the sample matrix, the arrays to keep)"""
+    p, keep = _problem(cov, data, eff_range)
+    gamma = _f(gamma).ravel(); u = _cols(u)
+    return (p.cov, p.cov_rows, p.data, p.data_len, p.eff_range, p.eff_len, _p(gamma), gamma.size, _p(u), u.shape[0],
+            u.shape[1]), gamma, u, keep
 
 
 def mvn_ll(cov, data, eff_range, gamma, u):
     """mvn_ll(cov, data, eff_range, gamma, u)  -- src/mcml_optim.cpp:406-414"""
-    cov = _i(cov); data = _f(data).ravel(); eff = _f(eff_range).ravel(); gamma = _f(gamma).ravel()
-    u = _f(u)
-    if u.ndim == 1:
-        u = u.reshape(-1, 1, order="F")
+    args, gamma, u, keep = _mvn_args(cov, data, eff_range, gamma, u)
     out = C.c_double()
-    _lib.check(_lib.lib().glmmr_mcml_mvn_ll(cov.ctypes.data_as(c_ip), cov.shape[0], _p(data), data.size,
-                                            _p(eff), eff.size, _p(gamma), gamma.size, _p(u), u.shape[0],
-                                            u.shape[1], C.byref(out)))
+    _lib.check(_lib.lib().glmmr_mcml_mvn_ll(*args, C.byref(out)))
     return out.value
 
 
 def mvn_ll_grad(cov, data, eff_range, gamma, u, weights=None):
     """(value, grad) of Context.mvn_ll_grad on a context made for the call (glmmr_mcml_mvn_ll_grad): the analytic score of
     mvn_ll in gamma; beyond the reference's exports"""
-    cov = _i(cov); data = _f(data).ravel(); eff = _f(eff_range).ravel(); gamma = _f(gamma).ravel()
-    u = _f(u)
-    if u.ndim == 1:
-        u = u.reshape(-1, 1, order="F")
+    args, gamma, u, keep = _mvn_args(cov, data, eff_range, gamma, u)
     w = _weights(weights, u.shape[1])
     out = C.c_double()
     grad = np.zeros(gamma.size)
-    _lib.check(_lib.lib().glmmr_mcml_mvn_ll_grad(cov.ctypes.data_as(c_ip), cov.shape[0], _p(data), data.size,
-                                                 _p(eff), eff.size, _p(gamma), gamma.size, _p(u), u.shape[0],
-                                                 u.shape[1], _p(w), C.byref(out), _p(grad)))
+    _lib.check(_lib.lib().glmmr_mcml_mvn_ll_grad(*args, _p(w), C.byref(out), _p(grad)))
     return out.value, grad

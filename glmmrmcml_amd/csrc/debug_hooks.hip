@@ -1,6 +1,7 @@
-// debug_hooks.hip -- C-ABI test/bench hooks for the GEMM building block
-// (declared in include/glmmr_mcml_c.h under "test hooks").  The hooks of the dense Cholesky stack built on it --
-// glmmr_mcml_dbg_chol, glmmr_mcml_dbg_mvn_workspace -- need a context and live in cabi.hip; glmmr_mcml_dbg_dgemm_at is here.
+// debug_hooks.hip -- the C-ABI test/bench hooks that need no context: the GEMM building block (glmmr_mcml_dbg_dgemm_at
+// among them), the RNG contract, the host optimiser and the staged copies (declared in include/glmmr_mcml_c.h under "test
+// hooks").  The hooks that take a context -- the dense Cholesky stack's glmmr_mcml_dbg_chol and glmmr_mcml_dbg_mvn_workspace,
+// the plans -- are ctx_hooks.hip.
 #include "dgemm_mfma.h"
 #include "dgemm_dl.h"
 #include "dgemm_band.h"

@@ -13,8 +13,7 @@
 //       serial loop.
 //   D11 the sampler is re-initialised every MCML iteration exactly as the
 //       reference does (mhmcmc.h:127), with seeds derived from (seed, iteration).
-#include "../../include/glmmr_mcml_c.h"
-#include "ctx.h"
+#include "entry.h"
 #include "glm.h"
 #include "optim.h"
 #include "theta_scale.h"
@@ -24,13 +23,8 @@
 #include <cstring>
 #include <map>
 #include <memory>
-#include <random>
 
 namespace mcml {
-
-int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed,
-               uint32_t iter_idx, const double* inj_init, const double* inj_mom, uint8_t* flags_out,
-               double* probs_out, glmmr_mcml_hmc_diag* diag, int* ncols_out);
 
 // ---- device-backed scalar evaluations (all-reduced over ranks) ----
 static int eval_loglik(Ctx& c, const double* beta, double var_par, double* ll)
@@ -373,13 +367,6 @@ struct McmlOptim {
         return MCML_OK;
     }
 };
-
-static uint64_t default_seed(const glmmr_mcml_ext* e)
-{
-    if (e && e->seed) return e->seed;
-    std::random_device rd;            // what the reference does (mhmcmc.h:55)
-    return ((uint64_t)rd() << 32) | rd();
-}
 
 // ---------------------------------------------------------------- ctx-level drivers
 int drv_optim(Ctx& c, const double* start, int nstart, int trace, int mcnr, const glmmr_mcml_ext* e,

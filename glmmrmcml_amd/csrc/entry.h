@@ -1,0 +1,56 @@
+// entry.h -- the host entry points one translation unit defines and another calls: the samplers (hmc.hip), the drivers
+// (drivers.hip, laplace.hip) and the launch counters behind the extern "C" layer (cabi.hip, ctx_hooks.hip).  The defining
+// files include this header, so a signature that drifts is a compile error, not a wrong link.
+#pragma once
+#include "../../include/glmmr_mcml_c.h"
+#include "ctx.h"
+#include <random>
+
+namespace mcml {
+
+// ---- hmc.hip (nuts_sample: nuts.h, part of the same translation unit) ----
+int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed,
+               uint32_t iter_idx, const double* inj_init, const double* inj_mom, uint8_t* flags_out,
+               double* probs_out, glmmr_mcml_hmc_diag* diag, int* ncols_out);
+int nuts_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_nuts_opts* o, uint64_t seed, uint32_t iter_idx,
+                int* depth_out, int* nleap_out, double* eps_out, double* accept_out, glmmr_mcml_nuts_diag* diag,
+                int* ncols_out);
+bool hmc_exact_applicable(const Ctx& c);
+int hmc_exact_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed, uint32_t iter_idx,
+                     const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out);
+bool hmc_exact_component_applicable(const Ctx& c);
+int hmc_exact_component_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed,
+                               uint32_t iter_idx, const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out);
+void hmc_exact_component_sizes(const Ctx& c, long long* out3);
+long long cm_traj_launch_count();
+
+// ---- drivers.hip ----
+int drv_optim(Ctx& c, const double* start, int nstart, int trace, int mcnr, const glmmr_mcml_ext* e,
+              double* beta, double* theta, double* sigma);
+int drv_simlik(Ctx& c, const double* start, int nstart, int trace, const glmmr_mcml_ext* e, double* beta,
+               double* theta, double* sigma);
+int drv_hess(Ctx& c, const double* start, int nstart, double tol, int trace, double* H);
+int drv_theta_round(Ctx& c, const double* thetas, int k, double* out);
+int drv_aic(Ctx& c, const double* beta_par, int nbeta, const double* cov_par, int ncov, double* out);
+int drv_full(Ctx& c, const double* start, int nstart, int mcnr, int m, int maxiter, int warmup, double tol,
+             int verbose, double lambda, int trace, int refresh, int maxsteps, double target_accept,
+             const glmmr_mcml_ext* e, double* beta_out, double* theta_out, double* sigma_out,
+             int* converged_out, int* iters_out, glmmr_mcml_hmc_diag* last_diag);
+
+// ---- laplace.hip ----
+int drv_la(Ctx& c, const double* start, int nstart, int nr, int usehess, double tol, int verbose, int trace,
+           int maxiter, const glmmr_mcml_ext* e, double* beta, double* theta, double* sigma, double* se, double* u,
+           int* converged, int* iters);
+int drv_la_probe(Ctx& c, const double* start, int nstart, int kind, const double* v, double var_par,
+                 const double* par, int npar, double* out, double* v_out, double* beta_out, double* sigma_out);
+long long la_component_launch_count();
+
+// the seed of a sampler run: the caller's, or one from std::random_device as the reference draws it (mhmcmc.h:55)
+inline uint64_t default_seed(const glmmr_mcml_ext* e)
+{
+    if (e && e->seed) return e->seed;
+    std::random_device rd;
+    return ((uint64_t)rd() << 32) | rd();
+}
+
+}  // namespace mcml

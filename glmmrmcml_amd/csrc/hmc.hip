@@ -17,8 +17,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include "../../include/glmmr_mcml_c.h"
-#include "ctx.h"
+#include "entry.h"
 #include "dgemm_mfma.h"
 #include "dgemm_dlds.h"
 #include "dgemm_band.h"
@@ -679,7 +678,7 @@ static int samples_to_U(Ctx& c, const DevMat& samp, int ncols)
 
 namespace mcml {
 
-// the exact path from outside this file (cabi.hip: the direct entry point and the plan hook)
+// the exact path from outside this file (entry.h; cabi.hip: the direct entry point, ctx_hooks.hip: the plan hook)
 bool hmc_exact_applicable(const Ctx& c) { return exact_applicable(c); }
 int hmc_exact_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed, uint32_t iter_idx,
                      const double* inj_z, glmmr_mcml_hmc_diag* diag, int* ncols_out)

@@ -20,8 +20,7 @@
 // instead of NaN; after an optimisation the model is left at the optimum (the reference
 // leaves it at rminqa's last evaluated point, which is optimiser-specific); hess_la for the
 // beta family is refused (its functor mis-sizes theta, likelihood.h:196-201).
-#include "../../include/glmmr_mcml_c.h"
-#include "ctx.h"
+#include "entry.h"
 #include "dgemm_mfma.h"
 #include "glm.h"
 #include "la_comp.h"
@@ -561,7 +560,7 @@ struct LaScope {
     ~LaScope() { c.no_sparse_zl = false; c.have_L = false; }
 };
 
-// ------------------------------------------------------------------ entry points (cabi.hip)
+// ------------------------------------------------------------------ entry points (entry.h)
 int drv_la(Ctx& c, const double* start, int nstart, int nr, int usehess, double tol, int verbose, int trace,
            int maxiter, const glmmr_mcml_ext* e, double* beta, double* theta, double* sigma, double* se, double* u,
            int* converged, int* iters)

@@ -1,6 +1,6 @@
 // sparse_plan.h -- host-side decisions of the sparse (chain-major) ZL operator: which backward kernel, which fused
 // block kernel, the chunk height of the per-chain sums.  hmc.hip launches by these functions and the test hook
-// glmmr_mcml_dbg_sparse_plan (cabi.hip) reports them, so the two cannot drift apart.
+// glmmr_mcml_dbg_sparse_plan (ctx_hooks.hip) reports them, so the two cannot drift apart.
 #pragma once
 #include <cstdlib>
 #include <cstring>

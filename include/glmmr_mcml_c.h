@@ -447,7 +447,8 @@ int glmmr_mcml_mvn_ll_grad(const int32_t* cov, int cov_rows, const double* data,
                            const double* eff_range, int eff_len, const double* gamma, int ngamma,
                            const double* u, int Q, int m, const double* weights, double* value, double* grad);
 
-/* ---- test hooks (building blocks exposed for tests/ and bench.py only) ---- */
+/* ---- test hooks (building blocks exposed for tests/ and bench.py only): csrc/ctx_hooks.hip defines the glmmr_mcml_dbg_*
+ * functions that take a context and the two launch counters, above and below; csrc/debug_hooks.hip the others ---- */
 /* every evaluation of the theta-step's objective on this context as a row (theta_1 .. theta_R, MVN log-likelihood):
  * enable 1 clears the log and starts it, 0 stops it, -1 leaves it as it is; out (nullable) receives the LAST cap_rows rows
  * (row-major, R + 1 doubles each), *nrows the number written (or held, when out is null) */
