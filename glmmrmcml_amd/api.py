@@ -547,7 +547,7 @@ class Context:
 
     def set_la_operator(self, mode):
         """how mcml_la / la_probe run on this context: "dense" (the dense ZL and M = ZL' W ZL + I), "component"
-        (csrc/la_comp.h: M one connected component at a time on the sparse operator, a wave each, where no component has
+        (csrc/component.hip: M one connected component at a time on the sparse operator, a wave each, where no component has
         more than 32 variables) or "component_wide" (the same up to 128 variables per component: a wave each, or a workgroup
         each where a component has more than 32 variables or 128 observations and more; GLMMR_MCML_LA_WAVES=1|4 forces a
         form).  Where the asked-for operator cannot run, the dense one does"""

@@ -1,7 +1,7 @@
-// component_plan.h -- host side of hmc_traj.h: the connected components of the coupling graph of ZL and the work
-// decomposition of the component-local trajectory kernel.  In the whitened variables the prior is N(0, I), so two
-// random effects interact only through an observation whose row of ZL touches both: a union-find over the ELL rows
-// gives components whose whole leapfrog trajectory needs no data of any other component (configs 1, 4, 5: 10 / 40 /
+// component_plan.h -- host side of component.h: the connected components of the coupling graph of ZL, the records its kernels
+// read (hmc_traj.h, component.hip, hmc_exact_comp.h) and the work items of the trajectory kernel.  In the whitened variables the
+// prior is N(0, I), so two random effects interact only through an observation whose row of ZL touches both: a union-find over
+// the ELL rows gives components whose whole leapfrog trajectory needs no data of any other component (configs 1, 4, 5: 10 / 40 /
 // 2000 components of at most 6 / 8 / 11 variables).  Plain vectors in, plain vectors out: no device, no HIP header, so
 // that tests/host_component_plan_driver.cpp compiles it with g++ under the sanitizers.
 #pragma once
@@ -20,7 +20,7 @@ constexpr int CP_LDS_BYTES_PER_CU = 160 * 1024;
 constexpr int CP_MAX_VARS = 32;
 static_assert(CP_MAX_VARS >= 16 && CP_MAX_VARS < 48, "the fallback tests rely on a sparse design above the cap");
 static_assert(CP_MAX_VARS * 3 * 512 * 3 <= CP_LDS_BYTES_PER_CU && CP_MAX_VARS * 6 * 512 + 8192 <= CP_LDS_BYTES_PER_CU, "LDS budget");
-// The Laplace kernels (la_comp.h) keep only the nv x nv matrix of a component in LDS: the workgroup form takes up to
+// The factor kernels (component.hip) keep only the nv x nv matrix of a component in LDS: the workgroup form takes up to
 // CP_WIDE_MAX_VARS variables (about 146 KB at the cap, one workgroup per CU).  The trajectory kernel keeps CP_MAX_VARS.
 constexpr int CP_WIDE_MAX_VARS = 128;
 static_assert(CP_WIDE_MAX_VARS >= CP_MAX_VARS, "a plan the trajectory kernel takes has records");
@@ -54,19 +54,32 @@ struct ComponentPlan {
     int nitems() const { return (int)item_ptr.size() - 1; }
 };
 
-// forced < 0: the rule; 1 or 4: that form
+// waves per component (or work item) of a kernel with two forms: k_cm_traj<FL, 1 | 4> on a feasible plan, k_lac_factor /
+// k_lac_factor_wg under "component_wide".  One wave below CP_WAVES4_ROWS observations in the largest component (config 5: 10), a
+// guess for both: config 4 (400) is the one measured point above it (profiles/la_component_wide_timing.json).  forced: 1 or 4
+// for that form, else the rule; above CP_MAX_VARS variables only the workgroup form exists: forcing one wave is ignored
 inline int cp_waves(const ComponentPlan& p, int forced = -1)
 {
+    if (p.max_vars > CP_MAX_VARS) return 4;
     if (forced == 1 || forced == 4) return forced;
     return p.max_rows >= CP_WAVES4_ROWS ? 4 : 1;
 }
-// GLMMR_MCML_TRAJ_WAVES=1|4: the A/B switch of the two kernel forms, read per call (a test runs both in one process)
-inline int cp_forced_waves()
+// the A/B switch of the two forms, = 1 | 4, read per call (a test runs both in one process)
+constexpr const char* CP_TRAJ_WAVES_ENV = "GLMMR_MCML_TRAJ_WAVES";   // the trajectory kernel's
+constexpr const char* CP_LA_WAVES_ENV = "GLMMR_MCML_LA_WAVES";       // the factor kernels'
+inline int cp_forced_waves(const char* env)
 {
-    const char* e = getenv("GLMMR_MCML_TRAJ_WAVES");
+    const char* e = getenv(env);
     if (e && !strcmp(e, "1")) return 1;
     if (e && !strcmp(e, "4")) return 4;
     return -1;
+}
+// where the nv x nv factor of each component starts in the exact draws' scratch: ncomp + 1 offsets in doubles
+inline std::vector<int> comp_factor_offsets(const ComponentPlan& p)
+{
+    std::vector<int> off(p.ncomp + 1, 0);
+    for (int k = 0; k < p.ncomp; ++k) { const int nv = p.var_ptr[k + 1] - p.var_ptr[k]; off[k + 1] = off[k] + nv * nv; }
+    return off;
 }
 
 // col, width: the ELL rows of ZL (col[i + k * n], k < width[i]), as sparse_zl_setup builds them

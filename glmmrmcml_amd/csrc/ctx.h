@@ -81,14 +81,13 @@ struct SparseZL {
     int nblk = 0, max_blk = 0;
 };
 
-// the components of ZL's coupling graph and the work items of the trajectory kernel (component_plan.h, hmc_traj.h): the
-// pattern is fixed per model (built by sparse_zl_setup), the values follow L (model_update_L)
+// the components of ZL's coupling graph, their records and the work items of the trajectory kernel (component_plan.h;
+// component.h describes a record and gives the kernels their view): the pattern is fixed per model (comp_setup, from
+// sparse_zl_setup), the values follow L (comp_fill_val, from model_update_L) and beta (comp_fill_xy)
 struct ComponentDev {
     ComponentPlan plan;
     bool ready = false;                        // the device copies below are there
     DevBuf item_ptr, var_ptr, vars, slot_ptr, slot_quarter, slot_i, slot_src, slot_d;
-    // slot_i, 8 ints per record: local columns [4], entries, last record of its observation, observation, 0
-    // slot_d, 8 doubles per record: values [4], xb_i, y_i (k_cp_fill_xy, hmc_traj.h), 0, 0
 };
 
 // HIP-event timing of the dominant kernels, on the stream they are launched on
@@ -150,10 +149,10 @@ struct ExactState {
 };
 
 // component-wise exact draws (hmc_exact_comp.h): the factors of every M_c (sum_c nv_c^2 doubles, at most Q * 128) and where
-// each starts, W = 1 / sigma^2 for every observation, b -> mu*, the factor kernel's log-determinants (not read), the draws
-// chain-major and transposed; kept between calls
+// each starts, b -> mu*, the factor kernel's log-determinants (not read), the draws chain-major and transposed; kept between
+// calls
 struct ExactCompState {
-    DevBuf fac, fac_ptr, W, b, mu, logdet, CM;
+    DevBuf fac, fac_ptr, b, mu, logdet, CM;
     DevMat T;
     long long fac_doubles = 0;          // 0: fac_ptr not uploaded yet
     bool prof = false;
@@ -178,7 +177,7 @@ struct Ctx {
     ExactState exact;
     ExactCompState exact_comp;
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT
-    int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (la_comp.h); 2 the same up
+    int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (component.hip); 2 the same up
                                 // to CP_WIDE_MAX_VARS variables per component, a wave or a workgroup each
     int la_last_op = 0;         // what the last Laplace call ran (0 dense, 1 component, 2 component_wide), its waves per
     int la_waves = 0;           // component (0 dense, 1, 4), its k_lac_factor / k_lac_factor_wg launches and the
@@ -303,17 +302,12 @@ int mvn_loglik_grad(Ctx& c, const double* theta, const double* weights, double* 
 // the same matrix as a query: built into `out` (allocated here), no state of the context changes
 int mvn_gen_D(Ctx& c, const double* theta, bool chol, DevMat& out);
 
-// ---- chol.hip: see chol.h; vecops.hip (the vector-sized kernels): see vecops.h ----
+// ---- chol.hip: see chol.h; vecops.hip (the vector-sized kernels): see vecops.h; component.hip: see component.h ----
 
 // ---- laplace.hip ----
 // M (Q x Q) = ZL' diag(W) ZL + I from the current c.ZL / c.ZLT.  W null: W = w0 for every observation, ZLT is multiplied as it
 // is (ZLTW is not touched).  lower_only: the tiles strictly above the diagonal are left zero
 int build_M_dense(Ctx& c, const double* W, double w0, DevMat& M, DevMat& ZLTW, bool lower_only);
-// every M_c = I + ZL_c' diag(W) ZL_c of the component records built and factorised in one launch (la_comp.h): waves = 1 a wave,
-// 4 a workgroup per component.  logdet: ncomp.  g / x nullable: x = M^-1 g (Q).  fac / fac_ptr nullable: the factors' lower
-// triangles, component c column-major (leading dimension nv_c) at fac + fac_ptr[c].  A failed pivot raises c.errflag()
-int lac_factor_launch(Ctx& c, const double* W, const double* g, double* x, double* logdet, double* fac, const int* fac_ptr, int waves);
-int lac_waves_now(const ComponentPlan& p);                   // the form "component_wide" takes now (honours GLMMR_MCML_LA_WAVES)
 
 // ---- model.hip ----
 int model_setup(Ctx& c, const double* Z, const double* X, const double* y);

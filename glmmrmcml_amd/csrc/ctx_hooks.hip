@@ -85,7 +85,7 @@ extern "C" int glmmr_mcml_dbg_component_plan(glmmr_mcml_ctx* h, int chains, long
     out11[1] = feasible ? 1 : 0; out11[2] = (feasible && c.traj_mode == 1) ? 1 : 0;
     out11[3] = p.ncomp; out11[4] = p.max_vars; out11[5] = p.max_rows; out11[6] = p.empty_comps;
     if (!feasible) return MCML_OK;
-    const int waves = cp_waves(p, cp_forced_waves());
+    const int waves = cp_waves(p, cp_forced_waves(CP_TRAJ_WAVES_ENV));
     out11[7] = p.nitems(); out11[8] = waves; out11[10] = cp_lds_bytes(p.max_vars, waves);
     return MCML_OK;
 }

@@ -1,5 +1,6 @@
 // entry.h -- the host entry points one translation unit defines and another calls: the samplers (hmc.hip), the drivers
-// (drivers.hip, laplace.hip) and the launch counters behind the extern "C" layer (cabi.hip, ctx_hooks.hip).  The defining
+// (drivers.hip, laplace.hip) and the launch counters (hmc.hip, component.hip) behind the extern "C" layer (cabi.hip,
+// ctx_hooks.hip).  The defining
 // files include this header, so a signature that drifts is a compile error, not a wrong link.
 #pragma once
 #include "../../include/glmmr_mcml_c.h"
@@ -43,6 +44,8 @@ int drv_la(Ctx& c, const double* start, int nstart, int nr, int usehess, double 
            int* converged, int* iters);
 int drv_la_probe(Ctx& c, const double* start, int nstart, int kind, const double* v, double var_par,
                  const double* par, int npar, double* out, double* v_out, double* beta_out, double* sigma_out);
+
+// ---- component.hip ----
 long long la_component_launch_count();
 
 // the seed of a sampler run: the caller's, or one from std::random_device as the reference draws it (mhmcmc.h:55)

@@ -389,12 +389,10 @@ long long cm_traj_launch_count() { return g_traj_launches.load(); }
 // one proposal's trajectories of every (component, chain): ONE launch whatever the step counts
 static int cm_traj_launch(Ctx& c, const TrajArgs& a)
 {
-    const ComponentDev& cp = c.cp;
-    const CpDev m{cp.item_ptr.as<int>(), cp.var_ptr.as<int>(), cp.vars.as<int>(), cp.slot_ptr.as<int>(), cp.slot_quarter.as<int>(),
-                  cp.slot_i.as<int>(), cp.slot_d.d()};
-    const int waves = cp_waves(cp.plan, cp_forced_waves());
-    const int lds = cp_lds_bytes(cp.plan.max_vars, waves);
-    const dim3 grid(cp.plan.nitems(), cm_chain_blocks(a.C));
+    const CompView m = comp_view(c);
+    const int waves = cp_waves(c.cp.plan, cp_forced_waves(CP_TRAJ_WAVES_ENV));
+    const int lds = cp_lds_bytes(m.max_vars, waves);
+    const dim3 grid(m.nitems, cm_chain_blocks(a.C));
     MCML_TRY((dispatch_flink<1, 3, 7, 12>(c.flink, [&](auto FL) {
         if (waves == 4) {
             MCML_TRY(ensure_dynamic_lds((const void*)k_cm_traj<FL(), 4>, cp_lds_bytes(CP_MAX_VARS, 4)));
@@ -696,9 +694,8 @@ int hmc_exact_component_sample(Ctx& c, const double* beta, double var_par, const
 void hmc_exact_component_sizes(const Ctx& c, long long* out3)
 {
     const ComponentPlan& p = c.cp.plan;
-    long long fac = 0;
-    for (int k = 0; k < p.ncomp; ++k) { const long long nv = p.var_ptr[k + 1] - p.var_ptr[k]; fac += nv * nv; }
-    out3[0] = lac_waves_now(p); out3[1] = exc_lds_bytes(p.max_vars); out3[2] = 8 * fac;
+    const int waves = cp_waves(p, cp_forced_waves(CP_LA_WAVES_ENV));
+    out3[0] = waves; out3[1] = exc_lds_bytes(p.max_vars); out3[2] = 8LL * comp_factor_offsets(p).back();
 }
 
 // ---- hmc_sample in parts ----
@@ -860,7 +857,7 @@ static int propose_component(Ctx& c, HmcCall& k, int it)
     TrajArgs a{h.V.d(), h.GRAD.d(), h.UP.d(), h.GRADP.d(), h.V.ld, k.sh.C, c.Q, k.ca, k.seed, (uint32_t)o->chain_offset,
                k.iter_idx, it, k.mom, k.pending_commit ? h.cm_acc.as<int>() : nullptr, o->lambda, o->max_steps, c.flink,
                k.var_par, glm_score_post(k.var_par, c.flink), tpart, tpart + tstride, tpart + 2 * tstride,
-               tpart + 3 * tstride, h.V.ld, c.cp.plan.max_vars};
+               tpart + 3 * tstride, h.V.ld};
     k.pending_commit = false;
     c.prof.skip = (it & 3) != 0;
     const int slot = c.prof.begin(c.stream, 0);     // counted (and timed) under the forward product's slot
@@ -936,12 +933,7 @@ int hmc_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_
     MCML_TRY(sampler_init_state(c, seed, (uint32_t)o->chain_offset, iter_idx, d_init.d()));
     MCML_TRY(hmc_eval_state(c, var_par));
     if (sh.single_chain_layout && o->warmup == 0) store_columns(c, samp, 0, 0);   // no warm-up: column 0 is the start value
-    if (traj) {                                 // xb follows beta: the records' copy of it
-        const int ns = c.cp.plan.nslots;
-        hipLaunchKernelGGL(k_cp_fill_xy, dim3((ns + 255) / 256), dim3(256), 0, c.stream, ns, c.cp.slot_i.as<int>(), c.xb.d(),
-                           c.y.d(), c.cp.slot_d.d());
-        MCML_HIP(hipGetLastError());
-    }
+    if (traj) MCML_TRY(comp_fill_xy(c));        // xb follows beta: the records' copy of it
     t.setup = t.phase_end();
     for (int it = 0; it < total; ++it) {
         t.proposal();

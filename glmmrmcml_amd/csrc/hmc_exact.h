@@ -65,61 +65,82 @@ struct ExactProf {
     ~ExactProf() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
 };
 
-// hmc_sample's signature and side effects (c.U = L * draws, c.mcols, c.niter); o->warmup, lambda, max_steps, target_accept and
-// adapt only size the flags / probs extents.  inj_z: host, Q x ncols, or null
-static int exact_gaussian_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed,
-                                 uint32_t iter_idx, const double* inj_z, uint8_t* flags_out, double* probs_out,
-                                 glmmr_mcml_hmc_diag* diag, int* ncols_out)
+// ---- what the two exact samplers (here and hmc_exact_comp.h) share: hmc_sample's signature and side effects (c.U = L * draws,
+// c.mcols, c.niter); o->warmup, lambda, max_steps, target_accept and adapt only size the flags / probs extents
+struct ExactCall : ExactProf {
+    using ExactProf::ExactProf;
+    SampleShape sh; double post;                 // post = 1 / sigma^2
+    DevBuf d_z;                                  // inj_z on the device, or null
+};
+
+// the argument checks, then `applicable` (false: MCML_EUNSUPPORTED with the message the caller has set); the shape (column 0 of
+// one chain is just another draw), xb = X beta, T (Q x ncols) with finite padding rows, inj_z (host, Q x ncols, or null) uploaded
+static int exact_begin(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, const double* inj_z,
+                       bool applicable, DevMat& T, ExactCall& k)
 {
     MCML_REQUIRE(o && o->nsamp > 0 && o->warmup >= 0, "exact draws: bad options");
     MCML_REQUIRE(beta, "exact draws: beta is null");
     MCML_REQUIRE(var_par > 0, "exact draws: var_par (sigma) must be positive");
-    if (!exact_applicable(c)) {
-        set_error("exact draws need a gaussian / identity model on the dense ZL operator with L set");
-        return MCML_EUNSUPPORTED;
-    }
-    const SampleShape sh = sample_shape(o->nsamp, o->warmup, o->chains);   // column 0 of one chain is just another draw
-    const int ncols = sh.ncols;
-    const int Q = c.Q, n = c.n;
-    const double post = glm_score_post(var_par, c.flink);
-    ExactState& x = c.exact;
-    ExactProf prof(x.prof, c.stream);
-
+    if (!applicable) return MCML_EUNSUPPORTED;
+    k.sh = sample_shape(o->nsamp, o->warmup, o->chains);
+    k.post = glm_score_post(var_par, c.flink);
     MCML_TRY(model_update_beta(c, beta));
-    prof.mark();
+    MCML_TRY(T.alloc(c.Q, k.sh.ncols));
+    MCML_HIP(hipMemsetAsync(T.d(), 0, sizeof(double) * (size_t)T.ld * k.sh.ncols, c.stream));
+    if (inj_z) {
+        MCML_TRY(k.d_z.ensure(sizeof(double) * (size_t)c.Q * k.sh.ncols));
+        MCML_TRY(copy_h2d(k.d_z.p, inj_z, sizeof(double) * (size_t)c.Q * k.sh.ncols, c.stream));
+    }
+    return MCML_OK;
+}
+
+// T holds the draws: U = L T as every sampler ends, the context's record of the call, the final synchronisation (notpd: the
+// message if a pivot failed on the way, or null where nothing raises the flag), the phases' times, the caller's outputs
+static int exact_end(Ctx& c, ExactCall& k, DevMat& T, int kernel, const char* notpd, double* ms, uint8_t* flags_out,
+                     double* probs_out, glmmr_mcml_hmc_diag* diag, int* ncols_out)
+{
+    MCML_TRY(samples_to_U(c, T, k.sh.ncols));                     // return (L * samples)  (mhmcmc.h:155)
+    k.mark();
+    c.niter = k.sh.niter; c.last_kernel[0] = c.last_kernel[1] = kernel;
+    const int rc = notpd ? check_errflag(c, notpd) : c.sync();
+    k.collect(ms);
+    MCML_TRY(rc);
+    exact_finish(k.sh, flags_out, probs_out, diag, ncols_out);
+    return MCML_OK;
+}
+
+// inj_z: host, Q x ncols, or null
+static int exact_gaussian_sample(Ctx& c, const double* beta, double var_par, const glmmr_mcml_hmc_opts* o, uint64_t seed,
+                                 uint32_t iter_idx, const double* inj_z, uint8_t* flags_out, double* probs_out,
+                                 glmmr_mcml_hmc_diag* diag, int* ncols_out)
+{
+    const bool ok = exact_applicable(c);
+    if (!ok) set_error("exact draws need a gaussian / identity model on the dense ZL operator with L set");
+    const int Q = c.Q, n = c.n;
+    ExactState& x = c.exact;
+    ExactCall k(x.prof, c.stream);
+    MCML_TRY(exact_begin(c, beta, var_par, o, inj_z, ok, x.T, k));
+    const int ncols = k.sh.ncols;
+    k.mark();
     DevMat unused;
-    MCML_TRY(build_M_dense(c, nullptr, post, x.M, unused, true));
-    prof.mark();
+    MCML_TRY(build_M_dense(c, nullptr, k.post, x.M, unused, true));
+    k.mark();
     MCML_TRY(potrf_lower_checked(c, x.M.d(), Q, x.M.ld));
-    prof.mark();
+    k.mark();
 
     MCML_TRY(x.b.ensure(sizeof(double) * (size_t)(pad_ld(Q) + 64)));
     MCML_HIP(hipMemsetAsync(x.b.p, 0, sizeof(double) * (size_t)(pad_ld(Q) + 64), c.stream));
-    hipLaunchKernelGGL(k_exact_rhs, dim3((Q + 3) / 4), dim3(256), 0, c.stream, c.ZL.d(), c.ZL.ld, n, Q, c.y.d(), c.xb.d(), post,
+    hipLaunchKernelGGL(k_exact_rhs, dim3((Q + 3) / 4), dim3(256), 0, c.stream, c.ZL.d(), c.ZL.ld, n, Q, c.y.d(), c.xb.d(), k.post,
                        x.b.d());
     MCML_HIP(hipGetLastError());
     MCML_TRY(trsm_left_lower(c, x.M.d(), x.M.ld, Q, x.b.d(), pad_ld(Q), 1));      // w = R^-1 b
-    MCML_TRY(x.T.alloc(Q, ncols));
-    MCML_HIP(hipMemsetAsync(x.T.d(), 0, sizeof(double) * (size_t)x.T.ld * ncols, c.stream));   // finite padding rows
-    DevBuf d_z;
-    if (inj_z) {
-        MCML_TRY(d_z.ensure(sizeof(double) * (size_t)Q * ncols));
-        MCML_TRY(copy_h2d(d_z.p, inj_z, sizeof(double) * (size_t)Q * ncols, c.stream));
-    }
     hipLaunchKernelGGL(k_exact_fill, dim3((Q + 255) / 256, ncols < 1024 ? ncols : 1024), dim3(256), 0, c.stream, x.T.d(), x.T.ld,
-                       Q, ncols, x.b.d(), d_z.d(), seed, (uint32_t)o->chain_offset, iter_idx, sh.C, sh.d);
+                       Q, ncols, x.b.d(), k.d_z.d(), seed, (uint32_t)o->chain_offset, iter_idx, k.sh.C, k.sh.d);
     MCML_HIP(hipGetLastError());
-    prof.mark();
+    k.mark();
     MCML_TRY(trsm_left_lower_trans(c, x.M.d(), x.M.ld, Q, x.T.d(), x.T.ld, ncols));
-    prof.mark();
-    MCML_TRY(samples_to_U(c, x.T, ncols));                        // return (L * samples)  (mhmcmc.h:155)
-    prof.mark();
-    c.niter = sh.niter;
-    c.last_kernel[0] = c.last_kernel[1] = KERNEL_EXACT;
-    MCML_HIP(hipStreamSynchronize(c.stream));
-    prof.collect(x.ms);
-    exact_finish(sh, flags_out, probs_out, diag, ncols_out);
-    return MCML_OK;
+    k.mark();
+    return exact_end(c, k, x.T, KERNEL_EXACT, nullptr, x.ms, flags_out, probs_out, diag, ncols_out);
 }
 
 }  // namespace mcml

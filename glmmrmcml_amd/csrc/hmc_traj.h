@@ -17,15 +17,9 @@
 // observations into contiguous quarters; their accumulators are added in wave order through LDS.
 #pragma once
 #include "hmc_cm.h"
-#include "component_plan.h"
+#include "component.h"
 
 namespace mcml {
-
-struct CpDev {                       // ComponentPlan on the device (ctx.h ComponentDev)
-    const int *item_ptr, *var_ptr, *vars, *slot_ptr, *slot_quarter;
-    const int* slot_i;               // the records, 8 ints and 8 doubles each (ComponentDev)
-    const double* slot_d;
-};
 
 struct TrajArgs {
     double *V, *GRAD, *UP, *GRADP;
@@ -37,22 +31,12 @@ struct TrajArgs {
     double lambda; int max_steps;
     int flink; double var_par, post;
     double *part_k0, *part_ll, *part_lp, *part_kin; int ldp;
-    int max_vars;                    // rows of the LDS arrays
 };
-
-// xb_i and y_i of a record's observation (xb changes with beta: once per sampler call)
-__global__ __launch_bounds__(256) void k_cp_fill_xy(int nslots, const int* slot_i, const double* xb, const double* y, double* slot_d)
-{
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= nslots) return;
-    const int i = slot_i[8 * (size_t)s + 6];
-    slot_d[8 * (size_t)s + 4] = xb[i]; slot_d[8 * (size_t)s + 5] = y[i];
-}
 
 // the observations of records [s0, s1) (whole observations): eta, score, accumulate.  xs / gs: this lane's column of the
 // LDS arrays (element j at [j * 64])
 template <int FL>
-__device__ __forceinline__ void cp_rows(const CpDev& m, int s0, int s1, const double* xs, double* gs, int flink,
+__device__ __forceinline__ void cp_rows(const CompView& m, int s0, int s1, const double* xs, double* gs, int flink,
                                         double var_par, bool want_ll, double& ll)
 {
     const int fl = FL ? FL : flink;
@@ -89,13 +73,13 @@ __device__ __forceinline__ void cp_rows(const CpDev& m, int s0, int s1, const do
     }
 }
 
-// grid (work items, chain blocks of 64), 64 * WAVES threads, dynamic LDS of cp_lds_bytes(max_vars, WAVES)
+// grid (work items, chain blocks of 64), 64 * WAVES threads, dynamic LDS of cp_lds_bytes(m.max_vars, WAVES)
 template <int FL, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_cm_traj(CpDev m, TrajArgs a)
+__global__ __launch_bounds__(64 * WAVES) void k_cm_traj(CompView m, TrajArgs a)
 {
     extern __shared__ double cp_lds[];
     const int lane = threadIdx.x & 63, w = WAVES == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int MV = a.max_vars;
+    const int MV = m.max_vars;
     double* xs = cp_lds + lane;                              // x  [var][64]
     double* rs = xs + (size_t)MV * 64;                       // r
     double* g0 = rs + (size_t)MV * 64;                       // accumulator of wave 0; afterwards the gradient

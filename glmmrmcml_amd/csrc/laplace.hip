@@ -7,8 +7,8 @@
 // scalar; the Q x Q x n product ZL' W ZL and its Cholesky use the same MFMA GEMM / potrf as
 // the MCML path, the vector-sized pieces are plain streaming kernels.  Opt-in (glmmr_mcml_ctx_set_la_operator, DESIGN.md
 // 5.5): on a block-structured design the same statements run on the sparse ZL operator and factorise M component by
-// component (la_comp.h: a wave per component up to CP_MAX_VARS variables under "component", a wave or a workgroup up to
-// CP_WIDE_MAX_VARS under "component_wide"); nothing of size Q x n or Q x Q is then built per evaluation.
+// component (component.hip, lac_factor_launch: a wave per component up to CP_MAX_VARS variables under "component", a wave or a
+// workgroup up to CP_WIDE_MAX_VARS under "component_wide"); nothing of size Q x n or Q x Q is then built per evaluation.
 //
 // Reference behaviour reproduced on purpose (also restated in oracle/la.py):
 //   * v = u column 0 is the whitened effect, yet update_W(useL = false) forms Z v and
@@ -22,42 +22,45 @@
 // beta family is refused (its functor mis-sizes theta, likelihood.h:196-201).
 #include "entry.h"
 #include "dgemm_mfma.h"
+#include "component.h"
 #include "glm.h"
-#include "la_comp.h"
 #include "optim.h"
 #include "host_linalg.h"
 #include "reduce.h"
 #include "vecops.h"
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 
 namespace mcml {
 
-// k_lac_factor / k_lac_factor_wg launches of this process, over all contexts (glmmr_mcml_dbg_la_component_launches)
-static std::atomic<long long> g_lac_launches{0};
-long long la_component_launch_count() { return g_lac_launches.load(); }
-
-// one launch of k_lac_factor (waves = 1) or k_lac_factor_wg (4) over the resident component records: the Laplace fits below
-// and the component-wise exact draws (hmc_exact_comp.h, which passes fac / fac_ptr)
-int lac_factor_launch(Ctx& c, const double* W, const double* g, double* x, double* logdet, double* fac, const int* fac_ptr, int waves)
-{
-    const ComponentDev& cp = c.cp;
-    LacArgs a{cp.var_ptr.as<int>(), cp.vars.as<int>(), cp.slot_ptr.as<int>(), cp.slot_i.as<int>(), cp.slot_d.d(), W,
-              cp.plan.ncomp, g, x, logdet, c.errflag(), fac, fac_ptr};
-    if (waves == 4) {
-        MCML_TRY(ensure_dynamic_lds((const void*)k_lac_factor_wg, lacw_lds_bytes(CP_WIDE_MAX_VARS)));
-        hipLaunchKernelGGL(k_lac_factor_wg, dim3(cp.plan.ncomp), dim3(LACW_THREADS), lacw_lds_bytes(cp.plan.max_vars), c.stream, a,
-                           cp.plan.max_vars);
-    } else {
-        hipLaunchKernelGGL(k_lac_factor, dim3((cp.plan.ncomp + LAC_WAVES - 1) / LAC_WAVES), dim3(64 * LAC_WAVES), 0, c.stream, a);
-    }
-    MCML_HIP(hipGetLastError());
-    return MCML_OK;
-}
-int lac_waves_now(const ComponentPlan& p) { return lac_waves(p, lac_forced_waves()); }
-
 // ------------------------------------------------------------------ kernels
+// out_i = sum_k val[i + k n] v[idx[i + k n]], k ascending: ZL v over the ELL rows of ZL (sp.ell_col / sp.ell_val, width
+// sp.W) and Z v over the padded-CSR rows of Z (z_idx / z_val, width z_width); padding entries hold the value 0
+__global__ __launch_bounds__(256) void k_lac_rows_times_v(const int* idx, const double* val, int n, int width, const double* v,
+                                                          double* out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0;
+    for (int k = 0; k < width; ++k) s += val[i + (size_t)k * n] * v[idx[i + (size_t)k * n]];
+    out[i] = s;
+}
+
+// out_q = post (ZL' score)_q - (D0 v)_q.  ZL' by its CSR rows, observations ascending.  D0 = L L' at the starting theta
+// couples the variables of a COVARIANCE block, which can span several components (a variable whose observations were
+// dropped is a component of its own): row q of D0 over the columns [row_start[q], row_end[q]) of its block
+__global__ __launch_bounds__(256) void k_lac_vgrad(const int* csr_ptr, const int* csr_i, const double* csr_val, const double* score,
+                                                   double post, const double* D0, int ldd, const int* row_start, const int* row_end,
+                                                   const double* v, int Q, double* out)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Q) return;
+    const double s = csr_row_sum(csr_ptr, csr_i, csr_val, q, [&](int i) { return score[i]; });
+    double d = 0;
+    for (int j = row_start[q]; j < row_end[q]; ++j) d += D0[q + (size_t)j * ldd] * v[j];
+    out[q] = post * s - d;
+}
+
 // partial sums of log f(y_i | xb_i + zv_i)
 __global__ __launch_bounds__(256) void k_la_ll(const double* y, const double* xb, const double* zv, int n,
                                                double var_par, int flink, double* partials)
@@ -158,7 +161,7 @@ struct LaFit {
     DevBuf v, W, zv, tmpn, tmpn2, tmpn3, tmpq, tmpq2, part, small;
     DevMat M, ZLTW, D0;
     std::vector<double> hv;                         // host copy of v
-    bool comp = false;                              // the component operator (la_comp.h) instead of the dense ZL / M
+    bool comp = false;                              // the component operator (component.h) instead of the dense ZL / M
     int waves = 0;                                  // its form: 1 k_lac_factor, 4 k_lac_factor_wg; 0 with the dense operator
     DevBuf lac_ld;                                  // its per-component log-determinants
     size_t zl_bytes0 = 0;                           // what c.ZL + c.ZLT held when the call began
@@ -198,14 +201,14 @@ struct LaFit {
         MCML_HIP(hipMemsetAsync(v.p, 0, sizeof(double) * (size_t)(Q + 64), c.stream));
         // the component operator: asked for, and the model has the sparse ZL with a component plan its kernel takes (L
         // always comes from theta here: gen_L).  Otherwise, silently, the dense ZL as ever.  "component" is the one-wave
-        // kernel and its cap; "component_wide" takes components up to CP_WIDE_MAX_VARS and picks the form (lac_waves)
+        // kernel and its cap; "component_wide" takes components up to CP_WIDE_MAX_VARS and picks the form (cp_waves)
         if (c.la_mode == 1 || c.la_mode == 2) {
             MCML_TRY(model_sparse_setup(c));
             comp = c.sp.possible && c.cp.ready && (c.la_mode == 2 ? c.cp.plan.records : c.cp.plan.feasible);
         }
         if (comp) {
             MCML_TRY(lac_ld.ensure(sizeof(double) * (size_t)c.cp.plan.ncomp));
-            waves = c.la_mode == 2 ? lac_waves(c.cp.plan, lac_forced_waves()) : 1;
+            waves = c.la_mode == 2 ? cp_waves(c.cp.plan, cp_forced_waves(CP_LA_WAVES_ENV)) : 1;
         }
         c.la_last_op = comp ? c.la_mode : 0;
         c.la_waves = waves;
@@ -248,25 +251,22 @@ struct LaFit {
         MCML_HIP(hipStreamSynchronize(c.stream));
         return MCML_OK;
     }
+    int rows_times_v(const DevBuf& idx, const DevBuf& val, int width, double* out)   // the component operator's products with v
+    {
+        hipLaunchKernelGGL(k_lac_rows_times_v, dim3((n + 255) / 256), dim3(256), 0, c.stream, idx.as<int>(), val.d(), n, width,
+                           v.d(), out);
+        MCML_HIP(hipGetLastError());
+        return MCML_OK;
+    }
     // out = ZL v from the current c.ZLT (Q x n): column i of ZLT is row i of ZL
     int zl_times_v(double* out)
     {
-        if (comp) {
-            hipLaunchKernelGGL(k_lac_rows_times_v, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.sp.ell_col.as<int>(),
-                               c.sp.ell_val.d(), n, c.sp.W, v.d(), out);
-            MCML_HIP(hipGetLastError());
-            return MCML_OK;
-        }
+        if (comp) return rows_times_v(c.sp.ell_col, c.sp.ell_val, c.sp.W, out);
         return dev_gemv_t(c, c.ZLT.d(), c.ZLT.ld, Q, n, v.d(), out, 1.0, 0.0);
     }
     int z_times_v(double* out)
     {
-        if (comp) {
-            hipLaunchKernelGGL(k_lac_rows_times_v, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.z_idx.as<int>(),
-                               c.z_val.d(), n, c.z_width, v.d(), out);
-            MCML_HIP(hipGetLastError());
-            return MCML_OK;
-        }
+        if (comp) return rows_times_v(c.z_idx, c.z_val, c.z_width, out);
         return dev_gemv_n(c, c.Z.d(), c.Z.ld, n, Q, v.d(), out);
     }
     int scalar_from(const double* dev, double* host)
@@ -309,12 +309,10 @@ struct LaFit {
 
     // M = ZL' W ZL + I from the current c.ZL / c.ZLT
     int build_M() { return build_M_dense(c, W.d(), 1.0, M, ZLTW, false); }
-    // every M_c built and factorised from the current record values and W (la_comp.h); with g, x = M^-1 g as well
+    // every M_c built and factorised from the current record values and W (component.h); with g, x = M^-1 g as well
     int lac_factor(const double* g, double* x)
     {
-        MCML_TRY(lac_factor_launch(c, W.d(), g, x, lac_ld.d(), nullptr, nullptr, waves));
-        ++c.la_launches; ++g_lac_launches;
-        return MCML_OK;
+        return lac_factor_launch(c, W.d(), 1.0, g, x, lac_ld.d(), nullptr, nullptr, waves, &c.la_launches);
     }
     // a non-positive pivot of some M_c, as potrf_lower_checked reports one of M; synchronises the stream
     int lac_check() { return check_errflag(c, "mcml_la: ZL' W ZL + I is not positive definite"); }

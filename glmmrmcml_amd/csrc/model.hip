@@ -10,6 +10,7 @@
 // Z is held dense for the MFMA products and, when it is an indicator-like
 // matrix, also as padded-CSR rows so that Z u and Z L are row gathers.
 #include "ctx.h"
+#include "component.h"
 #include "dgemm_mfma.h"
 #include "dgemm_band.h"
 #include "glm.h"
@@ -138,14 +139,6 @@ __global__ void k_csr_fill(const int* pos, const double* ell_val, long nnz, doub
     if (t < nnz) csr_val[t] = ell_val[pos[t]];
 }
 
-// the trajectory kernel's metadata records (hmc_traj.h, 4 values + xb, y, 0, 0 each): ell_val permuted, whenever L changes
-__global__ __launch_bounds__(256) void k_cp_fill_val(long tot, const int* slot_src, const double* ell_val, double* slot_d)
-{
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= tot) return;
-    const int src = slot_src[t];
-    slot_d[8 * (t >> 2) + (t & 3)] = src >= 0 ? ell_val[src] : 0.0;
-}
 static int sparse_zl_setup(Ctx& c)
 {
     SparseZL& sp = c.sp;
@@ -249,25 +242,7 @@ static int sparse_zl_setup(Ctx& c)
             if (!strcmp(e, "product")) sp.factored = false;
         }
     }
-    // the components of the coupling graph and the trajectory kernel's work items (component_plan.h)
-    {
-        ComponentDev& cp = c.cp;
-        component_plan_build(n, Q, W, col, width, cp.plan);
-        cp.ready = false;
-        if (cp.plan.records) {                 // item_ptr stays empty above CP_MAX_VARS: only the Laplace kernels run there
-            const ComponentPlan& p = cp.plan;
-            auto up = [&](DevBuf& b, const std::vector<int>& v) -> int {
-                MCML_TRY(b.ensure(sizeof(int) * (v.size() + 8)));
-                return copy_h2d(b.p, v.data(), sizeof(int) * v.size(), c.stream);
-            };
-            MCML_TRY(up(cp.item_ptr, p.item_ptr)); MCML_TRY(up(cp.var_ptr, p.var_ptr)); MCML_TRY(up(cp.vars, p.vars));
-            MCML_TRY(up(cp.slot_ptr, p.slot_ptr)); MCML_TRY(up(cp.slot_quarter, p.slot_quarter));
-            MCML_TRY(up(cp.slot_i, p.slot_i)); MCML_TRY(up(cp.slot_src, p.slot_src));
-            MCML_TRY(cp.slot_d.ensure(sizeof(double) * 8 * (size_t)(p.nslots + 1)));
-            MCML_HIP(hipMemsetAsync(cp.slot_d.p, 0, sizeof(double) * 8 * (size_t)(p.nslots + 1), c.stream));
-            cp.ready = true;
-        }
-    }
+    MCML_TRY(comp_setup(c, W, col, width));   // the components of the coupling graph and their records (component.h)
     MCML_HIP(hipStreamSynchronize(c.stream));
     sp.W = W; sp.nnz = nnz; sp.possible = true;
     return MCML_OK;
@@ -293,12 +268,8 @@ int model_update_L(Ctx& c)
         MCML_TRY(c.sp.csr_val.ensure(sizeof(double) * (size_t)(c.sp.nnz + 1)));
         hipLaunchKernelGGL(k_csr_fill, dim3((unsigned)((c.sp.nnz + 255) / 256)), dim3(256), 0, c.stream,
                            c.sp.csr_pos.as<int>(), c.sp.ell_val.d(), c.sp.nnz, c.sp.csr_val.d());
-        if (c.cp.ready) {
-            const long te = 4L * c.cp.plan.nslots;
-            hipLaunchKernelGGL(k_cp_fill_val, dim3((unsigned)((te + 255) / 256)), dim3(256), 0, c.stream, te,
-                               c.cp.slot_src.as<int>(), c.sp.ell_val.d(), c.cp.slot_d.d());
-        }
         MCML_HIP(hipGetLastError());
+        if (c.cp.ready) MCML_TRY(comp_fill_val(c));
         c.sp.active = true;
         return MCML_OK;
     }

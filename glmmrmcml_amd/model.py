@@ -415,7 +415,7 @@ class ModelMCML:
     # ---- LA ------------------------------------------------------------------------------------------------------
     def LA(self, y, *args, operator=None, **kwargs):
         """_la below (its arguments, unchanged); operator ("dense" / "component" / "component_wide", None = leave the
-        backend's default alone): how the Laplace fit forms and factorises ZL' W ZL + I (csrc/la_comp.h).  It becomes the backend's default
+        backend's default alone): how the Laplace fit forms and factorises ZL' W ZL + I (csrc/component.hip).  It becomes the backend's default
         for the duration of the call and is restored afterwards"""
         if operator is None:
             return self._la(y, *args, **kwargs)

@@ -1,4 +1,4 @@
-"""Wall-clock timing of the Laplace fit on the component operator (csrc/la_comp.h) against the dense operator.
+"""Wall-clock timing of the Laplace fit on the component operator (csrc/component.hip) against the dense operator.
 
 Shapes: config 5, synth.longitudinal(2000, 10) (n = 20000, Q = 22000, 2000 components of 11 variables), and config 4,
 synth.stepped_wedge(40, 8, 50) (n = 16000, Q = 320, 40 components of 8 variables and 400 observations).  The timed call is

@@ -11,7 +11,9 @@ of what a call returns is compared with tests/golden/dense_la_bits.json, recorde
   mvn_batch_*     mvn_ll_batch, 2 and 8 candidates at d = 300, 8 at d = 1153 (the first size with a super-panel regrouping)
   mixed_layout    diagonal rows, blocks up to 32 and one block above: mvn_ll (the accumulating sum) and gen_D(chol=True)
   la_dense_*      Laplace fits on the dense operator: the four probes, both drivers, the Hessian's inverse
-  la_component_*  the probes on the component operators, a wave and a workgroup per component
+  la_component_*  the probes on the component operators, a wave and a workgroup per component: rows of ZL two wide (rct), rows of
+                  8 = two records per observation (sw_blk8), 65 variables = a lane's second entry of a row (rct64), and a
+                  component of 48 variables over two covariance blocks, 12 records per observation (paired_ar1)
   beta_step       Context.mcnr: the Gauss-Jordan inverse at tolerance 0
   bobyqa          mcml_optim: the same elimination at 1e-14 inside the optimiser
 The input hashes are asserted first: a changed numpy stream fails there instead of comparing different problems."""
@@ -26,6 +28,7 @@ import chol_reference as cr
 import cov_layouts as cl
 import family_designs as fd
 import test_gpu_la_component as lc
+import test_gpu_la_component_wide as lw
 from test_gpu_la import CASES as LA_CASES
 from test_gpu_sparse_products import context as sparse_context, design as sparse_design
 
@@ -141,16 +144,18 @@ def la_dense(name, usehess=False):
     return run
 
 
-def la_component(mode, waves=None):
+def la_component(mode, waves=None, design=("rct", "poisson", "log"), counts=(7, 6, 15), want_waves=None):
+    """counts: components, most variables and most observations of a component; want_waves: the form without a forced one"""
     def run(mp):
         if waves:
             mp.setenv("GLMMR_MCML_LA_WAVES", waves)
-        d = lc.with_start(sparse_design("rct", "poisson", "log"))
+        d = lw.wide_design(*design)[0] if design[0] in ("rct64", "paired_ar1") else lc.with_start(sparse_design(*design))
         with sparse_context(d, mp, None) as ctx:
             ctx.set_la_operator(mode)
             out = _probes(ctx, d)
             p = ctx.la_plan()
-            assert p["operator"] == mode and p["waves"] == int(waves or 1) and p["launches"] == 1, p
+            assert p["operator"] == mode and p["waves"] == int(waves or want_waves or 1) and p["launches"] == 1, p
+            assert (p["ncomp"], p["max_vars"], p["max_rows"]) == counts and p["dense_bytes"] == 0, p
         return dict(out, inputs=_design_inputs(d))
     return run
 
@@ -190,6 +195,11 @@ CASES = {
     "la_component_rct": la_component("component"),
     "la_component_wide_rct_waves1": la_component("component_wide", "1"),
     "la_component_wide_rct_waves4": la_component("component_wide", "4"),
+    "la_component_sw_blk8": la_component("component", design=("sw_blk8", "poisson", "log"), counts=(5, 8, 24)),
+    "la_component_wide_sw_blk8_waves4": la_component("component_wide", "4", design=("sw_blk8", "poisson", "log"), counts=(5, 8, 24)),
+    "la_component_wide_rct64": la_component("component_wide", design=("rct64", "poisson", "log"), counts=(2, 65, 128), want_waves=4),
+    "la_component_wide_paired_ar1": la_component("component_wide", design=("paired_ar1", "binomial", "logit"), counts=(2, 48, 96),
+                                                 want_waves=4),
     "beta_step": beta_step,
     "bobyqa": bobyqa,
 }

@@ -51,7 +51,7 @@ DESIGNS = {
 }
 SIGMAS = {name: (0.8, 0.2) if name in ("rct", "cap32", "rct127") else (0.8,) for name in DESIGNS}
 MEAN_DESIGNS = ("rct", "sw_blk16", "rct41")
-RULE_WAVES = {"rct": 1, "sw_long_ragged": 4}        # the form lac_waves picks; the test also forces the other one
+RULE_WAVES = {"rct": 1, "sw_long_ragged": 4}        # the form cp_waves picks; the test also forces the other one
 
 
 def make(name):

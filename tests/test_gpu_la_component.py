@@ -1,4 +1,4 @@
-"""The component operator of the Laplace fits (csrc/la_comp.h; Context.set_la_operator("component")): on a
+"""The component operator of the Laplace fits (csrc/component.hip; Context.set_la_operator("component")): on a
 block-structured design M = ZL' W ZL + I is block diagonal over the connected components of ZL's coupling graph, and the
 functors, the Newton step and the drivers run on the sparse ZL operator with M built, factorised and solved one component
 at a time.

@@ -1,4 +1,4 @@
-"""The "component_wide" operator of the Laplace fits (csrc/la_comp.h k_lac_factor_wg; Context.set_la_operator(
+"""The "component_wide" operator of the Laplace fits (csrc/component.hip k_lac_factor_wg; Context.set_la_operator(
 "component_wide")): the component operator of test_gpu_la_component.py for components of up to 128 variables, a wave
 (k_lac_factor) or a workgroup of four waves (k_lac_factor_wg) per component.
 

@@ -66,7 +66,7 @@ def test_functors_and_newton_step_match_oracle(key, family, link):
 
 @pytest.mark.parametrize("family,link,vp", fd.CASES, ids=fd.IDS)
 def test_component_operator_runs_every_family(family, link, vp, monkeypatch):
-    """the component operator (csrc/la_comp.h) shares k_la_ll / k_la_W / k_la_nr_obs with the dense one: the same twelve
+    """the component operator (csrc/component.hip) shares k_la_ll / k_la_W / k_la_nr_obs with the dense one: the same twelve
     families at the block-structured shape, one functor (kind 2: W, the log density and the log-determinant) and the
     step, where la_plan() reports that it ran"""
     monkeypatch.delenv("GLMMR_MCML_ZL", raising=False)

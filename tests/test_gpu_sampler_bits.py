@@ -13,7 +13,8 @@ cases are the smallest that reach each copy of the rules the back ends once carr
   step_*        chain-major state, a launch pair per leapfrog step (k_cm_init / k_cm_propose_fin / k_cm_accept_fin<false>):
                 130 chains (two groups of 64 and one of 2), one chain, and 5 chains x 2 draws for 7 samples (10 columns)
   component_*   component trajectories (k_cm_traj, k_cm_accept_fin<true>), both forms of the kernel
-  exact_*       exact conditional draws, dense and component-wise (factor kernel a wave / a workgroup per component)
+  exact_*       exact conditional draws, dense and component-wise (factor kernel a wave / a workgroup per component); on rct64
+                (components of 65 variables) the draw kernel reads the factors unstaged, 9 columns and 70 (a second block of 64)
   nuts_*        NUTS on a dense and a sparse design (sampler_init_state, store_columns, the shape), nsamp not a multiple of chains
 The input hashes are asserted first: a changed numpy stream fails there instead of comparing different problems."""
 import hashlib
@@ -26,6 +27,7 @@ import pytest
 import nuts_cases as nc
 import test_gpu_dense_products as dp
 import test_gpu_sparse_products as sp
+from test_gpu_la_component_wide import wide_design
 from test_gpu_dense_products import ADAPT, IT, LAM, MS, SEED, TA, WARM
 
 pytestmark = pytest.mark.gpu
@@ -96,6 +98,21 @@ def sparse(kind, opts, chains, nsamp, warm=WARM, trajectory="step", traj_waves=N
     return run
 
 
+def exact_rct64(chains, nsamp):
+    """cluster_rct(2, 64, 2), gaussian / identity: 2 components of 65 variables, above the staged draw kernel's cap"""
+    def run(mp):
+        d = wide_design("rct64", "gaussian", "identity")[0]
+        with sp.context(d, mp, None) as ctx:
+            ctx.set_draws("exact_component")
+            p = ctx.exact_component_plan()
+            assert p["applicable"] and (p["ncomp"], p["max_vars"], p["max_rows"]) == (2, 65, 128), p
+            assert p["factor_waves"] == 4 and p["draw_lds_bytes"] == 8 * 64 * 65 and p["factor_bytes"] == 8 * 2 * 65 * 65, p
+            out = _hmc(ctx, d, chains, nsamp, WARM)
+            assert ctx.last_kernels() == ("exact_component",) * 2, ctx.last_kernels()
+        return dict(out, inputs=_inputs(d))
+    return run
+
+
 def nuts(name):
     def run(mp):
         c = nc.CASES[name]
@@ -141,6 +158,8 @@ CASES = {
     "exact_component_waves1_3_chains_7_samples": sparse(*SW_LONG, 3, 7, draws="exact_component", la_waves="1", **GAUSS),
     "exact_component_waves4_1x4": sparse(*SW_LONG, 1, 4, draws="exact_component", la_waves="4", **GAUSS),
     "exact_component_waves4_3_chains_7_samples": sparse(*SW_LONG, 3, 7, draws="exact_component", la_waves="4", **GAUSS),
+    "exact_component_rct64_3_chains_7_samples": exact_rct64(3, 7),
+    "exact_component_rct64_1x69": exact_rct64(1, 69),
     "nuts_dense_96x40": nuts("dense_96x40"),
     "nuts_sparse_repack_128": nuts("repack"),
 }
