@@ -1,6 +1,7 @@
 // comm.hip -- the cross-rank exchanges of the MCML path:
 //   * an in-place sum of a few doubles (per-chain sufficient statistics of the MCNR step, (sum, count) of an objective
-//     evaluation, the values of one round of candidate thetas);
+//     evaluation, the values of one round of candidate thetas: exchange_round, which under rank emulation records or
+//     replays them instead);
 //   * ONE all-gather of the sample columns per MCML iteration (Q x m doubles, 41 MB at config 3): every rank then holds
 //     all of u, so the theta-step shards over candidate thetas instead of replicating its factorisation on every rank
 //     (drivers.hip::d_optim), and mcml_full can hand back all of u as the reference does (mcml_full.cpp:144-145).
@@ -85,7 +86,7 @@ void comm_release(Ctx& c)
 // sum n doubles at dev (device memory) over the ranks, in place, ordered behind everything already on c.stream
 int allreduce_dev(Ctx& c, double* dev, int n)
 {
-    if (!c.comm && c.world <= 1 && c.emu_world > 1) {
+    if (comm_emulated(c)) {
         c.coll_calls += 1; c.coll_doubles += n;
         hipLaunchKernelGGL(k_emu_scale, dim3((n + 255) / 256), dim3(256), 0, c.stream, dev, n, (double)c.emu_world);
         MCML_HIP(hipGetLastError());
@@ -116,7 +117,7 @@ int allreduce_dev(Ctx& c, double* dev, int n)
 int allgather_dev(Ctx& c, const double* send, double* recv, size_t count)
 {
     double* mine = recv + (size_t)c.rank * count;
-    if (!c.comm && c.world <= 1 && c.emu_world > 1) {
+    if (comm_emulated(c)) {
         c.gather_calls += 1; c.gather_doubles += (long long)count * c.emu_world;
         for (int r = 0; r < c.emu_world; ++r)
             if (recv + (size_t)r * count != send)
@@ -178,6 +179,23 @@ int allreduce_host(Ctx& c, double* vals, int n)
     MCML_TRY(allreduce_dev(c, c.reduce_buf.d(), n));
     MCML_TRY(copy_d2h(vals, c.reduce_buf.p, sizeof(double) * n, c.stream));
     MCML_HIP(hipStreamSynchronize(c.stream));
+    return MCML_OK;
+}
+
+// The values of one round of the sharded theta-step (drivers.hip): candidate j was evaluated by rank j mod world, every other slot is zero, so one
+// sum carries them all.  Rank emulation: recording, every slot was evaluated here and the round is kept; replaying, this rank's must equal the record's.
+int exchange_round(Ctx& c, std::vector<double>& vals)
+{
+    const int nc = (int)vals.size(), wr = comm_world(c);
+    if (!comm_emulated(c)) return allreduce_host(c, vals.data(), nc);
+    if (c.emu_mode == 1) { c.emu_trace.push_back(vals); return MCML_OK; }
+    MCML_REQUIRE(c.emu_pos < c.emu_trace.size() && (int)c.emu_trace[c.emu_pos].size() == nc,
+                 "rank emulation: replay ran past its record (round %zu)", c.emu_pos);
+    const std::vector<double>& rec = c.emu_trace[c.emu_pos++];
+    for (int j = 0; j < nc; ++j) {
+        if ((j % wr) == c.rank) MCML_REQUIRE(vals[j] == rec[j] || (vals[j] != vals[j]), "rank emulation: replayed value differs from the recorded one (%.17g vs %.17g)", vals[j], rec[j]);
+        else vals[j] = rec[j];
+    }
     return MCML_OK;
 }
 

@@ -279,6 +279,7 @@ int allreduce_dev(Ctx& c, double* dev, int n);              // in place on devic
 int allgather_dev(Ctx& c, const double* send, double* recv, size_t count);
 int gather_samples(Ctx& c);                                  // c.Uall <- all ranks' sample columns
 inline int comm_world(const Ctx& c) { return c.emu_world > 1 ? c.emu_world : c.world; }
+inline bool comm_emulated(const Ctx& c) { return !c.comm && c.world <= 1 && c.emu_world > 1; }   // rank emulation is on
 inline void Ctx::comm_release_hook() { comm_release(*this); }
 
 // ---- mvn.hip ----
@@ -312,6 +313,7 @@ int build_M_dense(Ctx& c, const double* W, double w0, DevMat& M, DevMat& ZLTW, b
 // ---- model.hip ----
 int model_setup(Ctx& c, const double* Z, const double* X, const double* y);
 int allreduce_host(Ctx& c, double* vals, int n);             // comm.hip
+int exchange_round(Ctx& c, std::vector<double>& vals);      // comm.hip: a round's candidate values, each set on its owner
 int model_update_beta(Ctx& c, const double* beta);          // xb = X beta
 int model_update_zu(Ctx& c);                                // ZU = Z U (cached)
 int model_update_L(Ctx& c);                                 // ZL = Z L, ZLT (dense) or the ELL/CSR pair (sparse)

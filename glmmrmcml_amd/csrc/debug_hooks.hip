@@ -354,22 +354,40 @@ extern "C" int glmmr_mcml_dbg_minstd(uint32_t seed, int n, double* out)
 #include "optim.h"
 #include "theta_scale.h"
 #include <cmath>
+// what the optimiser hooks share: the caller's point and bounds (null: free) as vectors, its options, the result copied out
+struct HookProblem {
+    std::vector<double> x, lo, up;
+    BobyqaOpts o; BobyqaResult r;
+    HookProblem(int n, const double* x0, const double* lower, const double* upper, double rhobeg = 0, double rhoend = 0, int maxfun = 0, int npt = 0)
+        : x(x0, x0 + n), lo(n, -HUGE_VAL), up(n, HUGE_VAL)
+    {
+        if (lower) lo.assign(lower, lower + n);
+        if (upper) up.assign(upper, upper + n);
+        o.rhobeg = rhobeg; o.rhoend = rhoend; o.npt = npt; if (maxfun > 0) o.maxfun = maxfun;
+    }
+    int result(double* x_out, double* f_out, int* nfev_out, int* rounds_out = nullptr) const
+    {
+        std::copy(r.x.begin(), r.x.end(), x_out);
+        if (f_out) *f_out = r.fval;
+        if (nfev_out) *nfev_out = r.nfev;
+        if (rounds_out) *rounds_out = r.rounds;
+        return MCML_OK;
+    }
+};
+static objective_fn hook_objective(glmmr_mcml_objective f, int n, void* user) { return [=](const std::vector<double>& x, double* v) { *v = f(x.data(), n, user); return 0; }; }
+static std::vector<double> flat_round(const std::vector<std::vector<double>>& X, int n)        // n x k, column-major
+{
+    std::vector<double> flat((size_t)n * X.size());
+    for (size_t j = 0; j < X.size(); ++j) for (int i = 0; i < n; ++i) flat[j * n + i] = X[j][i];
+    return flat;
+}
+
 extern "C" int glmmr_mcml_dbg_bobyqa(glmmr_mcml_objective f, void* user, int n, const double* x0,
                                      const double* lower, const double* upper, double rhobeg, double rhoend,
                                      int maxfun, double* x_out, double* f_out, int* nfev_out)
 {
     MCML_REQUIRE(f && n > 0 && x0 && x_out, "dbg_bobyqa: bad argument");
-    objective_fn obj = [&](const std::vector<double>& x, double* v) { *v = f(x.data(), n, user); return 0; };
-    std::vector<double> x(x0, x0 + n), lo(n, -HUGE_VAL), up(n, HUGE_VAL);
-    if (lower) lo.assign(lower, lower + n);
-    if (upper) up.assign(upper, upper + n);
-    BobyqaOpts o; o.rhobeg = rhobeg; o.rhoend = rhoend; if (maxfun > 0) o.maxfun = maxfun;
-    BobyqaResult r;
-    MCML_TRY(bobyqa(obj, x, lo, up, o, &r));
-    for (int i = 0; i < n; ++i) x_out[i] = r.x[i];
-    if (f_out) *f_out = r.fval;
-    if (nfev_out) *nfev_out = r.nfev;
-    return MCML_OK;
+    return glmmr_mcml_dbg_bobyqa_npt(f, user, n, x0, lower, upper, rhobeg, rhoend, maxfun, 0, x_out, f_out, nfev_out);
 }
 // the same with the number of interpolation points given (0: the default, min(n + 2, 2n) as minqa)
 extern "C" int glmmr_mcml_dbg_bobyqa_npt(glmmr_mcml_objective f, void* user, int n, const double* x0,
@@ -377,17 +395,9 @@ extern "C" int glmmr_mcml_dbg_bobyqa_npt(glmmr_mcml_objective f, void* user, int
                                          int maxfun, int npt, double* x_out, double* f_out, int* nfev_out)
 {
     MCML_REQUIRE(f && n > 0 && x0 && x_out && npt >= 0, "dbg_bobyqa_npt: bad argument");
-    objective_fn obj = [&](const std::vector<double>& x, double* v) { *v = f(x.data(), n, user); return 0; };
-    std::vector<double> x(x0, x0 + n), lo(n, -HUGE_VAL), up(n, HUGE_VAL);
-    if (lower) lo.assign(lower, lower + n);
-    if (upper) up.assign(upper, upper + n);
-    BobyqaOpts o; o.rhobeg = rhobeg; o.rhoend = rhoend; o.npt = npt; if (maxfun > 0) o.maxfun = maxfun;
-    BobyqaResult r;
-    MCML_TRY(bobyqa(obj, x, lo, up, o, &r));
-    for (int i = 0; i < n; ++i) x_out[i] = r.x[i];
-    if (f_out) *f_out = r.fval;
-    if (nfev_out) *nfev_out = r.nfev;
-    return MCML_OK;
+    HookProblem p(n, x0, lower, upper, rhobeg, rhoend, maxfun, npt);
+    MCML_TRY(bobyqa(hook_objective(f, n, user), p.x, p.lo, p.up, p.o, &p.r));
+    return p.result(x_out, f_out, nfev_out);
 }
 extern "C" int glmmr_mcml_dbg_bobyqa_batch(glmmr_mcml_objective f, void* user, int n, const double* x0,
                                            const double* lower, const double* upper, double rhobeg, double rhoend,
@@ -399,17 +409,9 @@ extern "C" int glmmr_mcml_dbg_bobyqa_batch(glmmr_mcml_objective f, void* user, i
         F->resize(X.size());
         for (size_t i = 0; i < X.size(); ++i) (*F)[i] = f(X[i].data(), n, user);
         return 0; };
-    std::vector<double> x(x0, x0 + n), lo(n, -HUGE_VAL), up(n, HUGE_VAL);
-    if (lower) lo.assign(lower, lower + n);
-    if (upper) up.assign(upper, upper + n);
-    BobyqaOpts o; o.rhobeg = rhobeg; o.rhoend = rhoend; if (maxfun > 0) o.maxfun = maxfun;
-    BobyqaResult r;
-    MCML_TRY(bobyqa_batch(obj, x, lo, up, o, width, &r));
-    for (int i = 0; i < n; ++i) x_out[i] = r.x[i];
-    if (f_out) *f_out = r.fval;
-    if (nfev_out) *nfev_out = r.nfev;
-    if (rounds_out) *rounds_out = r.rounds;
-    return MCML_OK;
+    HookProblem p(n, x0, lower, upper, rhobeg, rhoend, maxfun);
+    MCML_TRY(bobyqa_batch(obj, p.x, p.lo, p.up, p.o, width, &p.r));
+    return p.result(x_out, f_out, nfev_out, rounds_out);
 }
 // the same with a BATCH callback: fb(X /* n x k, column-major */, n, k, F /* k values out */, user) evaluates a whole round --
 // what a rank of a sharded job does (its own candidates, then the exchange); tests/test_dist_gloo.py runs it over gloo
@@ -420,26 +422,17 @@ extern "C" int glmmr_mcml_dbg_bobyqa_rounds(glmmr_mcml_batch_objective fb, void*
 {
     MCML_REQUIRE(fb && n > 0 && x0 && x_out && width >= 1, "dbg_bobyqa_rounds: bad argument");
     batch_objective_fn obj = [&](const std::vector<std::vector<double>>& X, std::vector<double>* F) {
-        const int k = (int)X.size();
-        std::vector<double> flat((size_t)n * k);
-        for (int j = 0; j < k; ++j) for (int i = 0; i < n; ++i) flat[(size_t)j * n + i] = X[j][i];
-        F->assign(k, 0.0);
-        return fb(flat.data(), n, k, F->data(), user); };
-    std::vector<double> x(x0, x0 + n), lo(n, -HUGE_VAL), up(n, HUGE_VAL);
-    if (lower) lo.assign(lower, lower + n);
-    if (upper) up.assign(upper, upper + n);
-    BobyqaOpts o; o.rhobeg = rhobeg; o.rhoend = rhoend; if (maxfun > 0) o.maxfun = maxfun;
-    BobyqaResult r;
-    MCML_TRY(bobyqa_batch(obj, x, lo, up, o, width, &r));
-    for (int i = 0; i < n; ++i) x_out[i] = r.x[i];
-    if (f_out) *f_out = r.fval;
-    if (nfev_out) *nfev_out = r.nfev;
-    if (rounds_out) *rounds_out = r.rounds;
-    return MCML_OK;
+        F->assign(X.size(), 0.0);
+        return fb(flat_round(X, n).data(), n, (int)X.size(), F->data(), user); };
+    HookProblem p(n, x0, lower, upper, rhobeg, rhoend, maxfun);
+    MCML_TRY(bobyqa_batch(obj, p.x, p.lo, p.up, p.o, width, &p.r));
+    return p.result(x_out, f_out, nfev_out, rounds_out);
 }
 // bobyqa_batch over log(theta) on the grouped round evaluation of the theta-step (theta_scale.h), the factorisations left
 // to the caller: fb(X, n, k, logdet, sumsq, status, user) is asked for the representatives only (grouped != 0) or for
-// every candidate; the objective is -(MVN sum) / m from the two scalars, +inf where status != 0
+// every candidate; the objective is -(MVN sum) / m from the two scalars, +inf where status != 0.  It runs the memo's plan /
+// finish itself and not through the theta-step's round evaluator (drivers.hip eval_theta_round): that one factorises on a
+// context's device, here there is no context and the factorisation is the caller's
 extern "C" int glmmr_mcml_dbg_theta_scale_rounds(glmmr_mcml_parts_objective fb, void* user, int n, const int* exps, int dim,
                                                  int m, int grouped, const double* x0, const double* lower,
                                                  const double* upper, double rhobeg, double rhoend, int maxfun, int width,
@@ -451,8 +444,7 @@ extern "C" int glmmr_mcml_dbg_theta_scale_rounds(glmmr_mcml_parts_objective fb, 
     ts.reset(grouped ? std::vector<int>(exps, exps + n) : std::vector<int>(n, 0), true);
     batch_objective_fn obj = [&](const std::vector<std::vector<double>>& X, std::vector<double>* F) {
         const int k = (int)X.size();
-        std::vector<double> flat((size_t)n * k);
-        for (int j = 0; j < k; ++j) for (int i = 0; i < n; ++i) flat[(size_t)j * n + i] = X[j][i];
+        const std::vector<double> flat = flat_round(X, n);
         const std::vector<int> reps = ts.plan(flat.data(), n, k);
         const int nr = (int)reps.size();
         std::vector<double> rx((size_t)n * nr + 1), parts((size_t)2 * nr + 2), ld(nr + 1), ss(nr + 1), rsums(nr + 1), sums(k);
@@ -467,28 +459,18 @@ extern "C" int glmmr_mcml_dbg_theta_scale_rounds(glmmr_mcml_parts_objective fb, 
         F->resize(k);
         for (int j = 0; j < k; ++j) (*F)[j] = rcs[j] == MCML_OK ? -1.0 * (sums[j] / m) : HUGE_VAL;
         return (int)MCML_OK; };
-    std::vector<double> x(x0, x0 + n), lo(n, -HUGE_VAL), up(n, HUGE_VAL);
-    if (lower) lo.assign(lower, lower + n);
-    if (upper) up.assign(upper, upper + n);
-    BobyqaOpts o; o.rhobeg = rhobeg; o.rhoend = rhoend; if (maxfun > 0) o.maxfun = maxfun;
-    BobyqaResult r;
-    MCML_TRY(bobyqa_batch(obj, x, lo, up, o, width, &r));
-    for (int i = 0; i < n; ++i) x_out[i] = r.x[i];
-    if (f_out) *f_out = r.fval;
-    if (nfev_out) *nfev_out = r.nfev;
-    if (rounds_out) *rounds_out = r.rounds;
+    HookProblem p(n, x0, lower, upper, rhobeg, rhoend, maxfun);
+    MCML_TRY(bobyqa_batch(obj, p.x, p.lo, p.up, p.o, width, &p.r));
     if (factorised_out) *factorised_out = ts.factorised;
-    return MCML_OK;
+    return p.result(x_out, f_out, nfev_out, rounds_out);
 }
 extern "C" int glmmr_mcml_dbg_fd_hessian(glmmr_mcml_objective f, void* user, int n, const double* x, double ndeps,
                                          int usebounds, const double* lower, const double* upper, double* H)
 {
     MCML_REQUIRE(f && n > 0 && x && H, "dbg_fd_hessian: bad argument");
-    objective_fn obj = [&](const std::vector<double>& xx, double* v) { *v = f(xx.data(), n, user); return 0; };
-    std::vector<double> xv(x, x + n), nd(n, ndeps), lo(n, -HUGE_VAL), up(n, HUGE_VAL), h;
-    if (lower) lo.assign(lower, lower + n);
-    if (upper) up.assign(upper, upper + n);
-    MCML_TRY(fd_hessian(obj, xv, nd, usebounds != 0, lo, up, &h));
+    const HookProblem p(n, x, lower, upper);
+    std::vector<double> nd(n, ndeps), h;
+    MCML_TRY(fd_hessian(hook_objective(f, n, user), p.x, nd, usebounds != 0, p.lo, p.up, &h));
     for (int i = 0; i < n * n; ++i) H[i] = h[i];
     return MCML_OK;
 }

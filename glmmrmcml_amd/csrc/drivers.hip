@@ -4,7 +4,9 @@
 //   drivers mcml_full, mcmc_sample                src/mcml_full.cpp:41-148,314-338
 //   mcml_optim, mcml_simlik, mcml_hess, aic_mcml  src/mcml_optim.cpp:35-392
 // Host code; every objective evaluation runs on the device with u, Z, X, y
-// resident and returns one scalar.
+// resident and returns one scalar.  The MVN term has two forms: eval_mvn (one
+// theta) and eval_theta_round (a round of candidates).  The spaces the steps
+// search are parspace.h's; a round's values cross the ranks in comm.hip.
 //
 // Deliberate departures from the reference:
 //   D4  the importance ratio exp(ll+logl)/exp(denom) underflows to NaN for any
@@ -16,6 +18,7 @@
 #include "entry.h"
 #include "glm.h"
 #include "optim.h"
+#include "parspace.h"
 #include "theta_scale.h"
 #include "trace.h"
 #include <algorithm>
@@ -41,17 +44,69 @@ static int eval_loglik(Ctx& c, const double* beta, double var_par, double* ll)
 // A theta at which some block is not positive definite has no likelihood: the
 // reference would return NaN from its unchecked Cholesky; the optimiser is told
 // "infinitely bad" so that it backs away instead of aborting the fit.
+static const double LOGL_NO_VALUE = -HUGE_VAL;
+
+// tests (ctx.h theta_log): one MVN objective evaluation
+static void log_theta(Ctx& c, const double* theta, double logl)
+{
+    if (c.theta_log_on) { c.theta_log.insert(c.theta_log.end(), theta, theta + c.cov.npar); c.theta_log.push_back(logl); }
+}
+
+// the single-candidate form
 static int eval_mvn(Ctx& c, const double* theta, double* logl)
 {
     double s = 0;
     int rc = mvn_loglik_sum(c, theta, &s);
-    if (rc == MCML_ENOTPD) { *logl = -HUGE_VAL; return MCML_OK; }
+    if (rc == MCML_ENOTPD) { *logl = LOGL_NO_VALUE; return MCML_OK; }
     MCML_TRY(rc);
     double tot[2] = {s, (double)c.mcols};
     MCML_TRY(allreduce_host(c, tot, 2));
     *logl = tot[0] / tot[1];
-    if (c.theta_log_on) { c.theta_log.insert(c.theta_log.end(), theta, theta + c.cov.npar); c.theta_log.push_back(*logl); }
+    log_theta(c, theta, *logl);
     return MCML_OK;
+}
+
+// D is large dense blocks only (the geospatial configs): a round of candidate thetas is evaluated in ONE pass of the
+// factorisation's schedule (mvn.hip mvn_loglik_batch), so rounds of candidates are the schedule there
+static bool dense_only(const Ctx& c) { return c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0; }
+
+// Candidates that differ in a pure scale parameter only share a factorisation (theta_scale.h): where rounds of candidates
+// are the schedule and the specification proves a scale.  GLMMR_MCML_THETA_SCALE=0: one factorisation per candidate.
+static bool scale_active(const Ctx& c) { return dense_only(c) && theta_scale_any(c.theta_scale_p) && theta_scale_enabled(); }
+
+// One round of candidate thetas on the m columns of Us, the only place that does any of it: cand[j] -> the R coordinates of
+// candidate j as the optimiser holds them (theta or log theta: sp); logl[j] = sum_j / m, LOGL_NO_VALUE where rcs[j] is not
+// MCML_OK; returns the batch call's code, which rcs[j] may not show; (log) logs the candidates that have a value.  With a
+// memo (ts, alive for one theta-step: the samples are fixed in it) only the first member of every group not seen before is
+// factorised, the others are rescaled on the host; a round of ONE new candidate runs the single evaluation, leaves no entry.
+static int eval_theta_round(Ctx& c, const ParSpace& sp, ThetaScaleMemo* ts, const std::vector<const double*>& cand,
+                            const double* Us, int ldu, int m, bool log, std::vector<double>* logl, std::vector<int>* rcs)
+{
+    const int R = c.cov.npar, k = (int)cand.size();
+    std::vector<double> X((size_t)R * k), ths((size_t)R * k), sums(k, 0.0);
+    for (int j = 0; j < k; ++j) for (int i = 0; i < R; ++i) { X[(size_t)j * R + i] = cand[j][i]; ths[(size_t)j * R + i] = sp.theta_at(cand[j][i]); }
+    rcs->assign(k, 0);
+    int brc = MCML_OK;
+    const std::vector<int> reps = ts ? ts->plan(X.data(), R, k) : std::vector<int>();
+    const int nr = (int)reps.size();
+    if (!ts || (k == 1 && nr == 1)) {
+        c.theta_factorised += k;
+        brc = mvn_loglik_batch(c, ths.data(), k, Us, ldu, m, sums.data(), rcs->data());
+    } else {
+        std::vector<double> rth((size_t)R * nr), rsums(nr, 0.0), parts((size_t)2 * nr, 0.0);
+        std::vector<int> rrcs(nr, 0);
+        for (int q = 0; q < nr; ++q) memcpy(&rth[(size_t)q * R], &ths[(size_t)reps[q] * R], sizeof(double) * R);
+        if (nr > 0) brc = mvn_loglik_batch_parts(c, rth.data(), nr, k, Us, ldu, m, rsums.data(), rrcs.data(), parts.data());
+        if (brc != MCML_OK) rcs->assign(k, brc);
+        else {
+            c.theta_factorised += nr;
+            ts->finish(X.data(), R, k, reps, rsums.data(), parts.data(), rrcs.data(), c.cov.N, m, sums.data(), rcs->data());
+        }
+    }
+    logl->assign(k, LOGL_NO_VALUE);
+    for (int j = 0; j < k; ++j)
+        if (brc == MCML_OK && (*rcs)[j] == MCML_OK) { (*logl)[j] = sums[j] / m; if (log) log_theta(c, &ths[(size_t)j * R], (*logl)[j]); }
+    return brc;
 }
 
 // mcmloptim<T> (mcmloptim.h:16-369)
@@ -67,43 +122,10 @@ struct McmlOptim {
     McmlOptim(Ctx& ctx, const double* start, int trace_, int maxfun_, double var_par0)
         : c(ctx), P(ctx.P), R(ctx.cov.npar), trace(trace_), maxfun(maxfun_), model_var_par(var_par0)
     {
-        beta.assign(start, start + P);
-        theta.assign(start + P, start + P + R);
+        parse_start(start, P, R, glm_is_gaussian(c.flink), &beta, &theta, &sigma);
         cov_par_fix = theta;
-        sigma = glm_is_gaussian(c.flink) ? start[P + R] : 0;         // mcmloptim.h:30
     }
-
-    BobyqaOpts bopts() const { BobyqaOpts o; o.iprint = trace; if (maxfun > 0) o.maxfun = maxfun; return o; }
-
-    // Candidates that differ in a pure scale parameter only share a factorisation (theta_scale.h): where rounds of
-    // candidates are the schedule -- D of large dense blocks only -- and the specification proves a scale.
-    // GLMMR_MCML_THETA_SCALE=0: one factorisation per candidate.
-    bool scale_active() const
-    {
-        return c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0 && theta_scale_any(c.theta_scale_p) && theta_scale_enabled();
-    }
-
-    // The MVN sums of one round: k candidates, X their coordinates as the optimiser holds them (candidate j at
-    // X[j * R ..], the memo says whether log theta or theta), ths the thetas themselves (R x k).  With a memo, only the
-    // first member of every group not seen in this theta-step is factorised (mvn_loglik_batch_parts); the others are
-    // rescaled on the host.  A round of ONE new candidate runs the single evaluation as before and leaves no entry.
-    int eval_round(ThetaScaleMemo* ts, const double* X, const double* ths, int k, const double* Us, int ldu, int m,
-                   double* sums, int* rcs)
-    {
-        if (!ts) { c.theta_factorised += k; return mvn_loglik_batch(c, ths, k, Us, ldu, m, sums, rcs); }
-        const std::vector<int> reps = ts->plan(X, R, k);
-        const int nr = (int)reps.size();
-        if (k == 1 && nr == 1) { c.theta_factorised += 1; return mvn_loglik_batch(c, ths, 1, Us, ldu, m, sums, rcs); }
-        std::vector<double> rth((size_t)R * nr), rsums(nr, 0.0), parts((size_t)2 * nr, 0.0);
-        std::vector<int> rrcs(nr, 0);
-        for (int q = 0; q < nr; ++q) memcpy(&rth[(size_t)q * R], ths + (size_t)reps[q] * R, sizeof(double) * R);
-        int brc = MCML_OK;
-        if (nr > 0) brc = mvn_loglik_batch_parts(c, rth.data(), nr, k, Us, ldu, m, rsums.data(), rrcs.data(), parts.data());
-        if (brc != MCML_OK) { for (int j = 0; j < k; ++j) rcs[j] = brc; return brc; }
-        c.theta_factorised += nr;
-        ts->finish(X, R, k, reps, rsums.data(), parts.data(), rrcs.data(), c.cov.N, m, sums, rcs);
-        return MCML_OK;
-    }
+    int result(double* b, double* t, double* s) const { std::copy(beta.begin(), beta.end(), b); std::copy(theta.begin(), theta.end(), t); *s = sigma; return MCML_OK; }
 
     // d_optim of a chain-sharded job (no reference counterpart: the reference is one process).  The
     // factorisation of D(theta) does not shard -- replicated, it was 43 % of a rank's step at 8 GPUs -- but the
@@ -120,63 +142,43 @@ struct McmlOptim {
         const int wr = comm_world(c), mall = c.mcols * wr;
         // one memo per rank whose share is evaluated here, alive for this theta-step only (the samples are fixed in it):
         // a rank groups inside its own share of a round, candidates are never re-dealt between ranks
-        std::vector<ThetaScaleMemo> memos(scale_active() ? wr : 0);
+        std::vector<ThetaScaleMemo> memos(scale_active(c) ? wr : 0);
         for (ThetaScaleMemo& ts : memos) ts.reset(c.theta_scale_p, true);
+        const ParSpace sp(0, R, false, true);
         batch_objective_fn fb = [&](const std::vector<std::vector<double>>& Zs, std::vector<double>* F) -> int {
             const int nc = (int)Zs.size();
             std::vector<double> vals(nc, 0.0);
-            const bool emu = c.world <= 1 && !c.comm && c.emu_world > 1;
             int first_rc = MCML_OK;
             // this rank's candidates of the round, factorised side by side (mvn.hip mvn_loglik_batch).  Rank emulation in
             // recording mode evaluates every rank's share here, one rank's share at a time -- exactly the batches the
             // ranks of the real job would run, so that the replay reproduces the recorded values to the bit
-            const int r_lo = (emu && c.emu_mode == 1) ? 0 : c.rank, r_hi = (emu && c.emu_mode == 1) ? wr : c.rank + 1;
-            for (int rr = r_lo; rr < r_hi; ++rr) {
-                std::vector<int> own;
-                for (int j = 0; j < nc; ++j) if ((j % wr) == rr) own.push_back(j);
-                if (own.empty()) continue;
-                std::vector<double> ths((size_t)R * own.size()), zs((size_t)R * own.size()), sums(own.size(), 0.0);
-                std::vector<int> rcs(own.size(), 0);
-                for (size_t q = 0; q < own.size(); ++q)
-                    for (int i = 0; i < R; ++i) { zs[q * R + i] = Zs[own[q]][i]; ths[q * R + i] = std::exp(Zs[own[q]][i]); }
-                const int brc = eval_round(memos.empty() ? nullptr : &memos[rr], zs.data(), ths.data(), (int)own.size(),
-                                           c.Uall.d(), c.Uall.ld, mall, sums.data(), rcs.data());
-                for (size_t q = 0; q < own.size(); ++q) {
-                    const int j = own[q];
+            const bool all_shares = comm_emulated(c) && c.emu_mode == 1;
+            for (int rr = all_shares ? 0 : c.rank; rr < (all_shares ? wr : c.rank + 1); ++rr) {
+                std::vector<const double*> cand;                 // candidates rr, rr + wr, ...
+                for (int j = rr; j < nc; j += wr) cand.push_back(Zs[j].data());
+                if (cand.empty()) continue;
+                std::vector<double> logl;
+                std::vector<int> rcs;
+                const int brc = eval_theta_round(c, sp, memos.empty() ? nullptr : &memos[rr], cand, c.Uall.d(), c.Uall.ld, mall,
+                                                 true, &logl, &rcs);
+                for (size_t q = 0; q < cand.size(); ++q) {
+                    const int j = rr + (int)q * wr;
                     const int rc = (rcs[q] == MCML_OK && brc != MCML_OK) ? brc : rcs[q];
-                    if (rc != MCML_OK && getenv("GLMMR_MCML_BOBYQA_TRACE")) fprintf(stderr, "theta-step: candidate %d (theta %.6g %.6g) rc %d brc %d: %s\n", j, ths[q * R], R > 1 ? ths[q * R + 1] : 0.0, rcs[q], brc, last_error());
-                    if (rc == MCML_ENOTPD) vals[j] = HUGE_VAL;               // as eval_mvn: infinitely bad, not an error
-                    else if (rc != MCML_OK) { vals[j] = NAN; if (first_rc == MCML_OK) first_rc = rc; }
-                    else vals[j] = -1 * (sums[q] / mall);
+                    if (rc != MCML_OK && getenv("GLMMR_MCML_BOBYQA_TRACE")) fprintf(stderr, "theta-step: candidate %d (theta %.6g %.6g) rc %d brc %d: %s\n", j, sp.theta_at(Zs[j][0]), R > 1 ? sp.theta_at(Zs[j][1]) : 0.0, rcs[q], brc, last_error());
+                    if (rc == MCML_OK || rc == MCML_ENOTPD) vals[j] = -1 * logl[q];     // no value: infinitely bad, not an error
+                    else { vals[j] = NAN; if (first_rc == MCML_OK) first_rc = rc; }
                     if (rr == c.rank) ++c.theta_evals_own;
-                    if (c.theta_log_on && rc == MCML_OK) { c.theta_log.insert(c.theta_log.end(), ths.begin() + q * R, ths.begin() + (q + 1) * R); c.theta_log.push_back(sums[q] / mall); }
                 }
             }
             c.theta_rounds += 1; c.theta_evals_all += nc;
-            if (!emu) MCML_TRY(allreduce_host(c, vals.data(), nc));      // every slot is zero on all ranks but its owner
-            else if (c.emu_mode == 1) c.emu_trace.push_back(vals);
-            else {
-                MCML_REQUIRE(c.emu_pos < c.emu_trace.size() && (int)c.emu_trace[c.emu_pos].size() == nc,
-                             "rank emulation: replay ran past its record (round %zu)", c.emu_pos);
-                const std::vector<double>& rec = c.emu_trace[c.emu_pos++];
-                for (int j = 0; j < nc; ++j) {
-                    if ((j % wr) == c.rank) MCML_REQUIRE(vals[j] == rec[j] || (vals[j] != vals[j]), "rank emulation: replayed value differs from the recorded one (%.17g vs %.17g)", vals[j], rec[j]);
-                    else vals[j] = rec[j];
-                }
-            }
+            MCML_TRY(exchange_round(c, vals));
             if (first_rc != MCML_OK) return first_rc;
             for (double v : vals)         // a rank that failed put NaN in its slot: every rank stops here, together
                 if (v != v) { set_error("theta-step: a rank failed to evaluate its candidate"); return MCML_EHIP; }
             *F = vals;
             return MCML_OK; };
-        std::vector<double> z(R), lo(R, std::log(1e-6)), up(R, HUGE_VAL);
-        for (int i = 0; i < R; ++i) z[i] = std::log(std::max(theta[i], 1e-6));
-        BobyqaOpts o = bopts();
-        o.rhobeg = 0.25; o.rhoend = 1e-7;
-        BobyqaResult r;
-        MCML_TRY(bobyqa_batch(fb, z, lo, up, o, width, &r));
-        for (int i = 0; i < R; ++i) theta[i] = std::exp(r.x[i]);
-        return MCML_OK;
+        BobyqaOpts o = bopts(trace, maxfun); o.rhobeg = 0.25; o.rhoend = 1e-7;
+        return sp.minimise(fb, o, width, &beta, &theta, &sigma);
     }
 
     // d_optim (mcmloptim.h:56-68), D_likelihood (likelihood.h:40-45)
@@ -184,39 +186,26 @@ struct McmlOptim {
     {
         static const bool shard = !(getenv("GLMMR_MCML_THETA_SHARD") && !strcmp(getenv("GLMMR_MCML_THETA_SHARD"), "0"));
         const int wr = comm_world(c);
-        // candidates per rank and round.  A model whose D is large dense blocks only (the geospatial configs) evaluates
-        // a round's candidates in ONE pass of the factorisation's schedule (mvn.hip mvn_loglik_batch): there the batch
-        // schedule is the default even for a single process, 8 candidates per round (batch_width());
-        // glmmr_mcml_ext.theta_batch wins, 1 = the reference's sequential BOBYQA.
+        // candidates per rank and round.  For a dense-only model (dense_only()) the batch schedule is the default even
+        // for a single process, 8 candidates per round (batch_width()); glmmr_mcml_ext.theta_batch wins, 1 = the
+        // reference's sequential BOBYQA.
         // a sharded job: rounds of about eight candidates in all -- 8 / world per rank for a dense-block model (at 2 ranks
         // four candidates per rank factorised side by side: 6 rounds of 8.7 ms instead of 20 of 3.6 ms), one otherwise
-        const bool dense_only = c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0;
-        const int k = wr > 1 ? (theta_batch > 0 ? theta_batch : dense_only ? std::max(1, 8 / wr) : 1) : batch_width();
+        const int k = wr > 1 ? (theta_batch > 0 ? theta_batch : dense_only(c) ? std::max(1, 8 / wr) : 1) : batch_width();
         if ((wr > 1 && shard) || k > 1) return d_optim_sharded(wr * std::max(1, k));
         objective_fn f = [&](const std::vector<double>& par, double* v) {
             double logl; MCML_TRY(eval_mvn(c, par.data(), &logl)); *v = -1 * logl; return (int)MCML_OK; };
-        std::vector<double> lo(R, 1e-6), up(R, HUGE_VAL);
-        BobyqaResult r;
-        MCML_TRY(bobyqa(f, theta, lo, up, bopts(), &r));
-        theta = r.x;
-        return MCML_OK;
+        return ParSpace(0, R, false).minimise(f, bopts(trace, maxfun), 0, &beta, &theta, &sigma);
     }
 
     // l_optim (mcmloptim.h:71-88), L_likelihood (likelihood.h:57-64)
     int l_optim()
     {
         if (c.flink == 12) { set_error("l_optim: beta family is not built (reference reads par[P] out of range, defect D8)"); return MCML_EUNSUPPORTED; }
-        const bool g = glm_is_gaussian(c.flink);
         objective_fn f = [&](const std::vector<double>& par, double* v) {
             model_var_par = glm_has_var_par(c.flink) ? par[P] : 0.0;   // fix_var_ = false, fix_var_par_ = 0
             double ll; MCML_TRY(eval_loglik(c, par.data(), model_var_par, &ll)); *v = -1 * ll; return (int)MCML_OK; };
-        std::vector<double> x = beta, lo(P, -HUGE_VAL), up(P, HUGE_VAL);
-        if (g) { x.push_back(sigma); lo.push_back(0.0); up.push_back(HUGE_VAL); }
-        BobyqaResult r;
-        MCML_TRY(bobyqa(f, x, lo, up, bopts(), &r));
-        beta.assign(r.x.begin(), r.x.begin() + P);
-        if (g) sigma = r.x[P];
-        return MCML_OK;
+        return ParSpace(P, 0, glm_is_gaussian(c.flink)).minimise(f, bopts(trace, maxfun), 0, &beta, &theta, &sigma);
     }
 
     // mcnr (mcmloptim.h:198-236)
@@ -261,7 +250,7 @@ struct McmlOptim {
         if (theta_batch > 0) return theta_batch;
         static const int envk = getenv("GLMMR_MCML_THETA_BATCH") ? atoi(getenv("GLMMR_MCML_THETA_BATCH")) : 0;
         if (envk > 0) return envk;
-        return (c.maxdim_large > 0 && c.n_small == 0 && c.n_diag_rows == 0) ? 8 : 1;
+        return dense_only(c) ? 8 : 1;
     }
 
     // f_optim on the batch schedule (single process, dense-block models): a round's candidates (beta, log theta[, sigma])
@@ -274,35 +263,26 @@ struct McmlOptim {
     {
         const double fix_var_par = sigma;
         ThetaScaleMemo memo;                                     // this call's: the samples are fixed in it
-        const bool scale = scale_active();
+        const bool scale = scale_active(c);
         if (scale) memo.reset(c.theta_scale_p, true);
+        const ParSpace sp(P, R, false, true);
         batch_objective_fn fb = [&](const std::vector<std::vector<double>>& Zs, std::vector<double>* F) -> int {
             const int nc = (int)Zs.size();
-            std::vector<double> ths((size_t)R * nc), zs((size_t)R * nc), sums(nc, 0.0);
-            std::vector<int> rcs(nc, 0);
-            for (int j = 0; j < nc; ++j) for (int i = 0; i < R; ++i) { zs[(size_t)j * R + i] = Zs[j][P + i]; ths[(size_t)j * R + i] = std::exp(Zs[j][P + i]); }
-            MCML_TRY(eval_round(scale ? &memo : nullptr, zs.data(), ths.data(), nc, c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
-            if (c.theta_log_on)
-                for (int j = 0; j < nc; ++j) if (rcs[j] == MCML_OK) { c.theta_log.insert(c.theta_log.end(), ths.begin() + (size_t)j * R, ths.begin() + (size_t)(j + 1) * R); c.theta_log.push_back(sums[j] / c.mcols); }
+            std::vector<const double*> cand;
+            for (const std::vector<double>& z : Zs) cand.push_back(z.data() + P);
+            std::vector<double> logl;
+            std::vector<int> rcs;
+            MCML_TRY(eval_theta_round(c, sp, scale ? &memo : nullptr, cand, c.U.d(), c.U.ld, c.mcols, true, &logl, &rcs));
             F->assign(nc, 0.0);
             for (int j = 0; j < nc; ++j) {
                 model_var_par = fix_var_par;
                 double ll = 0;
                 MCML_TRY(eval_loglik(c, Zs[j].data(), model_var_par, &ll));
-                const double logl = rcs[j] == MCML_OK ? sums[j] / c.mcols : -HUGE_VAL;
-                (*F)[j] = -1.0 * (ll + logl - denomD);
+                (*F)[j] = -1.0 * (ll + logl[j] - denomD);
             }
             return MCML_OK; };
-        std::vector<double> x = beta, lo(P, -HUGE_VAL), up;
-        for (int i = 0; i < R; ++i) { x.push_back(std::log(std::max(theta[i], 1e-6))); lo.push_back(std::log(1e-6)); }
-        up.assign(x.size(), HUGE_VAL);
-        BobyqaOpts o = bopts();
-        o.rhobeg = 0.25; o.rhoend = 1e-7;
-        BobyqaResult r;
-        MCML_TRY(bobyqa_batch(fb, x, lo, up, o, width, &r));
-        beta.assign(r.x.begin(), r.x.begin() + P);
-        for (int i = 0; i < R; ++i) theta[i] = std::exp(r.x[P + i]);
-        return MCML_OK;
+        BobyqaOpts o = bopts(trace, maxfun); o.rhobeg = 0.25; o.rhoend = 1e-7;
+        return sp.minimise(fb, o, width, &beta, &theta, &sigma);
     }
 
     // f_optim (mcmloptim.h:91-113)
@@ -313,22 +293,13 @@ struct McmlOptim {
         MCML_TRY(eval_mvn(c, cov_par_fix.data(), &denomD));      // constant in the parameters
         if (comm_world(c) == 1 && batch_width() > 1) return f_optim_batch(batch_width(), denomD);
         objective_fn f = make_F(true, sigma, denomD);
-        std::vector<double> x = beta, lo(P, -HUGE_VAL), up;
-        for (int i = 0; i < R; ++i) { x.push_back(theta[i]); lo.push_back(1e-6); }
-        if (g) { x.push_back(sigma); lo.push_back(0.0); }
-        up.assign(x.size(), HUGE_VAL);
         // 2n + 1 interpolation points, not the n + 2 the other steps take over from minqa: in the P + R dimensions of this
         // objective, whose curvatures differ by a factor of a hundred and more, a model on n + 2 points is all but linear --
         // the run crept along the weak directions in steps of its final radius and stopped 2e-6 to 4e-6 from the optimum
         // after 350 to 490 evaluations, where 2n + 1 points end within 4e-7 after 110 to 190
-        BobyqaOpts o = bopts();
-        o.npt = 2 * (int)x.size() + 1;
-        BobyqaResult r;
-        MCML_TRY(bobyqa(f, x, lo, up, o, &r));
-        beta.assign(r.x.begin(), r.x.begin() + P);
-        theta.assign(r.x.begin() + P, r.x.begin() + P + R);
-        if (g) sigma = r.x[P + R];
-        return MCML_OK;
+        BobyqaOpts o = bopts(trace, maxfun);
+        o.npt = 2 * (P + R + (g ? 1 : 0)) + 1;
+        return ParSpace(P, R, g).minimise(f, o, 0, &beta, &theta, &sigma);
     }
 
     // f_hess (mcmloptim.h:333-355)
@@ -337,8 +308,9 @@ struct McmlOptim {
         auto memo = std::make_shared<ThetaMemo>();
         objective_fn f = make_F(false, sigma, 0.0, true, memo);
         const int nv = P + R;
-        std::vector<double> x = beta, lo(P, -HUGE_VAL), up(nv, HUGE_VAL), nd(nv, tol), h;
-        for (int i = 0; i < R; ++i) { x.push_back(theta[i]); lo.push_back(1e-6); }
+        const ParSpace sp(P, R, false);
+        const ParSpace::Point p = sp.pack(beta, theta, sigma);
+        std::vector<double> nd(nv, tol), h;
         // The points of the finite differences do not depend on the values: a dry pass lists the thetas they will ask
         // for, and (single process) those are factorised side by side, a round at a time, before the real pass runs
         if (comm_world(c) == 1 && c.maxdim_large > 0) {
@@ -348,21 +320,19 @@ struct McmlOptim {
                 if (std::find(want.begin(), want.end(), th) == want.end()) want.push_back(th);
                 *v = 0.0; return (int)MCML_OK; };
             std::vector<double> hdry;
-            MCML_TRY(fd_hessian(dry, x, nd, true, lo, up, &hdry));
-            std::vector<double> ths((size_t)R * want.size()), sums(want.size(), 0.0);
-            std::vector<int> rcs(want.size(), 0);
-            for (size_t q = 0; q < want.size(); ++q) for (int i = 0; i < R; ++i) ths[q * R + i] = want[q][i];
+            MCML_TRY(fd_hessian(dry, p.x, nd, true, p.lower, p.upper, &hdry));
+            std::vector<const double*> cand;
+            for (const std::vector<double>& th : want) cand.push_back(th.data());
             // the points move one or two coordinates at a time: those that differ in a scale parameter only share a matrix
             ThetaScaleMemo ts;
-            const bool scale = scale_active();
+            const bool scale = scale_active(c);
             if (scale) ts.reset(c.theta_scale_p, false);         // these coordinates are theta itself
-            MCML_TRY(eval_round(scale ? &ts : nullptr, ths.data(), ths.data(), (int)want.size(), c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
-            if (c.theta_log_on)
-                for (size_t q = 0; q < want.size(); ++q) if (rcs[q] == MCML_OK) { c.theta_log.insert(c.theta_log.end(), ths.begin() + q * R, ths.begin() + (q + 1) * R); c.theta_log.push_back(sums[q] / c.mcols); }
-            for (size_t q = 0; q < want.size(); ++q)
-                (*memo)[want[q]] = rcs[q] == MCML_OK ? sums[q] / c.mcols : -HUGE_VAL;       // as eval_mvn
+            std::vector<double> logl;
+            std::vector<int> rcs;
+            MCML_TRY(eval_theta_round(c, sp, scale ? &ts : nullptr, cand, c.U.d(), c.U.ld, c.mcols, true, &logl, &rcs));
+            for (size_t q = 0; q < want.size(); ++q) (*memo)[want[q]] = logl[q];
         }
-        MCML_TRY(fd_hessian(f, x, nd, true, lo, up, &h));
+        MCML_TRY(fd_hessian(f, p.x, nd, true, p.lower, p.upper, &h));
         memcpy(H, h.data(), sizeof(double) * (size_t)nv * nv);
         return MCML_OK;
     }
@@ -383,10 +353,7 @@ int drv_optim(Ctx& c, const double* start, int nstart, int trace, int mcnr, cons
     }
     PhaseRange r("mcml:theta-step");
     MCML_TRY(mc.d_optim());
-    memcpy(beta, mc.beta.data(), sizeof(double) * P);
-    memcpy(theta, mc.theta.data(), sizeof(double) * R);
-    *sigma = mc.sigma;
-    return MCML_OK;
+    return mc.result(beta, theta, sigma);
 }
 
 int drv_simlik(Ctx& c, const double* start, int nstart, int trace, const glmmr_mcml_ext* e, double* beta,
@@ -398,10 +365,7 @@ int drv_simlik(Ctx& c, const double* start, int nstart, int trace, const glmmr_m
     McmlOptim mc(c, start, trace, e ? e->maxfun : 0, 1.0);
     mc.theta_batch = e ? e->theta_batch : 0;
     MCML_TRY(mc.f_optim());
-    memcpy(beta, mc.beta.data(), sizeof(double) * P);
-    memcpy(theta, mc.theta.data(), sizeof(double) * R);
-    *sigma = mc.sigma;
-    return MCML_OK;
+    return mc.result(beta, theta, sigma);
 }
 
 int drv_hess(Ctx& c, const double* start, int nstart, double tol, int trace, double* H)
@@ -419,15 +383,16 @@ int drv_theta_round(Ctx& c, const double* thetas, int k, double* out)
 {
     MCML_REQUIRE(thetas && out && k >= 1 && k <= 64, "theta_round: bad argument");
     MCML_REQUIRE(c.mcols > 0 && c.U.d(), "theta_round: no samples set");
-    const std::vector<double> start((size_t)c.P + c.cov.npar + 1, 0.0);
-    McmlOptim mc(c, start.data(), 0, 0, 1.0);
     ThetaScaleMemo ts;
-    const bool scale = mc.scale_active();
+    const bool scale = scale_active(c);
     if (scale) ts.reset(c.theta_scale_p, false);
-    std::vector<double> sums(k, 0.0);
-    std::vector<int> rcs(k, 0);
-    MCML_TRY(mc.eval_round(scale ? &ts : nullptr, thetas, thetas, k, c.U.d(), c.U.ld, c.mcols, sums.data(), rcs.data()));
-    for (int j = 0; j < k; ++j) out[j] = rcs[j] == MCML_OK ? sums[j] / c.mcols : NAN;
+    std::vector<const double*> cand;
+    for (int j = 0; j < k; ++j) cand.push_back(thetas + (size_t)j * c.cov.npar);
+    std::vector<double> logl;
+    std::vector<int> rcs;
+    MCML_TRY(eval_theta_round(c, ParSpace(0, c.cov.npar, false), scale ? &ts : nullptr, cand, c.U.d(), c.U.ld, c.mcols, false,
+                              &logl, &rcs));
+    for (int j = 0; j < k; ++j) out[j] = rcs[j] == MCML_OK ? logl[j] : NAN;
     return MCML_OK;
 }
 

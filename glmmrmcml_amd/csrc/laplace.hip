@@ -25,6 +25,7 @@
 #include "component.h"
 #include "glm.h"
 #include "optim.h"
+#include "parspace.h"
 #include "host_linalg.h"
 #include "reduce.h"
 #include "vecops.h"
@@ -182,10 +183,8 @@ struct LaFit {
 
     int init(const double* start)
     {
-        beta.assign(start, start + P);
-        theta.assign(start + P, start + P + R);
+        parse_start(start, P, R, glm_is_gaussian(flink), &beta, &theta, &sigma);
         theta_model = theta;
-        sigma = glm_is_gaussian(flink) ? start[P + R] : 0;         // mcmloptim.h:30
         var_par = 1.0;
         hv.assign(Q, 0.0);
         MCML_TRY(v.ensure(sizeof(double) * (size_t)(Q + 64)));
@@ -372,9 +371,7 @@ struct LaFit {
         return obj_theta_tail(par.data() + P, val);
     }
 
-    BobyqaOpts bopts() const { BobyqaOpts o; o.iprint = trace; if (maxfun > 0) o.maxfun = maxfun; return o; }
-
-    // mcmloptim.h:116-129
+    // mcmloptim.h:116-129: the (beta, v) space is all free
     int la_optim()
     {
         std::vector<double> x(beta);
@@ -382,49 +379,38 @@ struct LaFit {
         std::vector<double> lo(x.size(), -HUGE_VAL), up(x.size(), HUGE_VAL);
         objective_fn f = [&](const std::vector<double>& par, double* val) { return obj_bv(par, val); };
         BobyqaResult r;
-        MCML_TRY(bobyqa(f, x, lo, up, bopts(), &r));
+        MCML_TRY(bobyqa(f, x, lo, up, bopts(trace, maxfun), &r));
         beta.assign(r.x.begin(), r.x.begin() + P);
         MCML_TRY(set_v(r.x.data() + P));
+        return MCML_OK;
+    }
+    // bobyqa over a space (parspace.h); the model is left at the optimum
+    int minimise(const objective_fn& f, const ParSpace& sp)
+    {
+        MCML_TRY(sp.minimise(f, bopts(trace, maxfun), 0, &beta, &theta, &sigma));
+        if (sp.has_sigma) var_par = sigma;
         return MCML_OK;
     }
     // mcmloptim.h:131-151
     int la_optim_cov()
     {
-        std::vector<double> x(theta), lo(R, 1e-6), up;
-        if (glm_has_var_par(flink)) { x.push_back(sigma); lo.push_back(0.0); }
-        up.assign(x.size(), HUGE_VAL);
         objective_fn f = [&](const std::vector<double>& par, double* val) { return obj_cov(par, val); };
-        BobyqaResult r;
-        MCML_TRY(bobyqa(f, x, lo, up, bopts(), &r));
-        theta.assign(r.x.begin(), r.x.begin() + R);
-        if (glm_has_var_par(flink)) { sigma = r.x[R]; var_par = sigma; }   // model left at the optimum
-        return MCML_OK;
+        return minimise(f, ParSpace(0, R, glm_has_var_par(flink)));
     }
     // mcmloptim.h:153-178
     int la_optim_bcov()
     {
-        std::vector<double> x(beta), lo(P, -HUGE_VAL), up;
-        for (int i = 0; i < R; ++i) { x.push_back(theta[i]); lo.push_back(1e-6); }
-        if (glm_is_gaussian(flink)) { x.push_back(sigma); lo.push_back(0.0); }
-        up.assign(x.size(), HUGE_VAL);
         objective_fn f = [&](const std::vector<double>& par, double* val) { return obj_btheta(par, val); };
-        BobyqaResult r;
-        MCML_TRY(bobyqa(f, x, lo, up, bopts(), &r));
-        beta.assign(r.x.begin(), r.x.begin() + P);
-        theta.assign(r.x.begin() + P, r.x.begin() + P + R);
-        if (glm_is_gaussian(flink)) { sigma = r.x[P + R]; var_par = sigma; }
-        return MCML_OK;
+        return minimise(f, ParSpace(P, R, glm_is_gaussian(flink)));
     }
     // mcmloptim.h:180-195
     int hess_la(double tol, std::vector<double>* H)
     {
         if (flink == 12) { set_error("hess_la: the beta family is not built (the reference functor mis-sizes theta)"); return MCML_EUNSUPPORTED; }
-        std::vector<double> x(beta);
-        x.insert(x.end(), theta.begin(), theta.end());
-        if (glm_has_var_par(flink)) x.push_back(sigma);
-        std::vector<double> nd(x.size(), tol), none;
+        const ParSpace::Point p = ParSpace(P, R, glm_has_var_par(flink)).pack(beta, theta, sigma);
+        std::vector<double> nd(p.x.size(), tol);
         objective_fn f = [&](const std::vector<double>& par, double* val) { return obj_btheta(par, val); };
-        return fd_hessian(f, x, nd, false, none, none, H);
+        return fd_hessian(f, p.x, nd, false, p.lower, p.upper, H);      // without bounds, as the reference
     }
 
     // mcmloptim.h:238-293

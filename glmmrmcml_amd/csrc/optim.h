@@ -14,6 +14,12 @@
 // steps that maximise the outgoing point's Lagrange polynomial (ALTMOV's job),
 // Powell's rho / delta schedule.  Defaults follow minqa/rminqa: npt = min(n+2,
 // 2n), rhobeg = min(0.95, 0.2 max|x0|), rhoend = 1e-6 rhobeg, maxfun = 10000.
+//
+// Both entries run one class (optim.hip Bobyqa) on one objective type -- a batch of points; bobyqa()'s is a batch of
+// one -- and share its rules: the start (prepare), the rho schedule (next_rho), the delta update (next_delta), the
+// coordinate steps of the initial design (design_coord), and in front of it the GLMMR_MCML_BOBYQA_TRACE switch and the
+// embedding of a one-parameter problem in two dimensions (minimise).  The trajectories of both are pinned bit for bit
+// by tests/test_bobyqa_traces_cpu.py.  The search spaces the callers hand in are parspace.h's.
 #pragma once
 #include <functional>
 #include <vector>

@@ -82,12 +82,33 @@ static vec trust_step(const Quad& q, double delta, const vec& a, const vec& b, d
     return d;
 }
 
+// Powell's schedule: the rho that follows rho on the way down to rhoend
+static double next_rho(double rho, double rhoend)
+{
+    const double r = rho / rhoend;
+    return (r <= 16.0) ? rhoend : (r <= 250.0) ? std::sqrt(r) * rhoend : 0.1 * rho;
+}
+
+// the radius after a step of length dnorm at radius 2 radius_half, by the ratio of the actual to the predicted reduction
+static double next_delta(double ratio, double radius_half, double dnorm)
+{
+    if (ratio <= 0.1) return std::min(radius_half, dnorm);
+    return std::max(radius_half, ratio <= 0.7 ? dnorm : 2.0 * dnorm);
+}
+
+// one objective type for both schedules: the sequential entry's is a batch of one at a time
+static batch_objective_fn as_batch(const objective_fn& f)
+{
+    return [&f](const std::vector<vec>& X, vec* F) {
+        F->assign(X.size(), 0.0);
+        for (size_t i = 0; i < X.size(); ++i) MCML_TRY(f(X[i], &(*F)[i]));
+        return (int)MCML_OK; };
+}
+
 class Bobyqa {
 public:
-    Bobyqa(const objective_fn& f, const vec& x0, const vec& lo, const vec& up, const BobyqaOpts& o)
-        : f_(f), n_((int)x0.size()), lo_(lo), up_(up), o_(o), x0_(x0) {}
     Bobyqa(const batch_objective_fn& fb, const vec& x0, const vec& lo, const vec& up, const BobyqaOpts& o)
-        : f_(none_), fb_(&fb), n_((int)x0.size()), lo_(lo), up_(up), o_(o), x0_(x0) {}
+        : fb_(fb), n_((int)x0.size()), lo_(lo), up_(up), o_(o), x0_(x0) {}
 
     int run(BobyqaResult* res)
     {
@@ -95,56 +116,17 @@ public:
         npt_ = o_.npt > 0 ? o_.npt : std::min(n + 2, 2 * n);
         npt_ = std::max(npt_, std::min(n + 2, (n + 1) * (n + 2) / 2));
         npt_ = std::min(npt_, 2 * n + 1);
-        double xmax = 0; for (double v : x0_) xmax = std::max(xmax, std::fabs(v));
-        double rhobeg = o_.rhobeg > 0 ? o_.rhobeg : std::min(0.95, 0.2 * xmax);
-        if (!(rhobeg > 0)) rhobeg = 0.1;
-        for (int i = 0; i < n; ++i) {
-            double rng = up_[i] - lo_[i];
-            if (std::isfinite(rng)) { if (!(rng > 0)) { set_error("bobyqa: empty bound interval"); return MCML_EINVAL; } rhobeg = std::min(rhobeg, 0.5 * rng * 0.999); }
-        }
-        // BOBYQA moves a start that is closer than rhobeg to a bound onto that bound.  For the
-        // covariance parameters (lower bound 1e-6, mcmloptim.h:35-38) that means evaluating the
-        // MVN likelihood at a variance of 1e-12: an objective ~1e11 that wrecks the first models.
-        // When no rhobeg was asked for, keep an interior start interior instead: the default is
-        // also capped by half the distance to the nearest bound.  A coordinate that sits within
-        // 1e-3 of the nominal radius of a bound (e.g. a variance an earlier fit drove onto 1e-6, give
-        // or take round-off) IS on that bound: it is snapped there instead of shrinking the radius
-        // to nothing.
-        if (!(o_.rhobeg > 0)) {
-            const double near = 1e-3 * rhobeg;
-            for (int i = 0; i < n; ++i) {
-                double xi = std::min(std::max(x0_[i], lo_[i]), up_[i]);
-                const double dl = xi - lo_[i], du = up_[i] - xi;
-                if (std::isfinite(dl) && dl > 0) { if (dl < near) x0_[i] = lo_[i]; else rhobeg = std::min(rhobeg, 0.5 * dl); }
-                if (std::isfinite(du) && du > 0) { if (du < near) x0_[i] = up_[i]; else rhobeg = std::min(rhobeg, 0.5 * du); }
-            }
-        }
-        const double rhoend = o_.rhoend > 0 ? std::min(o_.rhoend, rhobeg) : 1e-6 * rhobeg;
-        // x0 is moved so that every coordinate is either on a bound or >= rhobeg from it (BOBYQA)
-        vec x = x0_;
-        for (int i = 0; i < n; ++i) {
-            x[i] = std::min(std::max(x[i], lo_[i]), up_[i]);
-            if (x[i] - lo_[i] < rhobeg && x[i] != lo_[i]) x[i] = (x[i] - lo_[i] < 0.5 * rhobeg) ? lo_[i] : lo_[i] + rhobeg;
-            if (up_[i] - x[i] < rhobeg && x[i] != up_[i]) x[i] = (up_[i] - x[i] < 0.5 * rhobeg) ? up_[i] : up_[i] - rhobeg;
-        }
-        nf_ = 0; rc_ = 0;
+        double rhobeg, rhoend; vec x;
+        MCML_TRY(prepare(rhobeg, rhoend, x));
         Y_.assign(npt_, x); F_.assign(npt_, 0.0);
         // initial points (PRELIM): x0, x0 +- rhobeg e_i
-        for (int k = 1; k < npt_; ++k) {
-            int i = (k - 1) % n; bool second = (k - 1) >= n;
-            double step = rhobeg;
-            if (!second) { if (up_[i] - x[i] < rhobeg * 0.999) step = -rhobeg; }
-            else { step = -rhobeg; if (x[i] - lo_[i] < rhobeg * 0.999) step = 2 * rhobeg; if (up_[i] - x[i] < rhobeg * 0.999) step = -2 * rhobeg; }
-            Y_[k][i] = std::min(std::max(x[i] + step, lo_[i]), up_[i]);
-        }
+        for (int k = 1; k < npt_; ++k) { const int i = (k - 1) % n; Y_[k][i] = design_coord(x, i, (k - 1) >= n, rhobeg); }
         // the initial design is this schedule's first round: the finite values of all of it count before any of its
         // points without a value is given one (as eval_batch does for a round)
         std::vector<char> nov(npt_, 0);
         for (int k = 0; k < npt_; ++k) { F_[k] = eval(Y_[k]); nov[k] = no_value_; if (rc_) return rc_; }
         for (int k = 0; k < npt_; ++k) if (nov[k]) F_[k] = no_value();
-        kopt_ = (int)(std::min_element(F_.begin(), F_.end()) - F_.begin());
-        q_.init(n); q_.c = 0; xb_ = Y_[kopt_];
-        if (!refit(true)) { set_error("bobyqa: initial interpolation set is degenerate"); return MCML_EINVAL; }
+        MCML_TRY(first_model());
 
         double rho = rhobeg, delta = rho;
         int ntrits = 0, nfsav = nf_;
@@ -157,8 +139,8 @@ public:
             if (nf_ >= o_.maxfun) { status = 1; break; }
             if (state == TRSTEP) {
                 move_base_to_opt();
-                vec a(n), b(n);
-                for (int i = 0; i < n; ++i) { a[i] = lo_[i] - xb_[i]; b[i] = up_[i] - xb_[i]; }
+                vec a, b;
+                box(a, b);
                 double crvmin = 0;
                 d = trust_step(q_, delta, a, b, &crvmin);
                 dnorm = std::min(delta, norm2(d));
@@ -174,21 +156,16 @@ public:
                 }
                 ++ntrits;
                 // evaluate the trial point
-                vec xnew(n);
-                for (int i = 0; i < n; ++i) xnew[i] = std::min(std::max(xb_[i] + d[i], lo_[i]), up_[i]);
-                for (int i = 0; i < n; ++i) d[i] = xnew[i] - xb_[i];
+                const vec xnew = from_base(d);
+                d = sub(xnew, xb_);
                 const double fopt = F_[kopt_];
                 const double vquad = q_.eval(d) - q_.c;
                 const double fnew = eval(xnew); if (rc_) return rc_;
                 const double diff = fnew - fopt - vquad;
                 diffc = diffb; diffb = diffa; diffa = std::fabs(diff);
                 if (dnorm > rho) nfsav = nf_;
-                if (!(vquad < 0.0)) { ratio = -1.0; }
-                else ratio = (fnew - fopt) / vquad;
-                const double hdelta = 0.5 * delta;
-                if (ratio <= 0.1) delta = std::min(hdelta, dnorm);
-                else if (ratio <= 0.7) delta = std::max(hdelta, dnorm);
-                else delta = std::max(hdelta, 2.0 * dnorm);
+                ratio = vquad < 0.0 ? (fnew - fopt) / vquad : -1.0;
+                delta = next_delta(ratio, 0.5 * delta, dnorm);
                 if (delta <= 1.5 * rho) delta = rho;
                 int knew = pick_replace(xnew, fnew < fopt, delta);
                 if (knew >= 0) { replace(knew, xnew, fnew); }
@@ -200,10 +177,7 @@ public:
             if (state == GEOM) {
                 move_base_to_opt();
                 int knew = -1; double dmax = distsq;
-                for (int k = 0; k < npt_; ++k) {
-                    double s = 0; for (int i = 0; i < n; ++i) { double t = Y_[k][i] - xb_[i]; s += t * t; }
-                    if (s > dmax) { dmax = s; knew = k; }
-                }
+                for (int k = 0; k < npt_; ++k) { const double s = dist2(Y_[k], xb_); if (s > dmax) { dmax = s; knew = k; } }
                 if (knew >= 0) {
                     const double dist = std::sqrt(dmax);
                     if (o_.iprint > 1) fprintf(stderr, "bobyqa geom: replace %d dist=%.3g ntrits=%d delta=%.3g rho=%.3g\n", knew, dist, ntrits, delta, rho);
@@ -213,8 +187,7 @@ public:
                     vec xnew;
                     if (!geometry_point(knew, adelt, &xnew)) { state = REDUCE; continue; }
                     const double fopt = F_[kopt_];
-                    vec dd(n); for (int i = 0; i < n; ++i) dd[i] = xnew[i] - xb_[i];
-                    const double vquad = q_.eval(dd) - q_.c;
+                    const double vquad = q_.eval(sub(xnew, xb_)) - q_.c;
                     const double fnew = eval(xnew); if (rc_) return rc_;
                     const double diff = fnew - fopt - vquad;
                     diffc = diffb; diffb = diffa; diffa = std::fabs(diff);
@@ -229,20 +202,15 @@ public:
             if (state == REDUCE) {
                 if (rho > rhoend) {
                     delta = 0.5 * rho;
-                    const double r = rho / rhoend;
-                    if (r <= 16.0) rho = rhoend;
-                    else if (r <= 250.0) rho = std::sqrt(r) * rhoend;
-                    else rho = 0.1 * rho;
+                    rho = next_rho(rho, rhoend);
                     delta = std::max(delta, rho);
                     ntrits = 0; nfsav = nf_;
                     if (o_.iprint > 0) fprintf(stderr, "bobyqa: rho -> %.3g  nf=%d  f=%.12g\n", rho, nf_, F_[kopt_]);
                     state = TRSTEP; continue;
                 }
                 if (ntrits == -1) {                    // one last evaluation at the short step
-                    vec xnew(n);
-                    for (int i = 0; i < n; ++i) xnew[i] = std::min(std::max(xb_[i] + d[i], lo_[i]), up_[i]);
-                    bool moved = false; for (int i = 0; i < n; ++i) if (xnew[i] != Y_[kopt_][i]) moved = true;
-                    if (moved && nf_ < o_.maxfun) {
+                    const vec xnew = from_base(d);
+                    if (xnew != Y_[kopt_] && nf_ < o_.maxfun) {
                         const double fnew = eval(xnew); if (rc_) return rc_;
                         if (fnew < F_[kopt_]) { Y_[kopt_] = xnew; F_[kopt_] = fnew; }
                     }
@@ -250,9 +218,7 @@ public:
                 state = DONE;
             }
         }
-        kopt_ = (int)(std::min_element(F_.begin(), F_.end()) - F_.begin());
-        res->x = Y_[kopt_]; res->fval = F_[kopt_]; res->nfev = nf_; res->status = status;
-        return MCML_OK;
+        return finish(res, status);
     }
 
     // ---------------------------------------------------------------- the batch schedule (optim.h)
@@ -263,50 +229,18 @@ public:
         const int nfull = (n + 1) * (n + 2) / 2;
         if (o_.npt > 0) npt_ = std::min(std::max(o_.npt, n + 2), nfull);
         else npt_ = (nfull <= std::max(W, 2 * n + 1)) ? nfull : 2 * n + 1;
-        // radius and start exactly as run() chooses them
-        double xmax = 0; for (double v : x0_) xmax = std::max(xmax, std::fabs(v));
-        double rhobeg = o_.rhobeg > 0 ? o_.rhobeg : std::min(0.95, 0.2 * xmax);
-        if (!(rhobeg > 0)) rhobeg = 0.1;
-        for (int i = 0; i < n; ++i) {
-            double rng = up_[i] - lo_[i];
-            if (std::isfinite(rng)) { if (!(rng > 0)) { set_error("bobyqa: empty bound interval"); return MCML_EINVAL; } rhobeg = std::min(rhobeg, 0.5 * rng * 0.999); }
-        }
-        if (!(o_.rhobeg > 0)) {
-            const double near = 1e-3 * rhobeg;
-            for (int i = 0; i < n; ++i) {
-                double xi = std::min(std::max(x0_[i], lo_[i]), up_[i]);
-                const double dl = xi - lo_[i], du = up_[i] - xi;
-                if (std::isfinite(dl) && dl > 0) { if (dl < near) x0_[i] = lo_[i]; else rhobeg = std::min(rhobeg, 0.5 * dl); }
-                if (std::isfinite(du) && du > 0) { if (du < near) x0_[i] = up_[i]; else rhobeg = std::min(rhobeg, 0.5 * du); }
-            }
-        }
-        const double rhoend = o_.rhoend > 0 ? std::min(o_.rhoend, rhobeg) : 1e-6 * rhobeg;
-        vec x = x0_;
-        for (int i = 0; i < n; ++i) {
-            x[i] = std::min(std::max(x[i], lo_[i]), up_[i]);
-            if (x[i] - lo_[i] < rhobeg && x[i] != lo_[i]) x[i] = (x[i] - lo_[i] < 0.5 * rhobeg) ? lo_[i] : lo_[i] + rhobeg;
-            if (up_[i] - x[i] < rhobeg && x[i] != up_[i]) x[i] = (up_[i] - x[i] < 0.5 * rhobeg) ? up_[i] : up_[i] - rhobeg;
-        }
-        nf_ = 0; rc_ = 0;
+        double rhobeg, rhoend; vec x;
+        MCML_TRY(prepare(rhobeg, rhoend, x));
         int rounds = 0;
-        auto clampv = [&](vec& y) { for (int i = 0; i < n; ++i) y[i] = std::min(std::max(y[i], lo_[i]), up_[i]); };
-        auto dist = [&](const vec& p, const vec& q) { double t = 0; for (int i = 0; i < n; ++i) { double e = p[i] - q[i]; t += e * e; } return std::sqrt(t); };
 
         // ---- initial design: x, x +- rhobeg e_i (run()'s points), the pair points of a full quadratic; a last round
         // that is not full also takes the opposite diagonals (they compete for the best point only)
         std::vector<vec> P0(1, x);
         vec s1(n, 0.0);
-        for (int i = 0; i < n; ++i) {
-            double step = rhobeg;
-            if (up_[i] - x[i] < rhobeg * 0.999) step = -rhobeg;
-            vec y = x; y[i] = std::min(std::max(x[i] + step, lo_[i]), up_[i]); s1[i] = y[i] - x[i];
-            P0.push_back(y);
-        }
-        for (int i = 0; i < n; ++i) {
-            double step = -rhobeg;
-            if (x[i] - lo_[i] < rhobeg * 0.999) step = 2 * rhobeg;
-            if (up_[i] - x[i] < rhobeg * 0.999) step = -2 * rhobeg;
-            vec y = x; y[i] = std::min(std::max(x[i] + step, lo_[i]), up_[i]);
+        for (int k = 0; k < 2 * n; ++k) {
+            const int i = k % n;
+            vec y = x; y[i] = design_coord(x, i, k >= n, rhobeg);
+            if (k < n) s1[i] = y[i] - x[i];
             P0.push_back(y);
         }
         for (int i = 0; i < n && (int)P0.size() < npt_; ++i)
@@ -334,9 +268,7 @@ public:
             return MCML_OK;
         }
         Y_.assign(P0.begin(), P0.begin() + npt_); F_.assign(F0.begin(), F0.begin() + npt_);
-        kopt_ = (int)(std::min_element(F_.begin(), F_.end()) - F_.begin());
-        q_.init(n); q_.c = 0; xb_ = Y_[kopt_];
-        if (!refit(true)) { set_error("bobyqa: initial interpolation set is degenerate"); return MCML_EINVAL; }
+        MCML_TRY(first_model());
         double rho = rhobeg, delta = rho;
         for (size_t k = npt_; k < P0.size(); ++k)
             if (F0[k] < F_[kopt_]) {
@@ -352,24 +284,19 @@ public:
             if (nf_ >= o_.maxfun) { status = 1; break; }
             move_base_to_opt();
             const int room = std::min(W, o_.maxfun - nf_);
-            vec a(n), b(n);
-            for (int i = 0; i < n; ++i) { a[i] = lo_[i] - xb_[i]; b[i] = up_[i] - xb_[i]; }
+            vec a, b;
+            box(a, b);
             vec d1 = trust_step(q_, delta, a, b, nullptr);
             const double dn1 = std::min(delta, norm2(d1));
             const bool short_step = dn1 < 0.5 * rho;
-            // the rho that follows this one (Powell's schedule; after a short step never larger than twice that step)
-            double rho_next = rho;
-            {
-                const double r = rho / rhoend;
-                rho_next = (r <= 16.0) ? rhoend : (r <= 250.0) ? std::sqrt(r) * rhoend : 0.1 * rho;
-                if (short_step) rho_next = std::max(rhoend, std::min(rho_next, std::max(2.0 * dn1, 1e-3 * rho)));
-            }
+            // the rho that follows this one (after a short step never larger than twice that step)
+            double rho_next = next_rho(rho, rhoend);
+            if (short_step) rho_next = std::max(rhoend, std::min(rho_next, std::max(2.0 * dn1, 1e-3 * rho)));
             const bool last_level = !(rho > rhoend);
             if (o_.iprint > 1) fprintf(stderr, "bobyqa_batch: round %d nf=%d f=%.12g rho=%.3g delta=%.3g dnorm=%.3g%s\n", rounds, nf_, F_[kopt_], rho, delta, dn1, short_step ? " (short)" : "");
             std::vector<Cand> cs;
             auto push_tr = [&](const vec& d, double radius, bool dedup) {
-                vec xn(n); for (int i = 0; i < n; ++i) xn[i] = std::min(std::max(xb_[i] + d[i], lo_[i]), up_[i]);
-                vec dd(n); for (int i = 0; i < n; ++i) dd[i] = xn[i] - xb_[i];
+                const vec xn = from_base(d), dd = sub(xn, xb_);
                 const double dn = norm2(dd);
                 if (!(dn > 1e-3 * rhoend)) return;
                 if (dedup) for (const Cand& c : cs) if (dist(c.x, xn) < 0.1 * rho) return;
@@ -434,9 +361,9 @@ public:
             if ((int)cs.size() < room && !cs.empty() && cs.back().kind == 0 && !(short_step && last_level)) {
                 const double rho_g = short_step ? rho_next : rho;
                 const double hst = short_step ? rho_next : std::max(rho, 0.5 * dn1);
-                vec xc(n); for (int i = 0; i < n; ++i) xc[i] = std::min(std::max(xb_[i] + d1[i], lo_[i]), up_[i]);
-                auto push_st = [&](const vec& y0) {
-                    vec y = y0; clampv(y);
+                const vec xc = from_base(d1);
+                auto push_st = [&](vec y) {
+                    clamp(y);
                     for (const Cand& c : cs) if (dist(c.x, y) < 0.25 * hst) return;
                     for (int k = 0; k < npt_; ++k) if (dist(Y_[k], y) < std::max(0.1 * rho_g, 0.25 * hst)) return;
                     cs.push_back(Cand{y, 2, -1, hst, 0.0, dist(y, xb_)});
@@ -473,7 +400,7 @@ public:
                             const vec oldx = Y_[knear]; const double oldf = F_[knear];
                             Y_[knear] = cs[i].x; F_[knear] = F[i];
                             if (!refit(true)) { Y_[knear] = oldx; F_[knear] = oldf; build_W(); }
-                            kopt_ = (int)(std::min_element(F_.begin(), F_.end()) - F_.begin());
+                            kopt_ = kbest();
                         }
                         continue;
                     }
@@ -485,10 +412,7 @@ public:
                     if (F[ibest] < fopt0) {
                         improved_tr = true;
                         const double ratio = cb.vquad < 0.0 ? (F[ibest] - fopt0) / cb.vquad : -1.0;
-                        const double h = 0.5 * cb.radius;
-                        if (ratio <= 0.1) delta = std::min(h, cb.dnorm);
-                        else if (ratio <= 0.7) delta = std::max(h, cb.dnorm);
-                        else delta = std::max(h, 2.0 * cb.dnorm);
+                        delta = next_delta(ratio, 0.5 * cb.radius, cb.dnorm);
                     } else delta = 0.5 * rmin;
                     if (delta <= 1.5 * rho) delta = rho;
                 }
@@ -506,15 +430,12 @@ public:
                 if (o_.iprint > 0) fprintf(stderr, "bobyqa_batch: rho -> %.3g  nf=%d rounds=%d f=%.12g\n", rho, nf_, rounds, F_[kopt_]);
             }
         }
-        kopt_ = (int)(std::min_element(F_.begin(), F_.end()) - F_.begin());
-        res->x = Y_[kopt_]; res->fval = F_[kopt_]; res->nfev = nf_; res->status = status; res->rounds = rounds;
-        return MCML_OK;
+        res->rounds = rounds;
+        return finish(res, status);
     }
 
 private:
-    objective_fn none_;
-    const objective_fn& f_;
-    const batch_objective_fn* fb_ = nullptr;
+    const batch_objective_fn& fb_;
     int n_, npt_ = 0, nf_ = 0, rc_ = 0, kopt_ = 0;
     vec lo_, up_;
     BobyqaOpts o_;
@@ -534,17 +455,83 @@ private:
     void note_finite(double v) { if (std::isfinite(v)) { fin_lo_ = std::min(fin_lo_, v); fin_hi_ = std::max(fin_hi_, v); } }
     double no_value() const { return (fin_hi_ >= fin_lo_) ? fin_hi_ + 10.0 * std::max(1.0, fin_hi_ - fin_lo_) : 1e30; }
 
-    double eval(const vec& x)
+    // ---- small vector rules, each written once
+    static vec sub(const vec& p, const vec& q) { vec r(p.size()); for (size_t i = 0; i < p.size(); ++i) r[i] = p[i] - q[i]; return r; }
+    static double dist2(const vec& p, const vec& q) { double t = 0; for (size_t i = 0; i < p.size(); ++i) { const double e = p[i] - q[i]; t += e * e; } return t; }
+    static double dist(const vec& p, const vec& q) { return std::sqrt(dist2(p, q)); }
+    double clamp(int i, double v) const { return std::min(std::max(v, lo_[i]), up_[i]); }
+    void clamp(vec& y) const { for (int i = 0; i < n_; ++i) y[i] = clamp(i, y[i]); }
+    vec from_base(const vec& d) const { vec y(n_); for (int i = 0; i < n_; ++i) y[i] = clamp(i, xb_[i] + d[i]); return y; }   // xb + d inside the bounds
+    void box(vec& a, vec& b) const { a = sub(lo_, xb_); b = sub(up_, xb_); }                                                 // the bounds on a step from xb
+    int kbest() const { return (int)(std::min_element(F_.begin(), F_.end()) - F_.begin()); }
+
+    // The start rule of both schedules: the radii, and x0 moved so that every coordinate is on a bound or >= rhobeg from it.
+    // BOBYQA moves a start that is closer than rhobeg to a bound onto that bound.  For the
+    // covariance parameters (lower bound 1e-6, mcmloptim.h:35-38) that means evaluating the
+    // MVN likelihood at a variance of 1e-12: an objective ~1e11 that wrecks the first models.
+    // When no rhobeg was asked for, keep an interior start interior instead: the default is
+    // also capped by half the distance to the nearest bound.  A coordinate that sits within
+    // 1e-3 of the nominal radius of a bound (e.g. a variance an earlier fit drove onto 1e-6, give
+    // or take round-off) IS on that bound: it is snapped there instead of shrinking the radius
+    // to nothing.
+    int prepare(double& rhobeg, double& rhoend, vec& x)
     {
-        double v = 0;
-        int rc;
-        if (fb_) {                      // batch mode: a batch of one (the rare rescue path)
-            std::vector<vec> X(1, x); vec F;
-            rc = (*fb_)(X, &F);
-            if (!rc) v = F.empty() ? HUGE_VAL : F[0];
-        } else rc = f_(x, &v);
+        const int n = n_;
+        double xmax = 0; for (double v : x0_) xmax = std::max(xmax, std::fabs(v));
+        rhobeg = o_.rhobeg > 0 ? o_.rhobeg : std::min(0.95, 0.2 * xmax);
+        if (!(rhobeg > 0)) rhobeg = 0.1;
+        for (int i = 0; i < n; ++i) {
+            double rng = up_[i] - lo_[i];
+            if (std::isfinite(rng)) { if (!(rng > 0)) { set_error("bobyqa: empty bound interval"); return MCML_EINVAL; } rhobeg = std::min(rhobeg, 0.5 * rng * 0.999); }
+        }
+        if (!(o_.rhobeg > 0)) {
+            const double near = 1e-3 * rhobeg;
+            for (int i = 0; i < n; ++i) {
+                const double xi = clamp(i, x0_[i]);
+                const double dl = xi - lo_[i], du = up_[i] - xi;
+                if (std::isfinite(dl) && dl > 0) { if (dl < near) x0_[i] = lo_[i]; else rhobeg = std::min(rhobeg, 0.5 * dl); }
+                if (std::isfinite(du) && du > 0) { if (du < near) x0_[i] = up_[i]; else rhobeg = std::min(rhobeg, 0.5 * du); }
+            }
+        }
+        rhoend = o_.rhoend > 0 ? std::min(o_.rhoend, rhobeg) : 1e-6 * rhobeg;
+        x = x0_; clamp(x);
+        for (int i = 0; i < n; ++i) {
+            if (x[i] - lo_[i] < rhobeg && x[i] != lo_[i]) x[i] = (x[i] - lo_[i] < 0.5 * rhobeg) ? lo_[i] : lo_[i] + rhobeg;
+            if (up_[i] - x[i] < rhobeg && x[i] != up_[i]) x[i] = (up_[i] - x[i] < 0.5 * rhobeg) ? up_[i] : up_[i] - rhobeg;
+        }
+        nf_ = 0; rc_ = 0;
+        return MCML_OK;
+    }
+
+    // coordinate i of the initial design's point along e_i (PRELIM): x_i + rhobeg, the second one opposite; inwards next to a bound
+    double design_coord(const vec& x, int i, bool second, double rhobeg) const
+    {
+        double step = rhobeg;
+        if (!second) { if (up_[i] - x[i] < rhobeg * 0.999) step = -rhobeg; }
+        else { step = -rhobeg; if (x[i] - lo_[i] < rhobeg * 0.999) step = 2 * rhobeg; if (up_[i] - x[i] < rhobeg * 0.999) step = -2 * rhobeg; }
+        return clamp(i, x[i] + step);
+    }
+
+    int first_model()                   // through Y_ / F_, about the best point
+    {
+        kopt_ = kbest(); q_.init(n_); q_.c = 0; xb_ = Y_[kopt_];
+        if (!refit(true)) { set_error("bobyqa: initial interpolation set is degenerate"); return MCML_EINVAL; }
+        return MCML_OK;
+    }
+    int finish(BobyqaResult* res, int status)
+    {
+        kopt_ = kbest();
+        res->x = Y_[kopt_]; res->fval = F_[kopt_]; res->nfev = nf_; res->status = status;
+        return MCML_OK;
+    }
+
+    double eval(const vec& x)           // a batch of one
+    {
+        vec F;
+        const int rc = fb_(std::vector<vec>(1, x), &F);
         ++nf_;
         if (rc) { rc_ = rc; return 0; }
+        const double v = F.empty() ? HUGE_VAL : F[0];
         note_finite(v);
         no_value_ = !std::isfinite(v);
         return no_value_ ? no_value() : v;
@@ -555,7 +542,7 @@ private:
     {
         F->assign(X.size(), 0.0);
         if (X.empty()) return true;
-        int rc = (*fb_)(X, F);
+        int rc = fb_(X, F);
         nf_ += (int)X.size();
         if (rc) { rc_ = rc; return false; }
         if (F->size() != X.size()) { rc_ = MCML_EINVAL; set_error("bobyqa_batch: objective returned %zu values for %zu points", F->size(), X.size()); return false; }
@@ -567,9 +554,10 @@ private:
 
     void move_base_to_opt()
     {
-        kopt_ = (int)(std::min_element(F_.begin(), F_.end()) - F_.begin());
-        vec d(n_); bool any = false;
-        for (int i = 0; i < n_; ++i) { d[i] = Y_[kopt_][i] - xb_[i]; if (d[i] != 0.0) any = true; }
+        kopt_ = kbest();
+        const vec d = sub(Y_[kopt_], xb_);
+        bool any = false;
+        for (double v : d) if (v != 0.0) any = true;
         if (any) { q_.shift(d); xb_ = Y_[kopt_]; build_W(); }
     }
 
@@ -578,7 +566,7 @@ private:
     {
         const int n = n_, m = npt_, N = m + n + 1;
         sc_ = 0;
-        for (int k = 0; k < m; ++k) { double s = 0; for (int i = 0; i < n; ++i) { double t = Y_[k][i] - xb_[i]; s += t * t; } sc_ = std::max(sc_, std::sqrt(s)); }
+        for (int k = 0; k < m; ++k) sc_ = std::max(sc_, dist(Y_[k], xb_));
         if (!(sc_ > 0)) return false;
         std::vector<double> S((size_t)n * m);
         for (int k = 0; k < m; ++k) for (int i = 0; i < n; ++i) S[i + (size_t)k * n] = (Y_[k][i] - xb_[i]) / sc_;
@@ -603,7 +591,7 @@ private:
         const int n = n_, m = npt_, N = m + n + 1;
         if (rebuild && !build_W()) return false;
         vec r(m);
-        for (int k = 0; k < m; ++k) { vec d(n); for (int i = 0; i < n; ++i) d[i] = Y_[k][i] - xb_[i]; r[k] = F_[k] - q_.eval(d); }
+        for (int k = 0; k < m; ++k) r[k] = F_[k] - q_.eval(sub(Y_[k], xb_));
         vec sol(N, 0.0);
         for (int a = 0; a < N; ++a) { double s = 0; for (int k = 0; k < m; ++k) s += Winv_[a + (size_t)k * N] * r[k]; sol[a] = s; }
         q_.c += sol[m];
@@ -636,23 +624,20 @@ private:
     // which point leaves when xnew enters: largest |l_t(xnew)| weighted by distance
     int pick_replace(const vec& xnew, bool improved, double delta)
     {
-        const int n = n_;
-        vec d(n); for (int i = 0; i < n; ++i) d[i] = xnew[i] - xb_[i];
-        int best = -1; double bw = 0;
+        const vec d = sub(xnew, xb_);
+        int knew = -1; double bw = 0;
         const double delsq = delta * delta;
         for (int t = 0; t < npt_; ++t) {
             if (t == kopt_ && !improved) continue;
             Quad l = lagrange(t);
             const double lv = l.eval(d);
-            double dist = 0;
-            const vec& ref = improved ? xnew : Y_[kopt_];
-            for (int i = 0; i < n; ++i) { double s = Y_[t][i] - ref[i]; dist += s * s; }
-            double w = std::max(1.0, (dist / delsq) * (dist / delsq));
+            const double dsq = dist2(Y_[t], improved ? xnew : Y_[kopt_]);
+            double w = std::max(1.0, (dsq / delsq) * (dsq / delsq));
             double sc = w * lv * lv;
-            if (sc > bw) { bw = sc; best = t; }
+            if (sc > bw) { bw = sc; knew = t; }
         }
-        if (best < 0 && improved) best = kopt_;
-        return best;
+        if (knew < 0 && improved) knew = kopt_;
+        return knew;
     }
 
     void replace(int knew, const vec& xnew, double fnew)
@@ -663,16 +648,18 @@ private:
             if (fnew < oldf) { reinit_around_best(); }
             else { Y_[knew] = oldx; F_[knew] = oldf; build_W(); }
         }
-        kopt_ = (int)(std::min_element(F_.begin(), F_.end()) - F_.begin());
+        kopt_ = kbest();
     }
 
-    // RESCUE's job: rebuild a well-poised set around the best point
+    // RESCUE's job: rebuild a well-poised set around the best point.  Its coordinate steps are not design_coord()'s: the
+    // radius is the set's own, and a step is turned round where the stepped-to point leaves the bounds, not where the
+    // centre is within 0.999 radius of one.
     void reinit_around_best()
     {
-        kopt_ = (int)(std::min_element(F_.begin(), F_.end()) - F_.begin());
+        kopt_ = kbest();
         vec x = Y_[kopt_]; double fx = F_[kopt_];
         double rad = 0;
-        for (int k = 0; k < npt_; ++k) { double s = 0; for (int i = 0; i < n_; ++i) { double t = Y_[k][i] - x[i]; s += t * t; } rad = std::max(rad, std::sqrt(s)); }
+        for (int k = 0; k < npt_; ++k) rad = std::max(rad, dist(Y_[k], x));
         if (!(rad > 0)) rad = 1e-3;
         rad = std::min(rad, 1.0);
         Y_[0] = x; F_[0] = fx;
@@ -682,7 +669,7 @@ private:
             double step = second ? -rad : rad;
             if (y[i] + step > up_[i]) step = -std::fabs(step) * (second ? 2 : 1);
             if (y[i] + step < lo_[i]) step = std::fabs(step) * (second ? 2 : 1);
-            y[i] = std::min(std::max(y[i] + step, lo_[i]), up_[i]);
+            y[i] = clamp(i, y[i] + step);
             Y_[k] = y; F_[k] = eval(y);
             if (rc_) return;
         }
@@ -695,25 +682,55 @@ private:
     {
         const int n = n_;
         Quad l = lagrange(knew);
-        vec a(n), b(n);
-        for (int i = 0; i < n; ++i) { a[i] = lo_[i] - xb_[i]; b[i] = up_[i] - xb_[i]; }
+        vec a, b;
+        box(a, b);
         Quad lneg = l; lneg.c = -l.c; for (auto& v : lneg.g) v = -v; for (auto& v : lneg.H) v = -v;
         vec d1 = trust_step(l, adelt, a, b, nullptr), d2 = trust_step(lneg, adelt, a, b, nullptr);
         double v1 = std::fabs(l.eval(d1)), v2 = std::fabs(l.eval(d2));
         vec best = v1 >= v2 ? d1 : d2; double bv = std::max(v1, v2);
         // also the straight line towards (and away from) the outgoing point, as ALTMOV tries
-        vec dir(n); double dn = 0; for (int i = 0; i < n; ++i) { dir[i] = Y_[knew][i] - xb_[i]; dn += dir[i] * dir[i]; }
-        dn = std::sqrt(dn);
+        const vec dir = sub(Y_[knew], xb_);
+        const double dn = norm2(dir);
         if (dn > 0) for (int sgn = -1; sgn <= 1; sgn += 2) {
             vec dd(n); for (int i = 0; i < n; ++i) dd[i] = std::min(std::max(sgn * adelt * dir[i] / dn, a[i]), b[i]);
             double v = std::fabs(l.eval(dd)); if (v > bv) { bv = v; best = dd; }
         }
         if (!(bv > 1e-12) || !(norm2(best) > 0)) return false;
-        out->resize(n);
-        for (int i = 0; i < n; ++i) (*out)[i] = std::min(std::max(xb_[i] + best[i], lo_[i]), up_[i]);
+        *out = from_base(best);
         return true;
     }
 };
+
+// What both entries share: the trace switch, the schedule by width (0 = bobyqa() itself; 1 = nothing to run side by side,
+// the sequential schedule with one point per exchange), and the embedding of ONE parameter in two dimensions -- BOBYQA
+// needs n >= 2 (npt in [n+2, (n+1)(n+2)/2] is empty for n = 1): f(x) + y^2 over y in [-1, 1].  *penalty = y^2 at the
+// result (0 without the embedding), which res->fval still contains: the two entries finish differently.
+static int minimise(const batch_objective_fn& f, const vec& x0, const vec& lower, const vec& upper, const BobyqaOpts& opts,
+                    int width, BobyqaResult* res, double* penalty)
+{
+    BobyqaOpts o = opts;
+    if (const char* t = getenv("GLMMR_MCML_BOBYQA_TRACE")) o.iprint = atoi(t);
+    auto schedule = [&](const batch_objective_fn& g, const vec& x, const vec& lo, const vec& up, BobyqaResult* r) {
+        Bobyqa b(g, x, lo, up, o);
+        if (width > 1) return b.run_batch(width, r);
+        const int rc = b.run(r);
+        if (width == 1) r->rounds = r->nfev;
+        return rc; };
+    *penalty = 0.0;
+    if (x0.size() > 1) return schedule(f, x0, lower, upper, res);
+    batch_objective_fn f2 = [&](const std::vector<vec>& X, vec* F) {
+        std::vector<vec> X1; for (const auto& x : X) X1.push_back(vec(1, x[0]));
+        int rc = f(X1, F);
+        if (!rc && F->size() == X.size()) for (size_t i = 0; i < X.size(); ++i) (*F)[i] += X[i][1] * X[i][1];
+        return rc; };
+    const vec x2{x0[0], 0.0}, l2{lower[0], -1.0}, u2{upper[0], 1.0};
+    if (!(o.rhobeg > 0)) { double a = std::fabs(x0[0]); o.rhobeg = std::min(0.95, 0.2 * a); if (!(o.rhobeg > 0)) o.rhobeg = 0.1; }
+    BobyqaResult r2;
+    MCML_TRY(schedule(f2, x2, l2, u2, &r2));
+    res->x.assign(1, r2.x[0]); res->fval = r2.fval; res->nfev = r2.nfev; res->status = r2.status; res->rounds = r2.rounds;
+    *penalty = r2.x[1] * r2.x[1];
+    return MCML_OK;
+}
 
 }  // namespace
 
@@ -721,56 +738,20 @@ int bobyqa(const objective_fn& f, const std::vector<double>& x0, const std::vect
            const std::vector<double>& upper, const BobyqaOpts& opts, BobyqaResult* res)
 {
     MCML_REQUIRE(res && !x0.empty() && lower.size() == x0.size() && upper.size() == x0.size(), "bobyqa: bad arguments");
-    if (x0.size() == 1) {
-        // BOBYQA needs n >= 2 (npt in [n+2, (n+1)(n+2)/2] is empty for n = 1): embed in two dimensions
-        objective_fn f2 = [&](const std::vector<double>& x, double* v) { std::vector<double> x1(1, x[0]); int rc = f(x1, v); if (!rc) *v += x[1] * x[1]; return rc; };
-        std::vector<double> x2{x0[0], 0.0}, l2{lower[0], -1.0}, u2{upper[0], 1.0};
-        BobyqaResult r2;
-        BobyqaOpts o2 = opts;
-        if (!(o2.rhobeg > 0)) { double a = std::fabs(x0[0]); o2.rhobeg = std::min(0.95, 0.2 * a); if (!(o2.rhobeg > 0)) o2.rhobeg = 0.1; }
-        Bobyqa b(f2, x2, l2, u2, o2);
-        int rc = b.run(&r2);
-        if (rc) return rc;
-        res->x.assign(1, r2.x[0]); res->nfev = r2.nfev; res->status = r2.status;
-        return f(res->x, &res->fval);
-    }
-    BobyqaOpts o = opts;
-    if (const char* t = getenv("GLMMR_MCML_BOBYQA_TRACE")) o.iprint = atoi(t);
-    Bobyqa b(f, x0, lower, upper, o);
-    return b.run(res);
+    double penalty;
+    MCML_TRY(minimise(as_batch(f), x0, lower, upper, opts, 0, res, &penalty));
+    // one parameter: the value at the result is the objective's own, evaluated once more (not counted in nfev)
+    return x0.size() == 1 ? f(res->x, &res->fval) : (int)MCML_OK;
 }
 
 int bobyqa_batch(const batch_objective_fn& f, const std::vector<double>& x0, const std::vector<double>& lower,
                  const std::vector<double>& upper, const BobyqaOpts& opts, int width, BobyqaResult* res)
 {
     MCML_REQUIRE(res && !x0.empty() && lower.size() == x0.size() && upper.size() == x0.size() && width >= 1, "bobyqa_batch: bad arguments");
-    BobyqaOpts o = opts;
-    if (const char* t = getenv("GLMMR_MCML_BOBYQA_TRACE")) o.iprint = atoi(t);
-    if (x0.size() == 1) {
-        // as bobyqa(): one parameter is embedded in two dimensions
-        batch_objective_fn f2 = [&](const std::vector<std::vector<double>>& X, std::vector<double>* F) {
-            std::vector<std::vector<double>> X1; for (const auto& x : X) X1.push_back(std::vector<double>(1, x[0]));
-            int rc = f(X1, F);
-            if (!rc && F->size() == X.size()) for (size_t i = 0; i < X.size(); ++i) (*F)[i] += X[i][1] * X[i][1];
-            return rc; };
-        std::vector<double> x2{x0[0], 0.0}, l2{lower[0], -1.0}, u2{upper[0], 1.0};
-        if (!(o.rhobeg > 0)) { double a = std::fabs(x0[0]); o.rhobeg = std::min(0.95, 0.2 * a); if (!(o.rhobeg > 0)) o.rhobeg = 0.1; }
-        BobyqaResult r2;
-        Bobyqa b(f2, x2, l2, u2, o);
-        int rc = width == 1 ? b.run(&r2) : b.run_batch(width, &r2);
-        if (width == 1) r2.rounds = r2.nfev;
-        if (rc) return rc;
-        res->x.assign(1, r2.x[0]); res->nfev = r2.nfev; res->status = r2.status; res->rounds = r2.rounds;
-        res->fval = r2.fval - r2.x[1] * r2.x[1];
-        return MCML_OK;
-    }
-    Bobyqa b(f, x0, lower, upper, o);
-    if (width == 1) {       // nothing to run side by side: the sequential schedule, one point per exchange
-        int rc = b.run(res);
-        res->rounds = res->nfev;
-        return rc;
-    }
-    return b.run_batch(width, res);
+    double penalty;
+    MCML_TRY(minimise(f, x0, lower, upper, opts, width, res, &penalty));
+    if (x0.size() == 1) res->fval = res->fval - penalty;     // one parameter: the model's value less the embedding's term
+    return MCML_OK;
 }
 
 // ---------------------------------------------------------------- finite differences
