@@ -1,4 +1,5 @@
-"""Loads the in-tree HIP library and gives every function of include/glmmr_mcml_c.h its prototype.  There is no CPU
+"""Loads the in-tree HIP library and gives every function of include/glmmr_mcml_c.h (and of the headers of the same
+directory it includes: glmmr_mcml_info.h) its prototype.  There is no CPU
 fallback: if the library (or the header the prototypes are read from) is missing, or no MI355X is visible when a compute
 entry point is called, the call fails loudly."""
 import ctypes as C
@@ -25,6 +26,17 @@ _RETURNS = {"int": C.c_int, "long long": C.c_longlong, "const char*": C.c_char_p
 _SCALARS = {"int": C.c_int, "double": C.c_double, "long long": C.c_longlong, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32}
 _CALLBACKS = ("glmmr_mcml_objective", "glmmr_mcml_batch_objective", "glmmr_mcml_parts_objective")
 _DECL = re.compile(r"(?<=[;{}]) ?([\w ]+?\*?) ?\b(glmmr_mcml_\w+) ?\(([^()]*)\) ?;")
+_INCLUDE = re.compile(r'^\s*#\s*include\s+"(glmmr_mcml_\w+\.h)"', re.M)
+
+
+def header_text():
+    """the public header followed by the text of each header of its directory it includes (one level: they include none)"""
+    with open(HEADER_PATH) as f:
+        text = f.read()
+    for name in _INCLUDE.findall(text):
+        with open(os.path.join(os.path.dirname(HEADER_PATH), name)) as f:
+            text += "\n" + f.read()
+    return text
 
 
 def prototypes(header):
@@ -58,10 +70,9 @@ def lib():
         if not os.path.exists(HEADER_PATH):
             raise ImportError("%s is missing: the prototypes of %s are read from it" % (HEADER_PATH, LIB_PATH))
         L = C.CDLL(LIB_PATH)
-        with open(HEADER_PATH) as f:
-            for name, (restype, argtypes) in prototypes(f.read()).items():
-                fn = getattr(L, name)
-                fn.restype, fn.argtypes = restype, argtypes
+        for name, (restype, argtypes) in prototypes(header_text()).items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 

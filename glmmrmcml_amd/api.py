@@ -98,6 +98,7 @@ class _Mode:
 _TRAJ = _Mode("trajectory", "step", "component")
 _DRAWS = _Mode("draws", "hmc", "exact", "exact_component")
 _LA_OP = _Mode("la_operator", "dense", "component", "component_wide")
+_INFO_OP = {None: 0, "dense": 1, "component": 2}            # glmmr_mcml_ctx_information's op; an unknown name is a KeyError
 
 
 def set_default_trajectory(mode):
@@ -559,6 +560,30 @@ class Context:
         keys = ("requested", "operator", "ncomp", "max_vars", "max_rows", "launches", "dense_bytes", "waves")
         return _plan(_lib.lib().glmmr_mcml_dbg_la_plan, C.c_longlong, keys, self._h, named=(_LA_OP, "requested", "operator"))
 
+    def information_matrix(self, beta, var_par, theta=None, operator=None):
+        """The GLS information of the fixed effects, X' (W^-1 + Z D Z')^-1 X (P x P), on the device (csrc/info.hip,
+        include/glmmr_mcml_info.h glmmr_mcml_ctx_information): the weights are dhdmu(X beta) times the family's scale in
+        var_par, with no random-effect term; y is not read.  theta = None: the resident L of the last update_L / set_L, the
+        context is left untouched; given: the context is left as update_L(theta) leaves it.  operator: None (the component
+        operator where the context runs the sparse one and no component has more than 128 variables, else the dense one),
+        "dense" or "component" (McmlError -2 where it does not apply).  McmlError -1 for a weight that is not finite, -3
+        for a failed pivot"""
+        beta = _f(beta).ravel()
+        if beta.size != self.P:
+            raise ValueError("beta must hold %d values" % self.P)
+        th = None if theta is None else _f(theta).ravel()
+        out = np.zeros((self.P, self.P), order="F")
+        _lib.check(_lib.lib().glmmr_mcml_ctx_information(self._h, _p(beta), float(var_par), _p(th), _INFO_OP[operator], _p(out),
+                                                         self.P))
+        return out
+
+    def information_plan(self):
+        """what the last information_matrix on this context was asked for and ran (test hook, include/glmmr_mcml_info.h
+        glmmr_mcml_dbg_information_plan): op 0 dense, 1 component (several components per wave), 2 component-wide; waves: per
+        component of the factor kernel, 0 (dense), 1 or 4"""
+        keys = ("requested", "op", "ncomp", "max_vars", "waves", "launches", "dense_bytes", "P")
+        return _plan(_lib.lib().glmmr_mcml_dbg_information_plan, C.c_longlong, keys, self._h)
+
     def mcml_optim(self, start, trace=0, mcnr=False, maxfun=0, theta_batch=0):
         start = _f(start).ravel(); R = self.npar()
         b = np.zeros(self.P); t = np.zeros(R); sg = C.c_double()
@@ -714,6 +739,20 @@ def mcml_la_nr(cov, data, eff_range, Z, X, y, family, link, start, usehess=False
     with _LA_OP.default(operator):
         return _la_call(_lib.lib().glmmr_mcml_la_nr, cov, data, eff_range, Z, X, y, family, link, start, usehess, tol,
                         verbose, trace, maxiter, maxfun)
+
+
+def information_matrix(cov, data, eff_range, Z, X, family, link, beta, theta, var_par=1.0, operator=None):
+    """Context.information_matrix on a context made for the call (glmmr_mcml_information): the P x P GLS information
+    X' (W^-1 + Z D(theta) Z')^-1 X at beta / var_par; beyond the reference's exports.  y is not read: zeros stand in for it"""
+    Z = _f(Z)
+    p, keep = _problem(cov, data, eff_range, Z, X, np.zeros(Z.shape[0]), family, link)
+    beta = _f(beta).ravel(); theta = _f(theta).ravel()
+    if beta.size != p.P:
+        raise ValueError("beta must hold %d values" % p.P)
+    out = np.zeros((p.P, p.P), order="F")
+    _lib.check(_lib.lib().glmmr_mcml_information(C.byref(p), _p(beta), _p(theta), theta.size, float(var_par),
+                                                 _INFO_OP[operator], _p(out), p.P))
+    return out
 
 
 def _sampler_args(Z, L, X, y, beta, family, link):

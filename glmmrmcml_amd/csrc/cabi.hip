@@ -336,6 +336,21 @@ extern "C" int glmmr_mcml_ctx_set_L(glmmr_mcml_ctx* h, const double* L, int ldl)
     return install_L(c);
 }
 
+// the GLS information of the fixed effects (info.hip).  theta: the context is first brought to where update_L(theta) leaves it
+extern "C" int glmmr_mcml_ctx_information(glmmr_mcml_ctx* h, const double* beta, double var_par, const double* theta, int op,
+                                          double* out, int ldo)
+{
+    MCML_REQUIRE(h && beta && out, "information: null argument");
+    Ctx& c = h->c;
+    MCML_HIP(hipSetDevice(c.device));
+    if (theta) {
+        MCML_REQUIRE(c.n > 0 && c.cov.npar > 0, "information: the context has no model / covariance");
+        MCML_TRY(mvn_gen_L(c, theta, true));
+        MCML_TRY(install_L(c));
+    }
+    return info_matrix(c, beta, var_par, op, out, ldo);
+}
+
 extern "C" int glmmr_mcml_ctx_hmc_sample(glmmr_mcml_ctx* h, const double* beta, double var_par,
                                          const glmmr_mcml_hmc_opts* opts, uint64_t seed, uint32_t iter_idx,
                                          const double* inj_init, const double* inj_mom, uint8_t* flags_out,
@@ -691,6 +706,17 @@ extern "C" int glmmr_mcml_la_nr(const glmmr_mcml_problem* prob, const double* st
     MCML_TRY(open_ctx(prob, ext, g));
     return glmmr_mcml_ctx_la(g.h, start, nstart, 1, usehess, tol, verbose, trace, maxiter, ext, beta, theta, sigma, se,
                              u, nullptr, nullptr);
+}
+
+extern "C" int glmmr_mcml_information(const glmmr_mcml_problem* prob, const double* beta, const double* theta, int ntheta,
+                                      double var_par, int op, double* out, int ldo)
+{
+    MCML_REQUIRE(prob && beta && theta && out, "information: null argument");
+    CtxGuard g;
+    MCML_TRY(open_ctx(prob, nullptr, g));
+    MCML_REQUIRE(ntheta >= g.h->c.cov.npar, "information: %d covariance parameters given, the covariance needs %d", ntheta,
+                 g.h->c.cov.npar);
+    return glmmr_mcml_ctx_information(g.h, beta, var_par, theta, op, out, ldo);
 }
 
 extern "C" int glmmr_mcml_mcmc_sample(const double* Z, const double* L, const double* X, const double* y, int n,

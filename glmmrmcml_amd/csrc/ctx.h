@@ -159,6 +159,16 @@ struct ExactCompState {
     double ms[5] = {0, 0, 0, 0, 0};     // factor + mean | draw kernel | transpose | L V | 0, of the last call
 };
 
+// the GLS information query (info.hip): beta, the reciprocal weights v, XV = diag(v) X, the right-hand sides / S (Q x P), the
+// Gram partials and the result with its two flags; the dense operator's M and ZLTW, the component operator's factors as
+// ExactCompState keeps them; kept between calls.  plan: what the last call did (glmmr_mcml_dbg_information_plan)
+struct InfoState {
+    DevBuf beta, v, bad, part, res, fac, fac_ptr, logdet;
+    DevMat XV, S, M, ZLTW;
+    long long fac_doubles = 0;          // 0: fac_ptr not uploaded yet
+    long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 struct Ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -176,6 +186,7 @@ struct Ctx {
                                 // 2 the same, and component by component where the sparse operator runs (hmc_exact_comp.h)
     ExactState exact;
     ExactCompState exact_comp;
+    InfoState info;
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT
     int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (component.hip); 2 the same up
                                 // to CP_WIDE_MAX_VARS variables per component, a wave or a workgroup each

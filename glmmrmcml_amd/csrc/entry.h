@@ -48,6 +48,12 @@ int drv_la_probe(Ctx& c, const double* start, int nstart, int kind, const double
 // ---- component.hip ----
 long long la_component_launch_count();
 
+// ---- info.hip ----
+// X' (W^-1 + Z D Z')^-1 X at beta / var_par with the context's resident L -> out (P x P, column-major, symmetric to the bit).
+// op: 0 the component operator where info_component_applicable, else the dense one; 1 dense; 2 component or MCML_EUNSUPPORTED
+bool info_component_applicable(const Ctx& c);
+int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out, int ldo);
+
 // the seed of a sampler run: the caller's, or one from std::random_device as the reference draws it (mhmcmc.h:55)
 inline uint64_t default_seed(const glmmr_mcml_ext* e)
 {

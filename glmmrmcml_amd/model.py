@@ -17,7 +17,9 @@ Differences from the R class, each deliberate:
     inverted and `fd_tol` is its step.
   * `mcml_simlik` is called without the non-existent `mcnr=` argument (defect D7).
   * `information_matrix()` lives in glmmrBase; its GLS form X' (W^-1 + Z D Z')^-1 X is restated from the
-    commented block of src/mcml_la.cpp:126-139 (INFERRED, unverifiable without glmmrBase).
+    commented block of src/mcml_la.cpp:126-139 (INFERRED, unverifiable without glmmrBase).  `MCML(..., information=)` and
+    `LA(..., information=)` say where it is computed: "host" (the default: numpy, from the backend's dense D) or "device"
+    (the backend's `information_matrix` export, the same definition in its Woodbury form; csrc/info.hip).
 """
 import math
 
@@ -216,8 +218,17 @@ class ModelMCML:
                 return names
         return ["cov%d" % (i + 1) for i in range(R)]
 
-    def information_matrix(self, theta_cov, beta, sigma):
-        """GLS information X' Sigma^-1 X, Sigma = W^-1 + Z D Z' (see module docstring; INFERRED)"""
+    def information_matrix(self, theta_cov, beta, sigma, on="host"):
+        """GLS information X' Sigma^-1 X, Sigma = W^-1 + Z D Z' (see module docstring; INFERRED).  on = "host": formed and
+        solved here in numpy from the backend's dense D; "device": the backend's `information_matrix` export computes the
+        same definition in its Woodbury form (csrc/info.hip) and nothing of size n x n is formed"""
+        if on == "device":
+            family = "gamma" if self.family == "Gamma" else self.family      # the exports' table is lower-case (mcmlmodel.h:83-85)
+            return np.asarray(self._be.information_matrix(*self._ddata(), self.Z, self.X, family, self.link,
+                                                          np.asarray(beta, float), np.asarray(theta_cov, float),
+                                                          var_par=float(sigma)))
+        if on != "host":
+            raise ValueError("information should be 'host' or 'device'")
         with self._be.Context(self.cov, self.data, self.eff_range) as ctx:
             D = ctx.gen_D(np.asarray(theta_cov, float))
         xb = self.X @ beta
@@ -246,7 +257,15 @@ class ModelMCML:
         return dict(par=list(names), est=est, SE=SE, lower=est - _Z975 * SE, upper=est + _Z975 * SE)
 
     # ---- MCML ----------------------------------------------------------------------------------------------------
-    def MCML(self, y, *args, trajectory=None, draws=None, theta_score=False, **kwargs):
+    _information = "host"                                      # what the SE sites hand to information_matrix(on=); MCML / LA set it
+
+    def _use_information(self, information):
+        """information=None / "host" / "device" of MCML() and LA(): the value for the duration of a call"""
+        if information not in (None, "host", "device"):
+            raise ValueError("information should be 'host', 'device' or None")
+        return "host" if information is None else information
+
+    def MCML(self, y, *args, trajectory=None, draws=None, theta_score=False, information=None, **kwargs):
         """_mcml below (its arguments, unchanged); trajectory ("step" / "component", None = leave the backend's default
         alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  draws ("hmc" / "exact" /
         "exact_component", None = leave the default alone): what the HMC sampler's call returns -- "exact" draws the conditional distribution of
@@ -257,12 +276,16 @@ class ModelMCML:
         restored; do not run two fits with different choices in one process at the same time.
         theta_score = True: the fit also carries `theta_score`, the analytic gradient of mvn_ll in the covariance parameters at
         the final estimate on re_samps (the backend's mvn_ll_grad) -- how far the theta-step stopped from a stationary point;
-        False: nothing more is called."""
+        False: nothing more is called.
+        information ("host" / "device", None = "host"): where the GLS information matrix behind the "approx" standard errors
+        (and behind the fallback of "lik" / "robust") is computed -- information_matrix(on=)."""
         prev_t = prev_d = None
+        prev_i, use_i = self._information, self._use_information(information)
         if trajectory is not None:
             prev_t = self._be.get_default_trajectory()
             self._be.set_default_trajectory(trajectory)
         try:
+            self._information = use_i
             if draws is not None:
                 prev_d = self._be.get_default_draws()
                 self._be.set_default_draws(draws)
@@ -273,6 +296,7 @@ class ModelMCML:
                 fit["theta_score"] = np.asarray(self._be.mvn_ll_grad(*self._ddata(), cov_par, fit["re_samps"])[1])
             return fit
         finally:
+            self._information = prev_i
             if prev_d is not None:
                 self._be.set_default_draws(prev_d)
             if prev_t is not None:
@@ -396,7 +420,7 @@ class ModelMCML:
             if se_method == "approx" or np.any(np.isnan(SE[:P])):
                 SE = np.full(P + R, np.nan)
                 hessused = False
-                M = self.information_matrix(theta[par["cov"]], theta[par["b"]], theta[par["sig"]])
+                M = self.information_matrix(theta[par["cov"]], theta[par["b"]], theta[par["sig"]], on=self._information)
                 SE[:P] = np.sqrt(np.diag(np.linalg.inv(M)))
             if self.family in _VAR_FAMILIES:
                 SE = np.r_[SE, np.nan]
@@ -413,18 +437,22 @@ class ModelMCML:
                        re_samps=dsamps, iter=it, warnings=warnings, theta=theta)
 
     # ---- LA ------------------------------------------------------------------------------------------------------
-    def LA(self, y, *args, operator=None, **kwargs):
+    def LA(self, y, *args, operator=None, information=None, **kwargs):
         """_la below (its arguments, unchanged); operator ("dense" / "component" / "component_wide", None = leave the
         backend's default alone): how the Laplace fit forms and factorises ZL' W ZL + I (csrc/component.hip).  It becomes the backend's default
-        for the duration of the call and is restored afterwards"""
-        if operator is None:
-            return self._la(y, *args, **kwargs)
-        prev = self._be.get_default_la_operator()
-        self._be.set_default_la_operator(operator)
+        for the duration of the call and is restored afterwards.  information ("host" / "device", None = "host"): where the
+        GLS information matrix behind the standard errors without use_hess is computed -- information_matrix(on=)"""
+        prev_i, self._information = self._information, self._use_information(information)
+        prev = None
         try:
+            if operator is not None:
+                prev = self._be.get_default_la_operator()
+                self._be.set_default_la_operator(operator)
             return self._la(y, *args, **kwargs)
         finally:
-            self._be.set_default_la_operator(prev)
+            self._information = prev_i
+            if prev is not None:
+                self._be.set_default_la_operator(prev)
 
     def _la(self, y, start=None, method="nloptim", use_hess=False, verbose=False, maxfun=0):
         """ModelMCML$LA (R6ModelExtMCML.R:627-845): mcml_la ("nloptim") or mcml_la_nr ("nr"), tol fixed at 1e-2"""
@@ -448,7 +476,7 @@ class ModelMCML:
         names = self.x_names + self._cov_par_names() + (["sigma"] if self.family in _VAR_FAMILIES else [])
         if not use_hess:
             SE = np.full(P + R, np.nan)
-            M = self.information_matrix(theta[par["cov"]], theta[par["b"]], theta[par["sig"]])
+            M = self.information_matrix(theta[par["cov"]], theta[par["b"]], theta[par["sig"]], on=self._information)
             SE[:P] = np.sqrt(np.diag(np.linalg.inv(M)))
             if self.family in _VAR_FAMILIES:
                 SE = np.r_[SE, np.nan]

@@ -558,6 +558,9 @@ int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, double* out3);
  * stamps of one launch, + 32 every workgroup's.  Bits 1, 2, 4 and 8 (the K loop with parts switched off) are retired
  * and rejected. */
 
+/* the GLS information matrix of the fixed effects on the device (csrc/info.hip): a header of its own */
+#include "glmmr_mcml_info.h"
+
 #ifdef __cplusplus
 }
 #endif
