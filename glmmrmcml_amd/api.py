@@ -188,6 +188,37 @@ def _weights(weights, m):
     return w
 
 
+def _newdata(newdata, cov):
+    """(nnew, flat, K) of the prediction calls: newdata is a list with one k_b x ncol_b array per covariance block (None or an
+    empty array: no new points there; a vector is one column for a block of one variable, else one point), ncol_b read off
+    the block's rows of cov"""
+    cov = np.asarray(cov)
+    first = np.r_[True, cov[1:, 0] != cov[:-1, 0]]
+    ncol = np.add.reduceat(cov[:, 3], np.flatnonzero(first))
+    if len(newdata) != ncol.size:
+        raise ValueError("newdata must list %d blocks (None for a block without new points)" % ncol.size)
+    nnew, flat = np.zeros(ncol.size, dtype=np.int32), []
+    for b, x in enumerate(newdata):
+        if x is None or np.size(x) == 0:
+            continue
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim == 1:
+            x = x.reshape(-1, 1) if ncol[b] == 1 else x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[1] != ncol[b]:
+            raise ValueError("newdata[%d] must have %d columns, the block's variables" % (b, ncol[b]))
+        nnew[b] = x.shape[0]
+        flat.append(x.ravel(order="F"))
+    flat = np.concatenate(flat) if flat else np.zeros(0)
+    return nnew, np.ascontiguousarray(flat), int(nnew.sum())
+
+
+def _prediction(summary, mm):
+    out = dict(mean=summary[:, 0].copy(), cond_var=summary[:, 1].copy(), sample_var=summary[:, 2].copy())
+    if mm is not None:
+        out["means"] = mm
+    return out
+
+
 def _cols(u):
     """samples as a column-major matrix; a vector is one column"""
     u = _f(u)
@@ -584,6 +615,29 @@ class Context:
         keys = ("requested", "op", "ncomp", "max_vars", "waves", "launches", "dense_bytes", "P")
         return _plan(_lib.lib().glmmr_mcml_dbg_information_plan, C.c_longlong, keys, self._h)
 
+    def predict_re(self, theta, newdata, means=False):
+        """Conditional (kriging) prediction of the random effects at new locations given the context's sample columns
+        (csrc/predict.hip, include/glmmr_mcml_predict.h glmmr_mcml_ctx_predict_re).  newdata: one k_b x ncol_b array per
+        covariance block with the columns of the block's data matrix, None for no new points.  -> dict(mean, cond_var,
+        sample_var[, means]) over the K = sum k_b new points in block order: the mean over the sample columns of the
+        conditional mean C D^-1 u_j, the conditional variance max(p - C D^-1 C', 0), the variance of the conditional mean
+        across the sample columns (divisor m - 1, NaN for one column) and, on request, the K x m conditional means.  A
+        query: the context is left as it was.  McmlError -1 without samples, for a wrong shape or K = 0, -3 where D(theta)
+        is not positive definite"""
+        theta = _f(theta).ravel()
+        nnew, flat, K = _newdata(newdata, self._keep["cov"])
+        summary = np.zeros((max(K, 1), 3), order="F")
+        mm = np.zeros((max(K, 1), self.mcols), order="F") if means else None
+        _lib.check(_lib.lib().glmmr_mcml_ctx_predict_re(self._h, _p(theta), _p(nnew), _p(flat), flat.size, _p(summary),
+                                                        summary.shape[0], _p(mm), summary.shape[0]))
+        return _prediction(summary, mm)
+
+    def predict_plan(self):
+        """what the last predict_re on this context did (test hook, include/glmmr_mcml_predict.h glmmr_mcml_dbg_predict_plan):
+        blocks served by each path, new points, chunks and factorisations run, workspace bytes, sample columns"""
+        keys = ("diag", "small", "large", "K", "chunks", "factorisations", "workspace_bytes", "m")
+        return _plan(_lib.lib().glmmr_mcml_dbg_predict_plan, C.c_longlong, keys, self._h)
+
     def mcml_optim(self, start, trace=0, mcnr=False, maxfun=0, theta_batch=0):
         start = _f(start).ravel(); R = self.npar()
         b = np.zeros(self.P); t = np.zeros(R); sg = C.c_double()
@@ -891,6 +945,18 @@ def mvn_ll(cov, data, eff_range, gamma, u):
     out = C.c_double()
     _lib.check(_lib.lib().glmmr_mcml_mvn_ll(*args, C.byref(out)))
     return out.value
+
+
+def predict_re(cov, data, eff_range, gamma, u, newdata, means=False):
+    """Context.predict_re on a context made for the call (glmmr_mcml_predict_re): the conditional prediction of the random
+    effects at the new points of newdata given the Q x m sample columns u; beyond the reference's exports"""
+    args, gamma, u, keep = _mvn_args(cov, data, eff_range, gamma, u)
+    nnew, flat, K = _newdata(newdata, keep["cov"])
+    summary = np.zeros((max(K, 1), 3), order="F")
+    mm = np.zeros((max(K, 1), u.shape[1]), order="F") if means else None
+    _lib.check(_lib.lib().glmmr_mcml_predict_re(*args, _p(nnew), _p(flat), flat.size, _p(summary), summary.shape[0], _p(mm),
+                                                summary.shape[0]))
+    return _prediction(summary, mm)
 
 
 def mvn_ll_grad(cov, data, eff_range, gamma, u, weights=None):

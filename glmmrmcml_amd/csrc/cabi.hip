@@ -247,6 +247,16 @@ extern "C" int glmmr_mcml_ctx_mvn_ll_grad(glmmr_mcml_ctx* h, const double* theta
     return mvn_loglik_grad(c, theta, weights, value, grad);
 }
 
+// conditional prediction at new points (predict.hip): the locally held sample columns, no collective
+extern "C" int glmmr_mcml_ctx_predict_re(glmmr_mcml_ctx* h, const double* theta, const int* nnew, const double* newdata,
+                                         long long newdata_len, double* summary, int lds, double* means, int ldm)
+{
+    MCML_REQUIRE(h && theta && nnew && newdata && summary, "predict_re: null argument");
+    Ctx& c = h->c;
+    MCML_HIP(hipSetDevice(c.device));
+    return predict_re(c, theta, nnew, newdata, newdata_len, summary, lds, means, ldm);
+}
+
 extern "C" int glmmr_mcml_ctx_mvn_ll_batch(glmmr_mcml_ctx* h, const double* thetas, int k, double* out)
 {
     MCML_REQUIRE(h && thetas && out && k >= 1 && k <= 64, "mvn_ll_batch: bad argument");
@@ -561,6 +571,17 @@ extern "C" int glmmr_mcml_mvn_ll_grad(const int32_t* cov, int cov_rows, const do
     MCML_TRY(glmmr_mcml_ctx_mvn_ll_grad(g.h, gamma, weights, value, grad));
     for (int k = g.h->c.cov.npar; k < ngamma; ++k) grad[k] = 0.0;
     return MCML_OK;
+}
+
+extern "C" int glmmr_mcml_predict_re(const int32_t* cov, int cov_rows, const double* data, int data_len,
+                                     const double* eff_range, int eff_len, const double* gamma, int ngamma, const double* u,
+                                     int Q, int m, const int* nnew, const double* newdata, long long newdata_len,
+                                     double* summary, int lds, double* means, int ldm)
+{
+    MCML_REQUIRE(cov && data && gamma && u && nnew && newdata && summary, "predict_re: null argument");
+    CtxGuard g;
+    MCML_TRY(open_cov("predict_re", cov, cov_rows, data, data_len, eff_range, eff_len, ngamma, u, Q, m, g));
+    return glmmr_mcml_ctx_predict_re(g.h, gamma, nnew, newdata, newdata_len, summary, lds, means, ldm);
 }
 
 extern "C" int glmmr_mcml_optim(const glmmr_mcml_problem* prob, const double* u, int ucols, const double* start,

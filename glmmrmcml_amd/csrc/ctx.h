@@ -169,6 +169,15 @@ struct InfoState {
     long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// the prediction query (predict.hip): the new points' data, the K x 3 summary, the large block at hand -- its matrix / factor D,
+// the solved samples Y, the chunk of C_b' / W' -- and the means of the chunks not yet flushed; allocated by the first call, kept
+// between calls.  plan: what the last call did (glmmr_mcml_dbg_predict_plan)
+struct PredictState {
+    DevBuf nd, sum;
+    DevMat D, Y, CT, M;
+    long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 struct Ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -187,6 +196,7 @@ struct Ctx {
     ExactState exact;
     ExactCompState exact_comp;
     InfoState info;
+    PredictState predict;
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT
     int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (component.hip); 2 the same up
                                 // to CP_WIDE_MAX_VARS variables per component, a wave or a workgroup each
@@ -313,6 +323,8 @@ int mvn_gen_L(Ctx& c, const double* theta, bool chol);
 int mvn_loglik_grad(Ctx& c, const double* theta, const double* weights, double* value, double* grad);
 // the same matrix as a query: built into `out` (allocated here), no state of the context changes
 int mvn_gen_D(Ctx& c, const double* theta, bool chol, DevMat& out);
+// block b's matrix alone, lower triangle with an identity border up to dpad, into A (enqueued; no state changes)
+int mvn_build_block(Ctx& c, double* A, int lda, int b, const double* theta, int dpad);
 
 // ---- chol.hip: see chol.h; vecops.hip (the vector-sized kernels): see vecops.h; component.hip: see component.h ----
 

@@ -180,6 +180,14 @@ extern "C" int glmmr_mcml_dbg_la_plan(glmmr_mcml_ctx* h, long long* out8)
     return MCML_OK;
 }
 
+// read-only: what the last glmmr_mcml_ctx_predict_re on this context did (predict.hip)
+extern "C" int glmmr_mcml_dbg_predict_plan(glmmr_mcml_ctx* h, long long* out8)
+{
+    MCML_REQUIRE(h && out8, "dbg_predict_plan: null argument");
+    std::copy(h->c.predict.plan, h->c.predict.plan + 8, out8);
+    return MCML_OK;
+}
+
 // read-only: what the last glmmr_mcml_ctx_information on this context was asked for and did (info.hip)
 extern "C" int glmmr_mcml_dbg_information_plan(glmmr_mcml_ctx* h, long long* out8)
 {

@@ -1,5 +1,5 @@
 // entry.h -- the host entry points one translation unit defines and another calls: the samplers (hmc.hip), the drivers
-// (drivers.hip, laplace.hip) and the launch counters (hmc.hip, component.hip) behind the extern "C" layer (cabi.hip,
+// (drivers.hip, laplace.hip), the queries (info.hip, predict.hip) and the launch counters (hmc.hip, component.hip) behind the extern "C" layer (cabi.hip,
 // ctx_hooks.hip).  The defining
 // files include this header, so a signature that drifts is a compile error, not a wrong link.
 #pragma once
@@ -53,6 +53,13 @@ long long la_component_launch_count();
 // op: 0 the component operator where info_component_applicable, else the dense one; 1 dense; 2 component or MCML_EUNSUPPORTED
 bool info_component_applicable(const Ctx& c);
 int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out, int ldo);
+
+// ---- predict.hip ----
+// conditional mean and variance of the random effects at nnew[b] new points per covariance block (newdata: every block's
+// k_b x ncol_b matrix, column-major, concatenated) given the resident samples -> summary (K x 3: mean over the samples,
+// conditional variance, variance between the samples) and, where means is not null, the K x mcols conditional means
+int predict_re(Ctx& c, const double* theta, const int* nnew, const double* newdata, long long newdata_len, double* summary,
+               int lds, double* means, int ldm);
 
 // the seed of a sampler run: the caller's, or one from std::random_device as the reference draws it (mhmcmc.h:55)
 inline uint64_t default_seed(const glmmr_mcml_ext* e)

@@ -20,6 +20,7 @@
 // exports) lives in mvn_grad.h, one gradient path per block kind.
 #include <cmath>
 #include "ctx.h"
+#include "cov_entry.h"
 #include "reduce.h"
 #include "theta_scale.h"
 #include "vecops.h"
@@ -66,25 +67,6 @@ __global__ __launch_bounds__(256) void k_diag_ll(const double* U, int ldu, int Q
     }
     double r = block_sum(acc, sh);
     if (threadIdx.x == 0) partials[blockIdx.y * gridDim.x + blockIdx.x] = r;
-}
-
-// ------------------------------------------------------------------ covariance entry
-__device__ __forceinline__ double cov_entry(const CovBlock& blk, const int32_t* cov, int rows,
-                                            const double* bd, const ThetaArg& th, int i, int j)
-{
-    double val = 1.0;
-    int coff = 0;
-    for (int r = blk.r0; r < blk.r1; ++r) {
-        const int fn = cov[r + 2 * rows], nv = cov[r + 3 * rows], pi = cov[r + 4 * rows];
-        double d2 = 0.0;
-        for (int p = 0; p < nv; ++p) {
-            double df = bd[i + (size_t)(coff + p) * blk.dim] - bd[j + (size_t)(coff + p) * blk.dim];
-            d2 += df * df;
-        }
-        val = cov_term(fn, sqrt(d2), &th.v[pi], val);
-        coff += nv;
-    }
-    return val;
 }
 
 // ------------------------------------------------------------------ small blocks
@@ -571,6 +553,19 @@ static int gen_D_into(Ctx& c, DevMat& L, const ThetaArg& th, bool chol)
     }
     MCML_HIP(hipGetLastError());
     return check_errflag(c, "genD: covariance block is not positive definite");
+}
+
+// block b's covariance matrix (lower triangle, identity border up to dpad) into the caller's array, enqueued: the build step
+// of mvn_large_blocks for a caller with a workspace of its own (predict.hip)
+int mvn_build_block(Ctx& c, double* A, int lda, int b, const double* theta, int dpad)
+{
+    ThetaArg th;
+    MCML_TRY(theta_arg(c, theta, th));
+    MCML_REQUIRE(b >= 0 && b < c.cov.B && A && dpad >= c.cov.blocks[b].dim && lda >= dpad, "mvn_build_block: bad argument");
+    hipLaunchKernelGGL(k_build_dense, dim3((dpad + 63) / 64, (dpad + 15) / 16), dim3(256), 0, c.stream, A, lda, b,
+                       c.d_blocks.as<CovBlock>(), c.d_cov.as<int32_t>(), c.cov.rows, c.d_data.d(), th, 0, dpad);
+    MCML_HIP(hipGetLastError());
+    return MCML_OK;
 }
 
 // A query (glmmr_mcml_ctx_gen_D): into the caller's matrix, so c.L, have_L and l_foreign stay as they are

@@ -75,6 +75,108 @@ def _dhdmu(xb, family, link):
     return xb * xb                                             # 11
 
 
+def _cov_factor(fn, d, t):
+    """one term of a covariance block at distances d, t = theta[par_index:] (the table of csrc/covspec.h, its expressions)"""
+    if fn == 1:
+        return np.where(d == 0, t[0] * t[0], 0.0)
+    if fn == 2:
+        return np.exp(-1.0 * d / t[0])
+    if fn == 3:
+        return np.power(t[0], d)
+    if fn == 4:
+        return t[0] * np.exp(-1.0 * d * d / (t[1] * t[1]))
+    if fn == 7:
+        return t[0] * np.exp(-1.0 * d / t[1])
+    if fn == 14:
+        return np.exp(-1.0 * d * d / (t[0] * t[0]))
+    raise ValueError("covariance function id %d is not built" % fn)
+
+
+def _cov_blocks(cov, data):
+    """[(dim, [(fn, x (dim x nv), parameter index), ...])]: the blocks of the get_D_data() pair"""
+    cov = np.asarray(cov)
+    data = np.asarray(data, float).ravel()
+    blocks, r, off = [], 0, 0
+    while r < cov.shape[0]:
+        dim, terms, bid = int(cov[r, 1]), [], cov[r, 0]
+        while r < cov.shape[0] and cov[r, 0] == bid:
+            nv = int(cov[r, 3])
+            terms.append((int(cov[r, 2]), data[off:off + dim * nv].reshape(dim, nv, order="F"), int(cov[r, 4])))
+            off += dim * nv
+            r += 1
+        blocks.append((dim, terms))
+    return blocks
+
+
+def _cov_product(terms, xa, theta):
+    """prod over the terms of cov_term(|xa_i - x_j|): len(xa) x dim; xa holds the terms' columns side by side"""
+    out, col = 1.0, 0
+    for fn, x, pi in terms:
+        nv = x.shape[1]
+        diff = xa[:, None, col:col + nv] - x[None, :, :]
+        out = out * _cov_factor(fn, np.sqrt((diff * diff).sum(-1)), theta[pi:])
+        col += nv
+    return out
+
+
+def _forward_solve(L, B, nb=64):
+    """L^-1 B by forward substitution, nb rows at a time"""
+    Y = np.array(B, dtype=np.float64)
+    n = L.shape[0]
+    for k in range(0, n, nb):
+        e = min(k + nb, n)
+        for i in range(k, e):
+            Y[i] = (Y[i] - L[i, k:i] @ Y[k:i]) / L[i, i]
+        if e < n:
+            Y[e:] -= L[e:, k:e] @ Y[k:e]
+    return Y
+
+
+def predict_host(cov, data, theta, u, newdata, means=False):
+    """The prediction of api.predict_re in numpy float64, block by block: D = L L', W' = L^-1 C', Y = L^-1 u, means = W Y,
+    cond_var = max(p - |W_i|^2, 0); all-gr blocks in their diagonal form, means = (C / D_kk) u.  -> the dict of
+    api.predict_re"""
+    theta = np.asarray(theta, float).ravel()
+    u = np.asarray(u, float)
+    u = u.reshape(-1, 1) if u.ndim == 1 else u
+    blocks = _cov_blocks(cov, data)
+    if len(newdata) != len(blocks):
+        raise ValueError("newdata must list %d blocks (None for a block without new points)" % len(blocks))
+    mean_rows, cvar, s = [], [], 0
+    for (dim, terms), xn in zip(blocks, newdata):
+        ub = u[s:s + dim]
+        s += dim
+        if xn is None or np.size(xn) == 0:
+            continue
+        ncol = sum(x.shape[1] for _, x, _ in terms)
+        xn = np.asarray(xn, float)
+        if xn.ndim == 1:
+            xn = xn.reshape(-1, 1) if ncol == 1 else xn.reshape(1, -1)
+        if xn.ndim != 2 or xn.shape[1] != ncol:
+            raise ValueError("a block's new points must have %d columns, the block's variables" % ncol)
+        xobs = np.column_stack([x for _, x, _ in terms])
+        Cb = _cov_product(terms, xn, theta)
+        p = float(_cov_product(terms, xobs[:1], theta)[0, 0])            # the product at distance 0
+        if all(fn == 1 for fn, _, _ in terms):
+            W = Cb / p
+            mean_rows.append(W @ ub)
+            cvar.append(np.maximum(p - (Cb * W).sum(1), 0.0))
+        else:
+            L = np.linalg.cholesky(_cov_product(terms, xobs, theta))
+            WT = _forward_solve(L, Cb.T)
+            mean_rows.append(WT.T @ _forward_solve(L, ub))
+            cvar.append(np.maximum(p - (WT * WT).sum(0), 0.0))
+    if not mean_rows:
+        raise ValueError("no new points")
+    mm = np.vstack(mean_rows)
+    m = mm.shape[1]
+    out = dict(mean=mm.mean(axis=1), cond_var=np.concatenate(cvar),
+               sample_var=mm.var(axis=1, ddof=1) if m > 1 else np.full(mm.shape[0], np.nan))
+    if means:
+        out["means"] = mm
+    return out
+
+
 class McmlFit(dict):
     """the `mcml` list MCML() / LA() return (R6ModelExtMCML.R:571-587); attribute access for convenience"""
 
@@ -496,6 +598,53 @@ class ModelMCML:
         return McmlFit(coefficients=coef, converged=True, method=method, hessian=False, m=None, tol=None, sim_lik=False,
                        aic=float(aic), Rsq=dict(cond=(vx + vz) / total, marg=vx / total), family=self.family,
                        link=self.link, re_samps=u, iter=0, warnings=[], theta=theta)
+
+    # ---- prediction --------------------------------------------------------------------------------------------
+    def predict(self, fit, newdata, X=None, Z=None, on="device"):
+        """The random effects at new locations given a fit (beyond the R class): newdata lists one k_b x ncol_b array per
+        covariance block -- rows in the layout of the block's get_D_data() matrix, the `gr` columns included -- or None
+        for a block without new points.  theta-hat and re_samps come from the fit (an LA fit has one column).  ->
+        dict(re_mean, re_var, cond_var, sample_var) over the K new points in block order: the mean over the samples of the
+        conditional mean C D^-1 u, the conditional (kriging) variance, the variance of the conditional mean across the
+        samples, and re_var = cond_var + sample_var (the law of total variance; cond_var alone for one sample column).
+        X (K' x P): also linear_predictor = X beta-hat + Z re_mean, Z (K' x K) defaulting to the identity, which needs
+        K' = K.  on = "device": the backend's `predict_re` export (csrc/predict.hip); "host": the same definition in numpy
+        float64 -- a Cholesky factor, two forward solves and a product per block"""
+        if on not in ("device", "host"):
+            raise ValueError("on should be 'device' or 'host'")
+        P, R = self.X.shape[1], self.cov_parameters.size
+        theta = np.asarray(fit["theta"], float)
+        cov_par, beta = theta[P:P + R], theta[:P]
+        u = np.asarray(fit["re_samps"], float)
+        u = u.reshape(-1, 1) if u.ndim == 1 else u
+        if u.shape[0] != self.Z.shape[1]:
+            raise ValueError("re_samps has %d rows, the model %d random effects" % (u.shape[0], self.Z.shape[1]))
+        if on == "device":
+            r = self._be.predict_re(*self._ddata(), cov_par, u, newdata)
+        else:
+            r = predict_host(self.cov, self.data, cov_par, u, newdata)
+        cond, samp = np.asarray(r["cond_var"], float), np.asarray(r["sample_var"], float)
+        out = dict(re_mean=np.asarray(r["mean"], float), re_var=cond + samp if u.shape[1] > 1 else cond.copy(),
+                   cond_var=cond, sample_var=samp)
+        K = out["re_mean"].size
+        if X is None:
+            if Z is not None:
+                raise ValueError("Z without X: the linear predictor needs the fixed effects' design")
+            return out
+        X = np.asarray(X, float)
+        if X.ndim != 2 or X.shape[1] != P:
+            raise ValueError("X must have %d columns" % P)
+        if Z is None:
+            if X.shape[0] != K:
+                raise ValueError("X has %d rows for %d new points: pass Z" % (X.shape[0], K))
+            zu = out["re_mean"]
+        else:
+            Z = np.asarray(Z, float)
+            if Z.shape != (X.shape[0], K):
+                raise ValueError("Z must be %d x %d" % (X.shape[0], K))
+            zu = Z @ out["re_mean"]
+        out["linear_predictor"] = X @ beta + zu
+        return out
 
     # ---- sparse helpers ------------------------------------------------------------------------------------------
     def _sparse_pattern(self):

@@ -560,6 +560,8 @@ int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, double* out3);
 
 /* the GLS information matrix of the fixed effects on the device (csrc/info.hip): a header of its own */
 #include "glmmr_mcml_info.h"
+/* conditional prediction of the random effects at new locations (csrc/predict.hip): a header of its own */
+#include "glmmr_mcml_predict.h"
 
 #ifdef __cplusplus
 }
