@@ -615,6 +615,31 @@ class Context:
         keys = ("requested", "op", "ncomp", "max_vars", "waves", "launches", "dense_bytes", "P")
         return _plan(_lib.lib().glmmr_mcml_dbg_information_plan, C.c_longlong, keys, self._h)
 
+    def sandwich(self, beta, var_par, theta=None, cluster=None, operator=None, scores=False):
+        """The cluster-robust (sandwich) covariance of the fixed effects on the device (csrc/sandwich.hip,
+        include/glmmr_mcml_sandwich.h glmmr_mcml_ctx_sandwich) -> dict(information, meat, vcov, ncluster[, scores]):
+        information = X' Sigma^-1 X (information_matrix's bits), meat = G' G with the cluster scores
+        G[c] = sum_{i in c} x_i (Sigma^-1 e)_i of the working residuals e = (y - h(X beta)) d eta / d mu, and
+        vcov = information^-1 meat information^-1, solved here.  cluster: n integer ids 0 .. ncl - 1, or None for the connected
+        components of ZL's coupling graph (McmlError -1 where the context does not run the sparse operator or an observation
+        has no entry of ZL).  theta and operator: as information_matrix.  McmlError -1 for an id out of range or a residual /
+        weight that is not finite, -2 for "component" where it does not apply, -3 for a failed pivot"""
+        beta = _f(beta).ravel()
+        if beta.size != self.P:
+            raise ValueError("beta must hold %d values" % self.P)
+        th = None if theta is None else _f(theta).ravel()
+        cl, ncl = _cluster_ids(cluster, self.n)
+        r = _sandwich_call(lambda *a: _lib.lib().glmmr_mcml_ctx_sandwich(self._h, _p(beta), float(var_par), _p(th),
+                                                                         _INFO_OP[operator], *a), self.n, self.P, cl, ncl, scores)
+        return r
+
+    def sandwich_plan(self):
+        """what the last sandwich on this context was asked for and ran (test hook, include/glmmr_mcml_sandwich.h
+        glmmr_mcml_dbg_sandwich_plan): op as information_plan's, the clusters and the rows of the largest, whether they were
+        the default ones, the launches of csrc/sandwich.hip's kernels"""
+        keys = ("requested", "op", "ncluster", "max_rows", "default_clusters", "launches", "dense_bytes", "P")
+        return _plan(_lib.lib().glmmr_mcml_dbg_sandwich_plan, C.c_longlong, keys, self._h, bools=("default_clusters",))
+
     def predict_re(self, theta, newdata, means=False):
         """Conditional (kriging) prediction of the random effects at new locations given the context's sample columns
         (csrc/predict.hip, include/glmmr_mcml_predict.h glmmr_mcml_ctx_predict_re).  newdata: one k_b x ncol_b array per
@@ -807,6 +832,41 @@ def information_matrix(cov, data, eff_range, Z, X, family, link, beta, theta, va
     _lib.check(_lib.lib().glmmr_mcml_information(C.byref(p), _p(beta), _p(theta), theta.size, float(var_par),
                                                  _INFO_OP[operator], _p(out), p.P))
     return out
+
+
+def _cluster_ids(cluster, n):
+    """(the ids as the C ABI takes them, their count) -- (None, 0) for the default clusters; a wrong length is refused here"""
+    if cluster is None:
+        return None, 0
+    cl = np.ascontiguousarray(np.asarray(cluster).ravel(), dtype=np.int32)
+    if cl.size != n:
+        raise ValueError("cluster must hold %d ids" % n)
+    return cl, int(cl.max()) + 1 if cl.size else 0
+
+
+def _sandwich_call(fn, n, P, cl, ncl, scores):
+    """fn(cluster, ncluster, info, ldi, meat, ldm, scores, lds, ncluster_out) -> the dict of Context.sandwich"""
+    info = np.zeros((P, P), order="F"); meat = np.zeros((P, P), order="F")
+    rows = max(ncl if cl is not None else n, 1)                     # the default clusters are at most n
+    G = np.zeros((rows, P), order="F") if scores else None
+    got = C.c_int()
+    _lib.check(fn(_p(cl), ncl, _p(info), P, _p(meat), P, _p(G), rows, C.byref(got)))
+    out = dict(information=info, meat=meat, vcov=np.linalg.solve(info, np.linalg.solve(info, meat).T), ncluster=got.value)
+    if scores:
+        out["scores"] = np.ascontiguousarray(G[:got.value])
+    return out
+
+
+def sandwich(cov, data, eff_range, Z, X, y, family, link, beta, theta, var_par=1.0, cluster=None, operator=None, scores=False):
+    """Context.sandwich on a context made for the call (glmmr_mcml_sandwich): the bread, the meat and the cluster-robust
+    covariance of the fixed effects at beta / theta / var_par; beyond the reference's exports.  y IS read"""
+    p, keep = _problem(cov, data, eff_range, Z, X, y, family, link)
+    beta = _f(beta).ravel(); theta = _f(theta).ravel()
+    if beta.size != p.P:
+        raise ValueError("beta must hold %d values" % p.P)
+    cl, ncl = _cluster_ids(cluster, p.n)
+    return _sandwich_call(lambda *a: _lib.lib().glmmr_mcml_sandwich(C.byref(p), _p(beta), _p(theta), theta.size, float(var_par),
+                                                                    _INFO_OP[operator], *a), p.n, p.P, cl, ncl, scores)
 
 
 def _sampler_args(Z, L, X, y, beta, family, link):

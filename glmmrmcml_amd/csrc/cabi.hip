@@ -361,6 +361,22 @@ extern "C" int glmmr_mcml_ctx_information(glmmr_mcml_ctx* h, const double* beta,
     return info_matrix(c, beta, var_par, op, out, ldo);
 }
 
+// the cluster-robust sandwich of the fixed effects (sandwich.hip).  theta: as glmmr_mcml_ctx_information
+extern "C" int glmmr_mcml_ctx_sandwich(glmmr_mcml_ctx* h, const double* beta, double var_par, const double* theta, int op,
+                                       const int* cluster, int ncluster, double* info, int ldi, double* meat, int ldm,
+                                       double* scores, int lds, int* ncluster_out)
+{
+    MCML_REQUIRE(h && beta && info && meat, "sandwich: null argument");
+    Ctx& c = h->c;
+    MCML_HIP(hipSetDevice(c.device));
+    if (theta) {
+        MCML_REQUIRE(c.n > 0 && c.cov.npar > 0, "sandwich: the context has no model / covariance");
+        MCML_TRY(mvn_gen_L(c, theta, true));
+        MCML_TRY(install_L(c));
+    }
+    return sandwich_matrices(c, beta, var_par, op, cluster, ncluster, info, ldi, meat, ldm, scores, lds, ncluster_out);
+}
+
 extern "C" int glmmr_mcml_ctx_hmc_sample(glmmr_mcml_ctx* h, const double* beta, double var_par,
                                          const glmmr_mcml_hmc_opts* opts, uint64_t seed, uint32_t iter_idx,
                                          const double* inj_init, const double* inj_mom, uint8_t* flags_out,
@@ -738,6 +754,19 @@ extern "C" int glmmr_mcml_information(const glmmr_mcml_problem* prob, const doub
     MCML_REQUIRE(ntheta >= g.h->c.cov.npar, "information: %d covariance parameters given, the covariance needs %d", ntheta,
                  g.h->c.cov.npar);
     return glmmr_mcml_ctx_information(g.h, beta, var_par, theta, op, out, ldo);
+}
+
+extern "C" int glmmr_mcml_sandwich(const glmmr_mcml_problem* prob, const double* beta, const double* theta, int ntheta,
+                                   double var_par, int op, const int* cluster, int ncluster, double* info, int ldi, double* meat,
+                                   int ldm, double* scores, int lds, int* ncluster_out)
+{
+    MCML_REQUIRE(prob && beta && theta && info && meat, "sandwich: null argument");
+    CtxGuard g;
+    MCML_TRY(open_ctx(prob, nullptr, g));
+    MCML_REQUIRE(ntheta >= g.h->c.cov.npar, "sandwich: %d covariance parameters given, the covariance needs %d", ntheta,
+                 g.h->c.cov.npar);
+    return glmmr_mcml_ctx_sandwich(g.h, beta, var_par, theta, op, cluster, ncluster, info, ldi, meat, ldm, scores, lds,
+                                   ncluster_out);
 }
 
 extern "C" int glmmr_mcml_mcmc_sample(const double* Z, const double* L, const double* X, const double* y, int n,

@@ -169,6 +169,14 @@ struct InfoState {
     long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// the sandwich query (sandwich.hip): the residual flag, the working residual e, v o e, a = Sigma^-1 e, the right-hand side / t (Q),
+// ZL t (dense operator), the clusters' CSR, the meat's partials and the result B | 2 flags | G; kept between calls.  plan: what
+// the last call did (glmmr_mcml_dbg_sandwich_plan)
+struct SandwichState {
+    DevBuf bad, e, ve, a, t, zt, cl_ptr, cl_rows, part, res;
+    long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 // the prediction query (predict.hip): the new points' data, the K x 3 summary, the large block at hand -- its matrix / factor D,
 // the solved samples Y, the chunk of C_b' / W' -- and the means of the chunks not yet flushed; allocated by the first call, kept
 // between calls.  plan: what the last call did (glmmr_mcml_dbg_predict_plan)
@@ -196,6 +204,7 @@ struct Ctx {
     ExactState exact;
     ExactCompState exact_comp;
     InfoState info;
+    SandwichState sand;
     PredictState predict;
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT
     int la_mode = 0;            // Laplace fits: 0 dense ZL and M; 1 the component operator where feasible (component.hip); 2 the same up
@@ -208,6 +217,7 @@ struct Ctx {
     CovSpec cov;
     DevMat Z, X;                // n x Q, n x P
     DevBuf y;                   // n
+    DevBuf y_given;             // n, gaussian / log only: y before model_setup took its logarithm (sandwich.hip)
     DevBuf d_cov, d_data, d_blocks, d_rowblock;   // covariance spec on the device
 
     // samples

@@ -188,6 +188,14 @@ extern "C" int glmmr_mcml_dbg_predict_plan(glmmr_mcml_ctx* h, long long* out8)
     return MCML_OK;
 }
 
+// read-only: what the last glmmr_mcml_ctx_sandwich on this context was asked for and did (sandwich.hip)
+extern "C" int glmmr_mcml_dbg_sandwich_plan(glmmr_mcml_ctx* h, long long* out8)
+{
+    MCML_REQUIRE(h && out8, "dbg_sandwich_plan: null argument");
+    std::copy(h->c.sand.plan, h->c.sand.plan + 8, out8);
+    return MCML_OK;
+}
+
 // read-only: what the last glmmr_mcml_ctx_information on this context was asked for and did (info.hip)
 extern "C" int glmmr_mcml_dbg_information_plan(glmmr_mcml_ctx* h, long long* out8)
 {

@@ -1,5 +1,5 @@
 // entry.h -- the host entry points one translation unit defines and another calls: the samplers (hmc.hip), the drivers
-// (drivers.hip, laplace.hip), the queries (info.hip, predict.hip) and the launch counters (hmc.hip, component.hip) behind the extern "C" layer (cabi.hip,
+// (drivers.hip, laplace.hip), the queries (info.hip, sandwich.hip, predict.hip) and the launch counters (hmc.hip, component.hip) behind the extern "C" layer (cabi.hip,
 // ctx_hooks.hip).  The defining
 // files include this header, so a signature that drifts is a compile error, not a wrong link.
 #pragma once
@@ -53,6 +53,13 @@ long long la_component_launch_count();
 // op: 0 the component operator where info_component_applicable, else the dense one; 1 dense; 2 component or MCML_EUNSUPPORTED
 bool info_component_applicable(const Ctx& c);
 int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out, int ldo);
+
+// ---- sandwich.hip ----
+// the bread X' Sigma^-1 X (info_matrix's, to the bit), the meat G' G and, where scores is not null, the ncl x P cluster scores G
+// of the working residuals at beta / var_par with the resident L.  cluster: n ids in [0, ncluster), or null for the components of
+// the plan (MCML_EINVAL where there is none or an observation has no entry of ZL).  op: as info_matrix.  On an error nothing is written
+int sandwich_matrices(Ctx& c, const double* beta, double var_par, int op, const int* cluster, int ncluster, double* info, int ldi,
+                      double* meat, int ldm, double* scores, int lds, int* ncluster_out);
 
 // ---- predict.hip ----
 // conditional mean and variance of the random effects at nnew[b] new points per covariance block (newdata: every block's

@@ -31,8 +31,11 @@ int model_setup(Ctx& c, const double* Z, const double* X, const double* y)
     MCML_HIP(hipMemsetAsync(c.y.p, 0, sizeof(double) * (size_t)pad_ld(n), c.stream));
     MCML_HIP(hipMemsetAsync(c.xb.p, 0, sizeof(double) * (size_t)pad_ld(n), c.stream));
     std::vector<double> yy(y, y + n);
-    if (c.flink == 8)                      // mcmlmodel.h:90-92: y_ = y_.log()
+    if (c.flink == 8) {                    // mcmlmodel.h:90-92: y_ = y_.log(); the sandwich query reads y as it was given
+        MCML_TRY(c.y_given.ensure(sizeof(double) * (size_t)pad_ld(n)));
+        MCML_TRY(copy_h2d(c.y_given.p, yy.data(), sizeof(double) * n, c.stream));
         for (auto& v : yy) v = log(v);
+    }
     MCML_TRY(copy_h2d(c.y.p, yy.data(), sizeof(double) * n, c.stream));
     // sparse rows of Z (indicator designs): padded CSR, width = max nnz per row
     size_t nnz = 0; int maxrow = 0;

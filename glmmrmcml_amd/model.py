@@ -14,7 +14,10 @@ Differences from the R class, each deliberate:
     `mcml_full`).
   * se.method "lik" / "robust": the R code assigns the dense Hessian to `newtheta` and then inverts an undefined
     `hess` (defect D6), and never forwards `fd_tol` (D12); here the Hessian returned by mcml_hess is the one
-    inverted and `fd_tol` is its step.
+    inverted and `fd_tol` is its step.  se.method = "robust" therefore still computes what "lik" computes, as in the
+    reference (its flag `robust` is never set, R6ModelExtMCML.R:442).  The cluster-robust standard errors an analyst expects
+    under that name come from the separate argument `MCML(..., sandwich="CR0" | "CR1")` / `LA(..., sandwich=)` and from
+    `ModelMCML.sandwich()` (csrc/sandwich.hip): the fit gains a `robust` record, its coefficient table is untouched.
   * `mcml_simlik` is called without the non-existent `mcnr=` argument (defect D7).
   * `information_matrix()` lives in glmmrBase; its GLS form X' (W^-1 + Z D Z')^-1 X is restated from the
     commented block of src/mcml_la.cpp:126-139 (INFERRED, unverifiable without glmmrBase).  `MCML(..., information=)` and
@@ -73,6 +76,58 @@ def _dhdmu(xb, family, link):
     if fl == 10:
         return 1 / (xb * xb)
     return xb * xb                                             # 11
+
+
+def _working_residual(y, xb, link):
+    """e = (y - h(eta)) d eta / d mu at eta = xb: csrc/glm.h glm_mod_inv and glm_detadmu (moremaths.h:118-161), their
+    expressions -- the unstable logistic form and the probit's 1 / dnorm included"""
+    xb = np.asarray(xb, float)
+    if link == "log":
+        mu, d = np.exp(xb), np.exp(-1.0 * xb)
+    elif link == "identity":
+        mu, d = xb, np.ones_like(xb)
+    elif link == "logit":
+        mu = np.exp(xb) / (1 + np.exp(xb))
+        d = 1 / (mu * (1.0 - mu))
+    elif link == "probit":
+        from math import erfc
+        mu = np.array([0.5 * erfc(-v * 0.70710678118654752440) for v in np.atleast_1d(xb)]).reshape(xb.shape)
+        d = 1 / (np.exp(-0.5 * xb * xb) * 0.39894228040143267794)
+    elif link == "inverse":
+        mu, d = 1 / xb, -1.0 * xb * xb
+    else:
+        raise ValueError("unknown link %s" % link)
+    return (np.asarray(y, float) - mu) * d
+
+
+def components_of_rows(ZL):
+    """The default clusters of the sandwich query on the host: the connected components of the graph that joins the columns
+    every row of ZL touches (a small union-find over its nonzero pattern), numbered by their smallest column as
+    csrc/component_plan.h numbers them -> (component of every row, number of components).  A row without an entry belongs
+    to no component: ValueError"""
+    ZL = np.asarray(ZL)
+    n, Q = ZL.shape
+    parent = list(range(Q))
+
+    def find(q):
+        while parent[q] != q:
+            parent[q] = parent[parent[q]]
+            q = parent[q]
+        return q
+
+    first = np.full(n, -1)
+    for i in range(n):
+        nz = np.nonzero(ZL[i])[0]
+        if nz.size == 0:
+            raise ValueError("observation %d has no entry of ZL and belongs to no component: pass explicit cluster ids" % i)
+        first[i] = nz[0]
+        for j in nz[1:]:
+            a, b = find(int(nz[0])), find(int(j))
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+    roots = [find(q) for q in range(Q)]
+    label = {r: k for k, r in enumerate(sorted(set(roots)))}          # the root is the smallest column of its component
+    return np.array([label[roots[q]] for q in first], dtype=np.int32), len(label)
 
 
 def _cov_factor(fn, d, t):
@@ -344,6 +399,74 @@ class ModelMCML:
         S = np.diag(w) + self.Z @ D @ self.Z.T
         return self.X.T @ np.linalg.solve(S, self.X)
 
+    def sandwich(self, y, theta_cov, beta, sigma, cluster=None, on="device", adjust="CR0"):
+        """The cluster-robust (sandwich) covariance of the fixed effects (beyond the R class, whose se.method = "robust" never
+        computes one): with eta = X beta, the weights w and Sigma = diag(w) + Z D Z' of information_matrix,
+            e = (y - h(eta)) d eta / d mu,   a = Sigma^-1 e,   G[c] = sum_{i in cluster c} x_i a_i,   B = G' G,
+            vcov = I^-1 B I^-1,   I = X' Sigma^-1 X.
+        cluster: n integer ids 0 .. ncl - 1, any partition of the observations; None: the connected components of the coupling
+        graph of Z L.  on = "device": the backend's `sandwich` export (csrc/sandwich.hip); "host": the definition as written,
+        in float64 numpy (np.linalg.solve(Sigma, e)), the components by components_of_rows(Z @ L).  adjust = "CR1" multiplies
+        vcov by G / (G - 1) * (n - 1) / (n - P), G the number of clusters; "CR0" leaves it.
+        -> dict(vcov, se, information, meat, scores, ncluster, adjust)"""
+        if on not in ("device", "host"):
+            raise ValueError("on should be 'device' or 'host'")
+        if adjust not in ("CR0", "CR1"):
+            raise ValueError("adjust should be 'CR0' or 'CR1'")
+        y = np.asarray(y, float).ravel()
+        beta, theta_cov = np.asarray(beta, float).ravel(), np.asarray(theta_cov, float).ravel()
+        n, P = self.X.shape
+        if cluster is not None:
+            cluster = np.asarray(cluster).ravel().astype(np.int32)
+            if cluster.size != n or cluster.min() < 0:
+                raise ValueError("cluster must hold %d ids from 0" % n)
+        if on == "device":
+            family = "gamma" if self.family == "Gamma" else self.family      # the exports' table is lower-case
+            r = self._be.sandwich(*self._ddata(), self.Z, self.X, y, family, self.link, beta, theta_cov, var_par=float(sigma),
+                                  cluster=cluster, scores=True)
+            info, meat, G, ncl = (np.asarray(r["information"]), np.asarray(r["meat"]), np.asarray(r["scores"]),
+                                  int(r["ncluster"]))
+        else:
+            with self._be.Context(self.cov, self.data, self.eff_range) as ctx:
+                D = ctx.gen_D(theta_cov)
+                if cluster is None:
+                    cluster, ncl = components_of_rows(self.Z @ ctx.gen_D(theta_cov, chol=True))
+                else:
+                    ncl = int(cluster.max()) + 1
+            xb = self.X @ beta
+            w = _dhdmu(xb, self.family, self.link)
+            if self.family == "gaussian":
+                w = w * sigma * sigma
+            elif self.family == "Gamma":
+                w = w * sigma
+            elif self.family == "beta":
+                w = w * (1 + sigma)
+            S = np.diag(w) + self.Z @ D @ self.Z.T
+            a = np.linalg.solve(S, _working_residual(y, xb, self.link))
+            G = np.zeros((ncl, P))
+            np.add.at(G, cluster, self.X * a[:, None])                  # observations ascending inside a cluster
+            info, meat = self.X.T @ np.linalg.solve(S, self.X), G.T @ G
+        vcov = np.linalg.solve(info, np.linalg.solve(info, meat).T)
+        if adjust == "CR1":
+            vcov = vcov * (ncl / (ncl - 1.0) * (n - 1.0) / (n - P))
+        with np.errstate(invalid="ignore"):
+            se = np.sqrt(np.diag(vcov))
+        return dict(vcov=vcov, se=se, information=info, meat=meat, scores=G, ncluster=ncl, adjust=adjust)
+
+    def _robust(self, fit, y, sandwich, cluster):
+        """MCML(..., sandwich=) / LA(..., sandwich=): the fit with its `robust` record, evaluated at the fitted parameters"""
+        P, R = self.X.shape[1], self.cov_parameters.size
+        th = fit["theta"]
+        sigma = th[P + R] if th.size > P + R else 1.0
+        r = self.sandwich(y, th[P:P + R], th[:P], sigma, cluster=cluster, on="device", adjust=sandwich)
+        fit["robust"] = dict(vcov=r["vcov"], se=r["se"], ncluster=r["ncluster"], adjust=r["adjust"])
+        return fit
+
+    @staticmethod
+    def _check_sandwich(sandwich):
+        if sandwich not in (None, "CR0", "CR1"):
+            raise ValueError("sandwich should be 'CR0', 'CR1' or None")
+
     def _rsq(self, theta, par_inds, zd):
         """approximate R-squared (R6ModelExtMCML.R:555-569)"""
         xb = self.X @ theta[par_inds["b"]]
@@ -367,7 +490,8 @@ class ModelMCML:
             raise ValueError("information should be 'host', 'device' or None")
         return "host" if information is None else information
 
-    def MCML(self, y, *args, trajectory=None, draws=None, theta_score=False, information=None, **kwargs):
+    def MCML(self, y, *args, trajectory=None, draws=None, theta_score=False, information=None, sandwich=None, cluster=None,
+             **kwargs):
         """_mcml below (its arguments, unchanged); trajectory ("step" / "component", None = leave the backend's default
         alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  draws ("hmc" / "exact" /
         "exact_component", None = leave the default alone): what the HMC sampler's call returns -- "exact" draws the conditional distribution of
@@ -380,7 +504,12 @@ class ModelMCML:
         the final estimate on re_samps (the backend's mvn_ll_grad) -- how far the theta-step stopped from a stationary point;
         False: nothing more is called.
         information ("host" / "device", None = "host"): where the GLS information matrix behind the "approx" standard errors
-        (and behind the fallback of "lik" / "robust") is computed -- information_matrix(on=)."""
+        (and behind the fallback of "lik" / "robust") is computed -- information_matrix(on=).
+        sandwich ("CR0" / "CR1", None = nothing more is called): the fit also carries `robust` = dict(vcov, se, ncluster,
+        adjust), the cluster-robust covariance of the fixed effects at the fitted parameters -- sandwich(on="device") with
+        `cluster` (n ids, None = the components of Z L's coupling graph).  The coefficient table and what se_method means
+        are untouched."""
+        self._check_sandwich(sandwich)
         prev_t = prev_d = None
         prev_i, use_i = self._information, self._use_information(information)
         if trajectory is not None:
@@ -396,6 +525,8 @@ class ModelMCML:
                 P = self.X.shape[1]
                 cov_par = fit["theta"][P:P + self.cov_parameters.size]
                 fit["theta_score"] = np.asarray(self._be.mvn_ll_grad(*self._ddata(), cov_par, fit["re_samps"])[1])
+            if sandwich is not None:
+                self._robust(fit, y, sandwich, cluster)
             return fit
         finally:
             self._information = prev_i
@@ -539,18 +670,21 @@ class ModelMCML:
                        re_samps=dsamps, iter=it, warnings=warnings, theta=theta)
 
     # ---- LA ------------------------------------------------------------------------------------------------------
-    def LA(self, y, *args, operator=None, information=None, **kwargs):
+    def LA(self, y, *args, operator=None, information=None, sandwich=None, cluster=None, **kwargs):
         """_la below (its arguments, unchanged); operator ("dense" / "component" / "component_wide", None = leave the
         backend's default alone): how the Laplace fit forms and factorises ZL' W ZL + I (csrc/component.hip).  It becomes the backend's default
         for the duration of the call and is restored afterwards.  information ("host" / "device", None = "host"): where the
-        GLS information matrix behind the standard errors without use_hess is computed -- information_matrix(on=)"""
+        GLS information matrix behind the standard errors without use_hess is computed -- information_matrix(on=).
+        sandwich ("CR0" / "CR1") and cluster: as MCML's -- the fit gains `robust`, the coefficient table is untouched"""
+        self._check_sandwich(sandwich)
         prev_i, self._information = self._information, self._use_information(information)
         prev = None
         try:
             if operator is not None:
                 prev = self._be.get_default_la_operator()
                 self._be.set_default_la_operator(operator)
-            return self._la(y, *args, **kwargs)
+            fit = self._la(y, *args, **kwargs)
+            return fit if sandwich is None else self._robust(fit, y, sandwich, cluster)
         finally:
             self._information = prev_i
             if prev is not None:

@@ -562,6 +562,8 @@ int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, double* out3);
 #include "glmmr_mcml_info.h"
 /* conditional prediction of the random effects at new locations (csrc/predict.hip): a header of its own */
 #include "glmmr_mcml_predict.h"
+/* the cluster-robust sandwich covariance of the fixed effects (csrc/sandwich.hip): a header of its own */
+#include "glmmr_mcml_sandwich.h"
 
 #ifdef __cplusplus
 }
