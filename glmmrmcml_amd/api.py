@@ -507,6 +507,18 @@ class Context:
         return _plan(_lib.lib().glmmr_mcml_dbg_band_plan, C.c_int, keys, self._h, {"fwd": 0, "bwd": 1}[which], int(chains),
                      bools=("used", "paired", "built"))
 
+    def band_extents(self, which="fwd"):
+        """the row-tile extents of the forward / backward operand of the banded kernel: (ext, issued, whole) -- an int
+        array (bands, 5, 2) of first / one-past-last nonzero K substep per 16-row tile, the MFMAs per 16-column strip
+        inside them, and those of the whole K tiles (test hook, include/glmmr_mcml_band.h glmmr_mcml_dbg_band_extents)"""
+        w = {"fwd": 0, "bwd": 1}[which]
+        out3 = (C.c_longlong * 3)()
+        _lib.check(_lib.lib().glmmr_mcml_dbg_band_extents(self._h, w, None, 0, out3))
+        ext = np.zeros((int(out3[0]), 5, 2), dtype=np.int32)
+        _lib.check(_lib.lib().glmmr_mcml_dbg_band_extents(self._h, w, ext.ctypes.data_as(C.POINTER(C.c_int)),
+                                                          int(ext.size), out3))
+        return ext, int(out3[1]), int(out3[2])
+
     def sparse_plan(self, chains):
         """the sparse chain-major operator as hmc_sample / log_prob_grad would run it with `chains` chains, valid after update_L (test hook,
         include/glmmr_mcml_c.h glmmr_mcml_dbg_sparse_plan)"""

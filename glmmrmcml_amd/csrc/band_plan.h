@@ -16,6 +16,9 @@ constexpr int BD_STAGE_BYTES = BD_A_BYTES + BD_B_BYTES;
 constexpr size_t BD_LDS_BYTES = (size_t)BD_STAGES * BD_STAGE_BYTES;   // 159744
 constexpr int BD_NA = 3, BD_NB = 4, BD_PER_TILE = BD_NA + BD_NB;      // LDS-DMA pieces per wave per tile
 constexpr int BD_TILE_ELEMS = BD_BM * BD_BN;                          // one raw accumulator tile (doubles)
+constexpr int BD_RT = BD_BM / 16;         // 16-row tiles of a band: one v_mfma_f64_16x16x4 accumulator each per strip
+constexpr int BD_SUB = BD_BK / 4;         // K substeps (4 columns: one MFMA per row tile and strip) of a K tile
+constexpr int BD_EXT = 2 * BD_RT;         // ints of a band's row-tile extents
 
 // one run of K tiles of one band.  slot < 0: the band's only run, the epilogue is applied here;
 // slot >= 0: the raw accumulator tile goes to partial slot `slot` of this column tile
@@ -23,11 +26,56 @@ struct BandItem { int band, kt0, kt1, slot; };
 // a band whose pieces k_band_reduce sums: slots [s0, s1) in K order
 struct BandRed { int band, s0, s1, pad; };
 
+// ---- row-tile extents ---------------------------------------------------------------------
+// Beside its K-tile range a band has, for each of its five 16-row tiles i, the K substeps [s0_i, s1_i) -- absolute,
+// 4 columns each -- outside which the row tile holds exact zeros (s0_i = s1_i: no nonzero, or past M): e[2 i], e[2 i + 1].
+// A K tile kt is INTERIOR when every row tile's extent covers all of it, [8 kt, 8 kt + 8): the kernel runs its plain tile
+// body there.  In an EDGE tile it issues the MFMA of row tile i in substep s only where band_ext_mask says so.  The same
+// three functions serve the kernel (dgemm_band.h), the flop accounting and the host test driver.
+#if defined(__HIPCC__)
+#define BD_HD __host__ __device__
+#else
+#define BD_HD
+#endif
+// the interior K tiles [lo, hi) of a band (absolute; lo >= hi: none)
+BD_HD inline void band_ext_interior(const int* e, int& lo, int& hi)
+{
+    int s0 = e[0], s1 = e[1];
+    for (int i = 1; i < BD_RT; ++i) { if (e[2 * i] > s0) s0 = e[2 * i]; if (e[2 * i + 1] < s1) s1 = e[2 * i + 1]; }
+    lo = (s0 + BD_SUB - 1) / BD_SUB; hi = s1 / BD_SUB;
+}
+// bit s (0..7) set: K substep 8 kt + s lies inside [s0, s1)
+BD_HD inline unsigned band_ext_mask(int s0, int s1, int kt)
+{
+    int a = s0 - BD_SUB * kt, b = s1 - BD_SUB * kt;
+    a = a < 0 ? 0 : a;
+    b = b > BD_SUB ? BD_SUB : b;
+    return b > a ? ((1u << b) - 1u) & ~((1u << a) - 1u) : 0u;      // 0 <= a < b <= 8 where it shifts
+}
+// MFMAs per 16-column strip that the K tiles [kt0, kt1) of a band issue
+inline long band_ext_issued(const int* e, int kt0, int kt1)
+{
+    long n = 0;
+    for (int i = 0; i < BD_RT; ++i) {
+        const int a = std::max(e[2 * i], BD_SUB * kt0), b = std::min(e[2 * i + 1], BD_SUB * kt1);
+        if (b > a) n += b - a;
+    }
+    return n;
+}
+
+// GLMMR_MCML_BAND_ROWTILES=0: every K tile of a band's range is multiplied whole, no row-tile extents (read per call)
+static inline bool band_rowtiles_enabled()
+{
+    const char* e = getenv("GLMMR_MCML_BAND_ROWTILES");
+    return !(e && !strcmp(e, "0"));
+}
+
 // ---- host: the decomposition ------------------------------------------------------------
 struct BandPlanDev {
     int gn = 0, nwg = 0, nred = 0, nslots = 0;
     int paired = 0;                       // decompose() chose whole bands, no partial sums (else streamed)
     DevBuf items, wg_ptr, red, part;
+    DevBuf ext;                           // the row-tile extents, BD_EXT ints per band
 };
 
 // the few-column products (dgemm_skinny.h): chunk range of every 256-row block, partial sums
@@ -40,18 +88,26 @@ struct SkinnyPlan {
 struct BandPlan {
     int M = 0, K = 0, nbands = 0;
     std::vector<int> kr;                  // host copy of the K-tile ranges, 2 per band
+    std::vector<int> ext;                 // host copy of the row-tile extents, BD_EXT per band
     long tiles = 0;                       // sum over bands of K tiles multiplied
+    long mfmas = 0;                       // sum over bands of the MFMAs per 16-column strip inside the extents
     std::map<int, std::unique_ptr<BandPlanDev>> by_gn;
     std::unique_ptr<SkinnyPlan> skinny;
 
-    void reset(int M_, int K_, const std::vector<int>& kr_)
+    void reset(int M_, int K_, const std::vector<int>& kr_, const std::vector<int>& ext_)
     {
-        M = M_; K = K_; kr = kr_; nbands = (M + BD_BM - 1) / BD_BM;
-        tiles = 0;
-        for (int b = 0; b < nbands; ++b) tiles += kr[2 * b + 1] - kr[2 * b];
+        M = M_; K = K_; kr = kr_; ext = ext_; nbands = (M + BD_BM - 1) / BD_BM;
+        tiles = 0; mfmas = 0;
+        for (int b = 0; b < nbands; ++b) {
+            tiles += kr[2 * b + 1] - kr[2 * b];
+            mfmas += band_ext_issued(ext.data() + BD_EXT * b, kr[2 * b], kr[2 * b + 1]);
+        }
         by_gn.clear();
         skinny.reset();
     }
+
+    // MFMAs per 16-column strip that a launch issues: inside the extents, or every one of the K tiles' (the switch off)
+    long issued(bool rowtiles) const { return rowtiles ? mfmas : tiles * (BD_RT * BD_SUB); }
 
     // target_wg: workgroups the launch should have in all (one per CU).  Returns true for the whole-band form.  The
     // plan is a function of (kr, nbands, gn, target_wg) alone.
@@ -151,6 +207,8 @@ struct BandPlan {
         MCML_TRY(d->wg_ptr.ensure(sizeof(int) * wg_ptr.size()));
         MCML_HIP(hipMemcpyAsync(d->items.p, items.data(), sizeof(BandItem) * items.size(), hipMemcpyHostToDevice, s));
         MCML_HIP(hipMemcpyAsync(d->wg_ptr.p, wg_ptr.data(), sizeof(int) * wg_ptr.size(), hipMemcpyHostToDevice, s));
+        MCML_TRY(d->ext.ensure(sizeof(int) * (ext.size() + 1)));
+        MCML_HIP(hipMemcpyAsync(d->ext.p, ext.data(), sizeof(int) * ext.size(), hipMemcpyHostToDevice, s));
         if (nslots > 0) {
             MCML_TRY(d->red.ensure(sizeof(BandRed) * red.size()));
             MCML_HIP(hipMemcpyAsync(d->red.p, red.data(), sizeof(BandRed) * red.size(), hipMemcpyHostToDevice, s));

@@ -419,8 +419,10 @@ extern "C" int glmmr_mcml_ctx_profile(glmmr_mcml_ctx* h, int enable, int reset, 
         double ff = dense, fb = dense, kind = 0;
         if (c.sp.active) { ff = fb = 2.0 * (double)c.sp.nnz * C; kind = 2; }
         else {
-            if (c.band_fwd) { ff = 2.0 * 80.0 * 32.0 * (double)c.band_fwd_tiles * C; kind = 1; }
-            if (c.band_bwd) { fb = 2.0 * 80.0 * 32.0 * (double)c.band_bwd_tiles * C; kind = 1; }
+            // the MFMAs issued (band_plan.h: inside the row-tile extents), 2 * 16 * 16 * 4 flop each, C / 16 strips
+            const bool rt = band_rowtiles_enabled();
+            if (c.band_fwd) { ff = 2.0 * 16.0 * 4.0 * (double)c.plan_fwd.issued(rt) * C; kind = 1; }
+            if (c.band_bwd) { fb = 2.0 * 16.0 * 4.0 * (double)c.plan_bwd.issued(rt) * C; kind = 1; }
         }
         out8[4] = ff; out8[5] = fb; out8[6] = dense; out8[7] = kind;
     }

@@ -54,6 +54,20 @@ extern "C" int glmmr_mcml_dbg_band_plan(glmmr_mcml_ctx* h, int which, int chains
     return MCML_OK;
 }
 
+// read-only: the host copy of the row-tile extents of the forward (which = 0) or backward (1) operand, 10 ints per band
+// (band_plan.h), as many bands as fit `cap` ints; out3 = [bands, MFMAs per 16-column strip inside the extents, MFMAs per
+// strip of the whole K tiles]
+extern "C" int glmmr_mcml_dbg_band_extents(glmmr_mcml_ctx* h, int which, int* ext, int cap, long long* out3)
+{
+    MCML_REQUIRE(h && (which == 0 || which == 1) && out3 && (ext || cap == 0), "dbg_band_extents: bad argument");
+    const Ctx& c = h->c;
+    const BandPlan& bp = which ? c.plan_bwd : c.plan_fwd;
+    const int nb = c.sp.active ? 0 : bp.nbands;
+    out3[0] = nb; out3[1] = nb ? bp.issued(true) : 0; out3[2] = nb ? bp.issued(false) : 0;
+    for (int i = 0; i < cap && i < BD_EXT * nb; ++i) ext[i] = bp.ext[i];
+    return MCML_OK;
+}
+
 // read-only: the form of the sparse (chain-major) ZL operator and the kernels the HMC sampler launches on it for `chains`
 // chains (ncb follows `chains`; nuts.h launches on the width of its active set) -- the decisions are the functions of sparse_plan.h that hmc.hip launches by
 extern "C" int glmmr_mcml_dbg_sparse_plan(glmmr_mcml_ctx* h, int chains, long long* out12)

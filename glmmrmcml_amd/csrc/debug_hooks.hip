@@ -142,12 +142,12 @@ extern "C" int glmmr_mcml_dbg_dgemm_bench2(int M, int N, int K, int b_nmajor, in
 // buffer whose columns are zero-padded to a multiple of 32, B's rows likewise, the K-tile ranges come from
 // k_band_ranges.  For tests/ only.
 static int dbg_dgemm_band(int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc,
-                          int* tiles_executed, int form, int* whole_band);
+                          int* tiles_executed, int form, int* whole_band, int* ext_out, int ext_cap, long long* mfmas_issued);
 
 extern "C" int glmmr_mcml_dbg_dgemm_band(int M, int N, int K, const double* A, int lda, const double* B, int ldb,
                                          double* C, int ldc, int* tiles_executed)
 {
-    return dbg_dgemm_band(M, N, K, A, lda, B, ldb, C, ldc, tiles_executed, BAND_FORM_AUTO, nullptr);
+    return dbg_dgemm_band(M, N, K, A, lda, B, ldb, C, ldc, tiles_executed, BAND_FORM_AUTO, nullptr, nullptr, 0, nullptr);
 }
 
 // The same through the form asked for -- 0: the 8-wave kernel, 1: the feeder form (dgemm_band.h), whatever production
@@ -156,11 +156,21 @@ extern "C" int glmmr_mcml_dbg_dgemm_band_form(int M, int N, int K, const double*
                                               double* C, int ldc, int* tiles_executed, int form, int* whole_band)
 {
     MCML_REQUIRE(form == BAND_FORM_8WAVE || form == BAND_FORM_FEED, "dbg_dgemm_band_form: form is 0 or 1");
-    return dbg_dgemm_band(M, N, K, A, lda, B, ldb, C, ldc, tiles_executed, form, whole_band);
+    return dbg_dgemm_band(M, N, K, A, lda, B, ldb, C, ldc, tiles_executed, form, whole_band, nullptr, 0, nullptr);
+}
+
+// The same, and the host copy of the operand's row-tile extents (band_plan.h: 10 ints per 80-row band, ext_cap ints of room)
+// with the MFMAs per 16-column strip the launch issued (GLMMR_MCML_BAND_ROWTILES honoured)
+extern "C" int glmmr_mcml_dbg_dgemm_band_ext(int M, int N, int K, const double* A, int lda, const double* B, int ldb,
+                                             double* C, int ldc, int form, int* ext_out, int ext_cap, long long* mfmas_issued)
+{
+    MCML_REQUIRE(form == BAND_FORM_8WAVE || form == BAND_FORM_FEED, "dbg_dgemm_band_ext: form is 0 or 1");
+    MCML_REQUIRE(ext_out && mfmas_issued, "dbg_dgemm_band_ext: null argument");
+    return dbg_dgemm_band(M, N, K, A, lda, B, ldb, C, ldc, nullptr, form, nullptr, ext_out, ext_cap, mfmas_issued);
 }
 
 static int dbg_dgemm_band(int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc,
-                          int* tiles_executed, int form, int* whole_band)
+                          int* tiles_executed, int form, int* whole_band, int* ext_out, int ext_cap, long long* mfmas_issued)
 {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -181,13 +191,19 @@ static int dbg_dgemm_band(int M, int N, int K, const double* A, int lda, const d
     MCML_REQUIRE(dlds_applicable(M, N, K, dA.d(), dA.ld, dA.cols_alloc, dB.d(), dB.ld), "dbg_dgemm_band: contract");
     const int nbands = (M + BD_BM - 1) / BD_BM;
     DevBuf kr;
-    MCML_TRY(kr.ensure(sizeof(int) * 2 * nbands));
-    hipLaunchKernelGGL(k_band_ranges, dim3(nbands), dim3(256), 0, s, dA.d(), dA.ld, M, K, kr.as<int>());
+    MCML_TRY(kr.ensure(sizeof(int) * (2 + BD_EXT) * nbands));
+    hipLaunchKernelGGL(k_band_ranges, dim3(nbands), dim3(256), 0, s, dA.d(), dA.ld, M, K, kr.as<int>(), kr.as<int>() + 2 * nbands);
     MCML_HIP(hipGetLastError());
-    std::vector<int> hk(2 * nbands);
+    std::vector<int> hk(2 * nbands), he(BD_EXT * nbands);
     MCML_HIP(hipMemcpy(hk.data(), kr.p, sizeof(int) * 2 * nbands, hipMemcpyDeviceToHost));
+    MCML_HIP(hipMemcpy(he.data(), kr.as<int>() + 2 * nbands, sizeof(int) * BD_EXT * nbands, hipMemcpyDeviceToHost));
     BandPlan plan;
-    plan.reset(M, K, hk);
+    plan.reset(M, K, hk, he);
+    if (ext_out) {
+        MCML_REQUIRE(ext_cap >= BD_EXT * nbands, "dbg_dgemm_band: ext_out too small");
+        memcpy(ext_out, he.data(), sizeof(int) * he.size());
+    }
+    if (mfmas_issued) *mfmas_issued = plan.issued(band_rowtiles_enabled());
     if (tiles_executed) *tiles_executed = (int)plan.tiles;
     EpiAxpby epi{dC.d(), dC.ld, 1.0, 0.0};
     MCML_TRY(launch_gemm_band(s, plan, N, dA.d(), dA.ld, dB.d(), dB.ld, epi, nullptr, 0, form, whole_band));
@@ -230,14 +246,15 @@ extern "C" int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, dou
     MCML_TRY(dC.alloc(M, N));
     const int nbands = (M + BD_BM - 1) / BD_BM;
     DevBuf kr, clk;
-    MCML_TRY(kr.ensure(sizeof(int) * 2 * nbands));
+    MCML_TRY(kr.ensure(sizeof(int) * (2 + BD_EXT) * nbands));
     MCML_TRY(clk.ensure(16));
     MCML_HIP(hipMemset(clk.p, 0, 16));
-    hipLaunchKernelGGL(k_band_ranges, dim3(nbands), dim3(256), 0, s, dA.d(), dA.ld, M, M, kr.as<int>());
-    std::vector<int> hk(2 * nbands);
+    hipLaunchKernelGGL(k_band_ranges, dim3(nbands), dim3(256), 0, s, dA.d(), dA.ld, M, M, kr.as<int>(), kr.as<int>() + 2 * nbands);
+    std::vector<int> hk(2 * nbands), he(BD_EXT * nbands);
     MCML_HIP(hipMemcpy(hk.data(), kr.p, sizeof(int) * 2 * nbands, hipMemcpyDeviceToHost));
+    MCML_HIP(hipMemcpy(he.data(), kr.as<int>() + 2 * nbands, sizeof(int) * BD_EXT * nbands, hipMemcpyDeviceToHost));
     BandPlan plan;
-    plan.reset(M, M, hk);
+    plan.reset(M, M, hk, he);
     const double tiles = (double)plan.tiles;
     EpiAxpby epi{dC.d(), dC.ld, 1.0, 0.0};
     if (mode < 0) {

@@ -6,6 +6,14 @@
 // nothing.  When L is refreshed, k_band_ranges records for every 80-row band of the A operand
 // the first and last K tile that holds a nonzero; the kernel runs each band's K loop over that
 // range only.  Skipping exact zeros does not change any sum (0*x adds nothing for finite x).
+// Inside that range the operand is still ragged at the granularity of an MFMA (a triangle's diagonal crosses the last
+// 2.5 - 3 K tiles of a band, the last band may have fewer than 80 rows, K is padded to a multiple of 32): the same scan
+// records per 16-row tile of a band the K substeps (4 columns = one v_mfma_f64_16x16x4) between its first and last nonzero
+// (the row-tile extents, band_plan.h).  K tiles that every row tile's extent covers whole are INTERIOR and run the plain
+// tile body; the others are EDGE tiles: same LDS reads, waits and barrier, but the MFMA of row tile i in substep s is
+// issued only inside the extent -- a scalar branch per row tile and substep in the MFMA waves.  An item's K loop is three
+// loops in a row, edge / interior / edge; fill, DMA, barriers, ring and epilogues do not know about it.
+// GLMMR_MCML_BAND_ROWTILES=0: no extents, every tile interior.
 //
 // Work decomposition (BandPlan, built on the host per number of column tiles):
 //   * whole bands (BandPlanDev::paired): a workgroup owns a group of whole bands of one column
@@ -61,37 +69,56 @@ struct BandP {
     GemmP g;
     const BandItem* items;
     const int* wg_ptr;     // items of workgroup w (of any column tile): [wg_ptr[w], wg_ptr[w+1])
+    const int* ext;        // row-tile extents, BD_EXT ints per band; null: every K tile is multiplied whole
     int nwg;               // workgroups per column tile
     double* part;          // partial tiles: [(slot * gn + column tile) * BD_TILE_ELEMS]
     int mode;              // DBG kernels only -- bit 16: per-workgroup phase stamps into clocks[8 ..]
     unsigned long long* clocks;   // DBG kernels only (nullable): workgroup 0 adds its shader-clock and 100 MHz real-time ticks
 };
 
-// first / last nonzero K tile of every 80-row band of A (M x K, column-major)
-static __global__ __launch_bounds__(256) void k_band_ranges(const double* A, int lda, int M, int K, int* krange)
+// first / last nonzero K tile of every 80-row band of A (M x K, column-major) -> krange, 2 ints per band, and of the
+// same scan the first / one-past-last nonzero K substep (4 columns) of each of the band's five 16-row tiles -> ext,
+// BD_EXT ints per band (band_plan.h; a row tile without a nonzero, or past M: s0 = s1 = 0)
+static __global__ __launch_bounds__(256) void k_band_ranges(const double* A, int lda, int M, int K, int* krange, int* ext)
 {
-    __shared__ int smin[256], smax[256];
+    __shared__ int smin[BD_RT][256], smax[BD_RT][256];
     const int band = blockIdx.x, r0 = band * BD_BM;
     const int rows = (M - r0 < BD_BM) ? (M - r0) : BD_BM;
-    int kmin = 1 << 30, kmax = -1;
+    int kmin[BD_RT], kmax[BD_RT];
+#pragma unroll
+    for (int i = 0; i < BD_RT; ++i) { kmin[i] = 1 << 30; kmax[i] = -1; }
     for (int k = threadIdx.x; k < K; k += 256) {
         const double* col = A + r0 + (size_t)k * lda;
-        bool nz = false;
-        for (int r = 0; r < rows; ++r) nz |= (col[r] != 0.0);
-        if (nz) { kmin = min(kmin, k); kmax = max(kmax, k); }
+#pragma unroll
+        for (int i = 0; i < BD_RT; ++i) {
+            bool nz = false;
+            for (int r = 16 * i; r < 16 * i + 16 && r < rows; ++r) nz |= (col[r] != 0.0);
+            if (nz) { kmin[i] = min(kmin[i], k); kmax[i] = max(kmax[i], k); }
+        }
     }
-    smin[threadIdx.x] = kmin; smax[threadIdx.x] = kmax;
+#pragma unroll
+    for (int i = 0; i < BD_RT; ++i) { smin[i][threadIdx.x] = kmin[i]; smax[i][threadIdx.x] = kmax[i]; }
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) {
-            smin[threadIdx.x] = min(smin[threadIdx.x], smin[threadIdx.x + o]);
-            smax[threadIdx.x] = max(smax[threadIdx.x], smax[threadIdx.x + o]);
+#pragma unroll
+            for (int i = 0; i < BD_RT; ++i) {
+                smin[i][threadIdx.x] = min(smin[i][threadIdx.x], smin[i][threadIdx.x + o]);
+                smax[i][threadIdx.x] = max(smax[i][threadIdx.x], smax[i][threadIdx.x + o]);
+            }
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        if (smax[0] < 0) { krange[2 * band] = 0; krange[2 * band + 1] = 0; }
-        else { krange[2 * band] = smin[0] / BD_BK; krange[2 * band + 1] = smax[0] / BD_BK + 1; }
+        int lo = 1 << 30, hi = -1;
+        for (int i = 0; i < BD_RT; ++i) {
+            const int a = smin[i][0], b = smax[i][0];
+            ext[BD_EXT * band + 2 * i] = b < 0 ? 0 : a / 4;
+            ext[BD_EXT * band + 2 * i + 1] = b < 0 ? 0 : b / 4 + 1;
+            lo = min(lo, a); hi = max(hi, b);
+        }
+        if (hi < 0) { krange[2 * band] = 0; krange[2 * band + 1] = 0; }
+        else { krange[2 * band] = lo / BD_BK; krange[2 * band + 1] = hi / BD_BK + 1; }
     }
 }
 
@@ -143,6 +170,20 @@ __device__ __forceinline__ void bd_mfma(d4 (&acc)[NS][5][1], const double (&a)[5
         for (int i = 0; i < 5; ++i) acc[j][i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a[i], acc[j][i][0], 0, 0, 0);
 }
 
+// the MFMAs of an edge K tile (band_plan.h): row tile i of substep KS only where its extent reaches, m[i] bit KS -- a
+// wave-uniform condition, a scalar branch around the row tile's NS MFMAs.  Every accumulator still sees its MFMAs in K order.
+template <int KS, int NS>
+__device__ __forceinline__ void bd_mfma_ext(d4 (&acc)[NS][5][1], const double (&a)[5], const double (&b)[NS], const unsigned (&m)[5])
+{
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+        if (m[i] & (1u << KS)) {
+            asm volatile("" ::: "memory");      // a branch, not both arms and a select
+#pragma unroll
+            for (int j = 0; j < NS; ++j) acc[j][i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a[i], acc[j][i][0], 0, 0, 0);
+        }
+}
+
 // The item list is read with a SCALAR load (hand-written: the compiler will not scalarise a load it
 // cannot prove unclobbered by the epilogue's stores).  A vector load here sits behind the previous item's
 // epilogue stores -- vector memory completes in order, its `s_waitcnt vmcnt(0)` drains every store before
@@ -159,6 +200,23 @@ __device__ __forceinline__ BandItem band_item(const BandItem* ip)
     item = *ip;
 #endif
     return item;
+}
+
+// a band's row-tile extents, read like the item
+__device__ __forceinline__ void band_ext_load(const int* ep, int (&e)[BD_EXT])
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef int i8s __attribute__((ext_vector_type(8)));
+    typedef int i2s __attribute__((ext_vector_type(2)));
+    i8s lo; i2s hi;
+    asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dwordx2 %1, %2, 0x20\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(lo), "=&s"(hi) : "s"(ep) : "memory");
+#pragma unroll
+    for (int i = 0; i < 8; ++i) e[i] = lo[i];
+    e[8] = hi.x; e[9] = hi.y;
+#else
+    for (int i = 0; i < BD_EXT; ++i) e[i] = ep[i];
+#endif
 }
 
 // ---- the fill role ------------------------------------------------------------------------
@@ -303,10 +361,25 @@ __device__ __forceinline__ void band_walk(const BandP& bp, const Epi& epi, const
     // fill's memory latency runs under the epilogue's loads and stores instead of after them
     bool pre = false;
     int issued = 0;
-    if (it0 < it1) fill.load_item(it0);
+    // MFMA waves: the item's band's row-tile extents (without them: every row tile reaches everywhere, every K tile is
+    // interior -- GLMMR_MCML_BAND_ROWTILES=0)
+    int ext[BD_EXT];
+    auto load_ext = [&]() {
+        if constexpr (NS > 0) {
+            if (bp.ext) band_ext_load(bp.ext + BD_EXT * fill.item.band, ext);
+            else {
+#pragma unroll
+                for (int i = 0; i < BD_RT; ++i) { ext[2 * i] = 0; ext[2 * i + 1] = 1 << 30; }
+            }
+        }
+    };
+    if (it0 < it1) { fill.load_item(it0); load_ext(); }
     for (int it = it0; it < it1;) {
         const int band = fill.item.band, slot = fill.item.slot;
-        const int nk = fill.item.kt1 - fill.item.kt0;
+        const int kt0 = fill.item.kt0, nk = fill.item.kt1 - kt0;
+        // tiles [il, ih) of this item are interior: two uniform bounds
+        int il = 0, ih = 0;
+        if constexpr (NS > 0) { band_ext_interior(ext, il, ih); il -= kt0; ih -= kt0; }
 
         d4 acc[NJ][5][1];
 #pragma unroll
@@ -325,43 +398,71 @@ __device__ __forceinline__ void band_walk(const BandP& bp, const Epi& epi, const
             int st = 0;
             double ra[2][5], rb[2][NJ];
             if constexpr (NS > 0) bd_read<0>(ra[0], rb[0], aoff, boff);
-            for (int kt = 0; kt < nk; ++kt) {
-                // the stage tile kt - 1 was read from: every wave finished its reads before that tile's barrier
-                if (issued < nk) {
-                    int sn = st + BD_STAGES - 1; if (sn >= BD_STAGES) sn -= BD_STAGES;
-                    fill.issue(sn);
-                    ++issued;
-                }
-                const unsigned aaddr = aoff + st * BD_STAGE_BYTES, baddr = boff + st * BD_STAGE_BYTES;
-                int stn = st + 1; if (stn >= BD_STAGES) stn = 0;
-                if constexpr (NS > 0) {
-#define BD_STEP(KS, CUR, NXT)                                   \
+            // The K loop: LAST tiles of it with the tile body BODY.  The stage of tile kt - 1 is free to fill: every wave
+            // finished its reads before that tile's barrier.
+#define BD_KLOOP(LAST, BODY)                                                                         \
+            for (; kt < (LAST); ++kt) {                                                              \
+                if (issued < nk) {                                                                   \
+                    int sn = st + BD_STAGES - 1; if (sn >= BD_STAGES) sn -= BD_STAGES;               \
+                    fill.issue(sn);                                                                  \
+                    ++issued;                                                                        \
+                }                                                                                    \
+                const unsigned aaddr = aoff + st * BD_STAGE_BYTES, baddr = boff + st * BD_STAGE_BYTES; \
+                int stn = st + 1; if (stn >= BD_STAGES) stn = 0;                                     \
+                BODY                                                                                 \
+                st = stn;                                                                            \
+            }
+            // The tile body of an MFMA wave, MFMA being all of a substep's MFMAs or those inside the extents.  Last
+            // substep: synchronise first (this wave's pieces of tile kt + 1 landed, its own reads of tile kt complete),
+            // start the next tile's first reads, then the MFMAs
+#define BD_STEP(KS, CUR, NXT, MFMA)                                  \
                     bd_read<KS + 1>(ra[NXT], rb[NXT], aaddr, baddr); \
                     bd_wait<5 + NS>(ra[CUR], rb[CUR]);               \
-                    bd_mfma(acc, ra[CUR], rb[CUR]);                  \
+                    MFMA(KS, CUR);                                   \
                     __builtin_amdgcn_sched_barrier(0);
-                    BD_STEP(0, 0, 1) BD_STEP(1, 1, 0) BD_STEP(2, 0, 1) BD_STEP(3, 1, 0)
-                    BD_STEP(4, 0, 1) BD_STEP(5, 1, 0) BD_STEP(6, 0, 1)
-#undef BD_STEP
-                }
-                // last substep: synchronise first (this wave's pieces of tile kt + 1 landed, its own
-                // reads of tile kt complete), start the next tile's first reads, then the MFMAs
-                fill.wait_leave(issued - kt - 2);
-                if constexpr (NS > 0) bd_wait<0>(ra[1], rb[1]);
-                __builtin_amdgcn_s_barrier();
-                if constexpr (NS > 0) {
-                    if (kt + 1 < nk) bd_read<0>(ra[0], rb[0], aoff + stn * BD_STAGE_BYTES, boff + stn * BD_STAGE_BYTES);
-                    bd_mfma(acc, ra[1], rb[1]);
+#define BD_TILE(MFMA)                                                                                                     \
+                    BD_STEP(0, 0, 1, MFMA) BD_STEP(1, 1, 0, MFMA) BD_STEP(2, 0, 1, MFMA) BD_STEP(3, 1, 0, MFMA)           \
+                    BD_STEP(4, 0, 1, MFMA) BD_STEP(5, 1, 0, MFMA) BD_STEP(6, 0, 1, MFMA)                                  \
+                    fill.wait_leave(issued - kt - 2);                                                                     \
+                    bd_wait<0>(ra[1], rb[1]);                                                                             \
+                    __builtin_amdgcn_s_barrier();                                                                         \
+                    if (kt + 1 < nk) bd_read<0>(ra[0], rb[0], aoff + stn * BD_STAGE_BYTES, boff + stn * BD_STAGE_BYTES);  \
+                    MFMA(7, 1);                                                                                           \
                     __builtin_amdgcn_sched_barrier(0);
-                }
-                st = stn;
+#define BD_MFMA_ALL(KS, CUR) bd_mfma(acc, ra[CUR], rb[CUR])
+#define BD_MFMA_EXT(KS, CUR) bd_mfma_ext<KS>(acc, ra[CUR], rb[CUR], em)
+            // an edge tile: the same reads, waits and barrier; per row tile the substeps inside its extent
+#define BD_TILE_EDGE                                                                                                      \
+                    unsigned em[BD_RT];                                                                                   \
+                    _Pragma("unroll")                                                                                     \
+                    for (int i = 0; i < BD_RT; ++i) em[i] = band_ext_mask(ext[2 * i], ext[2 * i + 1], kt0 + kt);          \
+                    BD_TILE(BD_MFMA_EXT)
+            int kt = 0;
+            if constexpr (NS > 0) {
+                // edge tiles [0, e0), interior tiles [e0, e1), edge tiles [e1, nk): three loops in a row, so that the
+                // accumulators stay in their registers from one to the next (as two arms of one loop's body they were
+                // copied, all 80 registers, where the arms meet) and the interior loop is the loop it was
+                const int e0 = il < 0 ? 0 : (il < nk ? il : nk);
+                const int e1 = ih < e0 ? e0 : (ih < nk ? ih : nk);
+                BD_KLOOP(e0, BD_TILE_EDGE)
+                BD_KLOOP(e1, BD_TILE(BD_MFMA_ALL))
+                BD_KLOOP(nk, BD_TILE_EDGE)
+            } else {
+                BD_KLOOP(nk, fill.wait_leave(issued - kt - 2); __builtin_amdgcn_s_barrier();)
             }
+#undef BD_TILE_EDGE
+#undef BD_MFMA_EXT
+#undef BD_MFMA_ALL
+#undef BD_TILE
+#undef BD_STEP
+#undef BD_KLOOP
         }
         if (first_item) stamp(2);
         ++it;
         pre = false;
         if (it < it1) {
             fill.load_item(it);
+            load_ext();
             const int nkn = fill.item.kt1 - fill.item.kt0;
             if (nk > 0 && nkn > 0) {
                 issued = 0;
@@ -486,6 +587,7 @@ static inline int launch_gemm_band(hipStream_t s, BandPlan& plan, int N, const d
     bp.items = d->items.as<BandItem>();
     bp.wg_ptr = d->wg_ptr.as<int>();
     bp.nwg = d->nwg;
+    bp.ext = band_rowtiles_enabled() ? d->ext.as<int>() : nullptr;
     bp.part = d->part.d();
     if (whole_band) *whole_band = d->paired;
     bool feed = false;

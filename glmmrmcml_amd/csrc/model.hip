@@ -296,25 +296,27 @@ int model_update_L(Ctx& c)
     c.band_fwd = c.band_bwd = false;
     const char* env = getenv("GLMMR_MCML_GEMM");
     if (!(env && (!strcmp(env, "reg") || !strcmp(env, "dlds")))) {
-        auto ranges = [&](const DevMat& A, int M, int K, BandPlan& plan, bool& use, long& ntiles) -> int {
+        auto ranges = [&](const DevMat& A, int M, int K, BandPlan& plan, bool& use) -> int {
             const int nb = (M + BD_BM - 1) / BD_BM;
-            MCML_TRY(c.kr_scratch.ensure(sizeof(int) * 2 * (size_t)nb));
-            hipLaunchKernelGGL(k_band_ranges, dim3(nb), dim3(256), 0, c.stream, A.d(), A.ld, M, K, c.kr_scratch.as<int>());
+            // the K-tile ranges, 2 ints per band, then the row-tile extents, BD_EXT per band
+            MCML_TRY(c.kr_scratch.ensure(sizeof(int) * (2 + BD_EXT) * (size_t)nb));
+            hipLaunchKernelGGL(k_band_ranges, dim3(nb), dim3(256), 0, c.stream, A.d(), A.ld, M, K, c.kr_scratch.as<int>(),
+                               c.kr_scratch.as<int>() + 2 * (size_t)nb);
             MCML_HIP(hipGetLastError());
-            std::vector<int> h(2 * (size_t)nb);
-            MCML_TRY(copy_d2h(h.data(), c.kr_scratch.p, sizeof(int) * h.size(), c.stream));
+            std::vector<int> all((2 + BD_EXT) * (size_t)nb);
+            MCML_TRY(copy_d2h(all.data(), c.kr_scratch.p, sizeof(int) * all.size(), c.stream));
             MCML_HIP(hipStreamSynchronize(c.stream));
-            // the K-tile ranges of a triangular ZL do not change from one MCML iteration to the next: keep the device
-            // plans (work lists, partial-tile buffers) unless they did
-            if (!(plan.M == M && plan.K == K && plan.kr == h))
-                plan.reset(M, K, h);           // the per-chain-count decompositions are rebuilt on first use
+            const std::vector<int> h(all.begin(), all.begin() + 2 * (size_t)nb), he(all.begin() + 2 * (size_t)nb, all.end());
+            // the K-tile ranges and the extents of a triangular ZL do not change from one MCML iteration to the next: keep
+            // the device plans (work lists, partial-tile buffers) unless they did
+            if (!(plan.M == M && plan.K == K && plan.kr == h && plan.ext == he))
+                plan.reset(M, K, h, he);       // the per-chain-count decompositions are rebuilt on first use
             const long dense = (long)nb * ((K + BD_BK - 1) / BD_BK);
             use = (env && !strcmp(env, "band")) || plan.tiles * 5 <= dense * 4;
-            ntiles = plan.tiles;
             return MCML_OK;
         };
-        MCML_TRY(ranges(c.ZL, c.n, c.Q, c.plan_fwd, c.band_fwd, c.band_fwd_tiles));
-        MCML_TRY(ranges(c.ZLT, c.Q, c.n, c.plan_bwd, c.band_bwd, c.band_bwd_tiles));
+        MCML_TRY(ranges(c.ZL, c.n, c.Q, c.plan_fwd, c.band_fwd));
+        MCML_TRY(ranges(c.ZLT, c.Q, c.n, c.plan_bwd, c.band_bwd));
     }
     return MCML_OK;
 }

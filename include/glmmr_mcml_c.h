@@ -564,6 +564,8 @@ int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, double* out3);
 #include "glmmr_mcml_predict.h"
 /* the cluster-robust sandwich covariance of the fixed effects (csrc/sandwich.hip): a header of its own */
 #include "glmmr_mcml_sandwich.h"
+/* test hooks of the banded products' row-tile extents (csrc/band_plan.h): a header of its own */
+#include "glmmr_mcml_band.h"
 
 #ifdef __cplusplus
 }
