@@ -1,9 +1,23 @@
 // component.h -- the device side of the component plan (component_plan.h), in one place: the view a kernel takes of the
 // resident records, the idioms every kernel on the components shares, and the launchers of component.hip.
 //
-// Three opt-in paths run on the components: the HMC trajectories of hmc_traj.h, the component operator of the
-// Laplace fits (laplace.hip, 5.5) and the exact draws of hmc_exact_comp.h (5.8); the last two factorise through lac_factor_launch.
+// Five opt-in paths run on the components: the HMC trajectories of hmc_traj.h, the component operator of the
+// Laplace fits (laplace.hip, 5.5), the exact draws of hmc_exact_comp.h (5.8), the information query (info.hip, 5.9) and the
+// sandwich (sandwich.hip, 5.11); the last four factorise through lac_factor_launch.
 // k_cm_traj and k_exc_draw stay in the sampler's translation unit (glm.h, rng.h, hmc_chain.h) and take the CompView.
+//
+// APPLYING A FACTOR.  Whoever needs M^-1 or R^-1 on a few columns after the factor kernels calls, in this order,
+//   comp_operator_ready    the one predicate: L set, the sparse operator active, records built
+//   comp_factors_ensure    the factor scratch (CompFactors, ctx.h): offsets uploaded once per model, fac and logdet sized
+//   comp_rhs_csr_launch    B = ZL' V over the CSR rows of ZL', observations ascending, for ncols columns
+//   lac_factor_launch      with fac / fac_ptr of the CompFactors
+//   comp_solve_launch      R_c s = b (and R_c' t = s) in place, component by component in LDS
+// The packed-triangle layout, its LDS budget and the two substitution kernels live in component.hip and nowhere else.  Three
+// solves stay where they are, on purpose:
+//   k_exc_draw (hmc_exact_comp.h)   its back substitution sums i ASCENDING over a square triangle with an odd leading dimension
+//                                   and is fused with the RNG fill and the mu* add: sharing the arithmetic would change its bits
+//   k_exc_rhs (hmc_exact_comp.h)    the right-hand side post * ZL' (y - xb): scaled, and a difference of two vectors per entry
+//   k_lac_factor / k_lac_factor_wg  their own solves run on the M_c they have just factorised in LDS, before it is stored
 //
 // A RECORD is CP_SLOT = 4 entries of one row of ZL, 8 ints in slot_i and 8 doubles in slot_d:
 //   slot_i  local columns [4] | entries in the record | 1 if the observation ends here | observation | 0
@@ -68,5 +82,20 @@ int comp_fill_xy(Ctx& c);                                    // the records' xb_
 // of their launches, which are the ones la_component_launch_count reports
 int lac_factor_launch(Ctx& c, const double* W, double w0, const double* g, double* x, double* logdet, double* fac,
                       const int* fac_ptr, int waves, long long* launches);
+
+// the component operator can be applied: L is set, the sparse ZL operator runs and the plan has records (no component above
+// CP_WIDE_MAX_VARS variables)
+inline bool comp_operator_ready(const Ctx& c) { return c.have_L && c.sp.active && c.cp.ready && c.cp.plan.records; }
+// f sized for the plan of c: fac_ptr uploaded once per model (the pattern is fixed), fac = comp_factor_doubles(c) doubles,
+// logdet = ncomp
+int comp_factors_ensure(Ctx& c, CompFactors& f);
+long long comp_factor_doubles(const Ctx& c);
+// B[q, a] = sum_t csr_val[t] V[csr_i[t], a], a < ncols: row q of ZL', observations ascending (csr_row_sum).  One launch
+int comp_rhs_csr_launch(Ctx& c, const double* V, int ldv, int ncols, double* B, int ldb);
+// R_c s = b_c for the ncols columns of X (Q x ncols) in place, every component; back: then R_c' t = s, and only t is stored.
+// One launch.  *form: 1 the plan's work items (a lane per (component, column) pair), 2 a wave per component -- the lanes take
+// the columns, or, for the forward-then-back solve of ONE column, work the column together.  back with more than one column
+// off the work items has no caller and no kernel
+int comp_solve_launch(Ctx& c, const CompFactors& f, double* X, int ldx, int ncols, bool back, int* form);
 
 }  // namespace mcml

@@ -1,5 +1,6 @@
 // component.hip -- the device side of the component plan (component.h): the upload of a ComponentPlan, the two kernels that fill
-// the records, and the component operator M = ZL' W ZL + I of the Laplace fits and the exact draws (5.8).
+// the records, the component operator M = ZL' W ZL + I of the Laplace fits, the exact draws (5.8) and the two
+// queries (5.9, 5.11), and what applies its factors afterwards: the scratch, the CSR right-hand side, the substitutions.
 // M couples two variables only through an observation whose row of ZL touches both, so it is block diagonal over the
 // connected components of component_plan.h: logdet M = sum_c logdet M_c and M^-1 g is solved component by component.
 // k_lac_factor builds, factorises and (optionally) solves every M_c in LDS, one wave per component; k_lac_factor_wg gives a
@@ -295,6 +296,192 @@ int lac_factor_launch(Ctx& c, const double* W, double w0, const double* g, doubl
     }
     MCML_HIP(hipGetLastError());
     if (launches) { ++*launches; ++g_lac_launches; }
+    return MCML_OK;
+}
+
+// ------------------------------------------------------------------ applying the factors: scratch, right-hand side, solves
+long long comp_factor_doubles(const Ctx& c) { return comp_factor_offsets(c.cp.plan).back(); }
+
+int comp_factors_ensure(Ctx& c, CompFactors& f)
+{
+    if (!f.doubles) {                                             // the pattern is fixed per model
+        const std::vector<int> off = comp_factor_offsets(c.cp.plan);
+        MCML_TRY(f.fac_ptr.ensure(sizeof(int) * off.size()));
+        MCML_TRY(copy_h2d(f.fac_ptr.p, off.data(), sizeof(int) * off.size(), c.stream));
+        MCML_HIP(hipStreamSynchronize(c.stream));
+        MCML_TRY(f.fac.ensure(sizeof(double) * (size_t)off.back()));
+        f.doubles = off.back();
+    }
+    return f.logdet.ensure(sizeof(double) * (size_t)c.cp.plan.ncomp);
+}
+
+__global__ __launch_bounds__(256) void k_comp_rhs_csr(const int* csr_ptr, const int* csr_i, const double* csr_val, const double* V,
+                                                      int ldv, int Q, int ncols, double* B, int ldb)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Q) return;
+    for (int a = blockIdx.y; a < ncols; a += gridDim.y) {
+        const double* col = V + (size_t)a * ldv;
+        B[q + (size_t)a * ldb] = csr_row_sum(csr_ptr, csr_i, csr_val, q, [&](int i) { return col[i]; });
+    }
+}
+int comp_rhs_csr_launch(Ctx& c, const double* V, int ldv, int ncols, double* B, int ldb)
+{
+    hipLaunchKernelGGL(k_comp_rhs_csr, dim3((c.Q + 255) / 256, ncols < 1024 ? ncols : 1024), dim3(256), 0, c.stream,
+                       c.sp.csr_ptr.as<int>(), c.sp.csr_i.as<int>(), c.sp.csr_val.d(), V, ldv, c.Q, ncols, B, ldb);
+    MCML_HIP(hipGetLastError());
+    return MCML_OK;
+}
+
+// ---- the substitutions.  R_c is staged from the factor scratch as PACKED ROWS -- entry (k, i), i <= k, at k (k + 1) / 2 + i --
+// so that a wave's own block of LDS holds the triangle and the vectors side by side at CP_WIDE_MAX_VARS (a square with an odd
+// leading dimension as in k_lac_factor_wg would take 129 KB and leave the vectors 31 KB).  Components staged side by side sit
+// at an ODD stride.  A lane that solves for its own component walks a row of its triangle in the forward substitution and a
+// COLUMN (entry (i, k), i descending) in the back substitution: either way the lanes of a group of 32 sit at the SAME offset
+// inside their triangles (lanes whose component is smaller are masked), so their addresses differ by multiples of the odd
+// stride and fall into 32 different pairs of banks; lanes of one component read one address, a broadcast.  The odd stride
+// that keeps the row walk free of conflicts keeps the column walk free of them as well (checked on the address formula, not
+// measured).
+constexpr int CSOLVE_WAVES = 4;
+constexpr int CSOLVE_R_DOUBLES = 1024;               // a wave's room for staged triangles in the item form
+constexpr int csolve_stride(int mv) { return (mv * (mv + 1) / 2) | 1; }
+constexpr int csolve_r_doubles(int mv) { return mv <= CP_MAX_VARS && csolve_stride(mv) < CSOLVE_R_DOUBLES ? CSOLVE_R_DOUBLES : csolve_stride(mv); }
+constexpr int csolve_waves(int mv) { return mv <= CP_MAX_VARS ? CSOLVE_WAVES : 1; }
+constexpr int csolve_lds_bytes(int mv) { return 8 * csolve_waves(mv) * (mv * 64 + csolve_r_doubles(mv)); }   // k_comp_solve
+constexpr int csolve_wave_lds_bytes(int mv) { return 8 * (csolve_stride(mv) + mv); }                         // k_comp_solve_wave
+constexpr int CSOLVE_LDS_CAP = csolve_lds_bytes(CP_MAX_VARS) > csolve_lds_bytes(CP_WIDE_MAX_VARS) ? csolve_lds_bytes(CP_MAX_VARS)
+                                                                                                    : csolve_lds_bytes(CP_WIDE_MAX_VARS);
+static_assert(CSOLVE_LDS_CAP <= CP_LDS_BYTES_PER_CU, "k_comp_solve, staged items and one wave at their caps");
+static_assert(csolve_wave_lds_bytes(CP_WIDE_MAX_VARS) <= CP_LDS_BYTES_PER_CU, "k_comp_solve_wave at the cap");
+
+struct CompSolveArgs {
+    CompView cv;                         // items != 0: a wave takes work item t = components [item_ptr[t], item_ptr[t + 1]); else component t
+    const int* fac_ptr;                  // CompFactors: the factors of lac_factor_launch, lower triangles, leading dimension nv_c
+    const double* fac;
+    double* X;                           // Q x ncols, in: b, out: s or t
+    size_t ldx;
+    int ncols, items;
+};
+
+// packed rows of the lower triangle of F (nv x nv, column-major) -> Rs, by the whole wave
+__device__ __forceinline__ void comp_stage_packed(const double* F, int nv, double* Rs, int lane)
+{
+    for (int e = lane; e < nv * nv; e += 64) {
+        const int i = e % nv, j = e / nv;
+        if (i >= j) Rs[i * (i + 1) / 2 + j] = F[e];
+    }
+}
+
+// A lane owns one (component, column) pair and runs the substitutions for it, its vector in LDS as [variable][lane] (the layout
+// of k_exc_draw: the 32 lanes of a half read consecutive doubles).  Two forms, picked by the plan as for k_exc_draw:
+//   staged items   components up to CP_MAX_VARS variables: CSOLVE_WAVES waves per workgroup, a wave per work item; the item's
+//                  components are staged G at a time and the lanes enumerate (component, column) pairs.  With 2 columns and
+//                  components of 11 variables (config 5) 15 components keep 30 lanes busy
+//   one component  up to CP_WIDE_MAX_VARS: one wave per workgroup and component, every read of R_c a broadcast
+// More than 64 pairs are worked through 64 at a time (one component: the columns in chunks of 64).  BACK = false stores s,
+// BACK = true only t.  grid ceil(items / waves), 64 * waves threads, csolve_lds_bytes(max_vars) of dynamic LDS.  No workgroup barrier
+template <bool BACK>
+__global__ __launch_bounds__(64 * CSOLVE_WAVES) void k_comp_solve(CompSolveArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double csolve_lds[];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int item = blockIdx.x * (a.items ? CSOLVE_WAVES : 1) + w;
+    if (item >= (a.items ? a.cv.nitems : a.cv.ncomp)) return;
+    const int mv = a.cv.max_vars, stride = csolve_stride(mv), rd = csolve_r_doubles(mv);
+    double* x = csolve_lds + (size_t)w * (mv * 64 + rd);                         // [variable][lane]
+    double* R = x + mv * 64;                                                     // slot s at R + s stride
+    const int G = a.items ? (rd / stride < 64 ? rd / stride : 64) : 1;           // components staged side by side, >= 1
+    const int c0 = a.items ? a.cv.item_ptr[item] : item, c1 = a.items ? a.cv.item_ptr[item + 1] : item + 1;
+    for (int cs = c0; cs < c1; cs += G) {
+        const int g = c1 - cs < G ? c1 - cs : G;
+        wave_lds_sync();                             // the previous group's reads of R
+        for (int s = 0; s < g; ++s)
+            comp_stage_packed(a.fac + a.fac_ptr[cs + s], a.cv.var_ptr[cs + s + 1] - a.cv.var_ptr[cs + s], R + s * stride, lane);
+        wave_lds_sync();
+        for (int e = lane; e < g * a.ncols; e += 64) {
+            const int s = e / a.ncols, col = e - s * a.ncols;
+            const int v0 = a.cv.var_ptr[cs + s], nv = a.cv.var_ptr[cs + s + 1] - v0;     // 1 <= nv <= mv
+            const double* Rs = R + s * stride;
+            double* Xc = a.X + (size_t)col * a.ldx;
+            // s_k = (b_k - sum_{i < k} R_c[k, i] s_i) / R_c[k, k], i ascending
+            for (int k = 0; k < nv; ++k) {
+                const int q = a.cv.vars[v0 + k];
+                const double* row = Rs + k * (k + 1) / 2;
+                double acc = Xc[q];
+                for (int i = 0; i < k; ++i) acc -= row[i] * x[i * 64 + lane];
+                acc = acc / row[k];
+                x[k * 64 + lane] = acc;
+                if (!BACK) Xc[q] = acc;
+            }
+            if (!BACK) continue;
+            // t_k = (s_k - sum_{i > k} R_c[i, k] t_i) / R_c[k, k], i descending: column k of the packed triangle
+            for (int k = nv - 1; k >= 0; --k) {
+                double acc = x[k * 64 + lane];
+                for (int i = nv - 1; i > k; --i) acc -= Rs[i * (i + 1) / 2 + k] * x[i * 64 + lane];
+                acc = acc / Rs[k * (k + 1) / 2 + k];
+                x[k * 64 + lane] = acc;
+                Xc[a.cv.vars[v0 + k]] = acc;
+            }
+        }
+    }
+}
+
+// R_c s = b, R_c' t = s for ONE column of a component of up to CP_WIDE_MAX_VARS variables, the whole wave on it (a lane-serial
+// solve would idle 63 lanes): the vector x[nv] in LDS, lane i takes x_i -= R[i, k] x_k (forward, a column of the packed
+// triangle: the offsets i (i + 1) / 2 of 32 consecutive i are distinct modulo 32, no conflict) or x_i -= R[k, i] x_k (back,
+// a row: consecutive).  Every x_i receives its updates in the order the lane of k_comp_solve<true> applies them -- forward k
+// ascending, back k descending -- so the two give the same bits.  grid ncomp, 64 threads, csolve_wave_lds_bytes(max_vars)
+__global__ __launch_bounds__(64) void k_comp_solve_wave(CompSolveArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double csolve_lds[];
+    const int lane = threadIdx.x & 63, comp = blockIdx.x;
+    if (comp >= a.cv.ncomp) return;
+    const int v0 = a.cv.var_ptr[comp], nv = a.cv.var_ptr[comp + 1] - v0;         // 1 <= nv <= max_vars
+    double* R = csolve_lds;
+    double* x = csolve_lds + csolve_stride(a.cv.max_vars);
+    comp_stage_packed(a.fac + a.fac_ptr[comp], nv, R, lane);
+    for (int k = lane; k < nv; k += 64) x[k] = a.X[a.cv.vars[v0 + k]];
+    wave_lds_sync();
+    for (int k = 0; k < nv; ++k) {                                               // R s = b
+        const double sk = x[k] / R[k * (k + 1) / 2 + k];
+        wave_lds_sync();                                                         // every lane has read x[k]
+        if (lane == 0) x[k] = sk;
+        for (int i = k + 1 + lane; i < nv; i += 64) x[i] -= R[i * (i + 1) / 2 + k] * sk;
+        wave_lds_sync();
+    }
+    for (int k = nv - 1; k >= 0; --k) {                                          // R' t = s
+        const double* row = R + k * (k + 1) / 2;
+        const double tk = x[k] / row[k];
+        wave_lds_sync();
+        if (lane == 0) x[k] = tk;
+        for (int i = lane; i < k; i += 64) x[i] -= row[i] * tk;
+        wave_lds_sync();
+    }
+    for (int k = lane; k < nv; k += 64) a.X[a.cv.vars[v0 + k]] = x[k];
+}
+
+int comp_solve_launch(Ctx& c, const CompFactors& f, double* X, int ldx, int ncols, bool back, int* form)
+{
+    const ComponentPlan& p = c.cp.plan;
+    const bool items = p.feasible;                                // max_vars <= CP_MAX_VARS: the plan's work items are built
+    MCML_REQUIRE(p.records && ncols >= 1 && (!back || items || ncols == 1), "component solve: %d columns, %d variables, back %d",
+                 ncols, p.max_vars, (int)back);
+    const CompSolveArgs a{comp_view(c), f.fac_ptr.as<int>(), f.fac.d(), X, (size_t)ldx, ncols, items ? 1 : 0};
+    const int nw = csolve_waves(p.max_vars), cnt = items ? a.cv.nitems : a.cv.ncomp;
+    const dim3 grid((cnt + nw - 1) / nw), block(64 * nw);
+    // the attribute is set once per kernel and device, so to the larger of the caps of its forms
+    if (!back) {
+        MCML_TRY(ensure_dynamic_lds((const void*)k_comp_solve<false>, CSOLVE_LDS_CAP));
+        hipLaunchKernelGGL(k_comp_solve<false>, grid, block, csolve_lds_bytes(p.max_vars), c.stream, a);
+    } else if (items) {
+        MCML_TRY(ensure_dynamic_lds((const void*)k_comp_solve<true>, CSOLVE_LDS_CAP));
+        hipLaunchKernelGGL(k_comp_solve<true>, grid, block, csolve_lds_bytes(p.max_vars), c.stream, a);
+    } else {
+        MCML_TRY(ensure_dynamic_lds((const void*)k_comp_solve_wave, csolve_wave_lds_bytes(CP_WIDE_MAX_VARS)));
+        hipLaunchKernelGGL(k_comp_solve_wave, dim3(a.cv.ncomp), dim3(64), csolve_wave_lds_bytes(p.max_vars), c.stream, a);
+    }
+    MCML_HIP(hipGetLastError());
+    *form = items ? 1 : 2;
     return MCML_OK;
 }
 

@@ -90,6 +90,14 @@ struct ComponentDev {
     DevBuf item_ptr, var_ptr, vars, slot_ptr, slot_quarter, slot_i, slot_src, slot_d;
 };
 
+// the Cholesky factors of every M_c as lac_factor_launch leaves them, for whoever applies them afterwards (component.h,
+// comp_factors_ensure): sum_c nv_c^2 doubles, at most Q * 128, where each starts, and the factor kernels' log-determinants
+// (not read); kept between calls
+struct CompFactors {
+    DevBuf fac, fac_ptr, logdet;
+    long long doubles = 0;              // 0: fac_ptr not uploaded yet
+};
+
 // HIP-event timing of the dominant kernels, on the stream they are launched on
 // (bench.py's roofline line).  kind 0 = HMC forward GEMM, 1 = HMC backward GEMM.
 struct KernelProf {
@@ -148,24 +156,23 @@ struct ExactState {
     double ms[5] = {0, 0, 0, 0, 0};   // M build | factorisation | right-hand side + fill | transposed solve | L V, of the last call
 };
 
-// component-wise exact draws (hmc_exact_comp.h): the factors of every M_c (sum_c nv_c^2 doubles, at most Q * 128) and where
-// each starts, b -> mu*, the factor kernel's log-determinants (not read), the draws chain-major and transposed; kept between
-// calls
+// component-wise exact draws (hmc_exact_comp.h): the factors of every M_c, b -> mu*, the draws chain-major and transposed;
+// kept between calls
 struct ExactCompState {
-    DevBuf fac, fac_ptr, b, mu, logdet, CM;
+    CompFactors f;
+    DevBuf b, mu, CM;
     DevMat T;
-    long long fac_doubles = 0;          // 0: fac_ptr not uploaded yet
     bool prof = false;
     double ms[5] = {0, 0, 0, 0, 0};     // factor + mean | draw kernel | transpose | L V | 0, of the last call
 };
 
 // the GLS information query (info.hip): beta, the reciprocal weights v, XV = diag(v) X, the right-hand sides / S (Q x P), the
-// Gram partials and the result with its two flags; the dense operator's M and ZLTW, the component operator's factors as
-// ExactCompState keeps them; kept between calls.  plan: what the last call did (glmmr_mcml_dbg_information_plan)
+// Gram partials and the result with its two flags; the dense operator's M and ZLTW, the component operator's factors; kept
+// between calls.  plan: what the last call did (glmmr_mcml_dbg_information_plan)
 struct InfoState {
-    DevBuf beta, v, bad, part, res, fac, fac_ptr, logdet;
+    DevBuf beta, v, bad, part, res;
+    CompFactors f;
     DevMat XV, S, M, ZLTW;
-    long long fac_doubles = 0;          // 0: fac_ptr not uploaded yet
     long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 

@@ -50,9 +50,21 @@ long long la_component_launch_count();
 
 // ---- info.hip ----
 // X' (W^-1 + Z D Z')^-1 X at beta / var_par with the context's resident L -> out (P x P, column-major, symmetric to the bit).
-// op: 0 the component operator where info_component_applicable, else the dense one; 1 dense; 2 component or MCML_EUNSUPPORTED
-bool info_component_applicable(const Ctx& c);
+// op: 0 the component operator where comp_operator_ready (component.h), else the dense one; 1 dense; 2 component or MCML_EUNSUPPORTED
 int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out, int ldo);
+// the chunked Gram reduction, two launches: out[a, b] = out[b, a] = sum_i U[i, a] W[i, b] - sum_q S[q, a] S[q, b], a >= b, over n
+// and Q rows in chunks of 2048, the partials in `part`, each sum in a fixed order (Q = 0: no second sum, S is not read); behind
+// the P x P matrix ride the two flags of the call: out[P P] = the context's "not positive definite" flag, out[P P + 1] = *bad
+int gram_launch(Ctx& c, const double* U, int ldu, const double* W, int ldw, int n, const double* S, int lds, int Q, int P,
+                DevBuf& part, const int* bad, double* out);
+// the tail of a query whose result gram_launch wrote: h <- the P P + 2 + extra doubles of res, the stream synchronised.  A
+// raised not-PD flag is cleared in the context; *bad raised: "<who>: <bad_what> is not finite", MCML_EINVAL; else not-PD:
+// MCML_ENOTPD.  The caller copies out only after MCML_OK, so nothing is written on an error
+int query_download(Ctx& c, const DevBuf& res, int P, size_t extra, const char* who, const char* bad_what, std::vector<double>& h);
+inline void copy_columns(double* dst, int ldd, const double* src, int rows, int cols)
+{
+    for (int b = 0; b < cols; ++b) memcpy(dst + (size_t)b * ldd, src + (size_t)b * rows, sizeof(double) * (size_t)rows);
+}
 
 // ---- sandwich.hip ----
 // the bread X' Sigma^-1 X (info_matrix's, to the bit), the meat G' G and, where scores is not null, the ncl x P cluster scores G

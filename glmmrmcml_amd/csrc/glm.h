@@ -12,6 +12,15 @@
 
 namespace mcml {
 
+// the fixed part of observation i's linear predictor, x_i' beta with p ascending (Eigen: X * beta): the one sum behind
+// model.hip's xb, the information query's weights and the sandwich's residuals, which must agree to the bit
+__device__ __forceinline__ double row_xb(const double* X, int ldx, int i, int P, const double* beta)
+{
+    double s = 0;
+    for (int p = 0; p < P; ++p) s += X[i + (size_t)p * ldx] * beta[p];
+    return s;
+}
+
 __device__ __forceinline__ double glm_pnorm(double x) { return 0.5 * erfc(-x * 0.70710678118654752440); }
 __device__ __forceinline__ double glm_dnorm(double x) { return exp(-0.5 * x * x) * 0.39894228040143267794; }
 

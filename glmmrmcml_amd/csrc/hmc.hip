@@ -695,7 +695,7 @@ void hmc_exact_component_sizes(const Ctx& c, long long* out3)
 {
     const ComponentPlan& p = c.cp.plan;
     const int waves = cp_waves(p, cp_forced_waves(CP_LA_WAVES_ENV));
-    out3[0] = waves; out3[1] = exc_lds_bytes(p.max_vars); out3[2] = 8LL * comp_factor_offsets(p).back();
+    out3[0] = waves; out3[1] = exc_lds_bytes(p.max_vars); out3[2] = 8LL * comp_factor_doubles(c);
 }
 
 // ---- hmc_sample in parts ----

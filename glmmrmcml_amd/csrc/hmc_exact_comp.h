@@ -9,20 +9,19 @@
 //   k_exc_rhs                       b = ZL' (y - X beta) / sigma^2 over the CSR rows of ZL', observations ascending
 //   k_lac_factor / k_lac_factor_wg  the component operator (component.hip, lac_factor_launch) with the constant weight 1 / sigma^2
 //                                   and g = b: they build and factorise every M_c in LDS, solve for mu*_c, and leave R_c in the
-//                                   factor scratch; a wave or a workgroup per component: cp_waves under GLMMR_MCML_LA_WAVES
+//                                   factor scratch (CompFactors, comp_factors_ensure: shared with the queries); a wave or a
+//                                   workgroup per component: cp_waves under GLMMR_MCML_LA_WAVES
 //   k_exc_draw                      lane = sample column: z, the backward solve R_c' s = z, v = mu* + s, stored chain-major
 //   k_cm_transpose, samples_to_U    to the Q x ncols sample matrix and U = L V, as every sampler ends
 // No atomics, every sum in a fixed order: two calls with one seed give the same bits, and a column's arithmetic does not
-// depend on the block of 64 it sits in.
+// depend on the block of 64 it sits in.  k_exc_rhs and k_exc_draw are this file's own and do not go through the shared
+// right-hand side and substitution kernels of component.hip: component.h says why.
 #pragma once
 #include "component.h"
 
 namespace mcml {
 
-static bool exact_component_applicable(const Ctx& c)
-{
-    return c.flink == 7 && c.have_L && c.sp.active && c.cp.ready && c.cp.plan.records;
-}
+static bool exact_component_applicable(const Ctx& c) { return c.flink == 7 && comp_operator_ready(c); }
 
 // b[q] = post * sum_t csr_val[t] (y - xb)[csr_i[t]]: row q of ZL', observations ascending
 __global__ __launch_bounds__(256) void k_exc_rhs(const int* csr_ptr, const int* csr_i, const double* csr_val, const double* y,
@@ -48,7 +47,7 @@ static_assert(exc_lds_bytes(CP_WIDE_MAX_VARS) <= CP_LDS_BYTES_PER_CU, "k_exc_dra
 
 struct ExcArgs {
     CompView cv;                         // STAGE: a wave takes work item t = components [item_ptr[t], item_ptr[t + 1]); else component t
-    const int* fac_ptr;                  // ExactCompState
+    const int* fac_ptr;                  // CompFactors
     const double *fac, *mu;              // the factors (k_lac_factor*), mu* (Q)
     const double* inj_z;                 // nullable: Q x ncols, no padding
     double* out;                         // chain-major: element (column j, variable q) at j + q * ld
@@ -125,16 +124,8 @@ static int exact_component_sample(Ctx& c, const double* beta, double var_par, co
     ExactCall k(x.prof, c.stream);
     MCML_TRY(exact_begin(c, beta, var_par, o, inj_z, ok, x.T, k));
     const int ncols = k.sh.ncols;
-    if (!x.fac_doubles) {                                         // the pattern is fixed per model
-        const std::vector<int> off = comp_factor_offsets(p);
-        MCML_TRY(x.fac_ptr.ensure(sizeof(int) * off.size()));
-        MCML_TRY(copy_h2d(x.fac_ptr.p, off.data(), sizeof(int) * off.size(), c.stream));
-        MCML_HIP(hipStreamSynchronize(c.stream));
-        MCML_TRY(x.fac.ensure(sizeof(double) * (size_t)off.back()));
-        x.fac_doubles = off.back();
-    }
+    MCML_TRY(comp_factors_ensure(c, x.f));
     MCML_TRY(x.b.ensure(sizeof(double) * (size_t)Q)); MCML_TRY(x.mu.ensure(sizeof(double) * (size_t)Q));
-    MCML_TRY(x.logdet.ensure(sizeof(double) * (size_t)p.ncomp));
     const size_t ldc = (size_t)round_up(ncols, 64);
     MCML_TRY(x.CM.ensure(sizeof(double) * ldc * (size_t)Q));
     k.mark();
@@ -142,12 +133,12 @@ static int exact_component_sample(Ctx& c, const double* beta, double var_par, co
     hipLaunchKernelGGL(k_exc_rhs, dim3((Q + 255) / 256), dim3(256), 0, c.stream, c.sp.csr_ptr.as<int>(), c.sp.csr_i.as<int>(),
                        c.sp.csr_val.d(), c.y.d(), c.xb.d(), k.post, Q, x.b.d());
     MCML_HIP(hipGetLastError());
-    MCML_TRY(lac_factor_launch(c, nullptr, k.post, x.b.d(), x.mu.d(), x.logdet.d(), x.fac.d(), x.fac_ptr.as<int>(),
+    MCML_TRY(lac_factor_launch(c, nullptr, k.post, x.b.d(), x.mu.d(), x.f.logdet.d(), x.f.fac.d(), x.f.fac_ptr.as<int>(),
                                cp_waves(p, cp_forced_waves(CP_LA_WAVES_ENV)), nullptr));
     k.mark();
     // ---- the draws, chain-major
     const bool stage = p.max_vars <= CP_MAX_VARS;                 // then the plan is feasible: its work items are built
-    const ExcArgs a{comp_view(c), x.fac_ptr.as<int>(), x.fac.d(), x.mu.d(), k.d_z.d(), x.CM.d(), ldc, Q, ncols, k.sh.C, k.sh.d,
+    const ExcArgs a{comp_view(c), x.f.fac_ptr.as<int>(), x.f.fac.d(), x.mu.d(), k.d_z.d(), x.CM.d(), ldc, Q, ncols, k.sh.C, k.sh.d,
                     seed, (uint32_t)o->chain_offset, 16u * iter_idx + 8u};
     const int lds = exc_lds_bytes(p.max_vars), items = stage ? a.cv.nitems : a.cv.ncomp;
     const dim3 grid((items + exc_waves(p.max_vars) - 1) / exc_waves(p.max_vars), (ncols + 63) / 64);

@@ -70,10 +70,7 @@ int model_setup(Ctx& c, const double* Z, const double* X, const double* y)
 __global__ void k_xb(const double* X, int ldx, int n, int P, const double* beta, double* xb)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s = 0;
-    for (int p = 0; p < P; ++p) s += X[i + (size_t)p * ldx] * beta[p];   // Eigen: X * beta
-    xb[i] = s;
+    if (i < n) xb[i] = row_xb(X, ldx, i, P, beta);
 }
 
 int model_update_beta(Ctx& c, const double* beta)

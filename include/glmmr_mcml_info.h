@@ -30,7 +30,7 @@ int glmmr_mcml_information(const glmmr_mcml_problem* prob, const double* beta, c
 /* test hook (csrc/ctx_hooks.hip): out8 = what the last information query on this context was asked for and did: [op
  * requested, operator run (0 dense, 1 component: work items of several components per wave, 2 component-wide: a wave per
  * component), components, most variables in one, waves per component of the factor kernel (0 dense, 1, 4), k_lac_factor* +
- * k_cinfo_solve launches (0 dense), bytes of the dense Q x Q / Q x n matrices the call built -- M, ZLTW, and ZL + ZL' on a
+ * k_comp_solve launches (0 dense), bytes of the dense Q x Q / Q x n matrices the call built -- M, ZLTW, and ZL + ZL' on a
  * sparse context -- (0 component), P] */
 int glmmr_mcml_dbg_information_plan(glmmr_mcml_ctx* ctx, long long* out8);
 

@@ -168,7 +168,7 @@ def twin_parts(c, D):
     s = cl.forward_sub(R, (ZL.T @ (v * e))[:, None])
     Q = R.shape[0]
     t = np.zeros(Q)
-    for k in range(Q - 1, -1, -1):                                    # the sum descending, as k_csand_solve's
+    for k in range(Q - 1, -1, -1):                                    # the sum descending, as k_comp_solve's
         acc = s[k, 0]
         for i in range(Q - 1, k, -1):
             if R[i, k] != 0.0:

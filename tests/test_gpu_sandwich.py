@@ -90,7 +90,7 @@ def test_staged_items_pack_components_into_a_wave(name, refs):
 @pytest.mark.parametrize("waves", ["1", "4"])
 @pytest.mark.parametrize("name", ir.WIDE_KEYS)
 def test_one_wave_per_component(name, waves, refs, monkeypatch):
-    """41 variables per component: k_csand_solve works a component with the whole wave"""
+    """41 variables per component: k_comp_solve_wave works a component with the whole wave"""
     monkeypatch.setenv("GLMMR_MCML_LA_WAVES", waves)                   # the factor kernel's, read per call
     r, plan = run(name, refs)
     assert plan["op"] == 2 and plan["dense_bytes"] == 0 and (plan["ncluster"], plan["launches"]) == (3, 7)
