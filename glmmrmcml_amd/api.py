@@ -627,6 +627,36 @@ class Context:
         keys = ("requested", "op", "ncomp", "max_vars", "waves", "launches", "dense_bytes", "P")
         return _plan(_lib.lib().glmmr_mcml_dbg_information_plan, C.c_longlong, keys, self._h)
 
+    def theta_information(self, beta, var_par, theta, operator=None):
+        """The GLS (expected) information of the covariance parameters, 1/2 tr(Sigma^-1 d_r Sigma Sigma^-1 d_s Sigma) with
+        Sigma = W^-1 + Z D(theta) Z', on the device (csrc/theta_info.hip, include/glmmr_mcml_theta_info.h
+        glmmr_mcml_ctx_theta_information) -> dict(information, names).  The weights are information_matrix's; neither y nor the
+        samples are read.  names: "theta0", "theta1", ... and, for gaussian / identity, "sigma" last -- there the matrix is the
+        (R + 1) x (R + 1) information of (theta, sigma), sigma = var_par.  theta is required (McmlError -1 for None) and the
+        context is left as update_L(theta) leaves it.  operator: None (the component operator where the context runs the sparse
+        one, no component has more than 64 variables and every covariance block lies inside one component, else the dense
+        one), "dense" or "component" (McmlError -2 where it does not apply).  McmlError -1 for a weight that is not finite, -3
+        for a failed pivot or a D(theta) that is not positive definite"""
+        beta = _f(beta).ravel()
+        if beta.size != self.P:
+            raise ValueError("beta must hold %d values" % self.P)
+        R = self.npar()
+        th = None if theta is None else _f(theta).ravel()
+        if th is not None and th.size < R:
+            raise ValueError("theta must hold %d values" % R)
+        out = np.zeros((R + 1, R + 1), order="F")
+        got = C.c_int()
+        _lib.check(_lib.lib().glmmr_mcml_ctx_theta_information(self._h, _p(beta), float(var_par), _p(th), _INFO_OP[operator],
+                                                               _p(out), R + 1, C.byref(got)))
+        return _theta_info_result(out, R, got.value)
+
+    def theta_information_plan(self):
+        """what the last theta_information on this context was asked for and ran (test hook, include/glmmr_mcml_theta_info.h
+        glmmr_mcml_dbg_theta_information_plan): op 0 dense, 1 component; launches: of csrc/theta_info.hip's own kernels;
+        dense_bytes: of the Q x Q / Q x n matrices the call built (0 on the component operator)"""
+        keys = ("requested", "op", "ncomp", "max_vars", "launches", "dense_bytes", "R", "rows")
+        return _plan(_lib.lib().glmmr_mcml_dbg_theta_information_plan, C.c_longlong, keys, self._h)
+
     def sandwich(self, beta, var_par, theta=None, cluster=None, operator=None, scores=False):
         """The cluster-robust (sandwich) covariance of the fixed effects on the device (csrc/sandwich.hip,
         include/glmmr_mcml_sandwich.h glmmr_mcml_ctx_sandwich) -> dict(information, meat, vcov, ncluster[, scores]):
@@ -844,6 +874,29 @@ def information_matrix(cov, data, eff_range, Z, X, family, link, beta, theta, va
     _lib.check(_lib.lib().glmmr_mcml_information(C.byref(p), _p(beta), _p(theta), theta.size, float(var_par),
                                                  _INFO_OP[operator], _p(out), p.P))
     return out
+
+
+def _theta_info_result(out, R, rows):
+    """dict(information, names) from the (R + 1) x (R + 1) buffer a theta_information call filled with `rows` rows"""
+    names = ["theta%d" % r for r in range(R)] + (["sigma"] if rows > R else [])
+    return dict(information=np.ascontiguousarray(out[:rows, :rows]), names=names)
+
+
+def theta_information(cov, data, eff_range, Z, X, family, link, beta, theta, var_par=1.0, operator=None):
+    """Context.theta_information on a context made for the call (glmmr_mcml_theta_information): the GLS information of the
+    covariance parameters (and of sigma for gaussian / identity) at beta / theta / var_par -> dict(information, names); beyond
+    the reference's exports.  y is not read: zeros stand in for it"""
+    Z = _f(Z)
+    p, keep = _problem(cov, data, eff_range, Z, X, np.zeros(Z.shape[0]), family, link)
+    beta = _f(beta).ravel(); theta = _f(theta).ravel()
+    if beta.size != p.P:
+        raise ValueError("beta must hold %d values" % p.P)
+    R = _npar_of(cov)
+    out = np.zeros((R + 1, R + 1), order="F")
+    got = C.c_int()
+    _lib.check(_lib.lib().glmmr_mcml_theta_information(C.byref(p), _p(beta), _p(theta), theta.size, float(var_par),
+                                                       _INFO_OP[operator], _p(out), R + 1, C.byref(got)))
+    return _theta_info_result(out, R, got.value)
 
 
 def _cluster_ids(cluster, n):

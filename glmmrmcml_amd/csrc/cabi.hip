@@ -361,6 +361,20 @@ extern "C" int glmmr_mcml_ctx_information(glmmr_mcml_ctx* h, const double* beta,
     return info_matrix(c, beta, var_par, op, out, ldo);
 }
 
+// the GLS information of the covariance parameters (theta_info.hip).  theta is required: the query needs the parameter values,
+// and the context is left as update_L(theta) leaves it
+extern "C" int glmmr_mcml_ctx_theta_information(glmmr_mcml_ctx* h, const double* beta, double var_par, const double* theta, int op,
+                                                double* out, int ldo, int* nout)
+{
+    MCML_REQUIRE(h && beta && theta && out && nout, "theta_information: null argument (theta is required)");
+    Ctx& c = h->c;
+    MCML_HIP(hipSetDevice(c.device));
+    MCML_REQUIRE(c.n > 0 && c.cov.npar > 0, "theta_information: the context has no model / covariance");
+    MCML_TRY(mvn_gen_L(c, theta, true));
+    MCML_TRY(install_L(c));
+    return theta_info(c, beta, var_par, theta, op, out, ldo, nout);
+}
+
 // the cluster-robust sandwich of the fixed effects (sandwich.hip).  theta: as glmmr_mcml_ctx_information
 extern "C" int glmmr_mcml_ctx_sandwich(glmmr_mcml_ctx* h, const double* beta, double var_par, const double* theta, int op,
                                        const int* cluster, int ncluster, double* info, int ldi, double* meat, int ldm,
@@ -756,6 +770,17 @@ extern "C" int glmmr_mcml_information(const glmmr_mcml_problem* prob, const doub
     MCML_REQUIRE(ntheta >= g.h->c.cov.npar, "information: %d covariance parameters given, the covariance needs %d", ntheta,
                  g.h->c.cov.npar);
     return glmmr_mcml_ctx_information(g.h, beta, var_par, theta, op, out, ldo);
+}
+
+extern "C" int glmmr_mcml_theta_information(const glmmr_mcml_problem* prob, const double* beta, const double* theta, int ntheta,
+                                            double var_par, int op, double* out, int ldo, int* nout)
+{
+    MCML_REQUIRE(prob && beta && theta && out && nout, "theta_information: null argument");
+    CtxGuard g;
+    MCML_TRY(open_ctx(prob, nullptr, g));
+    MCML_REQUIRE(ntheta >= g.h->c.cov.npar, "theta_information: %d covariance parameters given, the covariance needs %d", ntheta,
+                 g.h->c.cov.npar);
+    return glmmr_mcml_ctx_theta_information(g.h, beta, var_par, theta, op, out, ldo, nout);
 }
 
 extern "C" int glmmr_mcml_sandwich(const glmmr_mcml_problem* prob, const double* beta, const double* theta, int ntheta,

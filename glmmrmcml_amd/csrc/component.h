@@ -1,9 +1,10 @@
 // component.h -- the device side of the component plan (component_plan.h), in one place: the view a kernel takes of the
 // resident records, the idioms every kernel on the components shares, and the launchers of component.hip.
 //
-// Five opt-in paths run on the components: the HMC trajectories of hmc_traj.h, the component operator of the
-// Laplace fits (laplace.hip, 5.5), the exact draws of hmc_exact_comp.h (5.8), the information query (info.hip, 5.9) and the
-// sandwich (sandwich.hip, 5.11); the last four factorise through lac_factor_launch.
+// Six opt-in paths run on the components: the HMC trajectories of hmc_traj.h, the component operator of the
+// Laplace fits (laplace.hip, 5.5), the exact draws of hmc_exact_comp.h (5.8), the information query (info.hip, 5.9), the
+// sandwich (sandwich.hip, 5.11) and the covariance parameters' information (theta_info.hip, 5.12: its k_ti_comp reads the
+// factors and the plan's variable lists); the last five factorise through lac_factor_launch.
 // k_cm_traj and k_exc_draw stay in the sampler's translation unit (glm.h, rng.h, hmc_chain.h) and take the CompView.
 //
 // APPLYING A FACTOR.  Whoever needs M^-1 or R^-1 on a few columns after the factor kernels calls, in this order,

@@ -173,6 +173,18 @@ struct InfoState {
     DevBuf beta, v, bad, part, res;
     CompFactors f;
     DevMat XV, S, M, ZLTW;
+    int waves = 0;                      // of the factor kernel of the last component front half (info_front)
+    long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+// the information of the covariance parameters (theta_info.hip).  Dense operator: B = M^-1 N, the matrix at hand d_r D -> E_r, its
+// transposition, and one G_r = B E_r per parameter (Q x Q each); component operator: the block of every variable and the
+// per-component partials; the contraction's partials and the result with its two flags; kept between calls.  plan: what the last
+// call did (glmmr_mcml_dbg_theta_information_plan)
+struct ThetaInfoState {
+    DevMat B, E, T;
+    std::vector<DevMat> G;
+    DevBuf gptr, blk_of_var, part, tr, res;
     long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -211,6 +223,7 @@ struct Ctx {
     ExactState exact;
     ExactCompState exact_comp;
     InfoState info;
+    ThetaInfoState tinfo;
     SandwichState sand;
     PredictState predict;
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT

@@ -218,6 +218,14 @@ extern "C" int glmmr_mcml_dbg_information_plan(glmmr_mcml_ctx* h, long long* out
     return MCML_OK;
 }
 
+// read-only: what the last glmmr_mcml_ctx_theta_information on this context was asked for and did (theta_info.hip)
+extern "C" int glmmr_mcml_dbg_theta_information_plan(glmmr_mcml_ctx* h, long long* out8)
+{
+    MCML_REQUIRE(h && out8, "dbg_theta_information_plan: null argument");
+    std::copy(h->c.tinfo.plan, h->c.tinfo.plan + 8, out8);
+    return MCML_OK;
+}
+
 extern "C" int glmmr_mcml_dbg_emulate_world(glmmr_mcml_ctx* h, int world, int mode)
 {
     MCML_REQUIRE(h, "emulate_world: null context");

@@ -1,5 +1,5 @@
 // entry.h -- the host entry points one translation unit defines and another calls: the samplers (hmc.hip), the drivers
-// (drivers.hip, laplace.hip), the queries (info.hip, sandwich.hip, predict.hip) and the launch counters (hmc.hip, component.hip) behind the extern "C" layer (cabi.hip,
+// (drivers.hip, laplace.hip), the queries (info.hip, sandwich.hip, predict.hip, theta_info.hip) and the launch counters (hmc.hip, component.hip) behind the extern "C" layer (cabi.hip,
 // ctx_hooks.hip).  The defining
 // files include this header, so a signature that drifts is a compile error, not a wrong link.
 #pragma once
@@ -52,6 +52,24 @@ long long la_component_launch_count();
 // X' (W^-1 + Z D Z')^-1 X at beta / var_par with the context's resident L -> out (P x P, column-major, symmetric to the bit).
 // op: 0 the component operator where comp_operator_ready (component.h), else the dense one; 1 dense; 2 component or MCML_EUNSUPPORTED
 int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out, int ldo);
+// the dense operator on a context whose operator is the sparse one: the dense ZL / ZL' beside it, built as the Laplace fits' dense
+// operator builds them; the sparse pair and the records are not written, so the context's operator is the sparse one again on every exit
+struct InfoDenseScope {
+    Ctx& c;
+    bool on = false;
+    explicit InfoDenseScope(Ctx& ctx) : c(ctx) {}
+    int build()
+    {
+        on = true;
+        c.no_sparse_zl = true;
+        return model_update_L(c);
+    }
+    ~InfoDenseScope() { if (on) { c.no_sparse_zl = false; c.sp.active = true; } }
+};
+// the front half the queries on Sigma = diag(w) + Z D Z' share: the weights (c.info.v, c.info.bad) and the factor of
+// M = I + ZL' V ZL -- comp: every M_c in c.info.f; else c.info.M factorised on the dense ZL / ZL', which `dense` builds where the
+// context's operator is the sparse one.  rhs: info_matrix's right-hand sides ZL' V X into c.info.S on the way
+int info_front(Ctx& c, const double* beta, double var_par, bool comp, bool rhs, InfoDenseScope& dense);
 // the chunked Gram reduction, two launches: out[a, b] = out[b, a] = sum_i U[i, a] W[i, b] - sum_q S[q, a] S[q, b], a >= b, over n
 // and Q rows in chunks of 2048, the partials in `part`, each sum in a fixed order (Q = 0: no second sum, S is not read); behind
 // the P x P matrix ride the two flags of the call: out[P P] = the context's "not positive definite" flag, out[P P + 1] = *bad
@@ -72,6 +90,12 @@ inline void copy_columns(double* dst, int ldd, const double* src, int rows, int 
 // the plan (MCML_EINVAL where there is none or an observation has no entry of ZL).  op: as info_matrix.  On an error nothing is written
 int sandwich_matrices(Ctx& c, const double* beta, double var_par, int op, const int* cluster, int ncluster, double* info, int ldi,
                       double* meat, int ldm, double* scores, int lds, int* ncluster_out);
+
+// ---- theta_info.hip ----
+// the GLS information of the covariance parameters, 1/2 tr(Sigma^-1 d_r Sigma Sigma^-1 d_s Sigma), at beta / var_par / theta with
+// the resident L = L(theta) -> out (nout x nout, column-major, symmetric to the bit), *nout = npar, or npar + 1 with the sigma row
+// of gaussian / identity.  op: as info_matrix, the component operator where theta_info_component_ok.  On an error nothing is written
+int theta_info(Ctx& c, const double* beta, double var_par, const double* theta, int op, double* out, int ldo, int* nout);
 
 // ---- predict.hip ----
 // conditional mean and variance of the random effects at nnew[b] new points per covariance block (newdata: every block's

@@ -123,20 +123,48 @@ static double info_scale(int flink, double var_par)
     return 1.0;
 }
 
-// op = 1 on a context whose operator is the sparse one: the dense ZL / ZL' beside it, built as the Laplace fits' dense operator
-// builds them; the sparse pair and the records are not written, so the context's operator is the sparse one again on every exit
-struct InfoDenseScope {
-    Ctx& c;
-    bool on = false;
-    explicit InfoDenseScope(Ctx& ctx) : c(ctx) {}
-    int build()
-    {
-        on = true;
-        c.no_sparse_zl = true;
-        return model_update_L(c);
+// The front half of a query on Sigma = diag(w) + Z D Z' (info_matrix here, theta_info.hip): the weights with their flag, then the
+// factor of M = I + ZL' V ZL -- the component operator's factors in x.f (comp), or the dense M factorised in x.M, its inverted
+// diagonal blocks in c.chol.linv, on the dense ZL / ZL' that `dense` builds beside a sparse operator.  rhs: the right-hand
+// sides ZL' V X of the information query ride along into x.S (Q x P), at the places info_matrix has always launched them
+int info_front(Ctx& c, const double* beta, double var_par, bool comp, bool rhs, InfoDenseScope& dense)
+{
+    const int n = c.n, Q = c.Q, P = c.P;
+    InfoState& x = c.info;
+    const ComponentPlan& p = c.cp.plan;
+    // ---- weights, XV
+    MCML_TRY(x.beta.ensure(sizeof(double) * (size_t)P));
+    MCML_TRY(x.bad.ensure(sizeof(int)));
+    MCML_TRY(x.v.ensure(sizeof(double) * (size_t)pad_ld(n)));
+    MCML_TRY(x.XV.alloc(n, P));
+    if (rhs) MCML_TRY(x.S.alloc(Q, P));
+    MCML_TRY(copy_h2d(x.beta.p, beta, sizeof(double) * (size_t)P, c.stream));
+    MCML_HIP(hipMemsetAsync(x.bad.p, 0, sizeof(int), c.stream));
+    MCML_HIP(hipMemsetAsync(x.XV.d(), 0, sizeof(double) * (size_t)x.XV.ld * x.XV.cols_alloc, c.stream));   // the K padding of the GEMM
+    if (rhs) MCML_HIP(hipMemsetAsync(x.S.d(), 0, sizeof(double) * (size_t)x.S.ld * x.S.cols_alloc, c.stream));
+    hipLaunchKernelGGL(k_info_weights, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.X.d(), c.X.ld, n, P, x.beta.d(), c.flink,
+                       info_scale(c.flink, var_par), x.v.d(), x.XV.d(), x.XV.ld, x.bad.as<int>());
+    MCML_HIP(hipGetLastError());
+
+    if (comp) {
+        // ---- B by the CSR rows of ZL', every M_c factorised
+        MCML_TRY(comp_factors_ensure(c, x.f));
+        if (rhs) MCML_TRY(comp_rhs_csr_launch(c, x.XV.d(), x.XV.ld, P, x.S.d(), x.S.ld));
+        x.waves = cp_waves(p, cp_forced_waves(CP_LA_WAVES_ENV));
+        MCML_TRY(lac_factor_launch(c, x.v.d(), 0.0, nullptr, nullptr, x.f.logdet.d(), x.f.fac.d(), x.f.fac_ptr.as<int>(), x.waves, nullptr));
+    } else {
+        // ---- B = ZL' XV, M and its factor on the dense ZL / ZL'
+        if (c.sp.active) MCML_TRY(dense.build());
+        MCML_REQUIRE(c.ZL.d() && c.ZLT.d() && c.ZL.rows == n && c.ZL.cols == Q, "information: the dense ZL is not resident");
+        if (rhs) {
+            const EpiAxpby epi{x.S.d(), x.S.ld, 1.0, 0.0};
+            MCML_TRY(launch_gemm<false>(c.stream, Q, P, n, c.ZLT.d(), c.ZLT.ld, x.XV.d(), x.XV.ld, epi));
+        }
+        MCML_TRY(build_M_dense(c, x.v.d(), 1.0, x.M, x.ZLTW, true));
+        MCML_TRY(potrf_lower(c, x.M.d(), Q, x.M.ld));                 // a failed pivot raises c.errflag(): read at the end
     }
-    ~InfoDenseScope() { if (on) { c.no_sparse_zl = false; c.sp.active = true; } }
-};
+    return MCML_OK;
+}
 
 int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out, int ldo)
 {
@@ -158,41 +186,15 @@ int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out,
     }
     const bool comp = op != 1 && comp_ok;
 
-    // ---- weights, XV
-    MCML_TRY(x.beta.ensure(sizeof(double) * (size_t)P));
-    MCML_TRY(x.bad.ensure(sizeof(int)));
-    MCML_TRY(x.v.ensure(sizeof(double) * (size_t)pad_ld(n)));
-    MCML_TRY(x.XV.alloc(n, P));
-    MCML_TRY(x.S.alloc(Q, P));
-    MCML_TRY(copy_h2d(x.beta.p, beta, sizeof(double) * (size_t)P, c.stream));
-    MCML_HIP(hipMemsetAsync(x.bad.p, 0, sizeof(int), c.stream));
-    MCML_HIP(hipMemsetAsync(x.XV.d(), 0, sizeof(double) * (size_t)x.XV.ld * x.XV.cols_alloc, c.stream));   // the K padding of the GEMM
-    MCML_HIP(hipMemsetAsync(x.S.d(), 0, sizeof(double) * (size_t)x.S.ld * x.S.cols_alloc, c.stream));
-    hipLaunchKernelGGL(k_info_weights, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.X.d(), c.X.ld, n, P, x.beta.d(), c.flink,
-                       info_scale(c.flink, var_par), x.v.d(), x.XV.d(), x.XV.ld, x.bad.as<int>());
-    MCML_HIP(hipGetLastError());
-
+    InfoDenseScope dense(c);
+    MCML_TRY(info_front(c, beta, var_par, comp, true, dense));
     if (comp) {
-        // ---- B by the CSR rows of ZL', every M_c factorised, the forward solves
-        MCML_TRY(comp_factors_ensure(c, x.f));
-        MCML_TRY(comp_rhs_csr_launch(c, x.XV.d(), x.XV.ld, P, x.S.d(), x.S.ld));
-        const int waves = cp_waves(p, cp_forced_waves(CP_LA_WAVES_ENV));
-        MCML_TRY(lac_factor_launch(c, x.v.d(), 0.0, nullptr, nullptr, x.f.logdet.d(), x.f.fac.d(), x.f.fac_ptr.as<int>(), waves, nullptr));
         int form = 0;
         MCML_TRY(comp_solve_launch(c, x.f, x.S.d(), x.S.ld, P, false, &form));
-        x.plan[1] = form; x.plan[4] = waves; x.plan[5] = 2;
+        x.plan[1] = form; x.plan[4] = x.waves; x.plan[5] = 2;
     } else {
-        // ---- B = ZL' XV, M, its factor, S = R^-1 B on the dense ZL / ZL'
-        InfoDenseScope dense(c);
-        const bool sparse_ctx = c.sp.active;
-        if (sparse_ctx) MCML_TRY(dense.build());
-        MCML_REQUIRE(c.ZL.d() && c.ZLT.d() && c.ZL.rows == n && c.ZL.cols == Q, "information: the dense ZL is not resident");
-        const EpiAxpby epi{x.S.d(), x.S.ld, 1.0, 0.0};
-        MCML_TRY(launch_gemm<false>(c.stream, Q, P, n, c.ZLT.d(), c.ZLT.ld, x.XV.d(), x.XV.ld, epi));
-        MCML_TRY(build_M_dense(c, x.v.d(), 1.0, x.M, x.ZLTW, true));
-        MCML_TRY(potrf_lower(c, x.M.d(), Q, x.M.ld));                 // a failed pivot raises c.errflag(): read at the end
         MCML_TRY(trsm_left_lower(c, x.M.d(), x.M.ld, Q, x.S.d(), x.S.ld, P));
-        x.plan[6] = (long long)(x.M.buf.bytes + x.ZLTW.buf.bytes + (sparse_ctx ? c.ZL.buf.bytes + c.ZLT.buf.bytes : 0));
+        x.plan[6] = (long long)(x.M.buf.bytes + x.ZLTW.buf.bytes + (dense.on ? c.ZL.buf.bytes + c.ZLT.buf.bytes : 0));
     }
 
     // ---- the Gram reduction and the one download

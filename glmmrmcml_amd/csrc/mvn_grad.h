@@ -27,19 +27,7 @@ namespace mcml {
 
 constexpr int GRAD_SLOTS = 8;        // slots a reduction carries in registers; a block with more takes another pass
 
-// d log(term) / d t[q], t = the term's parameters (gr: where dist == 0; the term, and so the product, is 0 elsewhere)
-__device__ __forceinline__ double cov_term_dlog(int fn, double dist, const double* g, int q)
-{
-    switch (fn) {
-    case 1: return 2.0 / g[0];
-    case 2: return dist / (g[0] * g[0]);
-    case 3: return dist / g[0];
-    case 4: return q == 0 ? 1.0 / g[0] : 2.0 * dist * dist / (g[1] * g[1] * g[1]);
-    case 7: return q == 0 ? 1.0 / g[0] : dist / (g[1] * g[1]);
-    case 14: return 2.0 * dist * dist / (g[0] * g[0] * g[0]);
-    }
-    return 0.0;
-}
+// cov_term_dlog, the closed-form factor of a term's derivative: cov_entry.h
 
 // acc[s] += h * D_ij * dlog of slot slot0 + s, D_ij rebuilt term by term as cov_entry does
 __device__ __forceinline__ void grad_entry(const CovBlock& blk, const int32_t* cov, int rows, const double* bd,

@@ -399,6 +399,122 @@ class ModelMCML:
         S = np.diag(w) + self.Z @ D @ self.Z.T
         return self.X.T @ np.linalg.solve(S, self.X)
 
+    def _weights(self, beta, sigma):
+        """w of Sigma = diag(w) + Z D Z', as information_matrix forms it"""
+        w = _dhdmu(self.X @ np.asarray(beta, float), self.family, self.link)
+        if self.family == "gaussian":
+            w = w * sigma * sigma
+        elif self.family == "Gamma":
+            w = w * sigma
+        elif self.family == "beta":
+            w = w * (1 + sigma)
+        return w
+
+    def _dD_host(self, theta_cov):
+        """(D, [d D / d theta_r, r < R]) dense Q x Q in float64 numpy from the covariance spec: every block is the product of
+        its terms (gr, fexp0, ar1, sqexp, fexp, sqexp0 of the rows' Euclidean distance), and a product's derivative is the sum
+        over the terms that read theta_r of the term's derivative times the other terms"""
+        th = np.asarray(theta_cov, float).ravel()
+        cov = np.asarray(self.cov)
+        data = np.asarray(self.data, float).ravel()
+        R, Q = th.size, self.Z.shape[1]
+        D = np.zeros((Q, Q))
+        dD = [np.zeros((Q, Q)) for _ in range(R)]
+        r, off, s = 0, 0, 0
+        while r < cov.shape[0]:
+            bid, dim, r0 = int(cov[r, 0]), int(cov[r, 1]), r
+            terms = []                                      # (value, {parameter: derivative of the value})
+            while r < cov.shape[0] and int(cov[r, 0]) == bid:
+                fn, nv, pi = int(cov[r, 2]), int(cov[r, 3]), int(cov[r, 4])
+                x = data[off:off + dim * nv].reshape(dim, nv, order="F")
+                off += dim * nv
+                d = np.sqrt(((x[:, None, :] - x[None, :, :]) ** 2).sum(-1))
+                t = th[pi:]
+                if fn == 1:
+                    same = (d == 0).astype(float)
+                    terms.append((same * t[0] ** 2, {pi: same * 2 * t[0]}))
+                elif fn == 2:
+                    e = np.exp(-d / t[0])
+                    terms.append((e, {pi: e * d / t[0] ** 2}))
+                elif fn == 3:
+                    terms.append((t[0] ** d, {pi: np.where(d > 0, d * t[0] ** (d - 1), 0.0)}))
+                elif fn == 4:
+                    e = np.exp(-d * d / t[1] ** 2)
+                    terms.append((t[0] * e, {pi: e, pi + 1: t[0] * e * 2 * d * d / t[1] ** 3}))
+                elif fn == 7:
+                    e = np.exp(-d / t[1])
+                    terms.append((t[0] * e, {pi: e, pi + 1: t[0] * e * d / t[1] ** 2}))
+                elif fn == 14:
+                    e = np.exp(-d * d / t[0] ** 2)
+                    terms.append((e, {pi: e * 2 * d * d / t[0] ** 3}))
+                else:
+                    raise ValueError("covariance function id %d is not built" % fn)
+                r += 1
+            sl = slice(s, s + dim)
+            # a block of gr terms alone is the diagonal matrix the backend makes of it (mcmldmatrix.h:61)
+            keep = np.eye(dim) if np.all(cov[r0:r, 2] == 1) else np.ones((dim, dim))
+            D[sl, sl] = np.prod([v for v, _ in terms], axis=0) * keep
+            for k, (_, ders) in enumerate(terms):
+                others = np.prod([v for j, (v, _) in enumerate(terms) if j != k] + [keep], axis=0)
+                for p, dv in ders.items():
+                    dD[p][sl, sl] += dv * others
+            s += dim
+        return D, dD
+
+    def theta_information(self, theta_cov, beta, sigma, on="device"):
+        """The GLS (expected) information of the covariance parameters, I[r, s] = 1/2 tr(Sigma^-1 d_r Sigma Sigma^-1 d_s Sigma)
+        with Sigma = diag(w) + Z D(theta) Z' and the weights of information_matrix (beyond the R class, which leaves these
+        standard errors to glmmrBase) -> dict(information, names).  gaussian / identity: sigma is a fitted parameter,
+        d_sigma Sigma = 2 sigma I, and the matrix is the information of (theta, sigma), "sigma" last.  on = "device": the
+        backend's `theta_information` export (csrc/theta_info.hip), the Q x Q form; "host": the n x n definition as written, in
+        float64 numpy, with the derivatives of D of _dD_host"""
+        names = self._cov_par_names()
+        with_sigma = self.family == "gaussian" and self.link == "identity"
+        if on == "device":
+            family = "gamma" if self.family == "Gamma" else self.family
+            r = self._be.theta_information(*self._ddata(), self.Z, self.X, family, self.link, np.asarray(beta, float),
+                                           np.asarray(theta_cov, float), var_par=float(sigma))
+            return dict(information=np.asarray(r["information"]), names=names + (["sigma"] if with_sigma else []))
+        if on != "host":
+            raise ValueError("theta_information: on should be 'host' or 'device'")
+        D, dD = self._dD_host(theta_cov)
+        S = np.diag(self._weights(beta, sigma)) + self.Z @ D @ self.Z.T
+        dS = [self.Z @ d @ self.Z.T for d in dD]
+        if with_sigma:
+            dS.append(2 * float(sigma) * np.eye(S.shape[0]))
+        A = [np.linalg.solve(S, d) for d in dS]
+        info = np.array([[0.5 * np.sum(a * b.T) for b in A] for a in A])
+        return dict(information=(info + info.T) / 2, names=names + (["sigma"] if with_sigma else []))
+
+    def _theta_se(self, fit, theta_se):
+        """MCML(..., theta_se=) / LA(..., theta_se=): the covariance parameters' standard errors (and sigma's, gaussian /
+        identity) become sqrt(diag(inv(I_theta))) and the fit carries `theta_information`.  The expected information is block
+        diagonal between beta and theta: the fixed effects' column is untouched.  I_theta not invertible: NaN and a warning"""
+        P, R = self.X.shape[1], self.cov_parameters.size
+        th = fit["theta"]
+        info = self.theta_information(th[P:P + R], th[:P], th[P + R], on=theta_se)
+        I = info["information"]
+        se = np.full(I.shape[0], np.nan)
+        try:
+            with np.errstate(invalid="ignore"):
+                v = np.diag(np.linalg.inv(I))
+                se = np.where(v > 0, np.sqrt(np.where(v > 0, v, 1.0)), np.nan)
+        except np.linalg.LinAlgError:
+            pass
+        if not np.all(np.isfinite(se)):
+            fit["warnings"].append("the information of the covariance parameters is not invertible")
+        co = fit["coefficients"]
+        co["SE"][P:P + I.shape[0]] = se
+        co["lower"] = co["est"] - _Z975 * co["SE"]
+        co["upper"] = co["est"] + _Z975 * co["SE"]
+        fit["theta_information"] = info
+        return fit
+
+    @staticmethod
+    def _check_theta_se(theta_se):
+        if theta_se not in (None, "host", "device"):
+            raise ValueError("theta_se should be 'host', 'device' or None")
+
     def sandwich(self, y, theta_cov, beta, sigma, cluster=None, on="device", adjust="CR0"):
         """The cluster-robust (sandwich) covariance of the fixed effects (beyond the R class, whose se.method = "robust" never
         computes one): with eta = X beta, the weights w and Sigma = diag(w) + Z D Z' of information_matrix,
@@ -491,7 +607,7 @@ class ModelMCML:
         return "host" if information is None else information
 
     def MCML(self, y, *args, trajectory=None, draws=None, theta_score=False, information=None, sandwich=None, cluster=None,
-             **kwargs):
+             theta_se=None, **kwargs):
         """_mcml below (its arguments, unchanged); trajectory ("step" / "component", None = leave the backend's default
         alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  draws ("hmc" / "exact" /
         "exact_component", None = leave the default alone): what the HMC sampler's call returns -- "exact" draws the conditional distribution of
@@ -508,8 +624,13 @@ class ModelMCML:
         sandwich ("CR0" / "CR1", None = nothing more is called): the fit also carries `robust` = dict(vcov, se, ncluster,
         adjust), the cluster-robust covariance of the fixed effects at the fitted parameters -- sandwich(on="device") with
         `cluster` (n ids, None = the components of Z L's coupling graph).  The coefficient table and what se_method means
-        are untouched."""
+        are untouched.
+        theta_se ("host" / "device", None = nothing more is called and the covariance parameters keep the standard errors
+        se_method gave them, NaN under "approx"): their standard errors, and sigma's for gaussian / identity, become
+        sqrt(diag(inv(I_theta))) of theta_information(on=theta_se) at the fitted parameters, and the fit carries
+        `theta_information`; the fixed effects' standard errors are untouched."""
         self._check_sandwich(sandwich)
+        self._check_theta_se(theta_se)
         prev_t = prev_d = None
         prev_i, use_i = self._information, self._use_information(information)
         if trajectory is not None:
@@ -527,6 +648,8 @@ class ModelMCML:
                 fit["theta_score"] = np.asarray(self._be.mvn_ll_grad(*self._ddata(), cov_par, fit["re_samps"])[1])
             if sandwich is not None:
                 self._robust(fit, y, sandwich, cluster)
+            if theta_se is not None:
+                self._theta_se(fit, theta_se)
             return fit
         finally:
             self._information = prev_i
@@ -670,13 +793,15 @@ class ModelMCML:
                        re_samps=dsamps, iter=it, warnings=warnings, theta=theta)
 
     # ---- LA ------------------------------------------------------------------------------------------------------
-    def LA(self, y, *args, operator=None, information=None, sandwich=None, cluster=None, **kwargs):
+    def LA(self, y, *args, operator=None, information=None, sandwich=None, cluster=None, theta_se=None, **kwargs):
         """_la below (its arguments, unchanged); operator ("dense" / "component" / "component_wide", None = leave the
         backend's default alone): how the Laplace fit forms and factorises ZL' W ZL + I (csrc/component.hip).  It becomes the backend's default
         for the duration of the call and is restored afterwards.  information ("host" / "device", None = "host"): where the
         GLS information matrix behind the standard errors without use_hess is computed -- information_matrix(on=).
-        sandwich ("CR0" / "CR1") and cluster: as MCML's -- the fit gains `robust`, the coefficient table is untouched"""
+        sandwich ("CR0" / "CR1") and cluster: as MCML's -- the fit gains `robust`, the coefficient table is untouched.
+        theta_se ("host" / "device", None = the covariance parameters' standard errors stay as they are): as MCML's"""
         self._check_sandwich(sandwich)
+        self._check_theta_se(theta_se)
         prev_i, self._information = self._information, self._use_information(information)
         prev = None
         try:
@@ -684,7 +809,9 @@ class ModelMCML:
                 prev = self._be.get_default_la_operator()
                 self._be.set_default_la_operator(operator)
             fit = self._la(y, *args, **kwargs)
-            return fit if sandwich is None else self._robust(fit, y, sandwich, cluster)
+            if sandwich is not None:
+                fit = self._robust(fit, y, sandwich, cluster)
+            return fit if theta_se is None else self._theta_se(fit, theta_se)
         finally:
             self._information = prev_i
             if prev is not None:

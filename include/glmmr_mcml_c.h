@@ -566,6 +566,8 @@ int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, double* out3);
 #include "glmmr_mcml_sandwich.h"
 /* test hooks of the banded products' row-tile extents (csrc/band_plan.h): a header of its own */
 #include "glmmr_mcml_band.h"
+/* the GLS information of the covariance parameters on the device (csrc/theta_info.hip): a header of its own */
+#include "glmmr_mcml_theta_info.h"
 
 #ifdef __cplusplus
 }
