@@ -21,6 +21,15 @@ namespace mcml {
 constexpr int MAX_COV_PAR = 32;
 struct ThetaArg { double v[MAX_COV_PAR]; };
 
+// th = theta[0 .. npar), zeros behind: the kernels' by-value argument from a host vector
+inline int theta_arg(const double* theta, int npar, ThetaArg& th)
+{
+    MCML_REQUIRE(theta, "theta is null");
+    th = ThetaArg{};
+    for (int i = 0; i < npar; ++i) th.v[i] = theta[i];
+    return MCML_OK;
+}
+
 struct CovBlock {
     int dim;        // block dimension
     int r0, r1;     // rows [r0, r1) of cov
@@ -37,13 +46,13 @@ struct CovSpec {
     std::vector<double> eff;
     std::vector<CovBlock> blocks;
 
-    static int fn_npar(int fn) {
-        static const int t[15] = {0, 1, 1, 1, 2, 2, 1, 2, 2, 2, 2, 2, 2, 2, 1};
-        return (fn >= 1 && fn <= 14) ? t[fn] : -1;
+    // parameters of a function (the vector in the file comment), on the host and on the device; -1: no such id
+    __host__ __device__ static constexpr int fn_npar(int fn) {
+        return (fn < 1 || fn > 14) ? -1 : (fn <= 3 || fn == 6 || fn == 14) ? 1 : 2;
     }
     // exponent of the function's FIRST parameter where that parameter only scales the term (cov_term): gr t^2, sqexp /
     // fexp t0; 0 = the function has no pure scale parameter (theta_scale.h)
-    static int fn_scale_exp(int fn) { return fn == 1 ? 2 : (fn == 4 || fn == 7) ? 1 : 0; }
+    __host__ __device__ static constexpr int fn_scale_exp(int fn) { return fn == 1 ? 2 : (fn == 4 || fn == 7) ? 1 : 0; }
     static bool fn_built(int fn) { return fn == 1 || fn == 2 || fn == 3 || fn == 4 || fn == 7 || fn == 14; }
     int c(int r, int col) const { return cov[r + (size_t)col * rows]; }
 

@@ -20,37 +20,16 @@
 // exports) lives in mvn_grad.h, one gradient path per block kind.
 #include <cmath>
 #include "ctx.h"
-#include "cov_entry.h"
+#include "cov_block.h"
+#include "mvn_grad.h"
 #include "reduce.h"
 #include "theta_scale.h"
 #include "vecops.h"
 
 namespace mcml {
 
-#define LOG_2PI 1.8378770664093454835606594728112   /* log(2*M_PI), mcmldmatrix.h:63,75 */
-
 // ------------------------------------------------------------------ diagonal blocks
-// the variance of a row of an all-gr block: prod_k theta^2 (mcmldmatrix.h:61-65)
-__device__ __forceinline__ double diag_variance(const CovBlock& blk, const int32_t* cov, int rows, const ThetaArg& th)
-{
-    double val = 1.0;
-    for (int r = blk.r0; r < blk.r1; ++r) val = cov_term(1, 0.0, &th.v[cov[r + 4 * rows]], val);
-    return val;
-}
-
-// dd[k] = prod_k theta^2 ("dmat(k,k)*dmat(k,k)"), dc[k] = -0.5 log(dd) - 0.5 log(2 pi)
-__global__ void k_diag_prep(int Q, const int* rowblock, const CovBlock* blocks, const int32_t* cov,
-                            int rows, ThetaArg th, double* dd, double* dc)
-{
-    int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= Q) return;
-    int b = rowblock[k];
-    if (b < 0) { dd[k] = 1.0; dc[k] = 0.0; return; }
-    double d = sqrt(diag_variance(blocks[b], cov, rows, th));   // the Cholesky factor of a diagonal block
-    dd[k] = d * d;
-    dc[k] = -0.5 * log(d * d) - 0.5 * LOG_2PI;
-}
-
+// the variance of a row and its constant: k_diag_prep (mvn_grad.h, whose diagonal rows read them too)
 __global__ __launch_bounds__(256) void k_diag_ll(const double* U, int ldu, int Q, int mcols,
                                                  const int* rowblock, const double* dd,
                                                  const double* dc, double* partials)
@@ -75,46 +54,18 @@ __global__ __launch_bounds__(64) void k_small_ll(const double* U, int ldu, int m
                                                  const int32_t* cov, int rows, const double* data,
                                                  ThetaArg th, double* partials, int* errflag)
 {
-    __shared__ double S[SMALL_BLOCK * (SMALL_BLOCK + 1)];
+    constexpr int LS = SMALL_LS;
+    __shared__ double S[SMALL_BLOCK * LS];
     __shared__ double Zs[SMALL_BLOCK * 64];
     const CovBlock blk = blocks[small_ids[blockIdx.x]];
     const int dim = blk.dim, lane = threadIdx.x;
-    constexpr int LS = SMALL_BLOCK + 1;
-    const double* bd = data + blk.doff;
-    for (int e = lane; e < dim * dim; e += 64) {
-        int i = e % dim, j = e / dim;
-        if (i >= j) S[i * LS + j] = cov_entry(blk, cov, rows, bd, th, i, j);
-    }
-    __syncthreads();
-    // left-looking column Cholesky, same operation order as the CPU oracle
-    for (int j = 0; j < dim; ++j) {
-        if (lane == j) {
-            double d = S[j * LS + j];
-            for (int k = 0; k < j; ++k) d -= S[j * LS + k] * S[j * LS + k];
-            if (!(d > 0.0)) { atomicExch(errflag, 1); d = 1.0; }
-            S[j * LS + j] = sqrt(d);
-        }
-        __syncthreads();
-        if (lane > j && lane < dim) {
-            double s = S[lane * LS + j];
-            for (int k = 0; k < j; ++k) s -= S[lane * LS + k] * S[j * LS + k];
-            S[lane * LS + j] = s / S[j * LS + j];
-        }
-        __syncthreads();
-    }
+    small_block_factor(S, blk, cov, rows, data + blk.doff, th, errflag);
     double logdet = 0;
     for (int i = 0; i < dim; ++i) logdet += 2 * log(S[i * LS + i]);
     double acc = 0;
     for (int col = blockIdx.y * 64 + lane; col < mcols; col += gridDim.y * 64) {
         const double* u = U + blk.matstart + (size_t)col * ldu;
-        double quad = 0;
-        for (int i = 0; i < dim; ++i) {                      // algo::forward_sub, moremaths.h:166-179
-            double lsum = 0;
-            for (int j = 0; j < i; ++j) lsum += S[i * LS + j] * Zs[j * 64 + lane];
-            double z = (u[i] - lsum) / S[i * LS + i];
-            Zs[i * 64 + lane] = z;
-            quad += z * z;
-        }
+        const double quad = small_block_forward(S, dim, Zs, lane, [&](int i) { return u[i]; });
         acc += (-0.5 * dim * LOG_2PI - 0.5 * logdet - 0.5 * quad);
     }
     acc = wave_sum(acc);
@@ -129,20 +80,14 @@ __global__ __launch_bounds__(64) void k_small_ll(const double* U, int ldu, int m
 __device__ __forceinline__ void build_dense_body(double* A, int lda, int bidx, const CovBlock* blocks, const int32_t* cov,
                                                  int rows, const double* data, const ThetaArg& th, int mirror, int dpad)
 {
-    // a workgroup = 64 rows x 16 columns, a wave = the 64 rows of four columns: every store is 512 contiguous bytes
-    // (16 x 16 tiles with 128-byte row groups ran 71 us for the 5000 x 5000 lower triangle)
-    if ((int)blockIdx.x * 64 + 63 < (int)blockIdx.y * 16) return;     // strictly above the diagonal
     const CovBlock blk = blocks[bidx];
-    const int i = blockIdx.x * 64 + (threadIdx.x & 63);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int j = blockIdx.y * 16 + (threadIdx.x >> 6) * 4 + u;
-        if (i >= blk.dim && i < dpad && j <= i) { A[i + (size_t)j * lda] = (i == j) ? 1.0 : 0.0; continue; }
-        if (i >= blk.dim || j >= blk.dim || i < j) continue;
+    lower_tile_walk([&](int i, int j) {
+        if (i >= blk.dim && i < dpad && j <= i) { A[i + (size_t)j * lda] = (i == j) ? 1.0 : 0.0; return; }
+        if (i >= blk.dim || j >= blk.dim || i < j) return;
         const double v = cov_entry(blk, cov, rows, data + blk.doff, th, i, j);
         A[i + (size_t)j * lda] = v;
         if (mirror && i != j) A[j + (size_t)i * lda] = v;
-    }
+    });
 }
 
 // the candidate thetas of one round (mvn_loglik_batch): blockIdx.z picks the candidate and its matrix
@@ -191,10 +136,6 @@ __global__ void k_zero_upper(double* A, int lda, int n)
     if (i < n && j < n && i < j) A[i + (size_t)j * lda] = 0.0;
 }
 
-}  // namespace mcml
-#include "mvn_grad.h"      // the score's kernels and per-kind steps: they use cov_entry, k_diag_prep and LOG_2PI above
-namespace mcml {
-
 // ------------------------------------------------------------------ setup
 int mvn_setup(Ctx& c)
 {
@@ -238,14 +179,6 @@ int mvn_setup(Ctx& c)
     }
     c.grad.ready = false;
     MCML_HIP(hipStreamSynchronize(c.stream));
-    return MCML_OK;
-}
-
-static int theta_arg(const Ctx& c, const double* theta, ThetaArg& th)
-{
-    MCML_REQUIRE(theta, "theta is null");
-    memset(&th, 0, sizeof th);
-    for (int i = 0; i < c.cov.npar; ++i) th.v[i] = theta[i];
     return MCML_OK;
 }
 
@@ -328,7 +261,7 @@ static int mvn_loglik_enqueue(Ctx& c, const double* theta, const double* Us, int
 {
     MCML_REQUIRE(m > 0 && Us, "mvn_ll: no samples set");
     ThetaArg th;
-    MCML_TRY(theta_arg(c, theta, th));
+    MCML_TRY(theta_arg(theta, c.cov.npar, th));
     const CovSpec& cs = c.cov;
     const int Q = cs.N;
     double* scal = c.scalars.d();
@@ -390,7 +323,7 @@ int mvn_loglik_grad(Ctx& c, const double* theta, const double* weights, double* 
     MCML_REQUIRE(theta && value && grad, "mvn_ll_grad: null argument");
     const int m = c.mcols, R = c.cov.npar;
     GradJob gj;
-    MCML_TRY(theta_arg(c, theta, gj.th));
+    MCML_TRY(theta_arg(theta, c.cov.npar, gj.th));
     gj.sw = (double)m;
     if (weights) {
         gj.sw = 0;
@@ -444,7 +377,7 @@ static int mvn_batch_pass(Ctx& c, const double* thetas, int k, int round, const 
     for (int j0 = 0; j0 < k; j0 += MVN_MAXBATCH) {
         const int kb = (k - j0 < MVN_MAXBATCH) ? k - j0 : MVN_MAXBATCH;
         ThetaArg th[MVN_MAXBATCH];
-        for (int j = 0; j < kb; ++j) MCML_TRY(theta_arg(c, thetas + (size_t)(j0 + j) * R, th[j]));
+        for (int j = 0; j < kb; ++j) MCML_TRY(theta_arg(thetas + (size_t)(j0 + j) * R, R, th[j]));
         const int dmax = round_up(c.maxdim_large, 16);
         if (c.Dbatch.rows < dmax + m || c.Dbatch.cols < kb * dmax) {
             MCML_TRY(c.Dbatch.alloc(dmax + m, MVN_MAXBATCH * dmax));
@@ -506,7 +439,7 @@ __global__ void k_diag_fill(double* L, int ldl, int Q, const int* rowblock, cons
     if (k >= Q) return;
     int b = rowblock[k];
     if (b < 0) return;
-    const double val = diag_variance(blocks[b], cov, rows, th);
+    const double val = cov_prior_variance(blocks[b], cov, rows, th);
     L[k + (size_t)k * ldl] = chol ? sqrt(val) : val;
 }
 
@@ -560,7 +493,7 @@ static int gen_D_into(Ctx& c, DevMat& L, const ThetaArg& th, bool chol)
 int mvn_build_block(Ctx& c, double* A, int lda, int b, const double* theta, int dpad)
 {
     ThetaArg th;
-    MCML_TRY(theta_arg(c, theta, th));
+    MCML_TRY(theta_arg(theta, c.cov.npar, th));
     MCML_REQUIRE(b >= 0 && b < c.cov.B && A && dpad >= c.cov.blocks[b].dim && lda >= dpad, "mvn_build_block: bad argument");
     hipLaunchKernelGGL(k_build_dense, dim3((dpad + 63) / 64, (dpad + 15) / 16), dim3(256), 0, c.stream, A, lda, b,
                        c.d_blocks.as<CovBlock>(), c.d_cov.as<int32_t>(), c.cov.rows, c.d_data.d(), th, 0, dpad);
@@ -572,7 +505,7 @@ int mvn_build_block(Ctx& c, double* A, int lda, int b, const double* theta, int 
 int mvn_gen_D(Ctx& c, const double* theta, bool chol, DevMat& out)
 {
     ThetaArg th;
-    MCML_TRY(theta_arg(c, theta, th));
+    MCML_TRY(theta_arg(theta, c.cov.npar, th));
     return gen_D_into(c, out, th, chol);
 }
 
@@ -581,7 +514,7 @@ int mvn_gen_D(Ctx& c, const double* theta, bool chol, DevMat& out)
 int mvn_gen_L(Ctx& c, const double* theta, bool chol)
 {
     ThetaArg th;
-    MCML_TRY(theta_arg(c, theta, th));
+    MCML_TRY(theta_arg(theta, c.cov.npar, th));
     c.have_L = false;
     MCML_TRY(gen_D_into(c, c.L, th, chol));
     if (chol) c.l_foreign = false;

@@ -1,5 +1,5 @@
-// mvn_grad.h -- the analytic score of the MVN log-likelihood mvn.hip evaluates (included by it, after the kernels of the
-// value):
+// mvn_grad.h -- the analytic score of the MVN log-likelihood mvn.hip evaluates: the score's kernels and its per-kind host
+// steps, included by mvn.hip alone (mvn_large_blocks calls mvn_grad_large between two blocks):
 //   value(theta) = sum_j w_j sum_b log N(u_bj; 0, D_b(theta)),     d value / d theta_k = sum_b 1/2 sum_ij (d_k D_b)_ij H_b,ij,
 //   H_b = A diag(w) A' - (sum w) inv(D_b),  A = inv(D_b) U_b.
 // Every function of covspec.h's table is a product of terms and the derivative of a term is the term times a closed-form
@@ -8,17 +8,20 @@
 // by terms and blocks of every kind), block by block.  One gradient path per block kind of mvn_setup:
 //   * all-gr rows: one streaming pass over U for q_k = sum_j w_j u_kj^2, then r_k = q_k / v_k - sum w and, per parameter p,
 //     sum_k c(block(k), p) r_k / theta_p with c = the gr terms of the row's block that read p;
-//   * blocks of dim <= 32: one wave per (block, slice of the columns, 64 at a time) builds and factorises the block as
-//     k_small_ll does, inverts the factor, solves A for its columns, accumulates the lower triangle of H in LDS and contracts
+//   * blocks of dim <= 32: one wave per (block, slice of the columns, 64 at a time) builds and factorises the block
+//     (small_block_factor, cov_block.h: k_small_ll's factor to the bit), inverts the factor (lower_inverse_column), solves A
+//     for its columns (small_block_forward, then backwards), accumulates the lower triangle of H in LDS and contracts
 //     it with D o dlog;
 //   * large blocks: after the factorisation the workspace holds L and the m solved rows X = (inv(L) U)'.  S = X' diag(w) X -
 //     (sum w) I (transposed-A GEMM, K = m, the weights on a copy of the rows), H = inv(L)' S inv(L) by two transposed solves
-//     with a transposition between them, and a reduction over the lower 64 x 16 tiles of H that rebuilds every entry's terms.
+//     with a transposition between them, and a reduction over the lower 64 x 16 tiles of H (lower_tile_walk) that rebuilds
+//     every entry's terms.
 //     A slot whose dlog is constant over the block (a pure scale) is coef trace(S) in closed form (k_grad_scale_slot).
 // All reductions are two-stage with a fixed order and there is no floating-point atomic: the result is run-to-run
 // bit-reproducible and does not depend on what the context did before.
 #pragma once
 #include "ctx.h"
+#include "cov_block.h"
 #include "dgemm_mfma.h"
 #include "reduce.h"
 #include "vecops.h"
@@ -29,32 +32,25 @@ constexpr int GRAD_SLOTS = 8;        // slots a reduction carries in registers; 
 
 // cov_term_dlog, the closed-form factor of a term's derivative: cov_entry.h
 
-// acc[s] += h * D_ij * dlog of slot slot0 + s, D_ij rebuilt term by term as cov_entry does
+// acc[s] += h * D_ij * dlog of slot slot0 + s: cov_entry's walk (cov_walk), the dlog of the slots inside the window
+// [slot0, slot0 + GRAD_SLOTS) collected on the way
 __device__ __forceinline__ void grad_entry(const CovBlock& blk, const int32_t* cov, int rows, const double* bd,
                                            const ThetaArg& th, int i, int j, double h, int slot0, double (&acc)[GRAD_SLOTS])
 {
-    double val = 1.0, dl[GRAD_SLOTS];
+    double dl[GRAD_SLOTS];
 #pragma unroll
     for (int s = 0; s < GRAD_SLOTS; ++s) dl[s] = 0.0;
-    int coff = 0, slot = -slot0;
-    for (int r = blk.r0; r < blk.r1; ++r) {
-        const int fn = cov[r + 2 * rows], nv = cov[r + 3 * rows], pi = cov[r + 4 * rows];
-        double d2 = 0.0;
-        for (int p = 0; p < nv; ++p) {
-            double df = bd[i + (size_t)(coff + p) * blk.dim] - bd[j + (size_t)(coff + p) * blk.dim];
-            d2 += df * df;
-        }
-        const double dist = sqrt(d2);
-        val = cov_term(fn, dist, &th.v[pi], val);
-        const int np = (fn == 4 || fn == 7) ? 2 : 1;
-        for (int q = 0; q < np; ++q, ++slot) {
-            if (slot < 0 || slot >= GRAD_SLOTS) continue;
-            const double x = cov_term_dlog(fn, dist, &th.v[pi], q);
+    int slot = -slot0;
+    const double val = cov_walk(
+        blk, cov, rows, th, [&](int c) { return bd[i + (size_t)c * blk.dim] - bd[j + (size_t)c * blk.dim]; },
+        [&](int fn, int pi, double dist) {
+            for (int q = 0; q < CovSpec::fn_npar(fn); ++q, ++slot) {
+                if (slot < 0 || slot >= GRAD_SLOTS) continue;
+                const double x = cov_term_dlog(fn, dist, &th.v[pi], q);
 #pragma unroll
-            for (int s = 0; s < GRAD_SLOTS; ++s) dl[s] = (s == slot) ? x : dl[s];
-        }
-        coff += nv;
-    }
+                for (int s = 0; s < GRAD_SLOTS; ++s) dl[s] = (s == slot) ? x : dl[s];
+            }
+        });
     const double hd = h * val;
 #pragma unroll
     for (int s = 0; s < GRAD_SLOTS; ++s) acc[s] += hd * dl[s];
@@ -71,6 +67,21 @@ __global__ __launch_bounds__(256) void k_grad_sum(const double* part, int n, siz
 }
 
 // ------------------------------------------------------------------ diagonal rows
+// dd[k] = prod_k theta^2 ("dmat(k,k)*dmat(k,k)"), dc[k] = -0.5 log(dd) - 0.5 log(2 pi); rows of no all-gr block: 1 and 0.
+// The value path of mvn.hip launches it as well: it is defined here, in the header that only mvn.hip includes, because a
+// kernel in cov_block.h would be emitted into every translation unit that includes that header
+__global__ void k_diag_prep(int Q, const int* rowblock, const CovBlock* blocks, const int32_t* cov, int rows, ThetaArg th,
+                            double* dd, double* dc)
+{
+    int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= Q) return;
+    int b = rowblock[k];
+    if (b < 0) { dd[k] = 1.0; dc[k] = 0.0; return; }
+    double d = sqrt(cov_prior_variance(blocks[b], cov, rows, th));   // the Cholesky factor of a diagonal block
+    dd[k] = d * d;
+    dc[k] = -0.5 * log(d * d) - 0.5 * LOG_2PI;
+}
+
 // qpart[by * Q + k] = sum over the columns by, by + gy, ... of w_j u_kj^2: the one pass over U
 __global__ __launch_bounds__(256) void k_diag_gradq(const double* U, int ldu, int Q, int mcols, const double* w,
                                                     const int* rowblock, double* qpart)
@@ -127,7 +138,7 @@ __global__ __launch_bounds__(64) void k_small_grad(const double* U, int ldu, int
                                                    const CovBlock* blocks, const int32_t* cov, int rows, const double* data,
                                                    ThetaArg th, double* gpart, double* vpart, int* errflag)
 {
-    constexpr int LS = SMALL_BLOCK + 1;
+    constexpr int LS = SMALL_LS;
     __shared__ double S[SMALL_BLOCK * LS], Li[SMALL_BLOCK * LS], Hs[SMALL_BLOCK * LS];
     __shared__ double Zs[SMALL_BLOCK * 64];
     __shared__ double Ws[64];
@@ -136,34 +147,10 @@ __global__ __launch_bounds__(64) void k_small_grad(const double* U, int ldu, int
     const double* bd = data + blk.doff;
     for (int e = lane; e < dim * dim; e += 64) {
         int i = e % dim, j = e / dim;
-        if (i >= j) { S[i * LS + j] = cov_entry(blk, cov, rows, bd, th, i, j); Hs[i * LS + j] = 0.0; }
+        if (i >= j) Hs[i * LS + j] = 0.0;
     }
-    __syncthreads();
-    // the factorisation of k_small_ll, operation by operation
-    for (int j = 0; j < dim; ++j) {
-        if (lane == j) {
-            double d = S[j * LS + j];
-            for (int k = 0; k < j; ++k) d -= S[j * LS + k] * S[j * LS + k];
-            if (!(d > 0.0)) { atomicExch(errflag, 1); d = 1.0; }
-            S[j * LS + j] = sqrt(d);
-        }
-        __syncthreads();
-        if (lane > j && lane < dim) {
-            double s = S[lane * LS + j];
-            for (int k = 0; k < j; ++k) s -= S[lane * LS + k] * S[j * LS + k];
-            S[lane * LS + j] = s / S[j * LS + j];
-        }
-        __syncthreads();
-    }
-    // inv(L), lane j its column j
-    if (lane < dim) {
-        const int j = lane;
-        for (int i = j; i < dim; ++i) {
-            double s = (i == j) ? 1.0 : 0.0;
-            for (int k = j; k < i; ++k) s -= S[i * LS + k] * Li[k * LS + j];
-            Li[i * LS + j] = s / S[i * LS + i];
-        }
-    }
+    small_block_factor(S, blk, cov, rows, bd, th, errflag);
+    if (lane < dim) lower_inverse_column(S, Li, LS, dim, lane);      // inv(L), lane j its column j
     __syncthreads();
     double logdet = 0;
     for (int i = 0; i < dim; ++i) logdet += 2 * log(S[i * LS + i]);
@@ -174,14 +161,7 @@ __global__ __launch_bounds__(64) void k_small_grad(const double* U, int ldu, int
         const double wj = active ? (w ? w[col] : 1.0) : 0.0;
         if (active) {
             const double* u = U + blk.matstart + (size_t)col * ldu;
-            double quad = 0;
-            for (int i = 0; i < dim; ++i) {                      // z = inv(L) u
-                double lsum = 0;
-                for (int j = 0; j < i; ++j) lsum += S[i * LS + j] * Zs[j * 64 + lane];
-                double z = (u[i] - lsum) / S[i * LS + i];
-                Zs[i * 64 + lane] = z;
-                quad += z * z;
-            }
+            const double quad = small_block_forward(S, dim, Zs, lane, [&](int i) { return u[i]; });   // z = inv(L) u
             acc += wj * (-0.5 * dim * LOG_2PI - 0.5 * logdet - 0.5 * quad);
             for (int i = dim - 1; i >= 0; --i) {                 // a = inv(L)' z, in place
                 double lsum = 0;
@@ -270,7 +250,7 @@ __global__ __launch_bounds__(256) void k_grad_sdiag(double* S, int lds, int d, i
 __global__ void k_grad_scale_slot(const double* trs, double coef, double* out) { out[0] = coef * trs[0]; }
 
 // partials[workgroup * GRAD_SLOTS + s] = the workgroup's sum of mult H_ij D_ij dlog_{slot0 + s} over its 64 x 16 tile of the
-// lower triangle (mult 1 on the diagonal, 2 below; the identity border i >= dim is skipped); tiles as build_dense_body
+// lower triangle (mult 1 on the diagonal, 2 below; the identity border i >= dim is skipped)
 __global__ __launch_bounds__(256) void k_grad_reduce_large(const double* H, int ldh, int bidx, const CovBlock* blocks,
                                                            const int32_t* cov, int rows, const double* data, ThetaArg th,
                                                            int slot0, double* partials)
@@ -279,17 +259,12 @@ __global__ __launch_bounds__(256) void k_grad_reduce_large(const double* H, int 
     double g[GRAD_SLOTS];
 #pragma unroll
     for (int s = 0; s < GRAD_SLOTS; ++s) g[s] = 0.0;
-    if (!((int)blockIdx.x * 64 + 63 < (int)blockIdx.y * 16)) {
-        const CovBlock blk = blocks[bidx];
-        const int i = blockIdx.x * 64 + (threadIdx.x & 63);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = blockIdx.y * 16 + (threadIdx.x >> 6) * 4 + u;
-            if (i >= blk.dim || j > i) continue;
-            const double h = H[i + (size_t)j * ldh];
-            grad_entry(blk, cov, rows, data + blk.doff, th, i, j, (i == j ? 1.0 : 2.0) * h, slot0, g);
-        }
-    }
+    const CovBlock blk = blocks[bidx];
+    lower_tile_walk([&](int i, int j) {
+        if (i >= blk.dim || j > i) return;
+        const double h = H[i + (size_t)j * ldh];
+        grad_entry(blk, cov, rows, data + blk.doff, th, i, j, (i == j ? 1.0 : 2.0) * h, slot0, g);
+    });
     const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
 #pragma unroll
     for (int s = 0; s < GRAD_SLOTS; ++s) {
@@ -324,10 +299,9 @@ static int mvn_grad_setup(Ctx& c)
             g.slot_base[b] = (int)g.slot_par.size();
             for (int r = blk.r0; r < blk.r1; ++r)
                 for (int q = 0; q < CovSpec::fn_npar(cs.c(r, 2)); ++q) {
-                    const int fn = cs.c(r, 2);
                     g.slot_par.push_back(cs.c(r, 4) + q);
                     // cov_term_dlog: gr 2 / t everywhere the product is not 0; sqexp and fexp 1 / t0
-                    g.slot_scale.push_back(fn == 1 ? 2 : ((fn == 4 || fn == 7) && q == 0) ? 1 : 0);
+                    g.slot_scale.push_back(q == 0 ? CovSpec::fn_scale_exp(cs.c(r, 2)) : 0);
                 }
             g.slot_count[b] = (int)g.slot_par.size() - g.slot_base[b];
             if (pass == 0) { sbase.push_back(g.slot_base[b]); scount.push_back(g.slot_count[b]); }

@@ -8,9 +8,9 @@
 //   k_pred_diag     all-gr blocks (diagonal): means[i, j] = sum_k (C_ik / D_kk) u_kj, cvar = max(p - sum_k C_ik (C_ik / D_kk), 0), k
 //                   ascending; a point that matches one level has C_ik / D_kk = 1 there and 0 elsewhere: the level's sample to
 //                   the bit and variance 0; one that matches none gets 0 and p
-//   k_pred_small    dim <= 32: a wave builds and factorises D_b in LDS operation by operation as k_small_ll does, forward-
-//                   substitutes 64 rows of C_b (a lane each) and 64 sample columns (a lane each), then forms the 64 x 64 tile
-//                   of means; further new points and sample columns are the two grid dimensions
+//   k_pred_small    dim <= 32: a wave builds and factorises D_b in LDS (small_block_factor, cov_block.h: k_small_ll's factor to
+//                   the bit), forward-substitutes 64 rows of C_b and 64 sample columns (small_block_forward, a lane each), then
+//                   forms the 64 x 64 tile of means; further new points and sample columns are the two grid dimensions
 //   larger blocks   D_b by k_build_dense into the query's own workspace, the eager potrf_blocked (never the captured graphs of
 //                   the theta-step: they are keyed by workspace pointer and stay where they are), Y by trsm_left_lower on a
 //                   copy of U_b -- once per block; then per chunk of new points k_build_cross (C_b' stored d x kc), the same
@@ -24,7 +24,7 @@
 // calls and two contexts return the same bits.  Nothing that a sampler, a fit, mvn_ll, its score, a Laplace call or an
 // information query reads is changed; c.chol.linv is overwritten, as by every factorisation.
 #include "entry.h"
-#include "cov_entry.h"
+#include "cov_block.h"
 #include "dgemm_mfma.h"
 #include "reduce.h"
 #include <algorithm>
@@ -68,54 +68,24 @@ __global__ __launch_bounds__(64) void k_pred_small(const double* U, int ldu, int
                                                    int knew, int kcur, ThetaArg th, double* Mn, int ldm, double* cvar,
                                                    int* errflag)
 {
-    __shared__ double S[SMALL_BLOCK * (SMALL_BLOCK + 1)];
+    __shared__ double S[SMALL_BLOCK * SMALL_LS];
     __shared__ double Zs[SMALL_BLOCK * 64];
     __shared__ double Ws[SMALL_BLOCK * 64];
     const CovBlock blk = blocks[b];
     const int dim = blk.dim, lane = threadIdx.x;
-    constexpr int LS = SMALL_BLOCK + 1;
     const double* bd = data + blk.doff;
-    for (int e = lane; e < dim * dim; e += 64) {
-        int i = e % dim, j = e / dim;
-        if (i >= j) S[i * LS + j] = cov_entry(blk, cov, rows, bd, th, i, j);
-    }
-    __syncthreads();
-    // left-looking column Cholesky, the operations of k_small_ll
-    for (int j = 0; j < dim; ++j) {
-        if (lane == j) {
-            double d = S[j * LS + j];
-            for (int k = 0; k < j; ++k) d -= S[j * LS + k] * S[j * LS + k];
-            if (!(d > 0.0)) { atomicExch(errflag, 1); d = 1.0; }
-            S[j * LS + j] = sqrt(d);
-        }
-        __syncthreads();
-        if (lane > j && lane < dim) {
-            double s = S[lane * LS + j];
-            for (int k = 0; k < j; ++k) s -= S[lane * LS + k] * S[j * LS + k];
-            S[lane * LS + j] = s / S[j * LS + j];
-        }
-        __syncthreads();
-    }
+    small_block_factor(S, blk, cov, rows, bd, th, errflag);
     const int i0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
     const int cnt = kcur - i0 < 64 ? kcur - i0 : 64, ccnt = m - c0 < 64 ? m - c0 : 64;
     if (lane < cnt) {                                                // row i0 + lane of C_b: w = L^-1 c
-        double q = 0;
-        for (int k = 0; k < dim; ++k) {
-            double lsum = 0;
-            for (int j = 0; j < k; ++j) lsum += S[k * LS + j] * Ws[j * 64 + lane];
-            const double w = (cov_cross_entry(blk, cov, rows, bd, xn, knew, th, i0 + lane, k) - lsum) / S[k * LS + k];
-            Ws[k * 64 + lane] = w;
-            q += w * w;
-        }
+        const double q = small_block_forward(S, dim, Ws, lane, [&](int k) {
+            return cov_cross_entry(blk, cov, rows, bd, xn, knew, th, i0 + lane, k);
+        });
         if (blockIdx.y == 0) cvar[i0 + lane] = fmax(cov_prior_variance(blk, cov, rows, th) - q, 0.0);
     }
     if (lane < ccnt) {                                               // sample column c0 + lane: y = L^-1 u
         const double* u = U + blk.matstart + (size_t)(c0 + lane) * ldu;
-        for (int k = 0; k < dim; ++k) {
-            double lsum = 0;
-            for (int j = 0; j < k; ++j) lsum += S[k * LS + j] * Zs[j * 64 + lane];
-            Zs[k * 64 + lane] = (u[k] - lsum) / S[k * LS + k];
-        }
+        small_block_forward(S, dim, Zs, lane, [&](int k) { return u[k]; });
     }
     __syncthreads();
     if (lane < cnt)
@@ -134,8 +104,8 @@ __global__ __launch_bounds__(256) void k_pred_copy_rows(double* dst, int ldd, co
     for (int j = blockIdx.y; j < m; j += gridDim.y) dst[i + (size_t)j * ldd] = i < d ? src[i + (size_t)j * lds] : 0.0;
 }
 
-// C_b' (dp x kcur, zero border rows): the 64 x 16 workgroup of build_dense_body, the 64 along the observed index, so every
-// store of a wave is 512 contiguous bytes
+// C_b' (dp x kcur, zero border rows), rectangular: a 64 x 16 workgroup as lower_tile_walk's (cov_block.h), the 64 along the
+// observed index, so every store of a wave is 512 contiguous bytes
 __global__ __launch_bounds__(256) void k_build_cross(double* CT, int ld, int b, const CovBlock* blocks, const int32_t* cov,
                                                      int rows, const double* data, const double* xn, int knew, int kcur,
                                                      ThetaArg th, int dp)
@@ -230,8 +200,7 @@ int predict_re(Ctx& c, const double* theta, const int* nnew, const double* newda
     const int K = (int)Kll;
     MCML_REQUIRE(lds >= K && (!means || ldm >= K), "predict_re: leading dimension below the %d new points", K);
     ThetaArg th;
-    memset(&th, 0, sizeof th);
-    for (int i = 0; i < cs.npar; ++i) th.v[i] = theta[i];
+    MCML_TRY(theta_arg(theta, cs.npar, th));
 
     PredictState& x = c.predict;
     const int dmaxp = c.maxdim_large ? round_up(c.maxdim_large, 16) : SMALL_BLOCK;

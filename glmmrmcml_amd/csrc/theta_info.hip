@@ -30,7 +30,7 @@
 // samples are read, no collective is issued, and nothing a sampler, a fit, mvn_ll or the information query reads is changed.
 #include "entry.h"
 #include "component.h"
-#include "cov_entry.h"
+#include "cov_block.h"
 #include "dgemm_mfma.h"
 #include "glm.h"
 #include "reduce.h"
@@ -68,8 +68,8 @@ __global__ __launch_bounds__(CHOL_NB) void k_ti_linv(const double* L, int ldl, i
     }
 }
 
-// block b's part of d_par D into the Q x Q matrix E (zero before): both triangles.  A dense block: 64 x 16 tiles of its lower
-// triangle as k_build_dense; an all-gr block: its diagonal, 256 rows per workgroup
+// block b's part of d_par D into the Q x Q matrix E (zero before): both triangles.  A dense block: the 64 x 16 tiles of its lower
+// triangle (lower_tile_walk, cov_block.h); an all-gr block: its diagonal, 256 rows per workgroup
 __global__ __launch_bounds__(256) void k_ti_build_dD(double* E, int lde, int bidx, const CovBlock* blocks, const int32_t* cov,
                                                      int rows, const double* data, ThetaArg th, int par)
 {
@@ -81,16 +81,12 @@ __global__ __launch_bounds__(256) void k_ti_build_dD(double* E, int lde, int bid
         if (k < blk.dim) A[k + (size_t)k * lde] = cov_dentry(blk, cov, rows, bd, th, k, k, par);
         return;
     }
-    if ((int)blockIdx.x * 64 + 63 < (int)blockIdx.y * 16) return;
-    const int i = blockIdx.x * 64 + (threadIdx.x & 63);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int j = blockIdx.y * 16 + (threadIdx.x >> 6) * 4 + u;
-        if (i >= blk.dim || j > i) continue;
+    lower_tile_walk([&](int i, int j) {
+        if (i >= blk.dim || j > i) return;
         const double v = cov_dentry(blk, cov, rows, bd, th, i, j, par);
         A[i + (size_t)j * lde] = v;
         A[j + (size_t)i * lde] = v;
-    }
+    });
 }
 
 // part[pair * gridDim.x + tile] = sum over the 32 x 32 tile (I, J) of G_r[i, j] G_s[j, i], pair = (r, s), r >= s, of the nm
@@ -243,12 +239,7 @@ __global__ __launch_bounds__(256) void k_ti_comp(const int* var_ptr, const int* 
             S2[i * TI_LS + j] = s / S0[i * TI_LS + i];
         }
     } else if (tid >= 64 && tid - 64 < nv) {
-        const int j = tid - 64;
-        for (int i = j; i < nv; ++i) {
-            double s = (i == j) ? 1.0 : 0.0;
-            for (int k = j; k < i; ++k) s -= S1[i * TI_LS + k] * S3[k * TI_LS + j];
-            S3[i * TI_LS + j] = s / S1[i * TI_LS + i];
-        }
+        lower_inverse_column(S1, S3, TI_LS, nv, tid - 64);
     }
     __syncthreads();
     // tr B and tr(B B)
@@ -467,8 +458,8 @@ int theta_info(Ctx& c, const double* beta, double var_par, const double* theta, 
         return MCML_EUNSUPPORTED;
     }
     const bool comp = op != 1 && comp_ok;
-    ThetaArg th{};
-    std::copy(theta, theta + R, th.v);
+    ThetaArg th;
+    MCML_TRY(theta_arg(theta, R, th));
     const CovSpec& cs = c.cov;
     std::vector<unsigned> mask(cs.B, 0u);                          // bit p: block b has a slot that reads parameter p
     for (int b = 0; b < cs.B; ++b)

@@ -36,6 +36,22 @@ def layout(blocks):
     return np.array(rows, dtype=np.int32, order="F"), np.concatenate(data)
 
 
+def from_wire(cov, data):
+    """the inverse of `layout`: the (cov, data) wire format back as a list of blocks (dim, [(fn, x, par_index), ...])"""
+    cov = np.asarray(cov)
+    data = np.asarray(data, dtype=np.float64).ravel()
+    blocks, r, off = [], 0, 0
+    while r < cov.shape[0]:
+        bid, dim, terms = cov[r, 0], int(cov[r, 1]), []
+        while r < cov.shape[0] and cov[r, 0] == bid:
+            nv = int(cov[r, 3])
+            terms.append((int(cov[r, 2]), data[off:off + dim * nv].reshape(dim, nv, order="F"), int(cov[r, 4])))
+            off += dim * nv
+            r += 1
+        blocks.append((dim, terms))
+    return blocks
+
+
 def starts(blocks):
     """first random-effect index of every block"""
     return [int(s) for s in np.cumsum([0] + [b[0] for b in blocks])[:-1]]
@@ -212,6 +228,15 @@ def _edge32():
     return blocks, np.array([0.13, 0.10])
 
 
+def _ten_slots():
+    """a small and a large block with ten parameter slots each (five fexp terms, two parameters a term, on the same ten
+    parameters): more than the eight slots one pass of the score's reductions carries (GRAD_SLOTS, csrc/mvn_grad.h).  The
+    product of the terms is an exponential covariance on five coordinates with ranges about 1: condition numbers 4.0 and 24.4"""
+    rng = np.random.default_rng(20261021)
+    blocks = [(dim, [(FEXP, rng.random((dim, 1)), 2 * k) for k in range(5)]) for dim in (6, 40)]
+    return blocks, np.array([1.1, 0.9, 0.8, 1.3, 1.2, 0.7, 0.9, 1.1, 1.05, 0.6])
+
+
 MIXED, MIXED_THETA = _mixed()
 TWO_LARGE_A, TWO_LARGE_THETA = _two_large("A")
 TWO_LARGE_B, _ = _two_large("B")
@@ -219,6 +244,12 @@ EDGE32, EDGE32_THETA = _edge32()
 
 MIXED_RHO = 2            # the AR1 parameter of MIXED's 5-dim block only
 TWO_LARGE_RHO = 3        # the AR1 parameter of the 161-dim block
+
+# NOT an entry of LAYOUTS: at condition numbers this small the float64 numpy twin of the score uses up to 0.035 of the gradient
+# bound 2^-52 kappa mag_k (m in {1, 7, 64, 70}, three thetas, weighted and not), above the 0.0101 that
+# test_mvn_grad_reference_cpu.py asserts over LAYOUTS.  Its samples: samples(TEN_SLOTS, 70, TEN_SLOTS_SEED)
+TEN_SLOTS, TEN_SLOTS_THETA = _ten_slots()
+TEN_SLOTS_SEED = 1021
 
 LAYOUTS = {"MIXED": (MIXED, MIXED_THETA), "TWO_LARGE_A": (TWO_LARGE_A, TWO_LARGE_THETA),
            "TWO_LARGE_B": (TWO_LARGE_B, TWO_LARGE_THETA), "EDGE32": (EDGE32, EDGE32_THETA)}

@@ -94,22 +94,6 @@ def cross_matrix(block, xn, theta, dtype=np.float64):
     return Cm, A
 
 
-def blocks_from_wire(cov, data):
-    """the (cov, data) wire format of csrc/covspec.h back as a list of cov_layouts blocks"""
-    cov = np.asarray(cov)
-    data = np.asarray(data, dtype=np.float64).ravel()
-    blocks, r, off = [], 0, 0
-    while r < cov.shape[0]:
-        dim, terms, bid = int(cov[r, 1]), [], cov[r, 0]
-        while r < cov.shape[0] and cov[r, 0] == bid:
-            nv = int(cov[r, 3])
-            terms.append((int(cov[r, 2]), data[off:off + dim * nv].reshape(dim, nv, order="F"), int(cov[r, 4])))
-            off += dim * nv
-            r += 1
-        blocks.append((dim, terms))
-    return blocks
-
-
 # ---------------------------------------------------------------------------------------------- cases
 def make_case(blocks, theta, counts, u, seed, why, chunk=None):
     rng = np.random.default_rng(seed)

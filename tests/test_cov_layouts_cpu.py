@@ -33,6 +33,44 @@ def test_layouts_are_what_they_are_named_for():
     assert [b[0] for b in cl.EDGE32] == [32, 33]
 
 
+@pytest.mark.parametrize("name", NAMES + ["TEN_SLOTS"])
+def test_from_wire_is_the_inverse_of_layout(name):
+    blocks = cl.TEN_SLOTS if name == "TEN_SLOTS" else cl.LAYOUTS[name][0]
+    back = cl.from_wire(*cl.layout(blocks))
+    assert len(back) == len(blocks)
+    for (dim, terms), (bdim, bterms) in zip(blocks, back):
+        assert bdim == dim and len(bterms) == len(terms)
+        for (fn, x, pi), (bfn, bx, bpi) in zip(terms, bterms):
+            assert (bfn, bpi) == (fn, pi)
+            assert np.array_equal(bx, np.asarray(x, dtype=np.float64).reshape(dim, -1))
+
+
+def test_ten_slots_is_what_it_is_named_for():
+    """two blocks of 6 and 40, a small and a large one, ten parameter slots each on the same ten parameters; both factorise in
+    float64, with the condition numbers the layout's comment states; the score's reference evaluates it"""
+    import mvn_grad_reference as gr
+    blocks, theta = cl.TEN_SLOTS, cl.TEN_SLOTS_THETA
+    assert "TEN_SLOTS" not in cl.LAYOUTS
+    assert [b[0] for b in blocks] == [6, 40] and [cl.kind(b) for b in blocks] == ["small", "large"]
+    cov, _ = cl.layout(blocks)
+    for b in (0, 1):
+        rows = cov[cov[:, 0] == b]
+        assert rows[:, 2].tolist() == [cl.FEXP] * 5 and rows[:, 3].tolist() == [1] * 5 and rows[:, 4].tolist() == [0, 2, 4, 6, 8]
+    assert theta.tolist() == [1.1, 0.9, 0.8, 1.3, 1.2, 0.7, 0.9, 1.1, 1.05, 0.6]
+    for block, kappa in zip(blocks, (4.0, 24.4)):
+        D = cl.block_matrix(block, theta)[0]
+        L = cl.cholesky(D)
+        assert np.abs(L @ L.T - D).max() < 1e-14 * np.abs(D).max() * block[0]
+        print("TEN_SLOTS block of %d: kappa_2 = %.3f" % (block[0], np.linalg.cond(D, 2)))
+        assert abs(np.linalg.cond(D, 2) - kappa) < 0.05
+    u = cl.samples(blocks, 70, cl.TEN_SLOTS_SEED)
+    assert u.shape == (46, 70)
+    for w in (None, gr.weights(70)):
+        value, grad, mag, kappa = gr.score(blocks, theta, u, w)
+        assert np.isfinite(float(value)) and grad.shape == (10,) and np.all(np.isfinite(grad.astype(float))) and np.all(mag > 0)
+        assert abs(kappa - 24.4) < 0.05
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_blocks_are_well_conditioned(name):
     """a condition on the inputs: every tolerance below assumes it"""

@@ -98,7 +98,7 @@ def test_chunked_call(monkeypatch):
 
 def test_on_a_context_that_also_samples():
     d = synth.geospatial(150)
-    blocks = kr.blocks_from_wire(d["cov"], d["data"])
+    blocks = cl.from_wire(d["cov"], d["data"])
     with api.Context(d["cov"], d["data"], d["eff_range"], d["Z"], d["X"], d["y"], d["family"], d["link"]) as ctx:
         ctx.update_L(d["theta"])
         ctx.hmc_sample(d["beta"], d["sigma"], 6, 8, 0.5, 5, 0.9, seed=11, chains=4)
@@ -224,7 +224,7 @@ def _end_to_end(name, mod, fit, d, newdata):
     host = mod.predict(fit, newdata, on="host")
     P, R = mod.X.shape[1], mod.cov_parameters.size
     u = np.asarray(fit["re_samps"], float).reshape(mod.Z.shape[1], -1)
-    c = kr.make_case(kr.blocks_from_wire(d["cov"], d["data"]), fit["theta"][P:P + R], [0 if x is None else len(x) for x in newdata],
+    c = kr.make_case(cl.from_wire(d["cov"], d["data"]), fit["theta"][P:P + R], [0 if x is None else len(x) for x in newdata],
                      u, 0, name)
     c["newdata"] = newdata
     ref = kr.evaluate(c)
@@ -243,7 +243,7 @@ def test_model_predict_on_a_laplace_fit():
     d = fd.la_design("small_144x24", "poisson", "log")
     mod = ModelMCML(d["cov"], d["data"], d["eff_range"], d["Z"], d["X"], "poisson", "log", d["beta"], d["theta"])
     fit = mod.LA(d["y"], method="nr")
-    blocks = kr.blocks_from_wire(d["cov"], d["data"])
+    blocks = cl.from_wire(d["cov"], d["data"])
     newdata = [None] * len(blocks)
     for b in (0, 3, 7, 23):                                      # a level that matches
         newdata[b] = kr._block_columns(blocks[b])[0][:1].copy()

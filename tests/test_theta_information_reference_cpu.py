@@ -28,7 +28,7 @@ def test_analytic_dD_against_central_differences(key):
     1e-9 guards formulas, not rounding"""
     c = tr.case(key)
     theta = c["theta"]
-    blocks = tr.blocks_of(c["cov"], c["data"])
+    blocks = cl.from_wire(c["cov"], c["data"])
 
     def dense(th):
         mats = []

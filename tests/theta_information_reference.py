@@ -134,22 +134,6 @@ def names(c):
     return ["theta%d" % r for r in range(c["theta"].size)] + (["sigma"] if sigma_row(c) else [])
 
 
-def blocks_of(cov, data):
-    """the (cov, data) wire format back into cov_layouts' blocks (dim, [(fn, x, par_index), ...])"""
-    cov = np.asarray(cov)
-    data = np.asarray(data, float).ravel()
-    out, r, off = [], 0, 0
-    while r < cov.shape[0]:
-        bid, dim, terms = cov[r, 0], int(cov[r, 1]), []
-        while r < cov.shape[0] and cov[r, 0] == bid:
-            nv = int(cov[r, 3])
-            terms.append((int(cov[r, 2]), data[off:off + dim * nv].reshape(dim, nv, order="F"), int(cov[r, 4])))
-            off += dim * nv
-            r += 1
-        out.append((dim, terms))
-    return out
-
-
 def dlog(block, theta, dtype=LD):
     """{parameter: sum over the block's terms that read it of d log(term) / d parameter}, dim x dim each.  From the table of
     cov_layouts._term: a term's second return value is |its exponent argument| a, so
@@ -191,7 +175,7 @@ def dD(c, D, dtype=LD):
     D = np.asarray(D, dtype=np.float64).astype(dtype)
     out = [np.zeros(D.shape, dtype=dtype) for _ in range(R)]
     s = 0
-    for block in blocks_of(c["cov"], c["data"]):
+    for block in cl.from_wire(c["cov"], c["data"]):
         sl = slice(s, s + block[0])
         for p, f in dlog(block, c["theta"], dtype).items():
             out[p][sl, sl] += D[sl, sl] * f
