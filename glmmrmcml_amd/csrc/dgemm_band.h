@@ -45,7 +45,9 @@
 // mod 64, so the two 16-lane halves of a ds_read_b64 (rows k, k+1) are conflict-free without a swizzle.  A wave of
 // the pipeline has up to two jobs: it FILLS the ring -- a BandFill issues every STRIDE-th of the 52 one-KiB LDS-DMA
 // pieces of a stage and keeps the counted vmcnt -- and it MULTIPLIES, NS 80 x 16 strips of the tile (5 x NS
-// v_mfma_f64_16x16x4 tiles per K substep, operands read from LDS by hand-scheduled ds_reads).  All waves walk the
+// v_mfma_f64_16x16x4 tiles per K substep, operands read from LDS by hand-scheduled ds_reads, the reads of substep
+// s + 1 issued between the MFMAs of substep s and the next tile's first reads between those of the last substep,
+// behind the barrier: profiles/band_kloop_codegen.txt has the compiled loops).  All waves walk the
 // same item list and pass the same barriers.  Two kernels instantiate it:
 //   * dgemm_band_kernel, the 8-wave form: every wave does both, pieces wave, wave + 8, ... (7 per tile) and strip
 //     `wave` (NS = 1).  Its waves issue their pieces back to back at the top of a K tile, and a wave inside that
@@ -127,61 +129,100 @@ static __global__ __launch_bounds__(256) void k_band_ranges(const double* A, int
 // which also waits for the reads just issued for the NEXT group: measured (with a compiler-scheduled
 // copy of the K loop, since removed) the matrix pipe then idles ~14% of the K loop on LDS latency.
 // The reads are therefore issued through inline asm the compiler does not track, and the
-// counted waits are placed by hand (LDS returns in order: lgkmcnt(5 + NS) = "everything but the
-// reads just issued").  The waits carry the operand registers as in/out operands so the MFMAs
-// that consume them cannot be scheduled above the wait.
+// waits are placed by hand.  A substep's reads are not a block in front of its MFMAs (a wave
+// issues in order: inside the block it issues no MFMA, and the MFMA waves of a workgroup reach
+// the CU's one LDS pipe with their blocks together) but go one or two at a time BEHIND
+// individual MFMAs of the substep before (bd_step), the last of them early enough that the
+// MFMAs behind it cover its latency; the next substep opens with lgkmcnt(0), nothing else being
+// in flight.  The waits carry the operand registers as in/out operands and pin the order
+// behind them, so the MFMAs that consume them cannot be scheduled above the wait; the
+// compiler knows of no read in flight, so none may be in flight where it may copy an operand
+// register -- where a loop closes or begins (BD_TILE).
 #if defined(__HIP_DEVICE_COMPILE__)
 #define BD_RD(dst, addr, off) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
 #else
 #define BD_RD(dst, addr, off) (dst = 0.0)
 #endif
-// operands of K substep KS (4 k's) of the stage whose per-lane byte addresses are aaddr / baddr, for NS adjacent
-// 16-column strips: the second strip's B is the first one's + 256 bytes
+// Read R (0 .. 4 + NS) of the operands of K substep KS (4 k's) of the stage whose per-lane byte addresses are aaddr /
+// baddr, for NS adjacent 16-column strips, in the order the MFMAs of a substep want them: b0, a0 .. a4, b1 (the second
+// strip's B is the first one's + 256 bytes)
+template <int KS, int NS, int R>
+__device__ __forceinline__ void bd_read1(double (&a)[5], double (&b)[NS], unsigned aaddr, unsigned baddr)
+{
+    static_assert(NS == 1 || NS == 2, "one or two strips per wave");
+    static_assert(R >= 0 && R < 5 + NS, "one substep's reads");
+    if constexpr (R == 0) BD_RD(b[0], baddr, KS * 2 * BD_BN * 16);
+    else if constexpr (R <= 5) BD_RD(a[R - 1], aaddr, KS * 4 * BD_BM * 8 + (R - 1) * 128);
+    else BD_RD(b[1], baddr, KS * 2 * BD_BN * 16 + 256);
+}
+// reads [R0, R1) of a substep, clipped to the reads there are
+template <int KS, int NS, int R0, int R1>
+__device__ __forceinline__ void bd_reads(double (&a)[5], double (&b)[NS], unsigned aaddr, unsigned baddr)
+{
+    if constexpr (R0 < R1 && R0 < 5 + NS) {
+        bd_read1<KS, NS, R0>(a, b, aaddr, baddr);
+        bd_reads<KS, NS, R0 + 1, R1>(a, b, aaddr, baddr);
+    }
+}
+// all of them as a block: the first reads of an item, which nothing is there to cover
 template <int KS, int NS>
 __device__ __forceinline__ void bd_read(double (&a)[5], double (&b)[NS], unsigned aaddr, unsigned baddr)
 {
-    static_assert(NS == 1 || NS == 2, "one or two strips per wave");
-    BD_RD(a[0], aaddr, KS * 4 * BD_BM * 8);
-    BD_RD(a[1], aaddr, KS * 4 * BD_BM * 8 + 128);
-    BD_RD(a[2], aaddr, KS * 4 * BD_BM * 8 + 256);
-    BD_RD(a[3], aaddr, KS * 4 * BD_BM * 8 + 384);
-    BD_RD(a[4], aaddr, KS * 4 * BD_BM * 8 + 512);
-    BD_RD(b[0], baddr, KS * 2 * BD_BN * 16);
-    if constexpr (NS == 2) BD_RD(b[1], baddr, KS * 2 * BD_BN * 16 + 256);
+    bd_reads<KS, NS, 0, 5 + NS>(a, b, aaddr, baddr);
 }
-// LEAVE: 5 + NS (the reads of the next substep stay in flight) or 0
-template <int LEAVE, int NS>
+// every read issued so far has landed (rule: an MFMA must not be scheduled above the wait that its operands need --
+// the operands are in / out operands of the wait, and the order is pinned behind it)
+template <int NS>
 __device__ __forceinline__ void bd_wait(double (&a)[5], double (&b)[NS])
 {
-    static_assert(LEAVE == 0 || LEAVE == 5 + NS, "one substep's reads");
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (NS == 1)
-        asm volatile("s_waitcnt lgkmcnt(%[n])" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]) : [n] "n"(LEAVE));
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]));
     else
-        asm volatile("s_waitcnt lgkmcnt(%[n])" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]), "+v"(b[1]) : [n] "n"(LEAVE));
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(b[0]), "+v"(b[1]));
+    __builtin_amdgcn_sched_barrier(0);
 #endif
 }
-template <int NS>
-__device__ __forceinline__ void bd_mfma(d4 (&acc)[NS][5][1], const double (&a)[5], const double (&b)[NS])
-{
-#pragma unroll
-    for (int j = 0; j < NS; ++j)
-#pragma unroll
-        for (int i = 0; i < 5; ++i) acc[j][i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a[i], acc[j][i][0], 0, 0, 0);
-}
 
-// the MFMAs of an edge K tile (band_plan.h): row tile i of substep KS only where its extent reaches, m[i] bit KS -- a
-// wave-uniform condition, a scalar branch around the row tile's NS MFMAs.  Every accumulator still sees its MFMAs in K order.
-template <int KS, int NS>
-__device__ __forceinline__ void bd_mfma_ext(d4 (&acc)[NS][5][1], const double (&a)[5], const double (&b)[NS], const unsigned (&m)[5])
+// The MFMAs of one K substep on the operands (a, b), which have landed, with the reads of the NEXT substep -- substep
+// KSN of the stage at aaddr / baddr, into (na, nb) -- slotted one or two at a time behind individual MFMAs: a wave
+// issues in order, so a block of reads in front of the MFMAs is time in which it issues none, and the four MFMA waves
+// of a workgroup, which leave every barrier together, put their blocks on the CU's one LDS pipe at the same moment.
+//   interior tile (EDGE = false), MFMAs in the order (b0, a0 .. a4), (b1, a0 .. a4):
+//     NS = 2: one read behind each of the first 7 of the 10 MFMAs; three MFMAs (192 cycles) follow the last read;
+//     NS = 1: two reads behind each of the first 3 of the 5 MFMAs; two MFMAs of this wave, and those of the SIMD's
+//             other wave, follow the last read.
+//   edge tile (band_plan.h): row tile i's NS MFMAs only where its extent reaches substep KS, m[i] bit KS -- a
+//     wave-uniform condition, a scalar branch around them; two reads behind each row tile, taken or not.
+// Every accumulator sees one MFMA per substep, in K order, whatever the order inside a substep: same bits.
+template <int KS, int KSN, int NS, bool EDGE>
+__device__ __forceinline__ void bd_step(d4 (&acc)[NS][5][1], const double (&a)[5], const double (&b)[NS],
+                                        double (&na)[5], double (&nb)[NS], unsigned aaddr, unsigned baddr,
+                                        const unsigned (&m)[5])
 {
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-        if (m[i] & (1u << KS)) {
-            asm volatile("" ::: "memory");      // a branch, not both arms and a select
-#pragma unroll
-            for (int j = 0; j < NS; ++j) acc[j][i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a[i], acc[j][i][0], 0, 0, 0);
-        }
+    if constexpr (EDGE) {
+#define BD_ROW(I)                                                                                                         \
+        if (m[I] & (1u << KS)) {                                                                                          \
+            asm volatile("" ::: "memory");      /* a branch, not both arms and a select */                                \
+            _Pragma("unroll")                                                                                             \
+            for (int j = 0; j < NS; ++j) acc[j][I][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a[I], acc[j][I][0], 0, 0, 0); \
+        }                                                                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                                \
+        bd_reads<KSN, NS, 2 * I, 2 * I + 2>(na, nb, aaddr, baddr);                                                        \
+        __builtin_amdgcn_sched_barrier(0);
+        BD_ROW(0) BD_ROW(1) BD_ROW(2) BD_ROW(3) BD_ROW(4)
+#undef BD_ROW
+    } else {
+        constexpr int PER = NS == 2 ? 1 : 2;    // reads behind one MFMA
+#define BD_ONE(J, I)                                                                                                      \
+        acc[J][I][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[J], a[I], acc[J][I][0], 0, 0, 0);                           \
+        __builtin_amdgcn_sched_barrier(0);                                                                                \
+        bd_reads<KSN, NS, PER * (5 * J + I), PER * (5 * J + I + 1)>(na, nb, aaddr, baddr);                                \
+        __builtin_amdgcn_sched_barrier(0);
+        BD_ONE(0, 0) BD_ONE(0, 1) BD_ONE(0, 2) BD_ONE(0, 3) BD_ONE(0, 4)
+        if constexpr (NS == 2) { BD_ONE(1, 0) BD_ONE(1, 1) BD_ONE(1, 2) BD_ONE(1, 3) BD_ONE(1, 4) }
+#undef BD_ONE
+    }
 }
 
 // The item list is read with a SCALAR load (hand-written: the compiler will not scalarise a load it
@@ -397,7 +438,7 @@ __device__ __forceinline__ void band_walk(const BandP& bp, const Epi& epi, const
             if (first_item) stamp(1);
             int st = 0;
             double ra[2][5], rb[2][NJ];
-            if constexpr (NS > 0) bd_read<0>(ra[0], rb[0], aoff, boff);
+            if constexpr (NS > 0) { bd_read<0>(ra[0], rb[0], aoff, boff); bd_wait(ra[0], rb[0]); }
             // The K loop: LAST tiles of it with the tile body BODY.  The stage of tile kt - 1 is free to fill: every wave
             // finished its reads before that tile's barrier.
 #define BD_KLOOP(LAST, BODY)                                                                         \
@@ -412,31 +453,41 @@ __device__ __forceinline__ void band_walk(const BandP& bp, const Epi& epi, const
                 BODY                                                                                 \
                 st = stn;                                                                            \
             }
-            // The tile body of an MFMA wave, MFMA being all of a substep's MFMAs or those inside the extents.  Last
-            // substep: synchronise first (this wave's pieces of tile kt + 1 landed, its own reads of tile kt complete),
-            // start the next tile's first reads, then the MFMAs
-#define BD_STEP(KS, CUR, NXT, MFMA)                                  \
-                    bd_read<KS + 1>(ra[NXT], rb[NXT], aaddr, baddr); \
-                    bd_wait<5 + NS>(ra[CUR], rb[CUR]);               \
-                    MFMA(KS, CUR);                                   \
-                    __builtin_amdgcn_sched_barrier(0);
-#define BD_TILE(MFMA)                                                                                                     \
-                    BD_STEP(0, 0, 1, MFMA) BD_STEP(1, 1, 0, MFMA) BD_STEP(2, 0, 1, MFMA) BD_STEP(3, 1, 0, MFMA)           \
-                    BD_STEP(4, 0, 1, MFMA) BD_STEP(5, 1, 0, MFMA) BD_STEP(6, 0, 1, MFMA)                                  \
+            // The tile body of an MFMA wave, EDGE: all of a substep's MFMAs or those inside the extents (bd_step).  A
+            // substep waits for its operands -- the only reads in flight -- and issues its MFMAs with the next substep's
+            // reads between them.  Last substep: synchronise first (this wave's pieces of tile kt + 1 landed, its own reads
+            // of tile kt complete); its operands are in registers, so the first instruction behind the barrier is an MFMA,
+            // and the next tile's first reads go between its MFMAs like any substep's.  Behind the item's last tile there
+            // is no next stage: the same reads go to the stage just finished, straight-line code instead of a second copy
+            // of the MFMAs; what they return is never an operand, and the wait that ends the tile retires them.
+            // The wait for substep 0's operands stands at the END of the tile before (and behind the item's first reads):
+            // the same place in the instruction stream, but no read is in flight where a loop closes or the next loop
+            // begins -- there the compiler may copy a loop-carried operand register, and it does not know of the reads.
+#define BD_STEP(KS, CUR, NXT, EDGE)                                                                                       \
+                    bd_step<KS, KS + 1, NS, EDGE>(acc, ra[CUR], rb[CUR], ra[NXT], rb[NXT], aaddr, baddr, em);             \
+                    bd_wait(ra[NXT], rb[NXT]);
+#define BD_TILE(EDGE)                                                                                                     \
+                    BD_STEP(0, 0, 1, EDGE) BD_STEP(1, 1, 0, EDGE) BD_STEP(2, 0, 1, EDGE) BD_STEP(3, 1, 0, EDGE)           \
+                    BD_STEP(4, 0, 1, EDGE) BD_STEP(5, 1, 0, EDGE)                                                         \
+                    bd_step<6, 7, NS, EDGE>(acc, ra[0], rb[0], ra[1], rb[1], aaddr, baddr, em);                           \
+                    const int sr = kt + 1 < nk ? stn : st;                                                                \
                     fill.wait_leave(issued - kt - 2);                                                                     \
-                    bd_wait<0>(ra[1], rb[1]);                                                                             \
+                    bd_wait(ra[1], rb[1]);                                                                                \
                     __builtin_amdgcn_s_barrier();                                                                         \
-                    if (kt + 1 < nk) bd_read<0>(ra[0], rb[0], aoff + stn * BD_STAGE_BYTES, boff + stn * BD_STAGE_BYTES);  \
-                    MFMA(7, 1);                                                                                           \
-                    __builtin_amdgcn_sched_barrier(0);
-#define BD_MFMA_ALL(KS, CUR) bd_mfma(acc, ra[CUR], rb[CUR])
-#define BD_MFMA_EXT(KS, CUR) bd_mfma_ext<KS>(acc, ra[CUR], rb[CUR], em)
+                    __builtin_amdgcn_sched_barrier(0);                                                                    \
+                    bd_step<7, 0, NS, EDGE>(acc, ra[1], rb[1], ra[0], rb[0], aoff + sr * BD_STAGE_BYTES,                  \
+                                            boff + sr * BD_STAGE_BYTES, em);                                              \
+                    bd_wait(ra[0], rb[0]);
+            // an interior tile: no mask is looked at
+#define BD_TILE_ALL                                                                                                       \
+                    const unsigned em[BD_RT] = {~0u, ~0u, ~0u, ~0u, ~0u};                                                 \
+                    BD_TILE(false)
             // an edge tile: the same reads, waits and barrier; per row tile the substeps inside its extent
 #define BD_TILE_EDGE                                                                                                      \
                     unsigned em[BD_RT];                                                                                   \
                     _Pragma("unroll")                                                                                     \
                     for (int i = 0; i < BD_RT; ++i) em[i] = band_ext_mask(ext[2 * i], ext[2 * i + 1], kt0 + kt);          \
-                    BD_TILE(BD_MFMA_EXT)
+                    BD_TILE(true)
             int kt = 0;
             if constexpr (NS > 0) {
                 // edge tiles [0, e0), interior tiles [e0, e1), edge tiles [e1, nk): three loops in a row, so that the
@@ -445,14 +496,13 @@ __device__ __forceinline__ void band_walk(const BandP& bp, const Epi& epi, const
                 const int e0 = il < 0 ? 0 : (il < nk ? il : nk);
                 const int e1 = ih < e0 ? e0 : (ih < nk ? ih : nk);
                 BD_KLOOP(e0, BD_TILE_EDGE)
-                BD_KLOOP(e1, BD_TILE(BD_MFMA_ALL))
+                BD_KLOOP(e1, BD_TILE_ALL)
                 BD_KLOOP(nk, BD_TILE_EDGE)
             } else {
                 BD_KLOOP(nk, fill.wait_leave(issued - kt - 2); __builtin_amdgcn_s_barrier();)
             }
 #undef BD_TILE_EDGE
-#undef BD_MFMA_EXT
-#undef BD_MFMA_ALL
+#undef BD_TILE_ALL
 #undef BD_TILE
 #undef BD_STEP
 #undef BD_KLOOP
