@@ -1,6 +1,6 @@
 """Loads the in-tree HIP library and gives every function of include/glmmr_mcml_c.h (and of the headers of the same
 directory it includes: glmmr_mcml_info.h, glmmr_mcml_predict.h, glmmr_mcml_sandwich.h, glmmr_mcml_band.h,
-glmmr_mcml_theta_info.h) its prototype.  There is no CPU
+glmmr_mcml_theta_info.h, glmmr_mcml_small_sample.h) its prototype.  There is no CPU
 fallback: if the library (or the header the prototypes are read from) is missing, or no MI355X is visible when a compute
 entry point is called, the call fails loudly."""
 import ctypes as C

@@ -657,6 +657,35 @@ class Context:
         keys = ("requested", "op", "ncomp", "max_vars", "launches", "dense_bytes", "R", "rows")
         return _plan(_lib.lib().glmmr_mcml_dbg_theta_information_plan, C.c_longlong, keys, self._h)
 
+    def small_sample(self, beta, var_par, theta, operator=None):
+        """The ingredients of the Kenward-Roger / Satterthwaite small-sample corrections of the fixed effects on the device
+        (csrc/small_sample.hip, include/glmmr_mcml_small_sample.h glmmr_mcml_ctx_small_sample) ->
+        dict(information, theta_information, P, Q, R, names): information = X' Sigma^-1 X (information_matrix's bits on the
+        operator run), theta_information = theta_information's bits, and with d_r Sigma = Z (d_r D) Z' (2 sigma I for "sigma")
+        P[r] = -X' Sigma^-1 d_r Sigma Sigma^-1 X, Q[r, s] = X' Sigma^-1 d_r Sigma Sigma^-1 d_s Sigma Sigma^-1 X,
+        R[r, s] = X' Sigma^-1 d2_rs Sigma Sigma^-1 X, arrays of shape (no, P, P) and (no, no, P, P); names as
+        theta_information.  theta, operator and the errors: as theta_information"""
+        beta = _f(beta).ravel()
+        if beta.size != self.P:
+            raise ValueError("beta must hold %d values" % self.P)
+        R = self.npar()
+        th = None if theta is None else _f(theta).ravel()
+        if th is not None and th.size < R:
+            raise ValueError("theta must hold %d values" % R)
+        buf = _small_sample_buffers(self.P, R)
+        got = C.c_int()
+        _lib.check(_lib.lib().glmmr_mcml_ctx_small_sample(self._h, _p(beta), float(var_par), _p(th), _INFO_OP[operator],
+                                                          _p(buf[0]), self.P, _p(buf[1]), R + 1, _p(buf[2]), _p(buf[3]),
+                                                          _p(buf[4]), C.byref(got)))
+        return _small_sample_result(buf, self.P, R, got.value)
+
+    def small_sample_plan(self):
+        """what the last small_sample on this context was asked for and ran (test hook, include/glmmr_mcml_small_sample.h
+        glmmr_mcml_dbg_small_sample_plan): op 0 dense, 1 component; launches: of csrc/small_sample.hip's own kernels; bytes: of
+        the matrices the new part allocated, Q x P, Q x (R + the pairs a block reads together) P and n x P ones -- none of them Q x Q"""
+        keys = ("requested", "op", "ncomp", "max_vars", "launches", "bytes", "R", "rows")
+        return _plan(_lib.lib().glmmr_mcml_dbg_small_sample_plan, C.c_longlong, keys, self._h)
+
     def sandwich(self, beta, var_par, theta=None, cluster=None, operator=None, scores=False):
         """The cluster-robust (sandwich) covariance of the fixed effects on the device (csrc/sandwich.hip,
         include/glmmr_mcml_sandwich.h glmmr_mcml_ctx_sandwich) -> dict(information, meat, vcov, ncluster[, scores]):
@@ -897,6 +926,41 @@ def theta_information(cov, data, eff_range, Z, X, family, link, beta, theta, var
     _lib.check(_lib.lib().glmmr_mcml_theta_information(C.byref(p), _p(beta), _p(theta), theta.size, float(var_par),
                                                        _INFO_OP[operator], _p(out), R + 1, C.byref(got)))
     return _theta_info_result(out, R, got.value)
+
+
+def _small_sample_buffers(P, R):
+    """the five outputs of a small_sample call, sized for the sigma row"""
+    no = R + 1
+    return (np.zeros((P, P), order="F"), np.zeros((no, no), order="F"), np.zeros(no * P * P), np.zeros(no * no * P * P),
+            np.zeros(no * no * P * P))
+
+
+def _small_sample_result(buf, P, R, rows):
+    """dict(information, theta_information, P, Q, R, names) from the buffers a small_sample call filled with `rows` rows: the
+    stacks hold column-major P x P matrices at r and r + rows s"""
+    ti = _theta_info_result(buf[1], R, rows)
+    Pm = buf[2][:rows * P * P].reshape(rows, P, P).transpose(0, 2, 1)
+    Qm, Rm = (b[:rows * rows * P * P].reshape(rows, rows, P, P).transpose(1, 0, 3, 2) for b in buf[3:])
+    return dict(information=buf[0], theta_information=ti["information"], P=np.ascontiguousarray(Pm), Q=np.ascontiguousarray(Qm),
+                R=np.ascontiguousarray(Rm), names=ti["names"])
+
+
+def small_sample(cov, data, eff_range, Z, X, family, link, beta, theta, var_par=1.0, operator=None):
+    """Context.small_sample on a context made for the call (glmmr_mcml_small_sample): the ingredients of the Kenward-Roger /
+    Satterthwaite corrections at beta / theta / var_par -> dict(information, theta_information, P, Q, R, names); beyond the
+    reference's exports.  y is not read: zeros stand in for it"""
+    Z = _f(Z)
+    p, keep = _problem(cov, data, eff_range, Z, X, np.zeros(Z.shape[0]), family, link)
+    beta = _f(beta).ravel(); theta = _f(theta).ravel()
+    if beta.size != p.P:
+        raise ValueError("beta must hold %d values" % p.P)
+    R = _npar_of(cov)
+    buf = _small_sample_buffers(p.P, R)
+    got = C.c_int()
+    _lib.check(_lib.lib().glmmr_mcml_small_sample(C.byref(p), _p(beta), _p(theta), theta.size, float(var_par), _INFO_OP[operator],
+                                                  _p(buf[0]), p.P, _p(buf[1]), R + 1, _p(buf[2]), _p(buf[3]), _p(buf[4]),
+                                                  C.byref(got)))
+    return _small_sample_result(buf, p.P, R, got.value)
 
 
 def _cluster_ids(cluster, n):

@@ -375,6 +375,20 @@ extern "C" int glmmr_mcml_ctx_theta_information(glmmr_mcml_ctx* h, const double*
     return theta_info(c, beta, var_par, theta, op, out, ldo, nout);
 }
 
+// the ingredients of the small-sample corrections (small_sample.hip).  theta is required, as for the query above
+extern "C" int glmmr_mcml_ctx_small_sample(glmmr_mcml_ctx* h, const double* beta, double var_par, const double* theta, int op,
+                                           double* info, int ldi, double* tinfo, int ldt, double* Pm, double* Qm, double* Rm,
+                                           int* nout)
+{
+    MCML_REQUIRE(h && beta && theta && info && tinfo && Pm && Qm && Rm && nout, "small_sample: null argument (theta is required)");
+    Ctx& c = h->c;
+    MCML_HIP(hipSetDevice(c.device));
+    MCML_REQUIRE(c.n > 0 && c.cov.npar > 0, "small_sample: the context has no model / covariance");
+    MCML_TRY(mvn_gen_L(c, theta, true));
+    MCML_TRY(install_L(c));
+    return small_sample(c, beta, var_par, theta, op, info, ldi, tinfo, ldt, Pm, Qm, Rm, nout);
+}
+
 // the cluster-robust sandwich of the fixed effects (sandwich.hip).  theta: as glmmr_mcml_ctx_information
 extern "C" int glmmr_mcml_ctx_sandwich(glmmr_mcml_ctx* h, const double* beta, double var_par, const double* theta, int op,
                                        const int* cluster, int ncluster, double* info, int ldi, double* meat, int ldm,
@@ -781,6 +795,18 @@ extern "C" int glmmr_mcml_theta_information(const glmmr_mcml_problem* prob, cons
     MCML_REQUIRE(ntheta >= g.h->c.cov.npar, "theta_information: %d covariance parameters given, the covariance needs %d", ntheta,
                  g.h->c.cov.npar);
     return glmmr_mcml_ctx_theta_information(g.h, beta, var_par, theta, op, out, ldo, nout);
+}
+
+extern "C" int glmmr_mcml_small_sample(const glmmr_mcml_problem* prob, const double* beta, const double* theta, int ntheta,
+                                       double var_par, int op, double* info, int ldi, double* tinfo, int ldt, double* Pm,
+                                       double* Qm, double* Rm, int* nout)
+{
+    MCML_REQUIRE(prob && beta && theta && info && tinfo && Pm && Qm && Rm && nout, "small_sample: null argument");
+    CtxGuard g;
+    MCML_TRY(open_ctx(prob, nullptr, g));
+    MCML_REQUIRE(ntheta >= g.h->c.cov.npar, "small_sample: %d covariance parameters given, the covariance needs %d", ntheta,
+                 g.h->c.cov.npar);
+    return glmmr_mcml_ctx_small_sample(g.h, beta, var_par, theta, op, info, ldi, tinfo, ldt, Pm, Qm, Rm, nout);
 }
 
 extern "C" int glmmr_mcml_sandwich(const glmmr_mcml_problem* prob, const double* beta, const double* theta, int ntheta,

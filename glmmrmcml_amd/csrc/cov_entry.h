@@ -7,6 +7,7 @@
 //   cov_prior_variance  the product at distance 0: the variance of a row of an all-gr block (k_diag_prep in mvn_grad.h,
 //                       k_diag_fill in mvn.hip) and of a new point (k_pred_diag, k_pred_small, k_pred_cvar)
 //   cov_dentry          (d D_b / d theta_par)[i, j]: k_ti_build_dD, k_ti_comp (theta_info.hip)
+//   cov_d2entry         (d^2 D_b / d theta_r d theta_s)[i, j]: k_ss_apply (small_sample.hip)
 //   grad_entry          (mvn_grad.h) h D_b[i, j] dlog of a window of the block's slots: k_small_grad, k_grad_reduce_large
 #pragma once
 #include "covspec.h"
@@ -90,6 +91,40 @@ __device__ __forceinline__ double cov_dentry(const CovBlock& blk, const int32_t*
                 if (pi + q == par) dl += cov_term_dlog(fn, dist, &th.v[pi], q);
         });
     return val * dl;
+}
+
+// d^2 log(term) / d t[q]^2 of the same terms; between two parameters of one term, and between two terms, the second
+// log-derivative is 0 (the log of every term is a sum of functions of one parameter each)
+__device__ __forceinline__ double cov_term_d2log(int fn, double dist, const double* g, int q)
+{
+    switch (fn) {
+    case 1: return -2.0 / (g[0] * g[0]);
+    case 2: return -2.0 * dist / (g[0] * g[0] * g[0]);
+    case 3: return -dist / (g[0] * g[0]);
+    case 4: return q == 0 ? -1.0 / (g[0] * g[0]) : -6.0 * dist * dist / (g[1] * g[1] * g[1] * g[1]);
+    case 7: return q == 0 ? -1.0 / (g[0] * g[0]) : -2.0 * dist / (g[1] * g[1] * g[1]);
+    case 14: return -6.0 * dist * dist / (g[0] * g[0] * g[0] * g[0]);
+    }
+    return 0.0;
+}
+
+// (d^2 D_b / d theta_r d theta_s)[i, j] = D_b[i, j] (dl_r dl_s + [r == s] the sum of cov_term_d2log over the slots that read r),
+// dl_p the sum of cov_dentry; one walk yields all three.  An all-gr block is diagonal, as in cov_dentry
+__device__ __forceinline__ double cov_d2entry(const CovBlock& blk, const int32_t* cov, int rows, const double* bd,
+                                              const ThetaArg& th, int i, int j, int r, int s)
+{
+    if (blk.all_gr && i != j) return 0.0;
+    double dlr = 0.0, dls = 0.0, d2 = 0.0;
+    const double val = cov_walk(
+        blk, cov, rows, th,
+        [&](int c) { return blk.all_gr ? 0.0 : bd[i + (size_t)c * blk.dim] - bd[j + (size_t)c * blk.dim]; },
+        [&](int fn, int pi, double dist) {
+            for (int q = 0; q < CovSpec::fn_npar(fn); ++q) {
+                if (pi + q == r) { dlr += cov_term_dlog(fn, dist, &th.v[pi], q); d2 += cov_term_d2log(fn, dist, &th.v[pi], q); }
+                if (pi + q == s) dls += cov_term_dlog(fn, dist, &th.v[pi], q);
+            }
+        });
+    return val * (dlr * dls + (r == s ? d2 : 0.0));
 }
 
 }  // namespace mcml

@@ -188,6 +188,17 @@ struct ThetaInfoState {
     long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// the small-sample query (small_sample.hip): c = M^-1 ZL' V X and d = L^-T c (Q x P), W = every U_r and V_rs side by side
+// (Q x (R + the pairs of parameters a block reads together) P), T / Y = the columns on their way to (Z' Sigma^-1 Z) U_r; gaussian / identity: A = Sigma^-1 X,
+// V A, A2 = Sigma^-1 A, ZL c (n x P), c2, d2 (Q x P); the work items of k_ss_apply, the jobs and partials of k_ss_gram and the
+// result I_beta | 2 flags | I_theta | P | Q | R; kept between calls.  plan: what the last call did
+// (glmmr_mcml_dbg_small_sample_plan)
+struct SmallSampleState {
+    DevMat C, Dm, W, T, Y, A, VA, A2, ZC, C2, D2;
+    DevBuf work, jobs, part, res;
+    long long plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 // the sandwich query (sandwich.hip): the residual flag, the working residual e, v o e, a = Sigma^-1 e, the right-hand side / t (Q),
 // ZL t (dense operator), the clusters' CSR, the meat's partials and the result B | 2 flags | G; kept between calls.  plan: what
 // the last call did (glmmr_mcml_dbg_sandwich_plan)
@@ -224,6 +235,7 @@ struct Ctx {
     ExactCompState exact_comp;
     InfoState info;
     ThetaInfoState tinfo;
+    SmallSampleState ss;
     SandwichState sand;
     PredictState predict;
     bool no_sparse_zl = false;  // the Laplace path works on the dense ZL / ZLT

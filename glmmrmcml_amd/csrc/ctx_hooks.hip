@@ -226,6 +226,14 @@ extern "C" int glmmr_mcml_dbg_theta_information_plan(glmmr_mcml_ctx* h, long lon
     return MCML_OK;
 }
 
+// read-only: what the last glmmr_mcml_ctx_small_sample on this context was asked for and did (small_sample.hip)
+extern "C" int glmmr_mcml_dbg_small_sample_plan(glmmr_mcml_ctx* h, long long* out8)
+{
+    MCML_REQUIRE(h && out8, "dbg_small_sample_plan: null argument");
+    std::copy(h->c.ss.plan, h->c.ss.plan + 8, out8);
+    return MCML_OK;
+}
+
 extern "C" int glmmr_mcml_dbg_emulate_world(glmmr_mcml_ctx* h, int world, int mode)
 {
     MCML_REQUIRE(h, "emulate_world: null context");

@@ -1,5 +1,5 @@
 // entry.h -- the host entry points one translation unit defines and another calls: the samplers (hmc.hip), the drivers
-// (drivers.hip, laplace.hip), the queries (info.hip, sandwich.hip, predict.hip, theta_info.hip) and the launch counters (hmc.hip, component.hip) behind the extern "C" layer (cabi.hip,
+// (drivers.hip, laplace.hip), the queries (info.hip, sandwich.hip, predict.hip, theta_info.hip, small_sample.hip) and the launch counters (hmc.hip, component.hip) behind the extern "C" layer (cabi.hip,
 // ctx_hooks.hip).  The defining
 // files include this header, so a signature that drifts is a compile error, not a wrong link.
 #pragma once
@@ -70,6 +70,9 @@ struct InfoDenseScope {
 // M = I + ZL' V ZL -- comp: every M_c in c.info.f; else c.info.M factorised on the dense ZL / ZL', which `dense` builds where the
 // context's operator is the sparse one.  rhs: info_matrix's right-hand sides ZL' V X into c.info.S on the way
 int info_front(Ctx& c, const double* beta, double var_par, bool comp, bool rhs, InfoDenseScope& dense);
+// what info_matrix launches behind info_front(rhs): S = R^-1 (ZL' V X) in c.info.S on the operator info_front ran, then gram_launch
+// -> c.info.res (P x P and the two flags).  dense_built: `dense` built the dense ZL / ZL' (the plan's byte count)
+int info_solve_gram(Ctx& c, bool comp, bool dense_built);
 // the chunked Gram reduction, two launches: out[a, b] = out[b, a] = sum_i U[i, a] W[i, b] - sum_q S[q, a] S[q, b], a >= b, over n
 // and Q rows in chunks of 2048, the partials in `part`, each sum in a fixed order (Q = 0: no second sum, S is not read); behind
 // the P x P matrix ride the two flags of the call: out[P P] = the context's "not positive definite" flag, out[P P + 1] = *bad
@@ -96,6 +99,28 @@ int sandwich_matrices(Ctx& c, const double* beta, double var_par, int op, const 
 // the resident L = L(theta) -> out (nout x nout, column-major, symmetric to the bit), *nout = npar, or npar + 1 with the sigma row
 // of gaussian / identity.  op: as info_matrix, the component operator where theta_info_component_ok.  On an error nothing is written
 int theta_info(Ctx& c, const double* beta, double var_par, const double* theta, int op, double* out, int ldo, int* nout);
+// its two halves, for a query that needs I_theta with more (small_sample.hip).  theta_info_begin: the operator for `op` (comp),
+// the kernels' theta and every block's parameter mask, c.tinfo.plan started; MCML_EUNSUPPORTED, in `who`'s name, where op = 2
+// does not apply.  theta_info_compute, after info_front on the same operator: every launch of the query -> c.tinfo.res (no x no
+// and the two flags); B = M^-1 N (c.tinfo.B, dense operator) and the inverted diagonal blocks of L in c.chol.linv stay behind it
+constexpr int TI_COMP_MAX_VARS = 64;              // variables of a component the component operator takes
+struct ThetaInfoCall {
+    ThetaArg th;
+    std::vector<unsigned> mask;                   // bit p: block b has a slot that reads parameter p
+    int R = 0, sigma_row = 0, no = 0;
+    bool comp = false, sparse_ctx = false;
+};
+bool theta_info_component_ok(const Ctx& c);
+int theta_info_begin(Ctx& c, const char* who, const double* theta, int op, ThetaInfoCall& k);
+int theta_info_compute(Ctx& c, const ThetaInfoCall& k, double var_par);
+
+// ---- small_sample.hip ----
+// I_beta and I_theta (information_matrix's and theta_info's, to the bit) and the P x P matrices of the Kenward-Roger /
+// Satterthwaite corrections, P_r (no of them), Q_rs and R_rs (no x no each, index r + no s), at beta / var_par / theta with the
+// resident L = L(theta); no = npar, or npar + 1 with sigma last for gaussian / identity.  op: as theta_info.  On an error nothing
+// is written
+int small_sample(Ctx& c, const double* beta, double var_par, const double* theta, int op, double* info, int ldi, double* tinfo,
+                 int ldt, double* Pm, double* Qm, double* Rm, int* nout);
 
 // ---- predict.hip ----
 // conditional mean and variance of the random effects at nnew[b] new points per covariance block (newdata: every block's

@@ -12,6 +12,8 @@
 // two calls give the same bits.  y is not read, no collective is issued, and nothing a sampler or a fit reads is changed.
 // Two rules the sandwich (sandwich.hip) shares live here and are declared in entry.h: the chunked Gram reduction (gram_launch:
 // its meat is the same reduction without the second sum) and the flagged tail that ends a query (query_download).
+// info_matrix itself is info_front, info_solve_gram and the download; the small-sample query (small_sample.hip) calls the
+// first two for its I_beta block and goes on from the S they leave.
 #include "entry.h"
 #include "component.h"
 #include "dgemm_mfma.h"
@@ -166,9 +168,26 @@ int info_front(Ctx& c, const double* beta, double var_par, bool comp, bool rhs, 
     return MCML_OK;
 }
 
-int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out, int ldo)
+int info_solve_gram(Ctx& c, bool comp, bool dense_built)
 {
     const int n = c.n, Q = c.Q, P = c.P;
+    InfoState& x = c.info;
+    if (comp) {
+        int form = 0;
+        MCML_TRY(comp_solve_launch(c, x.f, x.S.d(), x.S.ld, P, false, &form));
+        x.plan[1] = form; x.plan[4] = x.waves; x.plan[5] = 2;
+    } else {
+        MCML_TRY(trsm_left_lower(c, x.M.d(), x.M.ld, Q, x.S.d(), x.S.ld, P));
+        x.plan[6] = (long long)(x.M.buf.bytes + x.ZLTW.buf.bytes + (dense_built ? c.ZL.buf.bytes + c.ZLT.buf.bytes : 0));
+    }
+    // ---- the Gram reduction
+    MCML_TRY(x.res.ensure(sizeof(double) * ((size_t)P * P + 2)));
+    return gram_launch(c, c.X.d(), c.X.ld, x.XV.d(), x.XV.ld, n, x.S.d(), x.S.ld, Q, P, x.part, x.bad.as<int>(), x.res.d());
+}
+
+int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out, int ldo)
+{
+    const int n = c.n, P = c.P;
     MCML_REQUIRE(n > 0 && P > 0, "information: the context has no model");
     MCML_REQUIRE(beta && out && ldo >= P, "information: null argument / ldo too small");
     MCML_REQUIRE(op >= 0 && op <= 2, "information: op must be 0 (auto), 1 (dense) or 2 (component)");
@@ -188,18 +207,8 @@ int info_matrix(Ctx& c, const double* beta, double var_par, int op, double* out,
 
     InfoDenseScope dense(c);
     MCML_TRY(info_front(c, beta, var_par, comp, true, dense));
-    if (comp) {
-        int form = 0;
-        MCML_TRY(comp_solve_launch(c, x.f, x.S.d(), x.S.ld, P, false, &form));
-        x.plan[1] = form; x.plan[4] = x.waves; x.plan[5] = 2;
-    } else {
-        MCML_TRY(trsm_left_lower(c, x.M.d(), x.M.ld, Q, x.S.d(), x.S.ld, P));
-        x.plan[6] = (long long)(x.M.buf.bytes + x.ZLTW.buf.bytes + (dense.on ? c.ZL.buf.bytes + c.ZLT.buf.bytes : 0));
-    }
-
-    // ---- the Gram reduction and the one download
-    MCML_TRY(x.res.ensure(sizeof(double) * ((size_t)P * P + 2)));
-    MCML_TRY(gram_launch(c, c.X.d(), c.X.ld, x.XV.d(), x.XV.ld, n, x.S.d(), x.S.ld, Q, P, x.part, x.bad.as<int>(), x.res.d()));
+    MCML_TRY(info_solve_gram(c, comp, dense.on));
+    // ---- the one download
     std::vector<double> h;
     MCML_TRY(query_download(c, x.res, P, 0, "information", "a weight dhdmu(x' beta) * scale, or its reciprocal,", h));
     copy_columns(out, ldo, h.data(), P, P);

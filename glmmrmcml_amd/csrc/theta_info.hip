@@ -28,6 +28,8 @@
 // k_ti_final writes the matrix (r >= s, mirrored) and the two flags behind it; query_download ends the call.  Everything runs on
 // c.stream, there is no floating-point atomic and every sum has a fixed order: two calls give the same bits.  Neither y nor the
 // samples are read, no collective is issued, and nothing a sampler, a fit, mvn_ll or the information query reads is changed.
+// The call is two halves, declared in entry.h for the small-sample query (small_sample.hip), which needs I_theta with more:
+// theta_info_begin (the operator, the kernels' theta, the blocks' parameter masks) and theta_info_compute (every launch above).
 #include "entry.h"
 #include "component.h"
 #include "cov_block.h"
@@ -40,7 +42,6 @@
 
 namespace mcml {
 
-constexpr int TI_COMP_MAX_VARS = 64;              // variables of a component k_ti_comp takes
 constexpr int TI_LS = TI_COMP_MAX_VARS + 1;       // row stride of its LDS matrices
 constexpr size_t TI_COMP_LDS = sizeof(double) * 4 * TI_COMP_MAX_VARS * TI_LS;   // 130 KB of the 160 KB: one workgroup per CU
 constexpr int TI_TILE = 32;
@@ -322,7 +323,7 @@ __global__ __launch_bounds__(256) void k_ti_comp_sum(const double* cpart, int nc
 // the component operator applies: the sparse operator runs (comp_operator_ready), no component has more than TI_COMP_MAX_VARS
 // variables and every covariance block lies inside one component -- a variable with no observation is a component of its own and
 // can split a block
-static bool theta_info_component_ok(const Ctx& c)
+bool theta_info_component_ok(const Ctx& c)
 {
     if (!comp_operator_ready(c)) return false;
     const ComponentPlan& p = c.cp.plan;
@@ -436,6 +437,49 @@ static int theta_info_comp(Ctx& c, const ThetaArg& th, int R, const std::vector<
     return MCML_OK;
 }
 
+int theta_info_begin(Ctx& c, const char* who, const double* theta, int op, ThetaInfoCall& k)
+{
+    const int R = c.cov.npar;
+    k.R = R;
+    k.sigma_row = c.flink == 7 ? 1 : 0;                             // gaussian / identity
+    k.no = R + k.sigma_row;
+    ThetaInfoState& t = c.tinfo;
+    const ComponentPlan& p = c.cp.plan;
+    const bool comp_ok = theta_info_component_ok(c);
+    const long long plan0[8] = {op, 0, p.ncomp, p.max_vars, 0, 0, R, k.no};
+    std::copy(plan0, plan0 + 8, t.plan);
+    if (op == 2 && !comp_ok) {
+        set_error("%s: the component operator needs the sparse ZL operator, no component above %d variables and "
+                  "every covariance block inside one component", who, TI_COMP_MAX_VARS);
+        return MCML_EUNSUPPORTED;
+    }
+    k.comp = op != 1 && comp_ok;
+    MCML_TRY(theta_arg(theta, R, k.th));
+    const CovSpec& cs = c.cov;
+    k.mask.assign(cs.B, 0u);                                        // bit p: block b has a slot that reads parameter p
+    for (int b = 0; b < cs.B; ++b)
+        for (int r = cs.blocks[b].r0; r < cs.blocks[b].r1; ++r)
+            for (int q = 0; q < CovSpec::fn_npar(cs.c(r, 2)); ++q) k.mask[b] |= 1u << (cs.c(r, 4) + q);
+    k.sparse_ctx = c.sp.active;
+    return MCML_OK;
+}
+
+int theta_info_compute(Ctx& c, const ThetaInfoCall& k, double var_par)
+{
+    ThetaInfoState& t = c.tinfo;
+    const int R = k.R, no = k.no;
+    MCML_TRY(t.tr.ensure(sizeof(double) * (size_t)ti_red_len(R)));
+    MCML_HIP(hipMemsetAsync(t.tr.d(), 0, sizeof(double) * (size_t)ti_red_len(R), c.stream));
+    if (k.comp) MCML_TRY(theta_info_comp(c, k.th, R, k.mask));
+    else MCML_TRY(theta_info_dense(c, k.th, R, k.sigma_row, k.mask, k.sparse_ctx));
+    t.plan[1] = k.comp ? 1 : 0;
+    MCML_TRY(t.res.ensure(sizeof(double) * ((size_t)no * no + 2)));
+    hipLaunchKernelGGL(k_ti_final, dim3((no * no + 255) / 256), dim3(256), 0, c.stream, t.tr.d(), R, k.sigma_row, var_par, (double)c.n,
+                       c.errflag(), c.info.bad.as<int>(), t.res.d());
+    MCML_HIP(hipGetLastError());
+    return MCML_OK;
+}
+
 int theta_info(Ctx& c, const double* beta, double var_par, const double* theta, int op, double* out, int ldo, int* nout)
 {
     const int n = c.n, P = c.P, R = c.cov.npar;
@@ -444,44 +488,19 @@ int theta_info(Ctx& c, const double* beta, double var_par, const double* theta, 
     MCML_REQUIRE(op >= 0 && op <= 2, "theta_information: op must be 0 (auto), 1 (dense) or 2 (component)");
     MCML_REQUIRE(c.have_L && !c.l_foreign, "theta_information: the context holds no L made from theta");
     MCML_REQUIRE(std::isfinite(var_par), "theta_information: var_par is not finite");
-    const int sigma_row = c.flink == 7 ? 1 : 0, no = R + sigma_row;            // gaussian / identity
+    const int no = R + (c.flink == 7 ? 1 : 0);
     MCML_REQUIRE(ldo >= no, "theta_information: ldo %d too small for %d rows", ldo, no);
-    MCML_REQUIRE(!sigma_row || var_par != 0.0, "theta_information: sigma is 0");
-    ThetaInfoState& t = c.tinfo;
-    const ComponentPlan& p = c.cp.plan;
-    const bool comp_ok = theta_info_component_ok(c);
-    const long long plan0[8] = {op, 0, p.ncomp, p.max_vars, 0, 0, R, no};
-    std::copy(plan0, plan0 + 8, t.plan);
-    if (op == 2 && !comp_ok) {
-        set_error("theta_information: the component operator needs the sparse ZL operator, no component above %d variables and "
-                  "every covariance block inside one component", TI_COMP_MAX_VARS);
-        return MCML_EUNSUPPORTED;
-    }
-    const bool comp = op != 1 && comp_ok;
-    ThetaArg th;
-    MCML_TRY(theta_arg(theta, R, th));
-    const CovSpec& cs = c.cov;
-    std::vector<unsigned> mask(cs.B, 0u);                          // bit p: block b has a slot that reads parameter p
-    for (int b = 0; b < cs.B; ++b)
-        for (int r = cs.blocks[b].r0; r < cs.blocks[b].r1; ++r)
-            for (int q = 0; q < CovSpec::fn_npar(cs.c(r, 2)); ++q) mask[b] |= 1u << (cs.c(r, 4) + q);
+    MCML_REQUIRE(c.flink != 7 || var_par != 0.0, "theta_information: sigma is 0");
+    ThetaInfoCall k;
+    MCML_TRY(theta_info_begin(c, "theta_information", theta, op, k));
 
     InfoDenseScope dense(c);
-    const bool sparse_ctx = c.sp.active;
-    MCML_TRY(info_front(c, beta, var_par, comp, false, dense));
-    MCML_TRY(t.tr.ensure(sizeof(double) * (size_t)ti_red_len(R)));
-    MCML_HIP(hipMemsetAsync(t.tr.d(), 0, sizeof(double) * (size_t)ti_red_len(R), c.stream));
-    if (comp) MCML_TRY(theta_info_comp(c, th, R, mask));
-    else MCML_TRY(theta_info_dense(c, th, R, sigma_row, mask, sparse_ctx));
-    t.plan[1] = comp ? 1 : 0;
+    MCML_TRY(info_front(c, beta, var_par, k.comp, false, dense));
+    MCML_TRY(theta_info_compute(c, k, var_par));
 
-    // ---- the matrix, its flags and the one download
-    MCML_TRY(t.res.ensure(sizeof(double) * ((size_t)no * no + 2)));
-    hipLaunchKernelGGL(k_ti_final, dim3((no * no + 255) / 256), dim3(256), 0, c.stream, t.tr.d(), R, sigma_row, var_par, (double)n,
-                       c.errflag(), c.info.bad.as<int>(), t.res.d());
-    MCML_HIP(hipGetLastError());
+    // ---- the one download
     std::vector<double> h;
-    MCML_TRY(query_download(c, t.res, no, 0, "theta_information", "a weight dhdmu(x' beta) * scale, or its reciprocal,", h));
+    MCML_TRY(query_download(c, c.tinfo.res, no, 0, "theta_information", "a weight dhdmu(x' beta) * scale, or its reciprocal,", h));
     copy_columns(out, ldo, h.data(), no, no);
     *nout = no;
     return MCML_OK;

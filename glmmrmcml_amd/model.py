@@ -232,6 +232,31 @@ def predict_host(cov, data, theta, u, newdata, means=False):
     return out
 
 
+def _kenward_roger(info, tinfo, Pm, Qm, Rm, type):
+    """dict(vcov, se, dof, vcov_unadjusted) from I_beta, I_theta and the P_r, Q_rs, R_rs of ModelMCML.small_sample, by P x P
+    algebra; NaN throughout where a matrix cannot be inverted"""
+    info, tinfo = np.asarray(info, float), np.asarray(tinfo, float)
+    P, no = info.shape[0], tinfo.shape[0]
+    nan = dict(vcov=np.full((P, P), np.nan), se=np.full(P, np.nan), dof=np.full(P, np.nan), vcov_unadjusted=np.full((P, P), np.nan))
+    try:
+        Phi, W = np.linalg.inv(info), np.linalg.inv(tinfo)
+    except np.linalg.LinAlgError:
+        return nan
+    if not (np.all(np.isfinite(Phi)) and np.all(np.isfinite(W))):
+        return nan
+    vcov = Phi
+    if type != "sat":
+        kappa = 1.0 if type == "KR2" else 0.0
+        mid = sum(W[r, s] * (Qm[r, s] - Pm[r] @ Phi @ Pm[s] - kappa * 0.25 * Rm[r, s]) for r in range(no) for s in range(no))
+        vcov = Phi + 2 * Phi @ mid @ Phi
+        vcov = (vcov + vcov.T) / 2
+    g = np.array([np.diag(Phi @ Pm[r] @ Phi) for r in range(no)])       # no x P
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dof = 2 * np.diag(Phi) ** 2 / np.einsum("rk,rs,sk->k", g, W, g)
+        se = np.sqrt(np.diag(vcov))
+    return dict(vcov=vcov, se=se, dof=dof, vcov_unadjusted=Phi)
+
+
 class McmlFit(dict):
     """the `mcml` list MCML() / LA() return (R6ModelExtMCML.R:571-587); attribute access for convenience"""
 
@@ -277,6 +302,13 @@ class McmlFit(dict):
             out.append("%-14s %10.2f %10.2f %8.2f %8.2f %10.2f %10.2f" % r)
         out.append("cAIC: %.2f" % self["aic"])
         out.append("Approximate R-squared: Conditional: %.2f  Marginal: %.2f" % (self["Rsq"]["cond"], self["Rsq"]["marg"]))
+        if self.get("small_sample") is not None:
+            ss = self["small_sample"]
+            out.append("Small-sample correction of the fixed effects (%s): t-based intervals" % ss["type"])
+            out.append("%-14s %10s %10s %8s %10s %10s" % ("", "Estimate", "Std. Err.", "d.f.", "2.5% CI", "97.5% CI"))
+            for i, r in enumerate(self.table()[:len(ss["se"])]):
+                out.append("%-14s %10.2f %10.2f %8.1f %10.2f %10.2f" % (r[0], r[1], ss["se"][i], ss["dof"][i], ss["lower"][i],
+                                                                        ss["upper"][i]))
         if self.get("theta_score") is not None:
             out.append("Max. |score| of the covariance parameters: %.3g" % np.max(np.abs(self["theta_score"])))
         if not self["converged"]:
@@ -410,20 +442,24 @@ class ModelMCML:
             w = w * (1 + sigma)
         return w
 
-    def _dD_host(self, theta_cov):
+    def _dD_host(self, theta_cov, second=False):
         """(D, [d D / d theta_r, r < R]) dense Q x Q in float64 numpy from the covariance spec: every block is the product of
         its terms (gr, fexp0, ar1, sqexp, fexp, sqexp0 of the rows' Euclidean distance), and a product's derivative is the sum
-        over the terms that read theta_r of the term's derivative times the other terms"""
+        over the terms that read theta_r of the term's derivative times the other terms.  second: also {(r, s), r >= s:
+        d^2 D / d theta_r d theta_s} for the pairs a block reads together -- the terms' own second derivatives times the other
+        terms, plus the products of two different terms' first derivatives times the rest"""
         th = np.asarray(theta_cov, float).ravel()
         cov = np.asarray(self.cov)
         data = np.asarray(self.data, float).ravel()
         R, Q = th.size, self.Z.shape[1]
         D = np.zeros((Q, Q))
         dD = [np.zeros((Q, Q)) for _ in range(R)]
+        d2D = {}
         r, off, s = 0, 0, 0
         while r < cov.shape[0]:
             bid, dim, r0 = int(cov[r, 0]), int(cov[r, 1]), r
             terms = []                                      # (value, {parameter: derivative of the value})
+            terms2 = []                                     # {(p, q), p >= q: second derivative of the value}
             while r < cov.shape[0] and int(cov[r, 0]) == bid:
                 fn, nv, pi = int(cov[r, 2]), int(cov[r, 3]), int(cov[r, 4])
                 x = data[off:off + dim * nv].reshape(dim, nv, order="F")
@@ -433,20 +469,28 @@ class ModelMCML:
                 if fn == 1:
                     same = (d == 0).astype(float)
                     terms.append((same * t[0] ** 2, {pi: same * 2 * t[0]}))
+                    terms2.append({(pi, pi): same * 2})
                 elif fn == 2:
                     e = np.exp(-d / t[0])
                     terms.append((e, {pi: e * d / t[0] ** 2}))
+                    terms2.append({(pi, pi): e * (d * d / t[0] ** 4 - 2 * d / t[0] ** 3)})
                 elif fn == 3:
                     terms.append((t[0] ** d, {pi: np.where(d > 0, d * t[0] ** (d - 1), 0.0)}))
+                    terms2.append({(pi, pi): np.where(d > 0, d * (d - 1) * t[0] ** (d - 2), 0.0)})
                 elif fn == 4:
                     e = np.exp(-d * d / t[1] ** 2)
                     terms.append((t[0] * e, {pi: e, pi + 1: t[0] * e * 2 * d * d / t[1] ** 3}))
+                    terms2.append({(pi + 1, pi): e * 2 * d * d / t[1] ** 3,
+                                   (pi + 1, pi + 1): t[0] * e * (4 * d ** 4 / t[1] ** 6 - 6 * d * d / t[1] ** 4)})
                 elif fn == 7:
                     e = np.exp(-d / t[1])
                     terms.append((t[0] * e, {pi: e, pi + 1: t[0] * e * d / t[1] ** 2}))
+                    terms2.append({(pi + 1, pi): e * d / t[1] ** 2,
+                                   (pi + 1, pi + 1): t[0] * e * (d * d / t[1] ** 4 - 2 * d / t[1] ** 3)})
                 elif fn == 14:
                     e = np.exp(-d * d / t[0] ** 2)
                     terms.append((e, {pi: e * 2 * d * d / t[0] ** 3}))
+                    terms2.append({(pi, pi): e * (4 * d ** 4 / t[0] ** 6 - 6 * d * d / t[0] ** 4)})
                 else:
                     raise ValueError("covariance function id %d is not built" % fn)
                 r += 1
@@ -458,8 +502,23 @@ class ModelMCML:
                 others = np.prod([v for j, (v, _) in enumerate(terms) if j != k] + [keep], axis=0)
                 for p, dv in ders.items():
                     dD[p][sl, sl] += dv * others
+            if second:
+                read = sorted({p for _, ders in terms for p in ders})
+                for p in read:
+                    for q in read:
+                        if q > p:
+                            continue
+                        acc = np.zeros((dim, dim))
+                        for k, (_, dk) in enumerate(terms):
+                            if (p, q) in terms2[k]:
+                                acc += terms2[k][(p, q)] * np.prod([v for j, (v, _) in enumerate(terms) if j != k] + [keep], axis=0)
+                            for l, (_, dl) in enumerate(terms):
+                                if l != k and p in dk and q in dl:
+                                    acc += dk[p] * dl[q] * np.prod([v for j, (v, _) in enumerate(terms) if j not in (k, l)] + [keep],
+                                                                   axis=0)
+                        d2D.setdefault((p, q), np.zeros((Q, Q)))[sl, sl] += acc
             s += dim
-        return D, dD
+        return (D, dD, d2D) if second else (D, dD)
 
     def theta_information(self, theta_cov, beta, sigma, on="device"):
         """The GLS (expected) information of the covariance parameters, I[r, s] = 1/2 tr(Sigma^-1 d_r Sigma Sigma^-1 d_s Sigma)
@@ -514,6 +573,92 @@ class ModelMCML:
     def _check_theta_se(theta_se):
         if theta_se not in (None, "host", "device"):
             raise ValueError("theta_se should be 'host', 'device' or None")
+
+    def _small_sample_blocks(self, theta_cov, beta, sigma, on):
+        """dict(information, theta_information, P, Q, R) behind small_sample: I_beta (P x P), I_theta (no x no), P_r (no, P, P),
+        Q_rs and R_rs (no, no, P, P), from the backend's export (on = "device") or by the n x n definition in numpy ("host")"""
+        with_sigma = self.family == "gaussian" and self.link == "identity"
+        if on == "device":
+            family = "gamma" if self.family == "Gamma" else self.family
+            r = self._be.small_sample(*self._ddata(), self.Z, self.X, family, self.link, np.asarray(beta, float),
+                                      np.asarray(theta_cov, float), var_par=float(sigma))
+            info, tinfo, Pm, Qm, Rm = (np.asarray(r[k]) for k in ("information", "theta_information", "P", "Q", "R"))
+        elif on == "host":
+            R, P = self.cov_parameters.size, self.X.shape[1]
+            D, dD, d2D = self._dD_host(theta_cov, second=True)
+            Z, X = self.Z, self.X
+            S = np.diag(self._weights(beta, sigma)) + Z @ D @ Z.T
+            A = np.linalg.solve(S, X)
+            dS = [Z @ d @ Z.T for d in dD]
+            if with_sigma:
+                dS.append(2 * float(sigma) * np.eye(S.shape[0]))
+            no = len(dS)
+            SdA = [np.linalg.solve(S, d @ A) for d in dS]
+            info = X.T @ A
+            tinfo = self.theta_information(theta_cov, beta, sigma, on="host")["information"]
+            Pm = np.array([-(A.T @ d @ A) for d in dS])
+            Qm = np.array([[(dr @ A).T @ sa for sa in SdA] for dr in dS])
+            Rm = np.zeros((no, no, P, P))
+            ZA = Z.T @ A
+            for (p, q), m in d2D.items():
+                Rm[p, q] = ZA.T @ m @ ZA
+                Rm[q, p] = Rm[p, q]
+            if with_sigma:
+                Rm[R, R] = 2 * (A.T @ A)
+        else:
+            raise ValueError("small_sample: on should be 'host' or 'device'")
+        return dict(information=info, theta_information=tinfo, P=Pm, Q=Qm, R=Rm)
+
+    def small_sample(self, theta_cov, beta, sigma, on="device", type="KR"):
+        """Small-sample corrections of the fixed effects (beyond the R class; glmmrBase offers them as "KR", "KR2" and "sat")
+        -> dict(vcov, se, dof, vcov_unadjusted, information, theta_information, names, type).  With Phi = I_beta^-1,
+        W = I_theta^-1 (theta_information's matrix, sigma last for gaussian / identity) and
+            P_r = -X' Sigma^-1 d_r Sigma Sigma^-1 X,   Q_rs = X' Sigma^-1 d_r Sigma Sigma^-1 d_s Sigma Sigma^-1 X,
+            R_rs = X' Sigma^-1 d2_rs Sigma Sigma^-1 X,
+        type "KR" (Kenward & Roger 1997): vcov = Phi + 2 Phi [sum_rs W_rs (Q_rs - P_r Phi P_s)] Phi; "KR2": the bracket also
+        takes -R_rs / 4; "sat" (Satterthwaite): vcov = Phi.  All three: dof[k] = 2 Phi_kk^2 / (g_k' W g_k),
+        g_k[r] = (Phi P_r Phi)_kk -- Satterthwaite's degrees of freedom of one coefficient, which is also what Kenward and
+        Roger's m is for a one-row contrast (its scale factor is then 1).  Contrasts of several rows are not offered.
+        on = "device": the backend's `small_sample` export (csrc/small_sample.hip), the Q x Q form; "host": the n x n
+        definition as written, in float64 numpy, with the derivatives of D of _dD_host.  An I_theta (or I_beta) that cannot be
+        inverted gives NaN and a warning"""
+        if type not in ("KR", "KR2", "sat"):
+            raise ValueError("small_sample: type should be 'KR', 'KR2' or 'sat'")
+        names = self._cov_par_names()
+        with_sigma = self.family == "gaussian" and self.link == "identity"
+        blk = self._small_sample_blocks(theta_cov, beta, sigma, on)
+        info, tinfo, Pm, Qm, Rm = (blk[k] for k in ("information", "theta_information", "P", "Q", "R"))
+        out = _kenward_roger(info, tinfo, Pm, Qm, Rm, type)
+        if not (np.all(np.isfinite(out["dof"])) and np.all(np.isfinite(out["vcov"]))):
+            import warnings
+            warnings.warn("small_sample: the information of the covariance parameters (or of the fixed effects) is not invertible")
+        out.update(information=info, theta_information=tinfo, names=names + (["sigma"] if with_sigma else []), type=type)
+        return out
+
+    def _small_sample_fit(self, fit, small_sample):
+        """MCML(..., small_sample=) / LA(..., small_sample=): the fit with its `small_sample` record = dict(type, vcov, se, dof,
+        lower, upper) at the fitted parameters, the bounds est -+ qt(0.975, dof) se; the coefficient table is untouched"""
+        import warnings
+        from scipy import stats
+        P, R = self.X.shape[1], self.cov_parameters.size
+        th = fit["theta"]
+        sigma = th[P + R] if th.size > P + R else 1.0
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            r = self.small_sample(th[P:P + R], th[:P], sigma, on="device", type=small_sample)
+        if not (np.all(np.isfinite(r["dof"])) and np.all(np.isfinite(r["se"]))):
+            fit["warnings"].append("small_sample: the information of the covariance parameters is not invertible")
+        est = np.asarray(fit["coefficients"]["est"][:P], float)
+        with np.errstate(invalid="ignore"):
+            q = stats.t.ppf(0.975, r["dof"])
+        fit["small_sample"] = dict(type=r["type"], vcov=r["vcov"], se=r["se"], dof=r["dof"], lower=est - q * r["se"],
+                                   upper=est + q * r["se"])
+        return fit
+
+    @staticmethod
+    def _check_small_sample(small_sample):
+        if small_sample not in (None, "KR", "KR2", "sat"):
+            raise ValueError("small_sample should be 'KR', 'KR2', 'sat' or None")
 
     def sandwich(self, y, theta_cov, beta, sigma, cluster=None, on="device", adjust="CR0"):
         """The cluster-robust (sandwich) covariance of the fixed effects (beyond the R class, whose se.method = "robust" never
@@ -607,7 +752,7 @@ class ModelMCML:
         return "host" if information is None else information
 
     def MCML(self, y, *args, trajectory=None, draws=None, theta_score=False, information=None, sandwich=None, cluster=None,
-             theta_se=None, **kwargs):
+             theta_se=None, small_sample=None, **kwargs):
         """_mcml below (its arguments, unchanged); trajectory ("step" / "component", None = leave the backend's default
         alone): how the HMC sampler runs a trajectory on the sparse operator (csrc/hmc_traj.h).  draws ("hmc" / "exact" /
         "exact_component", None = leave the default alone): what the HMC sampler's call returns -- "exact" draws the conditional distribution of
@@ -628,9 +773,14 @@ class ModelMCML:
         theta_se ("host" / "device", None = nothing more is called and the covariance parameters keep the standard errors
         se_method gave them, NaN under "approx"): their standard errors, and sigma's for gaussian / identity, become
         sqrt(diag(inv(I_theta))) of theta_information(on=theta_se) at the fitted parameters, and the fit carries
-        `theta_information`; the fixed effects' standard errors are untouched."""
+        `theta_information`; the fixed effects' standard errors are untouched.
+        small_sample ("KR" / "KR2" / "sat", None = nothing more is called): the fit also carries `small_sample` = dict(type,
+        vcov, se, dof, lower, upper), the Kenward-Roger or Satterthwaite correction of the fixed effects at the fitted
+        parameters -- small_sample(on="device") -- with t-based bounds; it is shown in the print, and the coefficient table is
+        untouched."""
         self._check_sandwich(sandwich)
         self._check_theta_se(theta_se)
+        self._check_small_sample(small_sample)
         prev_t = prev_d = None
         prev_i, use_i = self._information, self._use_information(information)
         if trajectory is not None:
@@ -650,6 +800,8 @@ class ModelMCML:
                 self._robust(fit, y, sandwich, cluster)
             if theta_se is not None:
                 self._theta_se(fit, theta_se)
+            if small_sample is not None:
+                self._small_sample_fit(fit, small_sample)
             return fit
         finally:
             self._information = prev_i
@@ -793,15 +945,18 @@ class ModelMCML:
                        re_samps=dsamps, iter=it, warnings=warnings, theta=theta)
 
     # ---- LA ------------------------------------------------------------------------------------------------------
-    def LA(self, y, *args, operator=None, information=None, sandwich=None, cluster=None, theta_se=None, **kwargs):
+    def LA(self, y, *args, operator=None, information=None, sandwich=None, cluster=None, theta_se=None, small_sample=None,
+           **kwargs):
         """_la below (its arguments, unchanged); operator ("dense" / "component" / "component_wide", None = leave the
         backend's default alone): how the Laplace fit forms and factorises ZL' W ZL + I (csrc/component.hip).  It becomes the backend's default
         for the duration of the call and is restored afterwards.  information ("host" / "device", None = "host"): where the
         GLS information matrix behind the standard errors without use_hess is computed -- information_matrix(on=).
         sandwich ("CR0" / "CR1") and cluster: as MCML's -- the fit gains `robust`, the coefficient table is untouched.
-        theta_se ("host" / "device", None = the covariance parameters' standard errors stay as they are): as MCML's"""
+        theta_se ("host" / "device", None = the covariance parameters' standard errors stay as they are): as MCML's.
+        small_sample ("KR" / "KR2" / "sat", None = nothing more is called): as MCML's -- the fit gains `small_sample`"""
         self._check_sandwich(sandwich)
         self._check_theta_se(theta_se)
+        self._check_small_sample(small_sample)
         prev_i, self._information = self._information, self._use_information(information)
         prev = None
         try:
@@ -811,7 +966,9 @@ class ModelMCML:
             fit = self._la(y, *args, **kwargs)
             if sandwich is not None:
                 fit = self._robust(fit, y, sandwich, cluster)
-            return fit if theta_se is None else self._theta_se(fit, theta_se)
+            if theta_se is not None:
+                fit = self._theta_se(fit, theta_se)
+            return fit if small_sample is None else self._small_sample_fit(fit, small_sample)
         finally:
             self._information = prev_i
             if prev is not None:

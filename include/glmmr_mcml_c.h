@@ -568,6 +568,8 @@ int glmmr_mcml_dbg_band_clocks(int M, int N, int iters, int mode, double* out3);
 #include "glmmr_mcml_band.h"
 /* the GLS information of the covariance parameters on the device (csrc/theta_info.hip): a header of its own */
 #include "glmmr_mcml_theta_info.h"
+/* the small-sample corrections of the fixed effects, their ingredients (csrc/small_sample.hip): a header of its own */
+#include "glmmr_mcml_small_sample.h"
 
 #ifdef __cplusplus
 }
